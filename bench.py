@@ -17,13 +17,22 @@ to give ~1.05x at 8 GPUs (`expected_speedup_at_8` in its line) while this one sc
 
 `python bench.py --gpus N` without a launcher starts the N ranks itself (before anything touches the GPU).
 
-Prints ONE JSON line (rank 0) with
-  roofline      dominant kernel = site_apply_grouped (HBM-store bound): algorithmic bytes / live HIP-event time
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line (rank 0): metric, value, unit,
+higher_is_better, dtype, ms_per_step, the configuration and (apply workloads) the roofline of the timed launches.
+`--dump-outputs DIR` also writes what the last timed step computed to DIR/<name>.npy (float64; apply: a fixed, seeded
+sample of the 80 GB product, see apply_outputs; sweep: every coefficient of the sweep).  Inputs are seeded, so runs with
+the same arguments get the same inputs.  Everything else is measured and checked with `--full` only:
+  max_coeff_err the timed product's coefficients against the lazy HIP read-out and the CPU oracle (sweep: against
+                the closed form and the oracle)
+  roofline      + the box's own store-only ceiling (a run of its own before the warm-up)
   truncate      the other half of "apply-and-truncate": the fused apply_compress and the exact compress!(apply)
                 on the zT product of an encoded n=24 signal (chi 15 x D ~89, 48 sites, maxdim 64), with an MFMA
                 flop model against the f64 matrix peak
+  configs       one record per BASELINE.json configuration + the read-out and encode rooflines (bench_configs.py)
   cpu_baseline  the C++/OpenMP CPU backend behind the same C ABI (oracle/cpu, all cores and one thread) and the
                 numpy port of the oracle, timed on this box's host cores on the same workload
+  bound_by      (sweep) the builder launch timed on its own, its scaling with the number of values
+(--no-truncate / --no-configs / --no-cpu-baseline drop a block of the --full line.)
 """
 import argparse
 import hashlib
@@ -556,6 +565,69 @@ def emit(res):
     print(json.dumps(res), flush=True)
 
 
+# ---------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def site_samples(chain, per_site=4096, run=128):
+    """A fixed, seeded sample of every site tensor of a device chain, read straight from HBM (the cfg3 product is 80 GB):
+    a site of at most `per_site` entries whole, a larger one as per_site / run runs of `run` consecutive entries at seeded,
+    non-overlapping offsets.  Offsets are flat column-major indices, the layout of `chain.site(i)`.
+    Returns (values, [tensor, flat index] per value)."""
+    import ctypes as C
+    from qilaplace_jl_amd import _lib as L
+    memcpy = L.lib.hipMemcpy                    # the HIP runtime the library itself is linked against
+    memcpy.argtypes, memcpy.restype = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int], C.c_int
+    dt = np.dtype(chain.dtype)
+    chain.ctx.synchronize()
+    vals, where = [], []
+    for i in range(len(chain.bond_dims) + 1):
+        count = int(np.prod(chain.site_shape(i)))
+        nb = C.c_int64()
+        L.check(chain._fn("site_nbytes")(chain.handle, i, C.byref(nb)))
+        assert nb.value == count * dt.itemsize, (i, nb.value, count)
+        if count <= per_site:
+            starts, length = np.zeros(1, dtype=np.int64), count
+        else:
+            rng = np.random.default_rng([20240064, i])
+            starts, length = np.sort(rng.choice(count // run, per_site // run, replace=False)).astype(np.int64) * run, run
+        assert starts[-1] + length <= count
+        buf = np.empty(len(starts) * length, dtype=dt)
+        src = chain.site_device_ptr(i)
+        for k, s in enumerate(starts):
+            rc = memcpy(buf.ctypes.data + k * length * dt.itemsize, src + int(s) * dt.itemsize, length * dt.itemsize, 2)
+            if rc != 0:
+                raise RuntimeError(f"hipMemcpy of site {i} failed ({rc})")
+        vals.append(buf)
+        flat = (starts[:, None] + np.arange(length, dtype=np.int64)[None, :]).reshape(-1)
+        where.append(np.stack([np.full(len(flat), i, dtype=np.int64), flat], -1))
+    return np.concatenate(vals), np.concatenate(where)
+
+
+def as_real(c):
+    """complex (...) -> float64 (..., 2) = [real, imag]."""
+    c = np.asarray(c)
+    return np.stack([c.real, c.imag if np.iscomplexobj(c) else np.zeros_like(c.real)], -1).astype(np.float64)
+
+
+def apply_outputs(qil, out, bits, coeffs=None):
+    """What apply(W, psi) handed back in the last timed step: a seeded sample of the product's site tensors, its amplitude,
+    and its coefficients at the fixed configurations `bits` (the accuracy leg's)."""
+    vals, where = site_samples(out)
+    if coeffs is None:
+        coeffs = qil.coefficient_batch(out, bits)
+    return {"apply_site_samples": as_real(vals), "apply_site_sample_index": where.astype(np.float64),
+            "apply_amplitude": np.array([out.amplitude], dtype=np.float64), "apply_coefficients": as_real(coeffs)}
+
+
+def dump_outputs(path, arrays):
+    total = sum(np.asarray(a).nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}"
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 # ---------------------------------------------------------------------------------------------- workloads
 def run_apply(args, rk):
     import qilaplace_jl_amd as qil
@@ -580,9 +652,11 @@ def run_apply(args, rk):
     else:
         W = mpo_cls.alloc(db, dtype=np.complex128, ctx=ctx).fill_random(777)
     abytes = algorithmic_bytes(cb, db)
-    # the box's own store-only ceiling (8 GiB x 5 by four writers, < 0.1 s, same process, before the timed region): fractions
-    # measured on different boxes of the pool become comparable
-    box_peak, box_writer = ctx.hbm_store_peak(8 << 30 if args.workload != "tiny" else 1 << 28, 5)
+    box_peak = box_writer = None
+    if args.full:
+        # the box's own store-only ceiling (8 GiB x 5 by four writers, < 0.1 s, same process, before the timed region): fractions
+        # measured on different boxes of the pool become comparable
+        box_peak, box_writer = ctx.hbm_store_peak(8 << 30 if args.workload != "tiny" else 1 << 28, 5)
 
     out = None
     for _ in range(args.warmup):
@@ -601,33 +675,35 @@ def run_apply(args, rk):
     n_launch, kernel_ms = ctx.profile_read(reset=True)
     elapsed = rk.max_over_ranks([elapsed])[0]
 
-    # ---- accuracy: sampled coefficients of the materialised W*psi vs the lazy HIP path and vs
-    # the CPU oracle (lazy restatement on the same W, psi)
     rng = np.random.default_rng(12345)
     bits = rng.integers(0, 2, size=(args.queries, L)).astype(np.uint8)
-    c_mat = qil.coefficient_batch(out, bits)
-    c_lazy = qil.apply_coefficient_batch(W, psi, bits)
-    scale = max(np.abs(c_mat).max(), 1e-300)
-    err_lazy = float(np.abs(c_mat - c_lazy).max() / scale)
-    err_oracle = None
-    if rank == 0 and not args.no_cpu_baseline:
-        import oracle as O
-        Wh = O.SingleSiteMPO(w_natural if genuine else W.to_host())
-        ph = O.SignalMPS(psi.to_host(), amplitude=psi.amplitude)
-        c_ref = O.lazy_coefficient_batch(Wh, ph, bits)
-        err_oracle = float(np.abs(c_mat - c_ref).max() / max(np.abs(c_ref).max(), 1e-300))
-    if rk.comm is not None:                               # the one data collective, through the C ABI (qil_gather_coefficients)
-        rk.comm.gather_coefficients({rank: c_mat}, world, len(c_mat))
-    if rk.dist is not None:
-        import torch
-        mine = torch.tensor(np.stack([c_mat.real, c_mat.imag], -1), device=rk.device)
-        gathered = [torch.empty_like(mine) for _ in range(world)] if rank == 0 else None
-        rk.dist.gather(mine, gathered, dst=0)           # the one RCCL data collective (KB-scale)
-    readout = None
-    if world == 1 and not args.no_configs and args.workload == "zt_n24_chi64_D128":
-        # SURVEY.md 8(d) `coefficient_batch` roofline, on the product of the timed region itself (80 GB, still in HBM)
-        import bench_configs
-        readout = bench_configs.coefficient_batch_entry(qil, ctx, out)
+    c_mat = qil.coefficient_batch(out, bits) if args.full or args.dump_outputs else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, apply_outputs(qil, out, bits, c_mat))
+    err_lazy = err_oracle = readout = None
+    if args.full:
+        # ---- accuracy: sampled coefficients of the materialised W*psi vs the lazy HIP path and vs
+        # the CPU oracle (lazy restatement on the same W, psi)
+        c_lazy = qil.apply_coefficient_batch(W, psi, bits)
+        scale = max(np.abs(c_mat).max(), 1e-300)
+        err_lazy = float(np.abs(c_mat - c_lazy).max() / scale)
+        if rank == 0 and not args.no_cpu_baseline:
+            import oracle as O
+            Wh = O.SingleSiteMPO(w_natural if genuine else W.to_host())
+            ph = O.SignalMPS(psi.to_host(), amplitude=psi.amplitude)
+            c_ref = O.lazy_coefficient_batch(Wh, ph, bits)
+            err_oracle = float(np.abs(c_mat - c_ref).max() / max(np.abs(c_ref).max(), 1e-300))
+        if rk.comm is not None:                               # the one data collective, through the C ABI (qil_gather_coefficients)
+            rk.comm.gather_coefficients({rank: c_mat}, world, len(c_mat))
+        if rk.dist is not None:
+            import torch
+            mine = torch.tensor(np.stack([c_mat.real, c_mat.imag], -1), device=rk.device)
+            gathered = [torch.empty_like(mine) for _ in range(world)] if rank == 0 else None
+            rk.dist.gather(mine, gathered, dst=0)           # the one RCCL data collective (KB-scale)
+        if world == 1 and not args.no_configs and args.workload == "zt_n24_chi64_D128":
+            # SURVEY.md 8(d) `coefficient_batch` roofline, on the product of the timed region itself (80 GB, still in HBM)
+            import bench_configs
+            readout = bench_configs.coefficient_batch_entry(qil, ctx, out)
     del out
     if rank != 0:
         return
@@ -650,17 +726,23 @@ def run_apply(args, rk):
                            % max(t.shape[3] for t in w_natural[:-1])) if genuine else "seeded random fill",
                    "ranks_reported_by_collective_backend": world, "collective_backend": rk.backend_used,
                    "lib_sha16": lib_sha16()},
-        "max_coeff_err": err_oracle if err_oracle is not None else err_lazy,
-        "coeff_err": {"materialised_vs_lazy_hip": err_lazy, "materialised_vs_cpu_oracle": err_oracle,
-                      "queries": args.queries, "kind": "max relative"},
-        "roofline": {"bound": "hbm", "kernel": "site_apply_grouped<c64,double>",
-                     "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "frac_of_measured_copy_peak": achieved / HBM_COPY_GBS,
-                     "box_store_peak": box_peak, "box_store_peak_writer": box_writer,
-                     "frac_of_box_store_peak": achieved / box_peak if box_peak > 0 else None,
-                     "traffic": traffic, "traffic_source": tsrc, "kernel_ms": k_ms, "launches_timed": n_launch,
-                     "algorithmic_bytes_per_launch": abytes},
     }
+    if args.full:
+        res["max_coeff_err"] = err_oracle if err_oracle is not None else err_lazy
+        res["coeff_err"] = {"materialised_vs_lazy_hip": err_lazy, "materialised_vs_cpu_oracle": err_oracle,
+                            "queries": args.queries, "kind": "max relative"}
+    roof = {"bound": "hbm", "kernel": "site_apply_grouped<c64,double>",
+            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "frac_of_measured_copy_peak": achieved / HBM_COPY_GBS}
+    if args.full:
+        roof.update({"box_store_peak": box_peak, "box_store_peak_writer": box_writer,
+                     "frac_of_box_store_peak": achieved / box_peak if box_peak > 0 else None})
+    roof.update({"traffic": traffic, "traffic_source": tsrc, "kernel_ms": k_ms, "launches_timed": n_launch,
+                 "algorithmic_bytes_per_launch": abytes})
+    res["roofline"] = roof
+    if not args.full:
+        emit(res)
+        return
     heavy = world == 1 and (not args.no_truncate or not args.no_configs)
     if heavy:
         del W, psi
@@ -720,8 +802,26 @@ def run_sweep(args, rk):
     elapsed = rk.max_over_ranks([elapsed])[0]
     if rk.rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"sweep_coefficients": as_real(np.asarray(res))})     # (values, samples, re/im)
+    head = {
+        "metric": "MPO×MPS site-contractions/sec + max |coeff err|, n=24 damping sweep (configs[3])",
+        "value": nsig * 2 * n / (elapsed / args.steps), "unit": "site-contractions/s",
+        "n_gpus": rk.world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak" if weak else "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": args.workload, "description": WORKLOADS[args.workload][4], "sites": 2 * n,
+                   "damping_values": nsig, "samples_per_value": nsamp, "mps_bonds_max": max(psi.bond_dims),
+                   "parallelism": f"{nsig} damping values round-robin over {rk.world} rank(s), one all_gather",
+                   "ranks_reported_by_collective_backend": rk.world, "collective_backend": rk.backend_used,
+                   "values_per_rank": [len(range(r, nsig, rk.world)) for r in range(rk.world)],
+                   "lib_sha16": lib_sha16()},
+    }
+    if not args.full:
+        emit(head)
+        return
     err, shares, peak = bench_configs.cfg4_errors(res, x, sig, kk, jj, n)    # + the share of reference samples that are not negligible
     Ws = qil.build_dt_mpo_batch(psi, [sig[0], sig[-1]])
+    head["config"]["mpo_bonds_max"] = max(max(W.bond_dims) for W in Ws)
     ab = sum(algorithmic_bytes(psi.bond_dims, W.bond_dims, w_bytes=8, a_bytes=8, o_bytes=8) for W in Ws) / 2.0
     k_ms = kernel_ms / max(n_launch, 1)
     achieved = ab / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
@@ -768,17 +868,7 @@ def run_sweep(args, rk):
                "seconds_per_sweep_scaled": t_cpu, "build_seconds_per_value": t_b / len(sub),
                "hip_vs_cpu_max_err_rel_to_signal_peak": worst, "cpu_samples_above_1e-6_peak_min_share": live_cpu}
     emit({
-        "metric": "MPO×MPS site-contractions/sec + max |coeff err|, n=24 damping sweep (configs[3])",
-        "value": nsig * 2 * n / (elapsed / args.steps), "unit": "site-contractions/s",
-        "n_gpus": rk.world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "weak" if weak else "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": args.workload, "description": WORKLOADS[args.workload][4], "sites": 2 * n,
-                   "damping_values": nsig, "samples_per_value": nsamp, "mps_bonds_max": max(psi.bond_dims),
-                   "mpo_bonds_max": max(max(W.bond_dims) for W in Ws),
-                   "parallelism": f"{nsig} damping values round-robin over {rk.world} rank(s), one all_gather",
-                   "ranks_reported_by_collective_backend": rk.world, "collective_backend": rk.backend_used,
-                   "values_per_rank": [len(range(r, nsig, rk.world)) for r in range(rk.world)],
-                   "lib_sha16": lib_sha16()},
+        **head,
         # parity figure = HIP against the CPU restatement of the reference's algorithm on the same operands (when that leg ran);
         # the distance to the closed form is the ALGORITHM's own MPO-truncation error at the reference's default cutoff 1e-14
         # (3.5e-5 of the peak at sigma = 0.25, the numpy oracle shows the same value to five digits)
@@ -825,11 +915,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--workload", default="zt_n24_chi64_D128", choices=sorted(WORKLOADS))
     ap.add_argument("--queries", type=int, default=4096, help="coefficient samples for max|coeff err| (BASELINE.md 3.6: >= 4096)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-truncate", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the `configs` block (cfg2 / cfg4 / cfg5 + read-out roofline)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (accuracy legs, box store ceiling, truncate, "
+                         "configs, CPU baseline, builder timings); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, seeded sample of large outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU legs")
+    ap.add_argument("--no-truncate", action="store_true", help="--full: skip the `truncate` block")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the `configs` block (cfg2 / cfg4 / cfg5 + read-out roofline)")
     ap.add_argument("--random-mpo", action="store_true", help="seeded random MPO instead of the embedded genuine zT MPO")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     sweep = args.workload in ("dt_sweep_n24_s64", "dt_sweep_n24_weak")
     if args.steps is None:
         args.steps = 40 if sweep else 1000

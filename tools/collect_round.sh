@@ -31,8 +31,8 @@ cp $O/${P}_pmc_traffic.json $O/${P}_pmc_write_site_apply.csv $O/${P}_pmc_fetch_s
       if [ -n "$f" ]; then cp "$f" $O/${P}_kernel_stats_$name.csv; break; fi
     done
   }
-  run zt_n24_chi64_D128 python3 $R/bench.py --steps 12 --warmup 2 --no-cpu-baseline --no-truncate --no-configs
-  run dt_sweep_n24_s64 python3 $R/bench.py --workload dt_sweep_n24_s64 --steps 3 --warmup 1 --no-cpu-baseline
+  run zt_n24_chi64_D128 python3 $R/bench.py --full --steps 12 --warmup 2 --no-cpu-baseline --no-truncate --no-configs
+  run dt_sweep_n24_s64 python3 $R/bench.py --full --workload dt_sweep_n24_s64 --steps 3 --warmup 1 --no-cpu-baseline
   run compress_chi256 python3 $R/tools/_compress_one.py 256 f64 3
   run exact_compress python3 $R/tools/_exact_compress_time.py 3
   run coefficient_batch_cfg3 python3 $R/tools/_coeff_cfg3.py 3
@@ -41,17 +41,17 @@ cp $O/${P}_pmc_traffic.json $O/${P}_pmc_write_site_apply.csv $O/${P}_pmc_fetch_s
   rm -rf $O/prof
 )
 cd $R
-timeout 900 python3 bench.py > $O/${P}_bench_default.json 2> $O/bench_default.err
-timeout 900 python3 bench.py --workload dt_sweep_n24_s64 > $O/${P}_bench_sweep.json 2> $O/bench_sweep.err
-timeout 900 python3 bench.py --workload dt_sweep_n24_weak --no-cpu-baseline > $O/${P}_bench_sweep_weak.json 2> $O/bench_sweep_weak.err
-QIL_BENCH_BACKEND=gloo timeout 600 python3 bench.py --gpus 2 --steps 50 --no-cpu-baseline --no-truncate --no-configs > $O/${P}_bench_gpus2_gloo_apply.json 2> $O/gloo_apply.err
-QIL_BENCH_BACKEND=gloo timeout 900 python3 bench.py --gpus 8 --steps 5 --workload dt_sweep_n24_s64 --no-cpu-baseline > $O/${P}_bench_gpus8_gloo_sweep_strong.json 2> $O/gloo8_sweep.err
-QIL_BENCH_BACKEND=gloo timeout 900 python3 bench.py --gpus 8 --steps 5 --workload dt_sweep_n24_weak --no-cpu-baseline > $O/${P}_bench_gpus8_gloo_sweep_weak.json 2> $O/gloo8_weak.err
-QIL_BENCH_BACKEND=gloo timeout 600 python3 bench.py --gpus 8 --steps 20 --workload qft_n20_chi32_D64 --no-cpu-baseline --no-truncate --no-configs > $O/${P}_bench_gpus8_gloo_apply_cfg2.json 2> $O/gloo8_apply.err
-QIL_BENCH_FORCE_DIST=1 timeout 600 python3 bench.py --gpus 1 --steps 50 --no-cpu-baseline --no-truncate --no-configs > $O/${P}_bench_rccl_n1_apply.json 2> $O/rccl_apply.err
-QIL_BENCH_FORCE_DIST=1 timeout 600 python3 bench.py --gpus 1 --steps 10 --workload dt_sweep_n24_s64 --no-cpu-baseline > $O/${P}_bench_rccl_n1_sweep.json 2> $O/rccl_sweep.err
-QIL_BENCH_BACKEND=cabi QIL_BENCH_FORCE_DIST=1 timeout 600 python3 bench.py --gpus 1 --steps 50 --no-cpu-baseline --no-truncate --no-configs > $O/${P}_bench_cabi_n1_apply.json 2> $O/cabi_apply.err
-QIL_BENCH_BACKEND=cabi QIL_BENCH_FORCE_DIST=1 timeout 600 python3 bench.py --gpus 1 --steps 10 --workload dt_sweep_n24_s64 --no-cpu-baseline > $O/${P}_bench_cabi_n1_sweep.json 2> $O/cabi_sweep.err
+timeout 900 python3 bench.py --full > $O/${P}_bench_default.json 2> $O/bench_default.err
+timeout 900 python3 bench.py --full --workload dt_sweep_n24_s64 > $O/${P}_bench_sweep.json 2> $O/bench_sweep.err
+timeout 900 python3 bench.py --full --workload dt_sweep_n24_weak --no-cpu-baseline > $O/${P}_bench_sweep_weak.json 2> $O/bench_sweep_weak.err
+QIL_BENCH_BACKEND=gloo timeout 600 python3 bench.py --full --gpus 2 --steps 50 --no-cpu-baseline --no-truncate --no-configs > $O/${P}_bench_gpus2_gloo_apply.json 2> $O/gloo_apply.err
+QIL_BENCH_BACKEND=gloo timeout 900 python3 bench.py --full --gpus 8 --steps 5 --workload dt_sweep_n24_s64 --no-cpu-baseline > $O/${P}_bench_gpus8_gloo_sweep_strong.json 2> $O/gloo8_sweep.err
+QIL_BENCH_BACKEND=gloo timeout 900 python3 bench.py --full --gpus 8 --steps 5 --workload dt_sweep_n24_weak --no-cpu-baseline > $O/${P}_bench_gpus8_gloo_sweep_weak.json 2> $O/gloo8_weak.err
+QIL_BENCH_BACKEND=gloo timeout 600 python3 bench.py --full --gpus 8 --steps 20 --workload qft_n20_chi32_D64 --no-cpu-baseline --no-truncate --no-configs > $O/${P}_bench_gpus8_gloo_apply_cfg2.json 2> $O/gloo8_apply.err
+QIL_BENCH_FORCE_DIST=1 timeout 600 python3 bench.py --full --gpus 1 --steps 50 --no-cpu-baseline --no-truncate --no-configs > $O/${P}_bench_rccl_n1_apply.json 2> $O/rccl_apply.err
+QIL_BENCH_FORCE_DIST=1 timeout 600 python3 bench.py --full --gpus 1 --steps 10 --workload dt_sweep_n24_s64 --no-cpu-baseline > $O/${P}_bench_rccl_n1_sweep.json 2> $O/rccl_sweep.err
+QIL_BENCH_BACKEND=cabi QIL_BENCH_FORCE_DIST=1 timeout 600 python3 bench.py --full --gpus 1 --steps 50 --no-cpu-baseline --no-truncate --no-configs > $O/${P}_bench_cabi_n1_apply.json 2> $O/cabi_apply.err
+QIL_BENCH_BACKEND=cabi QIL_BENCH_FORCE_DIST=1 timeout 600 python3 bench.py --full --gpus 1 --steps 10 --workload dt_sweep_n24_s64 --no-cpu-baseline > $O/${P}_bench_cabi_n1_sweep.json 2> $O/cabi_sweep.err
 T=$O/${P}_compress_times.txt
 timeout 300 python3 tools/_compress_time.py 2>/dev/null > $T
 for nb in 8 16 32 64; do timeout 300 python3 tools/_compress_concurrent.py $nb 256 2>/dev/null | tail -1 >> $T; done
