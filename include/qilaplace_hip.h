@@ -189,6 +189,20 @@ QIL_API int qil_mps_block(const qil_mps* psi, const uint8_t* spec, int reverse, 
 /* norm(psi) src/mps.jl:754-771 (without amplitude). */
 QIL_API int qil_norm(const qil_mps* psi, double* out);
 
+/* ------------------------------------------------------------------ overlaps (ITensors' inner on device chains) */
+/* <phi|psi> = amp_phi * amp_psi * sum_x conj(phi_x) psi_x
+ *           = vdot(mps_to_vector(phi), mps_to_vector(psi)).  out: host, one complex double (re, im).
+ * phi and psi: same context, same paired flag (QIL_EINVAL_ARG), same number of sites (QIL_EINVAL_LENGTH), same
+ * site ids (QIL_EINVAL_SITES); bonds and dtypes (f64 / c64) are free.  Chains whose bonds are all <= 16 take
+ * one launch (the whole walk in one workgroup), the others two f64-MFMA GEMMs per site.                     */
+QIL_API int qil_inner(const qil_mps* phi, const qil_mps* psi, double* out);
+/* <phi|W psi> without materialising W psi: the same number as qil_inner(phi, qil_apply(W, psi)).
+ * (W, psi) pass the checks of qil_apply; phi is checked against psi as in qil_inner.                       */
+QIL_API int qil_apply_inner(const qil_mps* phi, const qil_mpo* W, const qil_mps* psi, double* out);
+/* norm(W psi) without materialising W psi: the same number as qil_norm(qil_apply(W, psi))
+ * (without amplitude, as qil_norm / mps.jl:754-771).  (W, psi) pass the checks of qil_apply.              */
+QIL_API int qil_apply_norm(const qil_mpo* W, const qil_mps* psi, double* out);
+
 /* ------------------------------------------------------------------ truncation (K1, K2) */
 /* canonicalize!(psi, direction; center, cutoff=1e-12, maxdim) src/mps.jl:787-847.
  * center = 0 selects the default (N for :right, 1 for :left); 1-based otherwise.    */

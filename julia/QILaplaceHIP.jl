@@ -7,7 +7,7 @@
 module QILaplaceHIP
 
 using ITensors
-import ITensors: apply
+import ITensors: apply, inner
 import Base: *, getindex, length
 import LinearAlgebra: norm
 import ..Mps
@@ -18,7 +18,7 @@ using ..ApplyMPO: _as_single_site_mpo
 
 export DeviceMPS, DeviceMPO, to_device, to_host, signal_mps_device, marginal, mps_block, apply_compress,
     compress_mpo!, build_dt_mpo_batch, build_qft_mpo_device, build_zt_qft_chain_device, apply_coefficient_sweep, apply!, rsvd_device, svd_device,
-    Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items
+    Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm
 
 const LIB = get(ENV, "QILHIP_LIB", "libqilhip.so")
 
@@ -210,6 +210,32 @@ end
 function norm(psi::DeviceMPS)                                                                      # mps.jl:754
     v = Ref{Cdouble}(0)
     check(ccall((:qil_norm, LIB), Cint, (Ptr{Cvoid}, Ref{Cdouble}), psi.h, v))
+    return v[]
+end
+# overlaps (ITensors' inner on device chains; amplitudes included): Float64 when every operand is real, ComplexF64 otherwise
+function _is_complex(x::Union{DeviceMPS,DeviceMPO})
+    d = Ref{Cint}(0)
+    if x isa DeviceMPS
+        check(ccall((:qil_mps_dtype, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}), x.h, d))
+    else
+        check(ccall((:qil_mpo_dtype, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}), x.h, d))
+    end
+    return d[] == 1
+end
+_overlap_value(v::Vector{Float64}, xs...) = any(_is_complex, xs) ? ComplexF64(v[1], v[2]) : v[1]
+function inner(phi::DeviceMPS, psi::DeviceMPS)
+    v = zeros(Float64, 2)
+    check(ccall((:qil_inner, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cdouble}), phi.h, psi.h, v))
+    return _overlap_value(v, phi, psi)
+end
+function inner(phi::DeviceMPS, W::DeviceMPO, psi::DeviceMPS)                   # <phi|W psi>, W psi never formed
+    v = zeros(Float64, 2)
+    check(ccall((:qil_apply_inner, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cdouble}), phi.h, W.h, psi.h, v))
+    return _overlap_value(v, phi, W, psi)
+end
+function apply_norm(W::DeviceMPO, psi::DeviceMPS)                              # norm(W * psi) without the product
+    v = Ref{Cdouble}(0)
+    check(ccall((:qil_apply_norm, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Cdouble}), W.h, psi.h, v))
     return v[]
 end
 function mps_to_vector(psi::DeviceMPS; reverse::Bool=false)                                        # mps.jl:716

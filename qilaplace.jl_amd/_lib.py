@@ -117,6 +117,9 @@ PROTOTYPES = {
     "qil_mps_to_vector": [_vp, _int, _vp],
     "qil_mps_block": [_vp, _pu8, _int, _vp],
     "qil_norm": [_vp, _pdbl],
+    "qil_inner": [_vp, _vp, _pdbl],
+    "qil_apply_inner": [_vp, _vp, _vp, _pdbl],
+    "qil_apply_norm": [_vp, _vp, _pdbl],
     "qil_canonicalize": [_vp, _int, _i64, _dbl, _i64],
     "qil_compress": [_vp, _i64, _dbl, _int],
     "qil_mpo_compress": [_vp, _int, _dbl, _i64],

@@ -336,6 +336,8 @@ int launch_apply(const qil_mpo* W, const qil_mps* psi, qil_mps* out) {
 
 }  // namespace
 
+int qil_check_apply_operands(const qil_mpo* W, const qil_mps* psi) { return check_apply_operands(W, psi); }
+
 extern "C" int qil_apply_into(const qil_mpo* W, const qil_mps* psi, qil_mps* out) {
     QIL_TRY(check_apply_operands(W, psi));
     QIL_REQUIRE(out, QIL_EINVAL_ARG, "qil_apply_into: null out");

@@ -1,0 +1,440 @@
+// Overlaps: <phi|psi> (qil_inner), <phi|W psi> (qil_apply_inner) and norm(W psi) (qil_apply_norm), none of which forms a
+// product or a dense vector.  Every call walks the chain left to right carrying one environment tensor (column-major, the
+// boundary's convention) on the device; nothing crosses to the host between sites and the one value is read back at the end.
+//
+//   qil_inner        E[phi, psi]:            E' = A_phi^H (E A_psi)                         (GEMM route, any bonds)
+//                                            the same contraction in ONE launch, E in LDS   (chain route, bonds <= 16)
+//   qil_apply_inner  E[phi, a, psi]:         T1 = E A_psi, T2_beta = T1_beta W, E' = A_phi^H T2
+//   qil_apply_norm   E[psi', a', a, psi]:    ket A, ket W, bra conj(W), bra conj(A)
+//
+// Mixed dtypes contract in c64; a real operand is widened once per site into a scratch block.
+#include "qil_internal.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+
+namespace {
+
+struct c64 {
+    double re, im;
+};
+
+__device__ __forceinline__ double cmul_add(double acc, double a, double b) { return fma(a, b, acc); }
+__device__ __forceinline__ c64 cmul_add(c64 acc, c64 a, c64 b) {
+    acc.re = fma(a.re, b.re, acc.re);
+    acc.re = fma(-a.im, b.im, acc.re);
+    acc.im = fma(a.re, b.im, acc.im);
+    acc.im = fma(a.im, b.re, acc.im);
+    return acc;
+}
+__device__ __forceinline__ c64 cmul_add(c64 acc, c64 a, double b) {
+    acc.re = fma(a.re, b, acc.re);
+    acc.im = fma(a.im, b, acc.im);
+    return acc;
+}
+__device__ __forceinline__ c64 cmul_add(c64 acc, double a, c64 b) {
+    acc.re = fma(a, b.re, acc.re);
+    acc.im = fma(a, b.im, acc.im);
+    return acc;
+}
+__device__ __forceinline__ double conj_t(double v) { return v; }
+__device__ __forceinline__ c64 conj_t(c64 v) { return c64{v.re, -v.im}; }
+__device__ __forceinline__ c64 to_c64(double v) { return c64{v, 0.0}; }
+__device__ __forceinline__ c64 to_c64(c64 v) { return v; }
+template <class TD>
+__device__ __forceinline__ TD cast_elem(double v);
+template <>
+__device__ __forceinline__ double cast_elem<double>(double v) { return v; }
+template <>
+__device__ __forceinline__ c64 cast_elem<c64>(double v) { return c64{v, 0.0}; }
+template <class TD>
+__device__ __forceinline__ TD cast_elem(c64 v) { return v; }
+
+// ---- small helpers ---------------------------------------------------------------------------------------------
+// p[0] = 1 (the left boundary of every environment; a kernel, so the chain starts without an upload)
+template <class T>
+__global__ void set_one(T* __restrict__ p) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) p[0] = cast_elem<T>(1.0);
+}
+__global__ void widen_f64(const double* __restrict__ src, c64* __restrict__ dst, long long n) {
+    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x)
+        dst[t] = c64{src[t], 0.0};
+}
+// W[a, s_in, s_out, b] -> Wr[a, s_out, s_in, b] (optionally widened): the bra side of norm(W psi) contracts (a', s_out), which
+// are then adjacent, and (s_in, b') become the columns
+template <class TS, class TD>
+__global__ void mpo_swap_phys(const TS* __restrict__ W, TD* __restrict__ Wr, int Dl, int Dr) {
+    const long long total = 4LL * Dl * Dr;
+    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
+        const int a = (int)(t % Dl);
+        long long u = t / Dl;
+        const int so = (int)(u & 1);
+        u >>= 1;
+        const int si = (int)(u & 1);
+        const long long b = u >> 1;
+        Wr[t] = cast_elem<TD>(W[a + (long long)Dl * (si + 2 * (so + 2 * b))]);
+    }
+}
+
+static unsigned grid_for(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, 4096)); }
+
+// a real operand of a complex contraction: widened into `buf` (elems entries), else used as it lies
+static int operand(qil_context* ctx, int dt, int src_dt, const void* src, long long elems, void* buf, const void** use) {
+    if (dt == QIL_C64 && src_dt == QIL_F64) {
+        hipLaunchKernelGGL(widen_f64, dim3(grid_for(elems)), dim3(256), 0, qil_stream(ctx), (const double*)src, (c64*)buf, elems);
+        QIL_HIP(hipGetLastError());
+        *use = buf;
+    } else {
+        *use = src;
+    }
+    return QIL_OK;
+}
+
+static int launch_set_one(qil_context* ctx, int dt, void* p) {
+    if (dt == QIL_C64) hipLaunchKernelGGL(set_one<c64>, dim3(1), dim3(64), 0, qil_stream(ctx), (c64*)p);
+    else hipLaunchKernelGGL(set_one<double>, dim3(1), dim3(64), 0, qil_stream(ctx), (double*)p);
+    QIL_HIP(hipGetLastError());
+    return QIL_OK;
+}
+
+// the batched product in grid-sized pieces (the batch is the grid's y dimension)
+static int gemm_batched_all(qil_context* ctx, int dt, int opA, int opB, int64_t m, int64_t n, int64_t k, const void* A, int64_t lda,
+                            const void* B, int64_t ldb, void* C, int64_t ldc, int64_t count, int64_t a_bs, int64_t b_bs, int64_t c_bs) {
+    const size_t e = qil_elem_size(dt);
+    for (int64_t b0 = 0; b0 < count; b0 += 65535) {
+        qil_gemm_batch bt;
+        bt.count = std::min<int64_t>(65535, count - b0);
+        bt.a_bs = a_bs;
+        bt.b_bs = b_bs;
+        bt.c_bs = c_bs;
+        QIL_TRY(qil_dev_gemm_batched(ctx, dt, opA, opB, m, n, k, static_cast<const char*>(A) + (size_t)(b0 * a_bs) * e, lda,
+                                     static_cast<const char*>(B) + (size_t)(b0 * b_bs) * e, ldb,
+                                     static_cast<char*>(C) + (size_t)(b0 * c_bs) * e, ldc, &bt));
+    }
+    return QIL_OK;
+}
+
+// the environment's last 1 x 1 value to the host
+static int read_scalar(qil_context* ctx, int dt, const void* E, double h[2]) {
+    h[0] = h[1] = 0.0;
+    return qil_read_back(ctx, h, E, qil_elem_size(dt));
+}
+
+// ---- <phi|psi>: chain route -------------------------------------------------------------------------------------
+struct InnerSite {
+    const void* P;   // phi site  (pl, 2, pr)
+    const void* S;   // psi site  (sl, 2, sr)
+    int pl, pr, sl, sr;
+};
+constexpr int kChainMax = 64;        // largest bond of either chain the one-workgroup route holds
+constexpr int kChainThreads = 512;
+constexpr int kChainPer = kChainMax * kChainMax / kChainThreads;   // entries of E' per thread (registers)
+
+// One workgroup walks every site.  E (pl x sl) and one physical slice of T = E A_psi (pl x sr) live in LDS; E' (pr x sr)
+// accumulates in registers over the two slices and replaces E at the end of the site:
+//   T_s[p, b]   = sum_k E[p, k] A_psi[k, s, b]
+//   E'[q, b]   += sum_p conj(A_phi[p, s, q]) T_s[p, b]
+template <class TP, class TS, class TE>
+__global__ __launch_bounds__(kChainThreads) void inner_chain(const InnerSite* __restrict__ sites, int n, double amplitude,
+                                                             c64* __restrict__ out) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    TE* E = reinterpret_cast<TE*>(lds_raw);
+    TE* T = E + kChainMax * kChainMax;
+    if (threadIdx.x == 0) E[0] = cast_elem<TE>(1.0);
+    __syncthreads();
+    for (int i = 0; i < n; ++i) {
+        const InnerSite S = sites[i];
+        const TP* __restrict__ P = static_cast<const TP*>(S.P);
+        const TS* __restrict__ A = static_cast<const TS*>(S.S);
+        TE acc[kChainPer];
+#pragma unroll
+        for (int r = 0; r < kChainPer; ++r) acc[r] = TE{};
+        const int nT = S.pl * S.sr, nE = S.pr * S.sr;
+        for (int s = 0; s < 2; ++s) {
+            for (int t = threadIdx.x; t < nT; t += kChainThreads) {
+                const int p = t % S.pl, b = t / S.pl;
+                const TS* col = A + (long long)S.sl * (s + 2 * b);
+                TE v{};
+                for (int k = 0; k < S.sl; ++k) v = cmul_add(v, E[p + S.pl * k], col[k]);
+                T[t] = v;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < kChainPer; ++r) {
+                const int t = threadIdx.x + r * kChainThreads;
+                if (t < nE) {
+                    const int q = t % S.pr, b = t / S.pr;
+                    const TP* pc = P + (long long)S.pl * (s + 2 * q);
+                    const TE* tc = T + S.pl * b;
+                    TE v = acc[r];
+                    for (int p = 0; p < S.pl; ++p) v = cmul_add(v, conj_t(pc[p]), tc[p]);
+                    acc[r] = v;
+                }
+            }
+            // slice 0: T is overwritten next; slice 1: every read of E (by the T_1 products) happened before the barrier above
+            if (s == 0) __syncthreads();
+        }
+#pragma unroll
+        for (int r = 0; r < kChainPer; ++r) {
+            const int t = threadIdx.x + r * kChainThreads;
+            if (t < nE) E[t] = acc[r];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const c64 r = to_c64(E[0]);
+        out[0] = c64{r.re * amplitude, r.im * amplitude};
+    }
+}
+
+template <class TP, class TS, class TE>
+static int launch_inner_chain(qil_context* ctx, const InnerSite* dtab, int n, double amp, c64* dout) {
+    static qil_lds_grant grant;
+    const size_t lds = 2 * (size_t)kChainMax * kChainMax * sizeof(TE);
+    QIL_HIP(grant.ensure(ctx->device, reinterpret_cast<const void*>(&inner_chain<TP, TS, TE>), lds));
+    hipLaunchKernelGGL((inner_chain<TP, TS, TE>), dim3(1), dim3(kChainThreads), lds, qil_stream(ctx), dtab, n, amp, dout);
+    QIL_HIP(hipGetLastError());
+    return QIL_OK;
+}
+
+// Crossover between the routes (bonds of both chains at most this: one launch).  Measured at n = 30 (f64 / c64, median of 10):
+// chi 16 chain 0.15 / 0.20 ms vs GEMM 0.25 / 0.35 ms, chi 24 0.34 / 0.51 vs 0.31 / 0.46, chi 64 3.3 / 6.4 vs 0.31 / 0.40 -- past
+// chi ~ 20 the one workgroup is bound by the arithmetic of ONE CU (2 chi^3 complex MACs per slice and site), not by launches.
+// QIL_INNER_ROUTE=chain / gemm forces one (read per call; the chain route only where its bonds fit).
+constexpr long long kChainAutoMax = 16;
+
+static int inner_chain_route(const qil_mps* phi, const qil_mps* psi, double h[2]) {
+    qil_context* ctx = psi->ctx;
+    const int64_t n = psi->n();
+    std::vector<InnerSite> tab((size_t)n);
+    for (int64_t i = 0; i < n; ++i)
+        tab[(size_t)i] = InnerSite{phi->site[(size_t)i], psi->site[(size_t)i], (int)phi->dims[(size_t)i], (int)phi->dims[(size_t)i + 1],
+                                   (int)psi->dims[(size_t)i], (int)psi->dims[(size_t)i + 1]};
+    void *pin = nullptr, *dtab = nullptr, *dout = nullptr;
+    int slot = 0;
+    QIL_TRY(qil_ctx_alloc(ctx, 16, &dout));
+    QIL_TRY(qil_ctx_desc_acquire(ctx, tab.size() * sizeof(InnerSite), &pin, &dtab, &slot));
+    memcpy(pin, tab.data(), tab.size() * sizeof(InnerSite));
+    QIL_HIP(hipMemcpyAsync(dtab, pin, tab.size() * sizeof(InnerSite), hipMemcpyHostToDevice, qil_stream(ctx)));
+    const double amp = phi->amplitude * psi->amplitude;
+    const bool pc = phi->dtype == QIL_C64, sc = psi->dtype == QIL_C64;
+    const InnerSite* t = static_cast<const InnerSite*>(dtab);
+    c64* o = static_cast<c64*>(dout);
+    if (pc && sc) QIL_TRY((launch_inner_chain<c64, c64, c64>(ctx, t, (int)n, amp, o)));
+    else if (pc) QIL_TRY((launch_inner_chain<c64, double, c64>(ctx, t, (int)n, amp, o)));
+    else if (sc) QIL_TRY((launch_inner_chain<double, c64, c64>(ctx, t, (int)n, amp, o)));
+    else QIL_TRY((launch_inner_chain<double, double, double>(ctx, t, (int)n, amp, o)));
+    QIL_TRY(qil_ctx_desc_commit(ctx, slot));
+    QIL_TRY(qil_read_back(ctx, h, dout, 16));
+    qil_ctx_free(ctx, dout);
+    return QIL_OK;
+}
+
+// ---- <phi|psi>: GEMM route --------------------------------------------------------------------------------------
+static int inner_gemm_route(const qil_mps* phi, const qil_mps* psi, double h[2]) {
+    qil_context* ctx = psi->ctx;
+    const int64_t n = psi->n();
+    const int dt = (phi->dtype == QIL_C64 || psi->dtype == QIL_C64) ? QIL_C64 : QIL_F64;
+    const size_t e = qil_elem_size(dt);
+    long long maxE = 1, maxT = 1, maxP = 1, maxS = 1;
+    for (int64_t i = 0; i < n; ++i) {
+        const long long pl = phi->dims[(size_t)i], pr = phi->dims[(size_t)i + 1];
+        const long long sl = psi->dims[(size_t)i], sr = psi->dims[(size_t)i + 1];
+        maxE = std::max(maxE, std::max(pl * sl, pr * sr));
+        maxT = std::max(maxT, pl * 2 * sr);
+        maxP = std::max(maxP, pl * 2 * pr);
+        maxS = std::max(maxS, sl * 2 * sr);
+    }
+    void *E = nullptr, *En = nullptr, *T = nullptr, *Pw = nullptr, *Sw = nullptr;
+    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxE * e, &E));
+    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxE * e, &En));
+    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxT * e, &T));
+    if (dt != phi->dtype) QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxP * e, &Pw));
+    if (dt != psi->dtype) QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxS * e, &Sw));
+    QIL_TRY(launch_set_one(ctx, dt, E));
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t pl = phi->dims[(size_t)i], pr = phi->dims[(size_t)i + 1];
+        const int64_t sl = psi->dims[(size_t)i], sr = psi->dims[(size_t)i + 1];
+        const void *Ap = nullptr, *As = nullptr;
+        QIL_TRY(operand(ctx, dt, phi->dtype, phi->site[(size_t)i], pl * 2 * pr, Pw, &Ap));
+        QIL_TRY(operand(ctx, dt, psi->dtype, psi->site[(size_t)i], sl * 2 * sr, Sw, &As));
+        // T (pl x 2sr) = E (pl x sl) * A_psi (sl x 2sr):  T[p, s, b]
+        QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, pl, 2 * sr, sl, E, pl, As, sl, T, pl));
+        // E' (pr x sr) = A_phi^H ((2pl) x pr)^H * T ((2pl) x sr)
+        QIL_TRY(qil_dev_gemm(ctx, dt, 2, 0, pr, sr, 2 * pl, Ap, 2 * pl, T, 2 * pl, En, pr));
+        std::swap(E, En);
+    }
+    QIL_TRY(read_scalar(ctx, dt, E, h));
+    const double amp = phi->amplitude * psi->amplitude;
+    h[0] *= amp;
+    h[1] *= amp;
+    qil_ctx_free(ctx, E);
+    qil_ctx_free(ctx, En);
+    qil_ctx_free(ctx, T);
+    if (Pw) qil_ctx_free(ctx, Pw);
+    if (Sw) qil_ctx_free(ctx, Sw);
+    return QIL_OK;
+}
+
+// phi against psi (or against the product W psi, which has psi's chain shape): same context, register kind, length, sites
+static int check_overlap_pair(const qil_mps* phi, const qil_mps* psi) {
+    QIL_REQUIRE(phi->ctx == psi->ctx, QIL_EINVAL_ARG, "inner: MPS belong to different contexts");
+    QIL_REQUIRE(phi->paired == psi->paired, QIL_EINVAL_ARG, "inner: cannot mix paired and single-register operands");
+    QIL_REQUIRE(phi->n() == psi->n(), QIL_EINVAL_LENGTH,
+                "inner: MPS must have the same number of sites. Found length(phi)=%lld, length(psi)=%lld",
+                (long long)phi->n(), (long long)psi->n());
+    QIL_REQUIRE(phi->site_ids == psi->site_ids, QIL_EINVAL_SITES, "inner: MPS must have the same site indices.");
+    return QIL_OK;
+}
+
+static long long max_bond(const qil_chain* c) {
+    long long m = 1;
+    for (int64_t d : c->dims) m = std::max<long long>(m, d);
+    return m;
+}
+
+}  // namespace
+
+extern "C" int qil_inner(const qil_mps* phi, const qil_mps* psi, double* out) {
+    QIL_REQUIRE(phi && psi && out, QIL_EINVAL_ARG, "inner: null argument");
+    QIL_TRY(check_overlap_pair(phi, psi));
+    qil_context* ctx = psi->ctx;
+    QIL_TRY(qil_ctx_activate(ctx));
+    qil_call_scope call_scope(ctx);
+    const char* route = getenv("QIL_INNER_ROUTE");
+    const long long mb = std::max(max_bond(phi), max_bond(psi));
+    const bool fits = mb <= kChainMax && (size_t)psi->n() * sizeof(InnerSite) <= qil_context::kDescSlotBytes;
+    bool chain = fits && mb <= kChainAutoMax;
+    if (route && !strcmp(route, "chain")) chain = fits;
+    else if (route && !strcmp(route, "gemm")) chain = false;
+    double h[2] = {0.0, 0.0};
+    QIL_TRY(chain ? inner_chain_route(phi, psi, h) : inner_gemm_route(phi, psi, h));
+    out[0] = h[0];
+    out[1] = h[1];
+    return QIL_OK;
+}
+
+// <phi|W psi>: E[p, a, s] (pl x Dl x sl) per site
+//   T1 ((pl Dl) x 2sr)      = E ((pl Dl) x sl) * A_psi (sl x 2sr)                    T1[p, a, s_in, beta]
+//   T2_beta (pl x 2Dr)      = T1_beta (pl x 2Dl) * W (2Dl x 2Dr)    (batch = beta)   T2[p, s_out, b, beta]
+//   E' (pr x Dr sr)         = A_phi^H (pr x 2pl) * T2 (2pl x Dr sr)                  E'[q, b, beta]
+extern "C" int qil_apply_inner(const qil_mps* phi, const qil_mpo* W, const qil_mps* psi, double* out) {
+    QIL_REQUIRE(phi && W && psi && out, QIL_EINVAL_ARG, "apply_inner: null argument");
+    QIL_TRY(qil_check_apply_operands(W, psi));
+    QIL_TRY(check_overlap_pair(phi, psi));
+    qil_context* ctx = psi->ctx;
+    QIL_TRY(qil_ctx_activate(ctx));
+    qil_call_scope call_scope(ctx);
+    const int64_t n = psi->n();
+    const int dt = (phi->dtype == QIL_C64 || W->dtype == QIL_C64 || psi->dtype == QIL_C64) ? QIL_C64 : QIL_F64;
+    const size_t e = qil_elem_size(dt);
+    long long maxE = 1, maxT1 = 1, maxT2 = 1, maxP = 1, maxS = 1, maxW = 1;
+    for (int64_t i = 0; i < n; ++i) {
+        const long long pl = phi->dims[(size_t)i], pr = phi->dims[(size_t)i + 1];
+        const long long sl = psi->dims[(size_t)i], sr = psi->dims[(size_t)i + 1];
+        const long long Dl = W->dims[(size_t)i], Dr = W->dims[(size_t)i + 1];
+        maxE = std::max(maxE, std::max(pl * Dl * sl, pr * Dr * sr));
+        maxT1 = std::max(maxT1, pl * Dl * 2 * sr);
+        maxT2 = std::max(maxT2, pl * 2 * Dr * sr);
+        maxP = std::max(maxP, pl * 2 * pr);
+        maxS = std::max(maxS, sl * 2 * sr);
+        maxW = std::max(maxW, Dl * 4 * Dr);
+    }
+    void *E = nullptr, *En = nullptr, *T1 = nullptr, *T2 = nullptr, *Pw = nullptr, *Sw = nullptr, *Ww = nullptr;
+    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxE * e, &E));
+    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxE * e, &En));
+    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxT1 * e, &T1));
+    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxT2 * e, &T2));
+    if (dt != phi->dtype) QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxP * e, &Pw));
+    if (dt != psi->dtype) QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxS * e, &Sw));
+    if (dt != W->dtype) QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxW * e, &Ww));
+    QIL_TRY(launch_set_one(ctx, dt, E));
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t pl = phi->dims[(size_t)i], pr = phi->dims[(size_t)i + 1];
+        const int64_t sl = psi->dims[(size_t)i], sr = psi->dims[(size_t)i + 1];
+        const int64_t Dl = W->dims[(size_t)i], Dr = W->dims[(size_t)i + 1];
+        const void *Ap = nullptr, *As = nullptr, *Wd = nullptr;
+        QIL_TRY(operand(ctx, dt, phi->dtype, phi->site[(size_t)i], pl * 2 * pr, Pw, &Ap));
+        QIL_TRY(operand(ctx, dt, psi->dtype, psi->site[(size_t)i], sl * 2 * sr, Sw, &As));
+        QIL_TRY(operand(ctx, dt, W->dtype, W->site[(size_t)i], Dl * 4 * Dr, Ww, &Wd));
+        QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, pl * Dl, 2 * sr, sl, E, pl * Dl, As, sl, T1, pl * Dl));
+        QIL_TRY(gemm_batched_all(ctx, dt, 0, 0, pl, 2 * Dr, 2 * Dl, T1, pl, Wd, 2 * Dl, T2, pl, sr, pl * 2 * Dl, 0, pl * 2 * Dr));
+        QIL_TRY(qil_dev_gemm(ctx, dt, 2, 0, pr, Dr * sr, 2 * pl, Ap, 2 * pl, T2, 2 * pl, En, pr));
+        std::swap(E, En);
+    }
+    double h[2];
+    QIL_TRY(read_scalar(ctx, dt, E, h));
+    const double amp = phi->amplitude * psi->amplitude;
+    out[0] = h[0] * amp;
+    out[1] = h[1] * amp;
+    for (void* p : {E, En, T1, T2, Pw, Sw, Ww})
+        if (p) qil_ctx_free(ctx, p);
+    return QIL_OK;
+}
+
+// norm(W psi): E[s', a', a, s] (sl x Dl x Dl x sl) per site, two buffers in ping-pong (X: E, T2, E'; Y: T1, T3)
+//   T1 ((sl Dl Dl) x 2sr)   = E * A_psi                                                T1[s', a', a, s_in, beta]
+//   T2_beta ((sl Dl) x 2Dr) = T1_beta ((sl Dl) x 2Dl) * W (2Dl x 2Dr)   (batch = beta) T2[s', a', s_out, b, beta]
+//   T3_bb (sl x 2Dr)        = T2_bb (sl x 2Dl) * conj(Wr) (2Dl x 2Dr)   (batch = (b, beta), Wr = W with s_in <-> s_out)
+//                                                                                      T3[s', s_in', b', b, beta]
+//   E' (sr x Dr Dr sr)      = A_psi^H (sr x 2sl) * T3 (2sl x Dr Dr sr)                 E'[beta', b', b, beta]
+extern "C" int qil_apply_norm(const qil_mpo* W, const qil_mps* psi, double* out) {
+    QIL_REQUIRE(W && psi && out, QIL_EINVAL_ARG, "apply_norm: null argument");
+    QIL_TRY(qil_check_apply_operands(W, psi));
+    qil_context* ctx = psi->ctx;
+    QIL_TRY(qil_ctx_activate(ctx));
+    qil_call_scope call_scope(ctx);
+    const int64_t n = psi->n();
+    const int dt = (W->dtype == QIL_C64 || psi->dtype == QIL_C64) ? QIL_C64 : QIL_F64;
+    const size_t e = qil_elem_size(dt);
+    long long maxX = 1, maxY = 1, maxS = 1, maxW = 1;
+    for (int64_t i = 0; i < n; ++i) {
+        const long long sl = psi->dims[(size_t)i], sr = psi->dims[(size_t)i + 1];
+        const long long Dl = W->dims[(size_t)i], Dr = W->dims[(size_t)i + 1];
+        maxX = std::max({maxX, sl * Dl * Dl * sl, sl * Dl * 2 * Dr * sr, sr * Dr * Dr * sr});
+        maxY = std::max({maxY, sl * Dl * Dl * 2 * sr, sl * 2 * Dr * Dr * sr});
+        maxS = std::max(maxS, sl * 2 * sr);
+        maxW = std::max(maxW, Dl * 4 * Dr);
+    }
+    void *X = nullptr, *Y = nullptr, *Sw = nullptr, *Ww = nullptr, *Wr = nullptr;
+    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxX * e, &X));
+    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxY * e, &Y));
+    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxW * e, &Wr));
+    if (dt != psi->dtype) QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxS * e, &Sw));
+    if (dt != W->dtype) QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxW * e, &Ww));
+    QIL_TRY(launch_set_one(ctx, dt, X));
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t sl = psi->dims[(size_t)i], sr = psi->dims[(size_t)i + 1];
+        const int64_t Dl = W->dims[(size_t)i], Dr = W->dims[(size_t)i + 1];
+        const void *As = nullptr, *Wd = nullptr;
+        QIL_TRY(operand(ctx, dt, psi->dtype, psi->site[(size_t)i], sl * 2 * sr, Sw, &As));
+        QIL_TRY(operand(ctx, dt, W->dtype, W->site[(size_t)i], Dl * 4 * Dr, Ww, &Wd));
+        {
+            const unsigned g = grid_for(Dl * 4 * Dr);
+            const void* Ws = W->site[(size_t)i];
+            if (dt == QIL_F64)
+                hipLaunchKernelGGL((mpo_swap_phys<double, double>), dim3(g), dim3(256), 0, qil_stream(ctx), (const double*)Ws, (double*)Wr,
+                                   (int)Dl, (int)Dr);
+            else if (W->dtype == QIL_C64)
+                hipLaunchKernelGGL((mpo_swap_phys<c64, c64>), dim3(g), dim3(256), 0, qil_stream(ctx), (const c64*)Ws, (c64*)Wr, (int)Dl,
+                                   (int)Dr);
+            else
+                hipLaunchKernelGGL((mpo_swap_phys<double, c64>), dim3(g), dim3(256), 0, qil_stream(ctx), (const double*)Ws, (c64*)Wr,
+                                   (int)Dl, (int)Dr);
+            QIL_HIP(hipGetLastError());
+        }
+        const int64_t rE = sl * Dl * Dl;
+        QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, rE, 2 * sr, sl, X, rE, As, sl, Y, rE));
+        QIL_TRY(gemm_batched_all(ctx, dt, 0, 0, sl * Dl, 2 * Dr, 2 * Dl, Y, sl * Dl, Wd, 2 * Dl, X, sl * Dl, sr, rE * 2, 0,
+                                 sl * Dl * 2 * Dr));
+        QIL_TRY(gemm_batched_all(ctx, dt, 0, 3, sl, 2 * Dr, 2 * Dl, X, sl, Wr, 2 * Dl, Y, sl, Dr * sr, sl * 2 * Dl, 0, sl * 2 * Dr));
+        QIL_TRY(qil_dev_gemm(ctx, dt, 2, 0, sr, Dr * Dr * sr, 2 * sl, As, 2 * sl, Y, 2 * sl, X, sr));
+    }
+    double h[2];
+    QIL_TRY(read_scalar(ctx, dt, X, h));
+    *out = sqrt(sqrt(h[0] * h[0] + h[1] * h[1]));
+    for (void* p : {X, Y, Sw, Ww, Wr})
+        if (p) qil_ctx_free(ctx, p);
+    return QIL_OK;
+}

@@ -4,6 +4,7 @@
   coefficient        src/mps.jl:669-693 (parsers :616-645)
   mps_to_vector      src/mps.jl:716-743
   norm               src/mps.jl:754-771
+  inner              ITensors' inner(phi, psi) / inner(phi, W, psi) on device chains (no reference counterpart)
   canonicalize       src/mps.jl:787-847, 866-901   (Julia: canonicalize!)
   compress           src/mps.jl:913-999            (Julia: compress!)
   signal_mps         src/signals/SignalConverters.jl:228-233
@@ -285,6 +286,83 @@ def norm(psi) -> float:
     v = C.c_double()
     L.check(L.lib.qil_norm(psi.handle, C.byref(v)))
     return v.value
+
+
+# ---------------------------------------------------------------- overlaps
+def _require_mps(x, what):
+    if not isinstance(x, SignalMPS):
+        raise TypeError(f"{what}: unsupported operand types")
+
+
+def _require_operator(W, psi):
+    """The operand checks of `apply`, made before any native call (the register kind is the container class's)."""
+    if not (isinstance(W, SingleSiteMPO) and isinstance(psi, SignalMPS)):
+        raise TypeError("apply: unsupported operand types")
+    if W._paired() != psi._paired():
+        raise TypeError("apply: PairedSiteMPO acts on ZTMPS, SingleSiteMPO on SignalMPS")
+
+
+def _scalar(v, *operands):
+    """float when every operand is real, complex otherwise (the rule of coefficient_batch)."""
+    z = complex(v[0], v[1])
+    return z if any(x.dtype == np.complex128 for x in operands) else z.real
+
+
+def inner(phi, *args):
+    """inner(phi, psi) = <phi|psi> and inner(phi, W, psi) = <phi|W psi>, amplitudes included: the same numbers as
+    np.vdot(mps_to_vector(phi), mps_to_vector(psi)) and inner(phi, W * psi), without a dense vector or the product.
+    float when every operand is real, complex otherwise."""
+    v = (C.c_double * 2)()
+    if len(args) == 1:
+        (psi,) = args
+        _require_mps(phi, "inner")
+        _require_mps(psi, "inner")
+        L.check(L.lib.qil_inner(phi.handle, psi.handle, v))
+        return _scalar(v, phi, psi)
+    if len(args) == 2:
+        W, psi = args
+        _require_mps(phi, "inner")
+        _require_operator(W, psi)
+        L.check(L.lib.qil_apply_inner(phi.handle, W.handle, psi.handle, v))
+        return _scalar(v, phi, W, psi)
+    raise TypeError(f"inner: expected inner(phi, psi) or inner(phi, W, psi), got {1 + len(args)} arguments")
+
+
+def apply_norm(W, psi) -> float:
+    """norm(W * psi) without the product (without amplitude, as `norm`)."""
+    _require_operator(W, psi)
+    v = C.c_double()
+    L.check(L.lib.qil_apply_norm(W.handle, psi.handle, C.byref(v)))
+    return v.value
+
+
+def _distance(nphi2, npsi2, overlap):
+    return float(np.sqrt(max(0.0, nphi2 + npsi2 - 2.0 * np.real(overlap))))
+
+
+def distance(phi, psi) -> float:
+    """||vec(phi) - vec(psi)||, amplitudes included, as sqrt(max(0, |phi|^2 + |psi|^2 - 2 Re<phi|psi>)).
+
+    The expansion has a floor: the squared distance carries an absolute error of a few eps * (|phi|^2 + |psi|^2), so
+    relative distances below about 1e-7 are not resolved (they come out as that floor or as 0)."""
+    _require_mps(phi, "inner")
+    _require_mps(psi, "inner")
+    npsi = psi.amplitude * norm(psi)
+    nphi = phi.amplitude * norm(phi)
+    return _distance(nphi * nphi, npsi * npsi, inner(phi, psi))
+
+
+def apply_distance(phi, W, psi) -> float:
+    """||vec(phi) - vec(W psi)||, amplitudes included, without the product: sqrt(max(0, |phi|^2 + |W psi|^2 -
+    2 Re<phi|W psi>)) from `norm`, `apply_norm` and `inner(phi, W, psi)`.
+
+    The same floor as `distance`: the squared distance carries an absolute error of a few eps * (|phi|^2 + |W psi|^2),
+    so relative distances below about 1e-7 are not resolved."""
+    _require_mps(phi, "inner")
+    _require_operator(W, psi)
+    nphi = phi.amplitude * norm(phi)
+    nwpsi = psi.amplitude * apply_norm(W, psi)
+    return _distance(nphi * nphi, nwpsi * nwpsi, inner(phi, W, psi))
 
 
 # ---------------------------------------------------------------- truncation
