@@ -19,12 +19,11 @@
 //     block -> (site, tile) map), so small-chi applies are not launch-bound and large ones
 //     keep > 2000 independent workgroups per site in flight over the 256 CUs.
 #include "qil_internal.h"
+#include "qil_device_utils.h"
 
 namespace {
 
-struct c64 {
-    double re, im;
-};
+using namespace qil_dev;
 
 struct ApplySite {
     const void* W;

@@ -1,6 +1,7 @@
-// Device-side helpers shared by the dense linear algebra (qil_linalg.hip) and the batched MPO builder
-// (qil_build.hip): complex arithmetic, DPP cross-lane sums, Jacobi rotations and the in-workgroup
-// one-sided Jacobi sweep loop.  gfx950 only.
+// Device-side helpers shared by the dense linear algebra (qil_linalg.hip), the MPO builders (qil_build*.hip), the
+// apply (qil_apply.hip), the read-outs (qil_readout.hip), the overlaps (qil_inner.hip) and the truncation
+// (qil_truncate.hip): the complex scalar type and its arithmetic, DPP cross-lane sums, Jacobi rotations and the
+// in-workgroup one-sided Jacobi sweep loop.  gfx950 only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -29,6 +30,34 @@ __device__ __forceinline__ double sub_t(double a, double b) { return a - b; }
 __device__ __forceinline__ c64 sub_t(c64 a, c64 b) { return c64{a.re - b.re, a.im - b.im}; }
 __device__ __forceinline__ double add_t(double a, double b) { return a + b; }
 __device__ __forceinline__ c64 add_t(c64 a, c64 b) { return c64{a.re + b.re, a.im + b.im}; }
+__device__ __forceinline__ double cmul_add(double acc, double a, double b) { return fma(a, b, acc); }
+__device__ __forceinline__ c64 cmul_add(c64 acc, c64 a, c64 b) {
+    acc.re = fma(a.re, b.re, acc.re);
+    acc.re = fma(-a.im, b.im, acc.re);
+    acc.im = fma(a.re, b.im, acc.im);
+    acc.im = fma(a.im, b.re, acc.im);
+    return acc;
+}
+__device__ __forceinline__ c64 cmul_add(c64 acc, c64 a, double b) {
+    acc.re = fma(a.re, b, acc.re);
+    acc.im = fma(a.im, b, acc.im);
+    return acc;
+}
+__device__ __forceinline__ c64 cmul_add(c64 acc, double a, c64 b) {
+    acc.re = fma(a, b.re, acc.re);
+    acc.im = fma(a, b.im, acc.im);
+    return acc;
+}
+__device__ __forceinline__ c64 to_c64(double v) { return c64{v, 0.0}; }
+__device__ __forceinline__ c64 to_c64(c64 v) { return v; }
+template <class TD>
+__device__ __forceinline__ TD cast_elem(double v);
+template <>
+__device__ __forceinline__ double cast_elem<double>(double v) { return v; }
+template <>
+__device__ __forceinline__ c64 cast_elem<c64>(double v) { return c64{v, 0.0}; }
+template <class TD>
+__device__ __forceinline__ TD cast_elem(c64 v) { return v; }
 
 // ------------------------------------------------------------------ block reductions
 // Cross-lane sums on the DPP path (no LDS crossbar): quad_perm butterflies inside each quad, then

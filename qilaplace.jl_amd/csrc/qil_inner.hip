@@ -1,14 +1,17 @@
-// Overlaps: <phi|psi> (qil_inner), <phi|W psi> (qil_apply_inner) and norm(W psi) (qil_apply_norm), none of which forms a
-// product or a dense vector.  Every call walks the chain left to right carrying one environment tensor (column-major, the
-// boundary's convention) on the device; nothing crosses to the host between sites and the one value is read back at the end.
+// Overlaps: <phi|psi> (qil_inner), norm(psi) (qil_norm), <phi|W psi> (qil_apply_inner) and norm(W psi) (qil_apply_norm),
+// none of which forms a product or a dense vector.  Every call walks the chain left to right carrying one environment
+// tensor (column-major, the boundary's convention) on the device; nothing crosses to the host between sites and the one
+// value is read back at the end.
 //
 //   qil_inner        E[phi, psi]:            E' = A_phi^H (E A_psi)                         (GEMM route, any bonds)
 //                                            the same contraction in ONE launch, E in LDS   (chain route, bonds <= 16)
+//   qil_norm         E[psi, psi]:            the GEMM route of qil_inner with phi = psi
 //   qil_apply_inner  E[phi, a, psi]:         T1 = E A_psi, T2_beta = T1_beta W, E' = A_phi^H T2
 //   qil_apply_norm   E[psi', a', a, psi]:    ket A, ket W, bra conj(W), bra conj(A)
 //
 // Mixed dtypes contract in c64; a real operand is widened once per site into a scratch block.
 #include "qil_internal.h"
+#include "qil_device_utils.h"
 
 #include <algorithm>
 #include <cmath>
@@ -16,40 +19,7 @@
 
 namespace {
 
-struct c64 {
-    double re, im;
-};
-
-__device__ __forceinline__ double cmul_add(double acc, double a, double b) { return fma(a, b, acc); }
-__device__ __forceinline__ c64 cmul_add(c64 acc, c64 a, c64 b) {
-    acc.re = fma(a.re, b.re, acc.re);
-    acc.re = fma(-a.im, b.im, acc.re);
-    acc.im = fma(a.re, b.im, acc.im);
-    acc.im = fma(a.im, b.re, acc.im);
-    return acc;
-}
-__device__ __forceinline__ c64 cmul_add(c64 acc, c64 a, double b) {
-    acc.re = fma(a.re, b, acc.re);
-    acc.im = fma(a.im, b, acc.im);
-    return acc;
-}
-__device__ __forceinline__ c64 cmul_add(c64 acc, double a, c64 b) {
-    acc.re = fma(a, b.re, acc.re);
-    acc.im = fma(a, b.im, acc.im);
-    return acc;
-}
-__device__ __forceinline__ double conj_t(double v) { return v; }
-__device__ __forceinline__ c64 conj_t(c64 v) { return c64{v.re, -v.im}; }
-__device__ __forceinline__ c64 to_c64(double v) { return c64{v, 0.0}; }
-__device__ __forceinline__ c64 to_c64(c64 v) { return v; }
-template <class TD>
-__device__ __forceinline__ TD cast_elem(double v);
-template <>
-__device__ __forceinline__ double cast_elem<double>(double v) { return v; }
-template <>
-__device__ __forceinline__ c64 cast_elem<c64>(double v) { return c64{v, 0.0}; }
-template <class TD>
-__device__ __forceinline__ TD cast_elem(c64 v) { return v; }
+using namespace qil_dev;
 
 // ---- small helpers ---------------------------------------------------------------------------------------------
 // p[0] = 1 (the left boundary of every environment; a kernel, so the chain starts without an upload)
@@ -232,7 +202,8 @@ static int inner_chain_route(const qil_mps* phi, const qil_mps* psi, double h[2]
 }
 
 // ---- <phi|psi>: GEMM route --------------------------------------------------------------------------------------
-static int inner_gemm_route(const qil_mps* phi, const qil_mps* psi, double h[2]) {
+// the contraction alone: the amplitudes are not applied (qil_inner scales, qil_norm takes phi = psi)
+static int inner_gemm_raw(const qil_mps* phi, const qil_mps* psi, double h[2]) {
     qil_context* ctx = psi->ctx;
     const int64_t n = psi->n();
     const int dt = (phi->dtype == QIL_C64 || psi->dtype == QIL_C64) ? QIL_C64 : QIL_F64;
@@ -266,9 +237,6 @@ static int inner_gemm_route(const qil_mps* phi, const qil_mps* psi, double h[2])
         std::swap(E, En);
     }
     QIL_TRY(read_scalar(ctx, dt, E, h));
-    const double amp = phi->amplitude * psi->amplitude;
-    h[0] *= amp;
-    h[1] *= amp;
     qil_ctx_free(ctx, E);
     qil_ctx_free(ctx, En);
     qil_ctx_free(ctx, T);
@@ -309,9 +277,28 @@ extern "C" int qil_inner(const qil_mps* phi, const qil_mps* psi, double* out) {
     if (route && !strcmp(route, "chain")) chain = fits;
     else if (route && !strcmp(route, "gemm")) chain = false;
     double h[2] = {0.0, 0.0};
-    QIL_TRY(chain ? inner_chain_route(phi, psi, h) : inner_gemm_route(phi, psi, h));
+    if (chain) {
+        QIL_TRY(inner_chain_route(phi, psi, h));   // the amplitudes are applied in the kernel
+    } else {
+        QIL_TRY(inner_gemm_raw(phi, psi, h));
+        const double amp = phi->amplitude * psi->amplitude;
+        h[0] *= amp;
+        h[1] *= amp;
+    }
     out[0] = h[0];
     out[1] = h[1];
+    return QIL_OK;
+}
+
+// norm(psi) = sqrt(|<psi|psi>|) without the amplitude (mps.jl:754-771), on the GEMM route
+extern "C" int qil_norm(const qil_mps* psi, double* out) {
+    QIL_REQUIRE(psi && out, QIL_EINVAL_ARG, "norm: null argument");
+    qil_context* ctx = psi->ctx;
+    QIL_TRY(qil_ctx_activate(ctx));
+    qil_call_scope call_scope(ctx);
+    double h[2] = {0.0, 0.0};
+    QIL_TRY(inner_gemm_raw(psi, psi, h));
+    *out = sqrt(sqrt(h[0] * h[0] + h[1] * h[1]));
     return QIL_OK;
 }
 

@@ -380,13 +380,12 @@ int gemm_launch(qil_context* ctx, long long m, long long n, long long k, const T
         splits = (int)std::min<long long>(std::min<long long>(k / 256, 512 / (tiles * bt.count)), 64);
     // one to four output tiles (complex: a 64 x 64 tile is 0.85 us of MFMA per 16 k on ITS ONE CU -- the projections and
     // environment products of the truncation chains spend 20-40 us there): slices of 64 k from K = 128 on
-    static const long long tiny_k = 128;   // (0 = off: fused apply-compress 263 -> 244 ms, exact route 439 -> 417 ms)
-    if (tiny_k > 0 && can_split && tiles * bt.count <= 4 && k >= tiny_k)
+    // (measured against no slicing: fused apply-compress 263 -> 244 ms, exact route 439 -> 417 ms)
+    if (can_split && tiles * bt.count <= 4 && k >= 128)
         splits = std::max<int>(splits, (int)std::min<long long>(k / 64, 32));
     // one wave of workgroups or less and a long K (the encoder's 16384 x 133 x 16384 sketches: 256 tiles): two to four K
     // slices fill the second workgroup slot of every CU (37.7 -> see DESIGN 3.4)
-    static const bool fill_split = true;
-    if (fill_split && splits < 2 && can_split && tiles * bt.count >= 128 && tiles * bt.count <= 384 && k >= 4096)
+    if (splits < 2 && can_split && tiles * bt.count >= 128 && tiles * bt.count <= 384 && k >= 4096)
         splits = (int)std::min<long long>(4, (767 / (tiles * bt.count)));
     if (splits < 2) splits = 1;
     long long kchunk = k, cstride = 0, c_bs = bt.c_bs;
@@ -403,8 +402,7 @@ int gemm_launch(qil_context* ctx, long long m, long long n, long long k, const T
         ldo = m;
     }
     // narrow outputs: neighbouring workgroups share the same rows of A (served from L2 / Infinity Cache)
-    static const bool xcd_order = true;
-    const int col_fastest = (tiles_n <= 8 ? 1 : 0) | (xcd_order ? 0 : 2);
+    const int col_fastest = tiles_n <= 8 ? 1 : 0;
 #define QIL_GEMM_K(ARCv, BKCv)                                                                                               \
     QIL_TRY((qil_klaunch<gemm_mfma_k<T, BM, BN, WM, WN, PIPE, ARCv, BKCv, GKT, DEEP>>(                                                      \
         ctx, dim3((unsigned)tiles, (unsigned)bt.count, (unsigned)splits), dim3(256), lds, m, n, k, A, a_rs, a_ks, conjA, B, b_ks, \
@@ -763,7 +761,7 @@ struct jacobi_block_round_k {
 
 // MODE 1: A and V staged in LDS for the whole iteration; MODE 2: only A in LDS, V in global memory (complex operands of
 // 2 chi x chi sites with chi ~ 64: A fits the CU's LDS, A and V together do not) -- the dot products and the rotation
-// of A, which every round's critical path waits for, still run out of LDS; MODE 0: both in global memory.
+// of A, which every round's critical path waits for, still run out of LDS.
 template <class T, int MODE>
 __device__ __forceinline__ void jacobi_fused_body(const uint3 blockIdx, const uint3 gridDim, T* __restrict__ A, long long lda, int m,
                                                      T* __restrict__ V, long long ldv, int n, double tol,
@@ -773,19 +771,16 @@ __device__ __forceinline__ void jacobi_fused_body(const uint3 blockIdx, const ui
     __shared__ double s_fro[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr int NW = 16;
-    T* Aw = A;
+    // odd leading dimension (in doubles): column pairs start on different banks
+    const int la = m | 1;
+    T* Aw = reinterpret_cast<T*>(jf_smem);
     T* Vw = V;
-    int la = (int)lda, lv = (int)ldv;
-    if (MODE != 0) {
-        // odd leading dimension (in doubles): column pairs start on different banks
-        la = m | 1;
-        Aw = reinterpret_cast<T*>(jf_smem);
-        if (MODE == 1) {
-            lv = n | 1;
-            Vw = Aw + (size_t)la * n;
-        }
-        for (int t = tid; t < m * n; t += 1024) Aw[(t % m) + la * (t / m)] = A[(t % m) + lda * (t / m)];
+    int lv = (int)ldv;
+    if (MODE == 1) {
+        lv = n | 1;
+        Vw = Aw + (size_t)la * n;
     }
+    for (int t = tid; t < m * n; t += 1024) Aw[(t % m) + la * (t / m)] = A[(t % m) + lda * (t / m)];
     for (int t = tid; t < n * n; t += 1024) {
         const int r = t % n, c = t / n;
         T v{};
@@ -817,12 +812,10 @@ __device__ __forceinline__ void jacobi_fused_body(const uint3 blockIdx, const ui
         v = wave_sum(v);
         if (lane == 0) norms[j] = sqrt(v);
     }
-    if (MODE != 0) {
-        __syncthreads();
-        for (int t = tid; t < m * n; t += 1024) A[(t % m) + lda * (t / m)] = Aw[(t % m) + la * (t / m)];
-        if (MODE == 1)
-            for (int t = tid; t < n * n; t += 1024) V[(t % n) + ldv * (t / n)] = Vw[(t % n) + lv * (t / n)];
-    }
+    __syncthreads();
+    for (int t = tid; t < m * n; t += 1024) A[(t % m) + lda * (t / m)] = Aw[(t % m) + la * (t / m)];
+    if (MODE == 1)
+        for (int t = tid; t < n * n; t += 1024) V[(t % n) + ldv * (t / n)] = Vw[(t % n) + lv * (t / n)];
 }
 template <class T, int MODE>
 struct jacobi_fused_k {
@@ -1515,8 +1508,7 @@ int gs_fused_launch(qil_context* ctx, unsigned nwg, T* A, long long lda, long lo
                     const double* ref_norm, long long chunk_rows) {
     const long long rows = chunk_rows > 0 ? std::min(chunk_rows, mtot) : mtot;
     const size_t lds = ((size_t)2 * (n + (n & 1)) + (size_t)(rows | 1) * n) * sizeof(T);
-    static const bool use_lds = true;
-    if (use_lds && lds <= 150 * 1024) {
+    if (lds <= 150 * 1024) {
         QIL_TRY((qil_klaunch<gs_fused_k<T, true>>(ctx, dim3(nwg), dim3(1024), lds, A, lda, mtot, n, R, ldr, ref_norm, chunk_rows)));
     } else {
         QIL_TRY((qil_klaunch<gs_fused_k<T, false>>(ctx, dim3(nwg), dim3(1024), (size_t)n * sizeof(T), A, lda, mtot, n, R, ldr, ref_norm, chunk_rows)));
@@ -1884,9 +1876,8 @@ struct offdiag_max_k {
 template <class T>
 int qr_reorthogonalise(qil_context* ctx, long long m, long long n, T* Q, long long ldq, T* R, long long ldr, bool dbg,
                        bool* orthonormal = nullptr) {
-    static const bool reorth = true;
     if (orthonormal) *orthonormal = true;
-    if (!reorth || n < 2) return QIL_OK;
+    if (n < 2) return QIL_OK;
     // r06: nothing to measure after a CholeskyQR2 whose second pass was the first-order one (A/B with the check forced on,
     // profiles/r06_qr_recheck_ab.txt: bit-identical results, zT compression 64.2 -> 62.6 ms, compress! chi 256 45.2 -> 44.4 ms)
     const bool known = ctx->qr_orthonormal;
@@ -3476,8 +3467,7 @@ int svd_left_mid(qil_context* ctx, long long p, long long q, T* B, long long ldb
         qil_ctx_free(ctx, tmp);
         return QIL_OK;
     };
-    static const bool sort_cols = getenv("QIL_SVD_NOSORT") == nullptr;
-    if (tall && sort_cols && q >= 17) {
+    if (tall && q >= 17) {
         void* nb_ = nullptr;
         QIL_TRY(qil_ctx_alloc(ctx, (size_t)q * sizeof(double), &nb_));
         QIL_TRY((qil_klaunch<col_norms_k<T>>(ctx, dim3((unsigned)q), dim3(256), 0, (const T*)B, ldb, p, (double*)nb_)));
@@ -3845,12 +3835,11 @@ int svd_impl(qil_context* ctx, long long m, long long n, T* A, long long lda, T*
     // the rows of a triangular factor are far closer to orthogonal than its columns, which saves sweeps
     // (the classical preconditioning of one-sided Jacobi); then R^H = L S V^H gives Wk = (Q V) S L^H.
     static const long long bj_min = 640;   // (crossover with the in-LDS block rounds: 600-700 columns)
-    static const bool bj_rt = true;
     // mid-size operands too: neutral on random matrices, but graded / low-rank spectra -- what truncation sees after an
     // apply -- need 2-4x fewer sweeps (512 x 256 graded: 36 -> 9 ms including the QR)
     static const long long rt_min = 97;
     const bool blocked = cols >= bj_min;
-    bool rt = (blocked && bj_rt) || cols >= rt_min;
+    bool rt = cols >= rt_min;   // (blocked implies it)
     T* Q = nullptr;
     long long ldq = 0, qrows = 0;
     void *rbuf = nullptr, *rtbuf = nullptr, *abuf = nullptr;
@@ -3873,12 +3862,12 @@ int svd_impl(qil_context* ctx, long long m, long long n, T* A, long long lda, T*
             rbuf = nullptr;
             rt = false;
         } else {
-        Q = Wk;
-        ldq = ldw;
-        qrows = rows;
-        Wk = static_cast<T*>(rbuf);
-        ldw = cols;
-        rows = cols;
+            Q = Wk;
+            ldq = ldw;
+            qrows = rows;
+            Wk = static_cast<T*>(rbuf);
+            ldw = cols;
+            rows = cols;
         }
         if (rt) {
             QIL_TRY(qil_ctx_alloc(ctx, (size_t)(cols * cols) * sizeof(T), &rtbuf));
@@ -3903,18 +3892,14 @@ int svd_impl(qil_context* ctx, long long m, long long n, T* A, long long lda, T*
     const double tol = std::max(1e-15, 4.0 * 1.1e-16 * std::sqrt((double)rows));
     const size_t lds_a = (size_t)((rows | 1) * cols) * sizeof(T);
     const size_t lds_av = lds_a + (size_t)((cols | 1) * cols) * sizeof(T);
-    static const bool a_in_lds = true;
-    static const bool fused_global = false;
     // one workgroup for the whole iteration only while (at least) A lives in LDS; a single workgroup working out of
     // L2 is slower than the tournament launches, which spread the pairs over the chip
     if (ncol <= 96 && rows * cols <= (1LL << 19) &&
-        (lds_av <= 150 * 1024 || (a_in_lds && rows <= 128 && lds_a <= 150 * 1024) || fused_global)) {
+        (lds_av <= 150 * 1024 || (rows <= 128 && lds_a <= 150 * 1024))) {
         if (lds_av <= 150 * 1024) {
             QIL_TRY((qil_klaunch<jacobi_fused_k<T, 1>>(ctx, dim3(1), dim3(1024), lds_av, Wk, ldw, (int)rows, V, cols, ncol, tol, 40, (double*)nrm, negl_rel)));
-        } else if (a_in_lds && rows <= 128 && lds_a <= 150 * 1024) {   // one DPP row per pair only up to 128 rows
+        } else {   // A only; one DPP row per pair only up to 128 rows
             QIL_TRY((qil_klaunch<jacobi_fused_k<T, 2>>(ctx, dim3(1), dim3(1024), lds_a, Wk, ldw, (int)rows, V, cols, ncol, tol, 40, (double*)nrm, negl_rel)));
-        } else {
-            QIL_TRY((qil_klaunch<jacobi_fused_k<T, 0>>(ctx, dim3(1), dim3(1024), 0, Wk, ldw, (int)rows, V, cols, ncol, tol, 40, (double*)nrm, negl_rel)));
         }
     } else {
         bool bj_done = false;
@@ -3940,12 +3925,10 @@ int svd_impl(qil_context* ctx, long long m, long long n, T* A, long long lda, T*
         const int nn = (int)nj, npad = nn + (nn & 1);
         // in-LDS block rounds when 2 BB columns of A and V fit one CU's LDS (not after the GEMM-shaped block sweeps:
         // their fallback keeps the scalar rounds)
-        static const bool block_rounds = true;
         int bb = 0;
-        if (block_rounds && !blocked && rows <= (1 << 20)) {
+        if (!blocked && rows <= (1 << 20)) {
             const size_t per_col = (size_t)((rows | 1) + (cols | 1)) * sizeof(T);
-            static const int bb_max = 8;
-            if (bb_max >= 8 && 16 * per_col <= 150 * 1024) bb = 8;
+            if (16 * per_col <= 150 * 1024) bb = 8;
             else if (8 * per_col <= 150 * 1024) bb = 4;
         }
         const int nblk = bb ? (int)(((cols + bb - 1) / bb + 1) / 2 * 2) : 0;
@@ -3965,8 +3948,7 @@ int svd_impl(qil_context* ctx, long long m, long long n, T* A, long long lda, T*
             int hv[2] = {0, 0};
             QIL_TRY(qil_read_back(ctx, hv, flag, 2 * sizeof(int)));
             if (getenv("QIL_SVD_DEBUG")) fprintf(stderr, "[svd] scalar sweep %d (cols %lld): rotated=%d above-quadratic=%d\n", sweep, nj, hv[0], hv[1]);
-            static const bool early = true;
-            if (!(early ? hv[1] : hv[0])) break;   // nothing rotated, or only pairs already below the quadratic-phase level
+            if (!hv[1]) break;   // nothing rotated, or only pairs already below the quadratic-phase level
         }
         QIL_TRY((qil_klaunch<col_norms_k<T>>(ctx, dim3((unsigned)nj), dim3(256), 0, Wk, ldw, rows, (double*)nrm)));
         if (blocked)   // padding columns are zero in the V part too; genuine columns have unit V columns
@@ -4216,7 +4198,6 @@ int tsqr_panel(qil_context* ctx, long long m, int b, T* P, long long lda, T* R, 
 template <class T>
 int qr_impl(qil_context* ctx, long long m, long long n, T* A, long long lda, T* R, long long ldr) {
     static const long long TALL = 2048;
-    static const bool hh_panels = true;
     ctx->qr_orthonormal = false;
     // Cholesky QR first where it pays (from a few panels on) and while it keeps succeeding on this context: a numerically
     // rank-deficient operand (product bonds, deficient sketches) costs the attempt a Gram product, a partial factorisation and
@@ -4246,7 +4227,7 @@ int qr_impl(qil_context* ctx, long long m, long long n, T* A, long long lda, T* 
     // (128 x 64: 274 -> ~140 us -- the CGS2 kernel pays ~4 us per column, the Householder panel ~1.5; compress! chi 64 -> 32
     // 28 -> 24.5 ms, 128 -> 64 50 -> 42 ms; narrower panels measured equal within noise either way)
     static const long long fused_max = 16;
-    const bool hh_ok = hh_panels && !tree && n > fused_max && hh_panel_fits<T>(m, (int)std::min<long long>(n, 32));
+    const bool hh_ok = !tree && n > fused_max && hh_panel_fits<T>(m, (int)std::min<long long>(n, 32));
     if (hh_ok && n <= 32) return hh_panel_launch<T>(ctx, A, lda, m, (int)n, R, ldr, (const double*)nullptr);
     if (n <= 16 || (fits_lds && !hh_ok)) {
         if (tree && n <= 16) {
@@ -4260,8 +4241,7 @@ int qr_impl(qil_context* ctx, long long m, long long n, T* A, long long lda, T* 
         return gs_fused_launch<T>(ctx, 1u, A, lda, m, (int)n, R, ldr, (const double*)nullptr, 0LL);
     }
     // panel width: 32 columns while a rows x 32 panel still fits one CU's LDS (half the launches), else 16
-    static const int pb_max = 32;
-    const bool wide = pb_max >= 32 && !tree && ((size_t)64 + (size_t)(m | 1) * 32) * sizeof(T) <= 150 * 1024;
+    const bool wide = !tree && ((size_t)64 + (size_t)(m | 1) * 32) * sizeof(T) <= 150 * 1024;
     const int PB = wide ? 32 : 16;
     if (R) QIL_TRY(qil_dev_zero(ctx, R, (size_t)(ldr * n) * sizeof(T)));
     void *cbuf = nullptr, *nbuf = nullptr;
@@ -4286,7 +4266,7 @@ int qr_impl(qil_context* ctx, long long m, long long n, T* A, long long lda, T* 
         T* Rjj = R ? R + j0 + ldr * j0 : (T*)nullptr;
         if (tree)
             QIL_TRY(tsqr_panel<T>(ctx, m, b, P, lda, Rjj, ldr, (const double*)nbuf + j0));
-        else if (hh_panels && hh_panel_fits<T>(m, b))
+        else if (hh_panel_fits<T>(m, b))
             QIL_TRY(hh_panel_launch<T>(ctx, P, lda, m, b, Rjj, ldr, (const double*)nbuf + j0));
         else
             QIL_TRY(gs_fused_launch<T>(ctx, 1u, P, lda, m, b, Rjj, ldr, (const double*)nbuf + j0, 0LL));
@@ -4647,8 +4627,6 @@ int qil_dev_transpose(qil_context* ctx, int dtype, int conj, int64_t m, int64_t 
 
 int qil_dev_svd(qil_context* ctx, int dtype, int64_t m, int64_t n, void* A, int64_t lda, void* U,
                 int64_t ldu, double* S_host, void* Vh, int64_t ldvh, double negligible_rel) {
-    static const bool skip = true;
-    if (!skip) negligible_rel = 0.0;
     if (dtype == QIL_C64)
         return svd_impl<c64>(ctx, m, n, (c64*)A, lda, (c64*)U, ldu, S_host, (c64*)Vh, ldvh, negligible_rel);
     return svd_impl<double>(ctx, m, n, (double*)A, lda, (double*)U, ldu, S_host, (double*)Vh, ldvh, negligible_rel);

@@ -1,8 +1,7 @@
-// Read-out kernels: coefficient (C1), lazy <bits|W psi>, mps_to_vector (C2), norm (K3).
+// Read-out kernels: coefficient (C1), lazy <bits|W psi>, mps_to_vector (C2).  norm (K3) is in qil_inner.hip.
 //
 //   coefficient(psi, cfg)   src/mps.jl:669-678   amplitude * prod_i A_i[:, cfg_i, :]
 //   mps_to_vector           src/mps.jl:716-743
-//   norm                    src/mps.jl:754-771
 //
 // The reference contracts the row vector with the WHOLE site tensor and projects afterwards
 // (mps.jl:675); here the physical slice is selected first (half the bytes, same arithmetic).
@@ -11,54 +10,21 @@
 // dot product along the contiguous alpha axis, reduced with wavefront shuffles.
 #include "qil_internal.h"
 #include "qil_launch.h"
+#include "qil_device_utils.h"
 #include <set>
 #include <mutex>
 #include <map>
 
 namespace {
 
-struct c64 {
-    double re, im;
-};
+using namespace qil_dev;
 
-__device__ __forceinline__ double cmul_add(double acc, double a, double b) { return fma(a, b, acc); }
-__device__ __forceinline__ c64 cmul_add(c64 acc, c64 a, c64 b) {
-    acc.re = fma(a.re, b.re, acc.re);
-    acc.re = fma(-a.im, b.im, acc.re);
-    acc.im = fma(a.re, b.im, acc.im);
-    acc.im = fma(a.im, b.re, acc.im);
-    return acc;
-}
-__device__ __forceinline__ c64 cmul_add(c64 acc, c64 a, double b) {
-    acc.re = fma(a.re, b, acc.re);
-    acc.im = fma(a.im, b, acc.im);
-    return acc;
-}
-__device__ __forceinline__ c64 cmul_add(c64 acc, double a, c64 b) {
-    acc.re = fma(a, b.re, acc.re);
-    acc.im = fma(a, b.im, acc.im);
-    return acc;
-}
 __device__ __forceinline__ double shfl_xor_t(double v, int m) { return __shfl_xor(v, m, 64); }
 __device__ __forceinline__ c64 shfl_xor_t(c64 v, int m) {
     return c64{__shfl_xor(v.re, m, 64), __shfl_xor(v.im, m, 64)};
 }
-__device__ __forceinline__ double add_t(double a, double b) { return a + b; }
-__device__ __forceinline__ c64 add_t(c64 a, c64 b) { return c64{a.re + b.re, a.im + b.im}; }
 __device__ __forceinline__ double one_t(double) { return 1.0; }
 __device__ __forceinline__ c64 one_t(c64) { return c64{1.0, 0.0}; }
-__device__ __forceinline__ c64 to_c64(double v) { return c64{v, 0.0}; }
-__device__ __forceinline__ c64 to_c64(c64 v) { return v; }
-template <class TD>
-__device__ __forceinline__ TD cast_elem(double v);
-template <>
-__device__ __forceinline__ double cast_elem<double>(double v) { return v; }
-template <>
-__device__ __forceinline__ c64 cast_elem<c64>(double v) { return c64{v, 0.0}; }
-template <class TD>
-__device__ __forceinline__ TD cast_elem(c64 v) { return v; }
-__device__ __forceinline__ double conj_t(double v) { return v; }
-__device__ __forceinline__ c64 conj_t(c64 v) { return c64{v.re, -v.im}; }
 
 struct ChainSite {
     const void* A;  // MPS site
@@ -642,8 +608,7 @@ int qil_apply_coefficient_sweep_dev(const qil_mpo* const* Ws, int64_t nw, const 
         qil_mps_destroy(prod);
         return st;
     };
-    static const bool concurrent = true;   // tuning aid
-    if (concurrent && distinct && nw >= 4) {
+    if (distinct && nw >= 4) {
         // every value's product + read-out is a chain of ~100 small launches: the values run concurrently on the context's
         // streams.  The operators move to their slot for the duration of the call (bookkeeping only); the state, the bits and the
         // results are shared device buffers (the state is read-only here and every slot's stream waits for the home stream first).
@@ -859,39 +824,4 @@ extern "C" int qil_mps_to_vector(const qil_mps* psi, int reverse, void* host_out
                 (long long)psi->n());
     std::vector<uint8_t> spec((size_t)psi->n(), (uint8_t)3);
     return qil_mps_block(psi, spec.data(), reverse, host_out);
-}
-
-// norm(psi) = sqrt(|<psi|psi>|): E' = A^H (E A) per site, two GEMMs on the matricised site tensor.
-extern "C" int qil_norm(const qil_mps* psi, double* out) {
-    QIL_REQUIRE(psi && out, QIL_EINVAL_ARG, "norm: null argument");
-    qil_context* ctx = psi->ctx;
-    QIL_TRY(qil_ctx_activate(ctx));
-    qil_call_scope call_scope(ctx);
-    const int64_t n = psi->n();
-    const size_t esz = qil_elem_size(psi->dtype);
-    long long maxchi = 1;
-    for (int64_t i = 0; i <= n; ++i) maxchi = std::max<long long>(maxchi, psi->dims[(size_t)i]);
-    void *E = nullptr, *En = nullptr, *T = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(maxchi * maxchi) * esz, &E));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(maxchi * maxchi) * esz, &En));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(2 * maxchi * maxchi) * esz, &T));
-    const double one[2] = {1.0, 0.0};
-    QIL_HIP(hipMemcpyAsync(E, one, esz, hipMemcpyHostToDevice, qil_stream(ctx)));
-    QIL_HIP(qil_stream_sync(ctx));
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1];
-        // T (cl x 2cr) = E (cl x cl) * A (cl x 2cr);   E[alpha', alpha]
-        QIL_TRY(qil_dev_gemm(ctx, psi->dtype, 0, 0, cl, 2 * cr, cl, E, cl, psi->site[(size_t)i], cl, T, cl));
-        // E' (cr x cr) = A^H ((2cl) x cr)^H * T ((2cl) x cr);  E'[beta', beta]
-        QIL_TRY(qil_dev_gemm(ctx, psi->dtype, 2, 0, cr, cr, 2 * cl, psi->site[(size_t)i], 2 * cl, T, 2 * cl, En, cr));
-        std::swap(E, En);
-    }
-    double h[2] = {0, 0};
-    QIL_HIP(hipMemcpyAsync(h, E, esz, hipMemcpyDeviceToHost, qil_stream(ctx)));
-    QIL_HIP(qil_stream_sync(ctx));
-    *out = sqrt(sqrt(h[0] * h[0] + h[1] * h[1]));
-    qil_ctx_free(ctx, E);
-    qil_ctx_free(ctx, En);
-    qil_ctx_free(ctx, T);
-    return QIL_OK;
 }

@@ -15,12 +15,11 @@
 
 #include "qil_internal.h"
 #include "qil_launch.h"
+#include "qil_device_utils.h"
 
 namespace {
 
-struct c64 {
-    double re, im;
-};
+using namespace qil_dev;
 
 constexpr int64_t kNoCap = INT64_MAX;
 
@@ -1149,10 +1148,9 @@ static int apply_compress_on(qil_context* ctx, const qil_mpo* W, const qil_mps* 
         t_prev = now;
     };
     // sketch matrix for capped bonds (one for the whole call: any sub-block of a Gaussian matrix is Gaussian)
-    static const bool sketch = true;   // tuning aid
     void* Om = nullptr;
     int64_t om_ld = 1;
-    if (sketch && zip_maxdim < kNoCap / 2) {
+    if (zip_maxdim < kNoCap / 2) {
         for (int64_t i = 0; i + 1 < N; ++i) om_ld = std::max<int64_t>(om_ld, phi->dims[(size_t)i + 1] * W->dims[(size_t)i + 1]);
         if (zip_maxdim < om_ld) {
             if ((st = take((size_t)(om_ld * zip_maxdim) * e, &Om)) != QIL_OK) return cleanup(st);
@@ -1175,7 +1173,7 @@ static int apply_compress_on(qil_context* ctx, const qil_mpo* W, const qil_mps* 
         int64_t r = 0;
         void *U = nullptr, *SV = nullptr;
         const int64_t rows = 2LL * R, Pc = (int64_t)cr * Dr;
-        if (sketch && zip_maxdim < std::min(rows, Pc)) {
+        if (zip_maxdim < std::min(rows, Pc)) {
             // capped bond: an orthonormal basis of theta Omega (Omega: Pc x zip_maxdim, seeded Gaussian) instead of
             // theta's truncated SVD -- the variational sweep below re-optimises every site anyway, and with it the
             // sketched zip-up reproduces the oracle's compress!(apply) on all 24 random products exactly as the SVD one

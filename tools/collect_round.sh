@@ -64,6 +64,5 @@ python3 -c "import qilaplace_jl_amd as q; print('qil_host_cpu_budget:', q.host_c
 QIL_DT_PROFILE=1 timeout 300 python3 tools/_dt_persist_value_scan.py 2>&1 | grep -v amdgpu.ids > $O/${P}_dt_persist_profile.txt
 timeout 600 python3 tools/_chain_persist_check.py 2>&1 | grep -v amdgpu.ids > $O/${P}_chain_builder.txt
 timeout 300 python3 tools/_zt_build_time.py 24 30 2>&1 | grep case > $O/${P}_zt_build_time.txt
-timeout 600 bash tools/_svd_sort_ab.sh > $O/${P}_svd_sort_ab.txt 2>&1
 timeout 1500 python3 -m pytest tests -m gpu -q > $O/${P}_pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -3 $O/${P}_pytest_gpu.log
 tail -c 1500 $O/${P}_bench_default.json; echo; tail -c 900 $O/${P}_bench_sweep.json; echo; cat $T; tail -4 $O/${P}_chain_builder.txt
