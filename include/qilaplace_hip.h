@@ -188,6 +188,25 @@ QIL_API int qil_mps_to_vector(const qil_mps* psi, int reverse, void* host_out);
 QIL_API int qil_mps_block(const qil_mps* psi, const uint8_t* spec, int reverse, void* host_out);
 /* norm(psi) src/mps.jl:754-771 (without amplitude). */
 QIL_API int qil_norm(const qil_mps* psi, double* out);
+/* Perfect sampling (ITensors' sample(::MPS)): nb configurations x drawn with probability |psi_x|^2 / |psi|^2.
+ * For the chain's n site tensors A_i[alpha, s, beta] (paired: the 2n interleaved tensors):
+ *   Right environments: R_n = [1], R_{i-1} = sum_s A_i[:, s, :] R_i A_i[:, s, :]^H (Hermitian PSD, chi_{i-1} x chi_{i-1}),
+ *   each normalised on the device by its trace (only ratios matter).
+ *   Sample r carries a row vector v (v = [1] at the start).  At site i: w_s = v A_i[:, s, :], q_s = Re(w_s R_i w_s^H);
+ *   s = 0 iff u_{r,i} (q_0 + q_1) < q_0, else s = 1; then v <- w_s / sqrt(q_s) and the sample's probability is
+ *   multiplied by q_s / (q_0 + q_1).
+ *   Uniforms: the caller's (host, nb x n, sample-major, each in [0, 1)), or when uniforms is null
+ *   u_{r,i} = (splitmix64(seed ^ splitmix64(r n + i)) >> 11) 2^-53.  Sample r depends only on (psi, seed, r): not on nb,
+ *   on the internal chunking of rows or on the route, up to rounding at a threshold.
+ *   The amplitude does not enter; prob_out (nullable, host, nb doubles) receives |psi_x|^2 / |psi|^2.
+ *   If q_0 + q_1 <= 0 on a reached prefix (rounding only), the larger q is taken, s = 0 when both are 0, and the
+ *   probability factor is 0.
+ * bits_out: host, nb x n bytes, the layout of qil_coefficient_batch's bits (the rows go straight back into it).
+ * Errors, before the context is activated: QIL_EINVAL_ARG for a null psi or bits_out or nb < 0, QIL_EINVAL_CONFIG
+ * for a uniform outside [0, 1).  QIL_EDOMAIN for a state of norm 0.  nb = 0 is a no-op.
+ * Bonds <= 64 (f64) / 32 (c64) take one fused f64-MFMA kernel per site, larger ones GEMMs and a reduce-and-choose kernel. */
+QIL_API int qil_sample(const qil_mps* psi, int64_t nb, uint64_t seed, const double* uniforms, uint8_t* bits_out,
+                       double* prob_out);
 
 /* ------------------------------------------------------------------ overlaps (ITensors' inner on device chains) */
 /* <phi|psi> = amp_phi * amp_psi * sum_x conj(phi_x) psi_x

@@ -7,7 +7,7 @@
 module QILaplaceHIP
 
 using ITensors
-import ITensors: apply, inner
+import ITensors: apply, inner, sample
 import Base: *, getindex, length
 import LinearAlgebra: norm
 import ..Mps
@@ -18,7 +18,7 @@ using ..ApplyMPO: _as_single_site_mpo
 
 export DeviceMPS, DeviceMPO, to_device, to_host, signal_mps_device, marginal, mps_block, apply_compress,
     compress_mpo!, build_dt_mpo_batch, build_qft_mpo_device, build_zt_qft_chain_device, apply_coefficient_sweep, apply!, rsvd_device, svd_device,
-    Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm
+    Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm, sample
 
 const LIB = get(ENV, "QILHIP_LIB", "libqilhip.so")
 
@@ -237,6 +237,16 @@ function apply_norm(W::DeviceMPO, psi::DeviceMPS)                              #
     v = Ref{Cdouble}(0)
     check(ccall((:qil_apply_norm, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Cdouble}), W.h, psi.h, v))
     return v[]
+end
+# perfect sampling (ITensors' sample on device chains): nsamples x length(psi) bit rows, sample-major as
+# coefficient takes them, and their probabilities |psi_x|^2 / |psi|^2 (the amplitude does not enter)
+function sample(psi::DeviceMPS, nsamples::Integer; seed::Integer=1234)
+    n = length(psi)
+    b = Matrix{UInt8}(undef, n, nsamples)                                       # the ABI's row-major nsamples x n
+    p = Vector{Float64}(undef, nsamples)
+    check(ccall((:qil_sample, LIB), Cint, (Ptr{Cvoid}, Int64, UInt64, Ptr{Cdouble}, Ptr{UInt8}, Ptr{Cdouble}),
+                psi.h, nsamples, UInt64(seed), C_NULL, b, p))
+    return Matrix{UInt8}(permutedims(b)), p
 end
 function mps_to_vector(psi::DeviceMPS; reverse::Bool=false)                                        # mps.jl:716
     d = Ref{Cint}(0)

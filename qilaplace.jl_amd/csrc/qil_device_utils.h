@@ -1,7 +1,7 @@
 // Device-side helpers shared by the dense linear algebra (qil_linalg.hip), the MPO builders (qil_build*.hip), the
-// apply (qil_apply.hip), the read-outs (qil_readout.hip), the overlaps (qil_inner.hip) and the truncation
-// (qil_truncate.hip): the complex scalar type and its arithmetic, DPP cross-lane sums, Jacobi rotations and the
-// in-workgroup one-sided Jacobi sweep loop.  gfx950 only.
+// apply (qil_apply.hip), the read-outs (qil_readout.hip), the overlaps (qil_inner.hip), the sampler (qil_sample.hip) and
+// the truncation (qil_truncate.hip): the complex scalar type and its arithmetic, the splitmix64 hash, DPP cross-lane sums,
+// Jacobi rotations and the in-workgroup one-sided Jacobi sweep loop.  gfx950 only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -58,6 +58,15 @@ template <>
 __device__ __forceinline__ c64 cast_elem<c64>(double v) { return c64{v, 0.0}; }
 template <class TD>
 __device__ __forceinline__ TD cast_elem(c64 v) { return v; }
+
+// ------------------------------------------------------------------ counter-based random numbers
+// splitmix64 finaliser: the hash behind qil_dev_fill_normal's normals and qil_sample's uniforms
+__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
 
 // ------------------------------------------------------------------ block reductions
 // Cross-lane sums on the DPP path (no LDS crossbar): quad_perm butterflies inside each quad, then

@@ -4466,13 +4466,6 @@ struct scale_kernel_k {
     }
 };
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
 // counter-based N(0,1): element i draws from hash(seed, 2i), hash(seed, 2i+1) via Box-Muller
 __global__ void fill_normal_kernel(double* __restrict__ p, long long n, uint64_t seed, double scale) {
     for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < n;

@@ -5,6 +5,7 @@
   mps_to_vector      src/mps.jl:716-743
   norm               src/mps.jl:754-771
   inner              ITensors' inner(phi, psi) / inner(phi, W, psi) on device chains (no reference counterpart)
+  sample             ITensors' sample(::MPS) on device chains (no reference counterpart)
   canonicalize       src/mps.jl:787-847, 866-901   (Julia: canonicalize!)
   compress           src/mps.jl:913-999            (Julia: compress!)
   signal_mps         src/signals/SignalConverters.jl:228-233
@@ -363,6 +364,45 @@ def apply_distance(phi, W, psi) -> float:
     nphi = phi.amplitude * norm(phi)
     nwpsi = psi.amplitude * apply_norm(W, psi)
     return _distance(nphi * nphi, nwpsi * nwpsi, inner(phi, W, psi))
+
+
+# ---------------------------------------------------------------- sampling
+def sample(psi, nsamples, seed=1234, uniforms=None, bits=False):
+    """Perfect sampling: `nsamples` configurations x drawn with probability |psi_x|^2 / |psi|^2 (ITensors' sample), with
+    those probabilities.  The amplitude does not enter.
+
+    Sample r depends only on (psi, seed, r): with uniforms=None the draw at site i uses u = (splitmix64(seed ^
+    splitmix64(r * n + i)) >> 11) * 2^-53 (n = number of site tensors); `uniforms` ((nsamples, n) in [0, 1)) replaces them.
+
+    Returns (samples, probs).  SignalMPS: big-endian indices (site 1 = MSB), the integers `coefficient(psi, int)` reads.
+    ZTMPS: a pair (k, l) decoded as `coefficient_grid` encodes it (lsb(k) on the main sites, lsb(l) on the copy sites).
+    bits=True: the raw (nsamples, n) uint8 rows, the layout of `coefficient_batch` (required when n > 62)."""
+    if not isinstance(psi, SignalMPS):
+        raise TypeError("sample: unsupported operand types")
+    nb = int(nsamples)
+    if nb < 0:
+        raise ValueError("sample: nsamples must be non-negative")
+    n = _ntensors(psi)
+    paired = isinstance(psi, ZTMPS)
+    if not bits and (n if not paired else n // 2) > 62:
+        raise ValueError(f"sample: {n} sites do not fit an integer index; use bits=True")
+    u_ptr = None
+    if uniforms is not None:
+        u = np.ascontiguousarray(uniforms, dtype=np.float64)
+        if u.shape != (nb, n):
+            raise ValueError(f"sample: uniforms must have shape ({nb}, {n}), got {u.shape}")
+        u_ptr = u.ctypes.data_as(C.POINTER(C.c_double))
+    out = np.zeros((nb, n), dtype=np.uint8)
+    probs = np.zeros(nb, dtype=np.float64)
+    L.check(L.lib.qil_sample(psi.handle, nb, int(seed) & 0xFFFFFFFFFFFFFFFF, u_ptr, out.ctypes.data_as(C.POINTER(C.c_uint8)),
+                             probs.ctypes.data_as(C.POINTER(C.c_double))))
+    if bits:
+        return out, probs
+    if paired:
+        w = np.int64(1) << np.arange(n // 2, dtype=np.int64)
+        return (out[:, 0::2].astype(np.int64) @ w, out[:, 1::2].astype(np.int64) @ w), probs
+    w = np.int64(1) << np.arange(n - 1, -1, -1, dtype=np.int64)
+    return out.astype(np.int64) @ w, probs
 
 
 # ---------------------------------------------------------------- truncation
