@@ -262,20 +262,7 @@ qil_call_scope::qil_call_scope(qil_context* c)
     : ctx(c), serial0(c ? c->alloc_serial : 0), fails0(qil_fail_count()) {
     // per-call heuristics state starts afresh: what one call learns about its operands (qr_impl's Cholesky QR refusals) must not
     // leak into the next one -- an item of a batch then takes exactly the route it takes alone (bit-identical results)
-    if (c) {
-        c->cholqr_skip = 0;
-        // ... and so does the R^-1 block CholeskyQR2 parks for a certificate (cholqr2 / certify_no_truncation): it is state of
-        // ONE call.  A pointer that survived the previous call is released only if the pool still knows THAT allocation
-        // (same address AND same allocation serial, not owned by a handle: the address alone may have been handed out again,
-        // ADVICE r04), and forgotten either way, so no call can free or certify against somebody else's block.
-        if (c->rinv) {
-            auto it = c->live_blocks.find(c->rinv);
-            if (it != c->live_blocks.end() && it->second.serial == c->rinv_serial && !it->second.owned) qil_ctx_free(c, c->rinv);
-        }
-        c->rinv = nullptr;
-        c->rinv_for = nullptr;
-        c->want_rinv = false;
-    }
+    if (c) c->cholqr_skip = 0;
 }
 
 qil_call_scope::~qil_call_scope() {
@@ -293,10 +280,6 @@ qil_call_scope::~qil_call_scope() {
             ++it;
         }
     }
-    // the parked R^-1 block (if any) has just gone back to the pool with the rest: forget the pointer, do not free it again
-    ctx->rinv = nullptr;
-    ctx->rinv_for = nullptr;
-    ctx->want_rinv = false;
 }
 
 int qil_ctx_pinned(qil_context* ctx, size_t bytes, void** out) {

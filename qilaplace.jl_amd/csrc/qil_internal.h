@@ -86,14 +86,6 @@ struct qil_context {
     hipEvent_t sync_event = nullptr;   // qil_stream_sync inside a lock-step batch
     uint64_t progress_key = 0;    // where the chain driven through this context is (qil_progress)
     int cholqr_skip = 0;          // Cholesky QR attempts to skip after a refusal (qr_impl)
-    bool qr_orthonormal = false;  // the last qr_impl took CholeskyQR2 with its first-order second pass: Q^H Q = I to O(|E|^2) < 1e-15 by construction (qr_reorthogonalise)
-    double svd_deflate = 0.0;     // weight (relative) the one-factor SVD may drop with negligible rows of R: set by the truncating caller
-    // CholeskyQR2 has R^-1 = X1 X2 at hand: a caller that is about to run the truncation certificate on R asks for it
-    // (want_rinv) and takes the block over (rinv, valid for the R at rinv_for; the caller frees it)
-    bool want_rinv = false;
-    void* rinv = nullptr;
-    uint64_t rinv_serial = 0;            // allocation serial of the parked block (the call scope frees it only if it still matches)
-    const void* rinv_for = nullptr;
     // small device -> host read-backs without a copy command or a stream synchronisation (qil_read_back): kRbSlots slots of
     // kRbSlotBytes in pinned, device-visible memory + a ticket word a kernel writes behind the data; the host polls the word
     static constexpr int kRbSlots = 4;
@@ -299,8 +291,10 @@ int qil_dev_svd(qil_context* ctx, int dtype, int64_t m, int64_t n, void* A, int6
 // *handled = 0 leaves B intact for the general qil_dev_svd.
 // cert_cutoff > 0: the caller truncates by that cutoff only and ignores S_host; when the triangular factor certifies that no
 // singular value can be dropped, the thin QR is returned as the gauge step (*handled = 2, S_host untouched).
+// deflate > 0: rows of the triangular factor whose weight stays below deflate |B|_F^2 may be dropped (rank-deficient products).
 int qil_dev_svd_left(qil_context* ctx, int dtype, int64_t p, int64_t q, void* B, int64_t ldb, void* Uiso, int64_t ldu,
-                     double* S_host, void* SVh, int64_t ldsvh, double negligible_rel, int* handled, double cert_cutoff = 0.0);
+                     double* S_host, void* SVh, int64_t ldsvh, double negligible_rel, int* handled, double cert_cutoff = 0.0,
+                     double deflate = 0.0);
 // The same certificate for operands of any size: thin QR of A (m >= n) or A^H (m < n) into Qout (max(m, n) x k, packed) and
 // Rout (k x k, packed); *certified says whether a truncation at `cutoff` can drop anything.  A is left intact.
 int qil_dev_qr_certified(qil_context* ctx, int dtype, int64_t m, int64_t n, const void* A, int64_t lda, double cutoff, void* Qout,

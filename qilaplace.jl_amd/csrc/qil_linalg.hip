@@ -1517,8 +1517,13 @@ int gs_fused_launch(qil_context* ctx, unsigned nwg, T* A, long long lda, long lo
     return QIL_OK;
 }
 
+// Optional out-arguments of qr_impl: *orthonormal = the factorisation was CholeskyQR2 with its first-order second pass, so
+// Q^H Q = I to O(|E|^2) < 1e-15 by construction (qr_reorthogonalise need not measure it).  rinv (with R): CholeskyQR2 also
+// hands over R^-1 (n x n, ld n) in a block of its own for the certificate that follows (the caller frees it); other routes
+// leave *rinv null.
 template <class T>
-int qr_impl(qil_context* ctx, long long m, long long n, T* A, long long lda, T* R, long long ldr);
+int qr_impl(qil_context* ctx, long long m, long long n, T* A, long long lda, T* R, long long ldr, bool* orthonormal = nullptr,
+            void** rinv = nullptr);
 template <class T>
 int gemm_dispatch(qil_context* ctx, int opA, int opB, long long m, long long n, long long k, const T* A,
                   long long lda, const T* B, long long ldb, T* C, long long ldc, const gemm_batch& batch);
@@ -1873,16 +1878,15 @@ struct offdiag_max_k {
 // singular values of R are then not those of the operand.  Q^H Q is measured (one small GEMM + a max-reduction), and
 // while it is not the identity to 1e-11, Q is factored once more: Q = Q2 R2 is a well-conditioned problem (columns
 // lying in the span of earlier ones come out as zero columns), and R <- R2 R.  At most two extra factorisations.
+// known_orthonormal: what qr_impl reported for Q.  rinv (may be null): an R^-1 the caller holds; a re-factorisation frees it.
 template <class T>
-int qr_reorthogonalise(qil_context* ctx, long long m, long long n, T* Q, long long ldq, T* R, long long ldr, bool dbg,
-                       bool* orthonormal = nullptr) {
+int qr_reorthogonalise(qil_context* ctx, long long m, long long n, T* Q, long long ldq, T* R, long long ldr, bool known_orthonormal,
+                       void** rinv, bool dbg, bool* orthonormal = nullptr) {
     if (orthonormal) *orthonormal = true;
     if (n < 2) return QIL_OK;
     // r06: nothing to measure after a CholeskyQR2 whose second pass was the first-order one (A/B with the check forced on,
     // profiles/r06_qr_recheck_ab.txt: bit-identical results, zT compression 64.2 -> 62.6 ms, compress! chi 256 45.2 -> 44.4 ms)
-    const bool known = ctx->qr_orthonormal;
-    ctx->qr_orthonormal = false;
-    if (known) return QIL_OK;
+    if (known_orthonormal) return QIL_OK;
     void *gbuf = nullptr, *mx = nullptr;
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)(n * n) * sizeof(T), &gbuf));
     QIL_TRY(qil_ctx_alloc(ctx, 256, &mx));
@@ -1897,9 +1901,10 @@ int qr_reorthogonalise(qil_context* ctx, long long m, long long n, T* Q, long lo
         if (!(worst > 1e-11) || pass == 2) break;
         QIL_TRY(qr_impl<T>(ctx, m, n, Q, ldq, static_cast<T*>(gbuf), n));                  // Q <- Q2, gbuf = R2
         if (R) {
-            if (ctx->rinv) qil_ctx_free(ctx, ctx->rinv);         // R changes: an inverse kept for the certificate is stale
-            ctx->rinv = nullptr;
-            ctx->rinv_for = nullptr;
+            if (rinv && *rinv) {                                 // R changes: an inverse kept for the certificate is stale
+                qil_ctx_free(ctx, *rinv);
+                *rinv = nullptr;
+            }
             void* rnew = nullptr;
             QIL_TRY(qil_ctx_alloc(ctx, (size_t)(n * n) * sizeof(T), &rnew));
             QIL_TRY(gemm_dispatch<T>(ctx, 0, 0, n, n, n, static_cast<const T*>(gbuf), n, (const T*)R, ldr,
@@ -1911,7 +1916,6 @@ int qr_reorthogonalise(qil_context* ctx, long long m, long long n, T* Q, long lo
     }
     qil_ctx_free(ctx, gbuf);
     qil_ctx_free(ctx, mx);
-    ctx->qr_orthonormal = false;                                 // (a re-factorisation above may have set it: it is consumed here)
     return QIL_OK;
 }
 
@@ -2435,8 +2439,10 @@ struct chol_near_identity_k {
 
 // A (m x n, m >= n) -> Q in place, R (n x n, ldr; may be null) with positive diagonal.  *done = false: the operand is not
 // well enough conditioned (or not positive definite to rounding) -- A and R are untouched, the caller factors it by reflectors.
+// orthonormal, rinv: qr_impl's optional out-arguments.
 template <class T>
-int cholqr2(qil_context* ctx, long long m, long long n, T* A, long long lda, T* R, long long ldr, bool* done) {
+int cholqr2(qil_context* ctx, long long m, long long n, T* A, long long lda, T* R, long long ldr, bool* done, bool* orthonormal,
+            void** rinv) {
     *done = false;
     const int opH = sizeof(T) == 16 ? 2 : 1;
     void *g = nullptr, *rx = nullptr, *r2 = nullptr, *x2 = nullptr, *q1 = nullptr;
@@ -2475,37 +2481,29 @@ int cholqr2(qil_context* ctx, long long m, long long n, T* A, long long lda, T* 
     }
     QIL_TRY(gemm_dispatch<T>(ctx, 0, 0, m, n, n, Q1, m, X2, n, A, lda));
     if (R) QIL_TRY(gemm_dispatch<T>(ctx, 0, 0, n, n, n, R2, n, R1, n, R, ldr));
-    if (R && ctx->want_rinv) {                                   // R^-1 = R1^-1 R2^-1 for the certificate that follows
-        if (ctx->rinv) qil_ctx_free(ctx, ctx->rinv);
-        ctx->rinv = nullptr;
-        QIL_TRY(qil_ctx_alloc(ctx, nn, &ctx->rinv));
-        ctx->rinv_serial = ctx->alloc_serial;                    // (the block just allocated)
-        QIL_TRY(gemm_dispatch<T>(ctx, 0, 0, n, n, n, X1, n, X2, n, static_cast<T*>(ctx->rinv), n));
-        ctx->rinv_for = R;
+    if (R && rinv) {                                             // R^-1 = R1^-1 R2^-1 for the certificate that follows
+        QIL_TRY(qil_ctx_alloc(ctx, nn, rinv));
+        QIL_TRY(gemm_dispatch<T>(ctx, 0, 0, n, n, n, X1, n, X2, n, static_cast<T*>(*rinv), n));
     }
     release();
     *done = true;
     // Q2 = Q1 (I - U) with Q1^H Q1 = I + E measured, n max |e| <= 3e-8: Q2^H Q2 = I + O(|E|^2), below 1e-15 -- the check that
     // qr_reorthogonalise would run (a Gram product, a max-reduction, a read-back: ~25 us per QR) can only confirm it
-    ctx->qr_orthonormal = first_order;
+    if (orthonormal) *orthonormal = first_order;
     return QIL_OK;
 }
 
-// *certified = true iff no singular value of the operand whose thin-QR factor is R can be dropped at `cutoff`
+// *certified = true iff no singular value of the operand whose thin-QR factor is R can be dropped at `cutoff`.
+// rinv: R^-1 (packed, ld k) as CholeskyQR2 left it, or null (then it is computed); freed here.
 template <class T>
-int certify_no_truncation(qil_context* ctx, const T* R, long long ldr, int k, double cutoff, bool* certified) {
+int certify_no_truncation(qil_context* ctx, const T* R, long long ldr, int k, double cutoff, void* rinv, bool* certified) {
     *certified = false;
-    struct drop_rinv {                                           // whatever happens, no inverse outlives this call
-        qil_context* c;
-        ~drop_rinv() {
-            if (c->rinv) qil_ctx_free(c, c->rinv);
-            c->rinv = nullptr;
-            c->rinv_for = nullptr;
-        }
-    } guard{ctx};
     const bool enabled = !(getenv("QIL_SVD_CERT") && atoi(getenv("QIL_SVD_CERT")) == 0);   // tuning aid (read per call: the tests toggle it)
-    if (!enabled || !(cutoff > 0.0) || k < 2) return QIL_OK;
-    void *st = nullptr, *xinv = nullptr;
+    if (!enabled || !(cutoff > 0.0) || k < 2) {
+        if (rinv) qil_ctx_free(ctx, rinv);
+        return QIL_OK;
+    }
+    void *st = nullptr, *xinv = rinv;
     constexpr int NB = 64;
     QIL_TRY(qil_ctx_alloc(ctx, 2 * NB * sizeof(double), &st));
     double hb[2 * NB];
@@ -2526,13 +2524,10 @@ int certify_no_truncation(qil_context* ctx, const T* R, long long ldr, int k, do
     // sigma_min <= min |r_ii|: a small diagonal entry settles it the other way without inverting anything
     if (!(fro2 > 0.0) || !std::isfinite(fro2) || !(h[1] > 16.0 * cutoff * fro2 * k)) {
         qil_ctx_free(ctx, st);
+        if (xinv) qil_ctx_free(ctx, xinv);
         return QIL_OK;
     }
-    if (ctx->rinv && ctx->rinv_for == R) {                       // CholeskyQR2 left R^-1 behind (packed, ld k)
-        xinv = ctx->rinv;
-        ctx->rinv = nullptr;
-        ctx->rinv_for = nullptr;
-    } else {
+    if (!xinv) {
         QIL_TRY(qil_ctx_alloc(ctx, (size_t)k * k * sizeof(T), &xinv));
         QIL_TRY(trtri_upper<T>(ctx, R, ldr, k, static_cast<T*>(xinv)));
     }
@@ -3216,13 +3211,14 @@ int svd_impl(qil_context* ctx, long long m, long long n, T* A, long long lda, T*
              long long ldvh, double negl_rel);
 
 // svd_left_mid's route for rank-deficient triangular factors (see there): R (k x k, ld k) = thin-QR factor of the tall operand,
-// Q (p x k, ldq) its basis, Xw (k x k workspace).  *done = 0: too few negligible rows, nothing written.
+// Q (p x k, ldq) its basis, Xw (k x k workspace).  Rows of R are dropped while their weight stays below deflate |R|_F^2.
+// *done = 0: too few negligible rows, nothing written.
 template <class T>
 int svd_left_mid(qil_context* ctx, long long p, long long q, T* B, long long ldb, T* Uiso, long long ldu, double* S_host,
-                 T* SVh, long long ldsvh, double negl_rel, int* handled, double cert_cutoff);
+                 T* SVh, long long ldsvh, double negl_rel, int* handled, double cert_cutoff, double deflate);
 template <class T>
 int svd_left_deflated(qil_context* ctx, long long p, long long k, const T* Q, long long ldq, const T* R, T* Xw, T* Uiso,
-                      long long ldu, double* S_host, T* SVh, long long ldsvh, double negl_rel, bool dbg, int* done) {
+                      long long ldu, double* S_host, T* SVh, long long ldsvh, double negl_rel, double deflate, bool dbg, int* done) {
     *done = 0;
     const int dtype = sizeof(T) == 16 ? QIL_C64 : QIL_F64;
     const unsigned gk = (unsigned)std::min<long long>((k * k + 255) / 256, 65536);
@@ -3247,7 +3243,7 @@ int svd_left_deflated(qil_context* ctx, long long p, long long k, const T* Q, lo
     double acc = 0.0;
     long long ndrop = 0;
     for (int j : order) {
-        if (!(acc + rn[(size_t)j] <= ctx->svd_deflate * total)) break;
+        if (!(acc + rn[(size_t)j] <= deflate * total)) break;
         acc += rn[(size_t)j];
         drop[(size_t)j] = 1;
         ++ndrop;
@@ -3283,7 +3279,7 @@ int svd_left_deflated(qil_context* ctx, long long p, long long k, const T* Q, lo
     qil_stage_commit(ctx, slot);
     // one-factor SVD of the wide block: Bk = Uk diag(S) V^H, SVk = diag(S) V^H
     int h2 = 0;
-    int st = svd_left_mid<T>(ctx, r, k, Bk, r, Uk, r, S_host, SVk, r, negl_rel, &h2, 0.0);
+    int st = svd_left_mid<T>(ctx, r, k, Bk, r, Uk, r, S_host, SVk, r, negl_rel, &h2, 0.0, deflate);
     if (st == QIL_OK && !h2) {                                   // outside the one-factor routine's range: the general SVD
         st = svd_impl<T>(ctx, r, k, Bk, r, Uk, r, S_host, SVk, r, negl_rel);
         if (st == QIL_OK) st = qil_dev_scale(ctx, dtype, 0, r, k, SVk, r, S_host);
@@ -3309,7 +3305,7 @@ int svd_left_deflated(qil_context* ctx, long long p, long long k, const T* Q, lo
 // S V^H = (S' V'^H) Q[:, K]^H.  Q (q x k, ldq); X is left intact.  *done = 0: nothing written.
 template <class T>
 int svd_left_deflated_wide(qil_context* ctx, long long k, long long q, const T* Q, long long ldq, const T* X, T* Uiso, long long ldu,
-                           double* S_host, T* SVh, long long ldsvh, double negl_rel, bool dbg, int* done) {
+                           double* S_host, T* SVh, long long ldsvh, double negl_rel, double deflate, bool dbg, int* done) {
     *done = 0;
     const int dtype = sizeof(T) == 16 ? QIL_C64 : QIL_F64;
     void* nrm = nullptr;
@@ -3331,7 +3327,7 @@ int svd_left_deflated_wide(qil_context* ctx, long long k, long long q, const T* 
     double acc = 0.0;
     long long ndrop = 0;
     for (int j : order) {
-        if (!(acc + rn[(size_t)j] <= ctx->svd_deflate * total)) break;
+        if (!(acc + rn[(size_t)j] <= deflate * total)) break;
         acc += rn[(size_t)j];
         drop[(size_t)j] = 1;
         ++ndrop;
@@ -3362,7 +3358,7 @@ int svd_left_deflated_wide(qil_context* ctx, long long k, long long q, const T* 
     QIL_TRY((qil_klaunch<gather_cols_k<T>>(ctx, dim3((unsigned)std::min<long long>((q * r + 255) / 256, 65536)), dim3(256), 0, Q, ldq, q, keepd, (const double*)nullptr, Qk, q, (int)r, 0)));
     qil_stage_commit(ctx, slot);
     int h2 = 0;
-    int st = svd_left_mid<T>(ctx, k, r, Xk, k, Uk, k, S_host, SVk, r, negl_rel, &h2, 0.0);
+    int st = svd_left_mid<T>(ctx, k, r, Xk, k, Uk, k, S_host, SVk, r, negl_rel, &h2, 0.0, deflate);
     if (st == QIL_OK && !h2) {
         st = svd_impl<T>(ctx, k, r, Xk, k, Uk, k, S_host, SVk, r, negl_rel);
         if (st == QIL_OK) st = qil_dev_scale(ctx, dtype, 0, r, r, SVk, r, S_host);
@@ -3384,7 +3380,7 @@ int svd_left_deflated_wide(qil_context* ctx, long long k, long long q, const T* 
 
 template <class T>
 int svd_left_mid(qil_context* ctx, long long p, long long q, T* B, long long ldb, T* Uiso, long long ldu, double* S_host,
-                 T* SVh, long long ldsvh, double negl_rel, int* handled, double cert_cutoff) {
+                 T* SVh, long long ldsvh, double negl_rel, int* handled, double cert_cutoff, double deflate) {
     *handled = 0;
     const long long k = std::min(p, q);
     if (k < 17 || k >= 640) return QIL_OK;
@@ -3434,13 +3430,12 @@ int svd_left_mid(qil_context* ctx, long long p, long long q, T* B, long long ldb
     const unsigned gk = (unsigned)std::min<long long>((k * k + 255) / 256, 65536);
     void *rbuf = nullptr, *xbuf = nullptr, *bh = nullptr, *flag = nullptr, *nrm = nullptr, *negl = nullptr, *wbuf = nullptr;
     void* permbuf = nullptr;                          // [q] column permutation, [q] its inverse (device), see "sorted by norm" below
+    void* rinv = nullptr;                             // R^-1 from CholeskyQR2 for the certificate (tall operands, cert_cutoff > 0)
     auto release = [&]() {
-        for (void* b : {rbuf, xbuf, bh, flag, nrm, negl, wbuf, permbuf})
+        for (void* b : {rbuf, xbuf, bh, flag, nrm, negl, wbuf, permbuf, rinv})
             if (b) qil_ctx_free(ctx, b);
         permbuf = nullptr;
-        if (ctx->rinv) qil_ctx_free(ctx, ctx->rinv);             // (an inverse CholeskyQR2 left for a certificate that did not run)
-        ctx->rinv = nullptr;
-        ctx->rinv_for = nullptr;
+        rinv = nullptr;
     };
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)(k * k) * sizeof(T), &rbuf));
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)(k * k) * sizeof(T), &xbuf));
@@ -3523,12 +3518,10 @@ int svd_left_mid(qil_context* ctx, long long p, long long q, T* B, long long ldb
         }
     }
     if (tall) {
-        ctx->want_rinv = cert_cutoff > 0.0;
-        const int qst = qr_impl<T>(ctx, p, q, B, ldb, R, k);
-        ctx->want_rinv = false;
-        QIL_TRY(qst);
+        bool known = false;
+        QIL_TRY(qr_impl<T>(ctx, p, q, B, ldb, R, k, &known, cert_cutoff > 0.0 ? &rinv : nullptr));
         bool ok = true;
-        QIL_TRY(qr_reorthogonalise<T>(ctx, p, q, B, ldb, R, k, dbg, &ok));
+        QIL_TRY(qr_reorthogonalise<T>(ctx, p, q, B, ldb, R, k, known, &rinv, dbg, &ok));
         if (!ok) {                                   // B = Q R reproduces the operand: hand it back intact
             void* tmp = nullptr;
             QIL_TRY(qil_ctx_alloc(ctx, (size_t)(p * q) * sizeof(T), &tmp));
@@ -3576,13 +3569,13 @@ int svd_left_mid(qil_context* ctx, long long p, long long q, T* B, long long ldb
             // truncation): rotating the k columns of R crawls (14-18 sweeps at 128 columns: the null space is a k - r fold
             // degenerate cluster), and most of the work is spent on directions the cutoff discards.  The rows of R say which:
             // dropping the rows with the smallest norms changes A by EXACTLY their weight (A = Q R), so rows are dropped while
-            // their weight stays below ctx->svd_deflate (1e-6 of the caller's cutoff) of the total, and the one-factor SVD of
+            // their weight stays below `deflate` (1e-6 of the caller's cutoff) of the total, and the one-factor SVD of
             // the remaining r x k block -- a wide, full-rank operand: QR of its r columns, r x r rotations -- gives the same
             // factors: U = Q[:, K] U_K, S V^H = S_K V_K^H.
             const bool deficient = std::isfinite(fro2) && fro2 >= grade_max * (double)k * dmin;
-            if (deficient && ctx->svd_deflate > 0.0 && k >= 64) {                // (such a factor never passes the certificate: min |r_ii| settles it)
+            if (deficient && deflate > 0.0 && k >= 64) {                         // (such a factor never passes the certificate: min |r_ii| settles it)
                 int done = 0;
-                QIL_TRY((svd_left_deflated<T>(ctx, p, k, Qm, ldq, R, X, Uiso, ldu, S_host, SVh, ldsvh, negl_rel, dbg, &done)));
+                QIL_TRY((svd_left_deflated<T>(ctx, p, k, Qm, ldq, R, X, Uiso, ldu, S_host, SVh, ldsvh, negl_rel, deflate, dbg, &done)));
                 if (done) {
                     QIL_TRY(put_back_columns(SVh, ldsvh, k));
                     lap("deflated route");
@@ -3597,8 +3590,9 @@ int svd_left_mid(qil_context* ctx, long long p, long long q, T* B, long long ldb
             void* r1 = nullptr;
             QIL_TRY(qil_ctx_alloc(ctx, (size_t)(k * k) * sizeof(T), &r1));
             QIL_TRY((qil_klaunch<conj_transpose_k<T>>(ctx, dim3(gk), dim3(256), 0, (const T*)R, k, k, k, X, k)));
-            QIL_TRY(qr_impl<T>(ctx, k, k, X, k, static_cast<T*>(r1), k));
-            QIL_TRY(qr_reorthogonalise<T>(ctx, k, k, X, k, static_cast<T*>(r1), k, dbg, nullptr));
+            bool known1 = false;
+            QIL_TRY(qr_impl<T>(ctx, k, k, X, k, static_cast<T*>(r1), k, &known1));
+            QIL_TRY(qr_reorthogonalise<T>(ctx, k, k, X, k, static_cast<T*>(r1), k, known1, &rinv, dbg, nullptr));
             QIL_TRY((qil_klaunch<conj_transpose_k<T>>(ctx, dim3(gk), dim3(256), 0, (const T*)r1, k, k, k, X, k)));
             qil_ctx_free(ctx, r1);
         } else {
@@ -3608,17 +3602,18 @@ int svd_left_mid(qil_context* ctx, long long p, long long q, T* B, long long ldb
         // B^H = Q R  =>  B = R^H Q^H: the left singular vectors of B are those of X = R^H
         QIL_TRY(qil_ctx_alloc(ctx, (size_t)(q * p) * sizeof(T), &bh));
         QIL_TRY((qil_klaunch<conj_transpose_k<T>>(ctx, dim3((unsigned)std::min<long long>((p * q + 255) / 256, 65536)), dim3(256), 0, (const T*)B, ldb, p, q, static_cast<T*>(bh), q)));
-        QIL_TRY(qr_impl<T>(ctx, q, p, static_cast<T*>(bh), q, R, k));
+        bool known = false;
+        QIL_TRY(qr_impl<T>(ctx, q, p, static_cast<T*>(bh), q, R, k, &known));
         bool ok = true;
-        QIL_TRY(qr_reorthogonalise<T>(ctx, q, p, static_cast<T*>(bh), q, R, k, dbg, &ok));
+        QIL_TRY(qr_reorthogonalise<T>(ctx, q, p, static_cast<T*>(bh), q, R, k, known, nullptr, dbg, &ok));
         if (!ok) {
             release();
             return QIL_OK;
         }
         QIL_TRY((qil_klaunch<conj_transpose_k<T>>(ctx, dim3(gk), dim3(256), 0, (const T*)R, k, k, k, X, k)));
-        if (ctx->svd_deflate > 0.0 && k >= 64) {                 // rank-deficient products: the negligible rows of R leave the problem
+        if (deflate > 0.0 && k >= 64) {                          // rank-deficient products: the negligible rows of R leave the problem
             int done = 0;
-            QIL_TRY((svd_left_deflated_wide<T>(ctx, k, q, static_cast<const T*>(bh), q, X, Uiso, ldu, S_host, SVh, ldsvh, negl_rel, dbg, &done)));
+            QIL_TRY((svd_left_deflated_wide<T>(ctx, k, q, static_cast<const T*>(bh), q, X, Uiso, ldu, S_host, SVh, ldsvh, negl_rel, deflate, dbg, &done)));
             if (done) {
                 lap("deflated route (wide)");
                 release();
@@ -3633,7 +3628,7 @@ int svd_left_mid(qil_context* ctx, long long p, long long q, T* B, long long ldb
         // the caller truncates by cutoff only and does not read the singular values: if nothing can be dropped, the thin
         // QR is the gauge step (*handled = 2, S_host untouched)
         bool certified = false;
-        QIL_TRY(certify_no_truncation<T>(ctx, R, k, (int)k, cert_cutoff, &certified));
+        QIL_TRY(certify_no_truncation<T>(ctx, R, k, (int)k, cert_cutoff, std::exchange(rinv, nullptr), &certified));   // (it frees R^-1)
         if (certified) {
             if (tall) {                                  // B = Q R: Uiso = Q (in B), S V^H = R
                 QIL_TRY(qil_dev_copy2d(ctx, Uiso, (size_t)ldu * sizeof(T), Qm, (size_t)ldq * sizeof(T), (size_t)p * sizeof(T), (size_t)k));
@@ -3846,9 +3841,10 @@ int svd_impl(qil_context* ctx, long long m, long long n, T* A, long long lda, T*
     static const long long qr_ratio = 8;
     if ((rows >= qr_ratio * cols && rows >= 512) || rt) {
         QIL_TRY(qil_ctx_alloc(ctx, (size_t)(cols * cols) * sizeof(T), &rbuf));
-        QIL_TRY(qr_impl<T>(ctx, rows, cols, Wk, ldw, static_cast<T*>(rbuf), cols));
+        bool known = false;
+        QIL_TRY(qr_impl<T>(ctx, rows, cols, Wk, ldw, static_cast<T*>(rbuf), cols, &known));
         bool q_ok = true;
-        QIL_TRY(qr_reorthogonalise<T>(ctx, rows, cols, Wk, ldw, static_cast<T*>(rbuf), cols, dbg, &q_ok));
+        QIL_TRY(qr_reorthogonalise<T>(ctx, rows, cols, Wk, ldw, static_cast<T*>(rbuf), cols, known, nullptr, dbg, &q_ok));
         if (!q_ok) {
             // the re-factorisations did not reach an orthonormal basis (spectra graded to rounding level on very tall
             // operands): Q R still reproduces the operand to rounding, so it is rebuilt and rotated as it is --
@@ -4196,9 +4192,9 @@ int tsqr_panel(qil_context* ctx, long long m, int b, T* P, long long lda, T* R, 
 //     MFMA GEMMs per pass (C = Q^H P, then P -= Q C in the second GEMM's epilogue) and orthonormalised internally by gs_fused -- the work is
 //     spread over the chip by the GEMMs and the launch count drops from ~5 n to ~7 n / 16.
 template <class T>
-int qr_impl(qil_context* ctx, long long m, long long n, T* A, long long lda, T* R, long long ldr) {
+int qr_impl(qil_context* ctx, long long m, long long n, T* A, long long lda, T* R, long long ldr, bool* orthonormal, void** rinv) {
     static const long long TALL = 2048;
-    ctx->qr_orthonormal = false;
+    if (orthonormal) *orthonormal = false;
     // Cholesky QR first where it pays (from a few panels on) and while it keeps succeeding on this context: a numerically
     // rank-deficient operand (product bonds, deficient sketches) costs the attempt a Gram product, a partial factorisation and
     // one synchronisation, so after a refusal the next attempts are skipped
@@ -4209,7 +4205,7 @@ int qr_impl(qil_context* ctx, long long m, long long n, T* A, long long lda, T* 
             --ctx->cholqr_skip;
         } else {
             bool done = false;
-            QIL_TRY(cholqr2<T>(ctx, m, n, A, lda, R, ldr, &done));
+            QIL_TRY(cholqr2<T>(ctx, m, n, A, lda, R, ldr, &done, orthonormal, rinv));
             if (done) return QIL_OK;
             ctx->cholqr_skip = 8;
         }
@@ -4626,12 +4622,13 @@ int qil_dev_svd(qil_context* ctx, int dtype, int64_t m, int64_t n, void* A, int6
 }
 
 int qil_dev_svd_left(qil_context* ctx, int dtype, int64_t p, int64_t q, void* B, int64_t ldb, void* Uiso, int64_t ldu,
-                     double* S_host, void* SVh, int64_t ldsvh, double negligible_rel, int* handled, double cert_cutoff) {
+                     double* S_host, void* SVh, int64_t ldsvh, double negligible_rel, int* handled, double cert_cutoff,
+                     double deflate) {
     if (dtype == QIL_C64)
         return svd_left_mid<c64>(ctx, p, q, static_cast<c64*>(B), ldb, static_cast<c64*>(Uiso), ldu, S_host,
-                                 static_cast<c64*>(SVh), ldsvh, negligible_rel, handled, cert_cutoff);
+                                 static_cast<c64*>(SVh), ldsvh, negligible_rel, handled, cert_cutoff, deflate);
     return svd_left_mid<double>(ctx, p, q, static_cast<double*>(B), ldb, static_cast<double*>(Uiso), ldu, S_host,
-                                static_cast<double*>(SVh), ldsvh, negligible_rel, handled, cert_cutoff);
+                                static_cast<double*>(SVh), ldsvh, negligible_rel, handled, cert_cutoff, deflate);
 }
 
 // thin QR of the tall orientation + the certificate, for operands outside the one-factor SVD's range (>= 640 columns):
@@ -4645,20 +4642,17 @@ static int qr_certified_t(qil_context* ctx, long long m, long long n, const T* A
         QIL_TRY(qil_dev_copy2d(ctx, Qout, (size_t)rows * sizeof(T), A, (size_t)lda * sizeof(T), (size_t)m * sizeof(T), (size_t)n));
     else
         QIL_TRY((qil_klaunch<conj_transpose_k<T>>(ctx, dim3((unsigned)std::min<long long>((m * n + 255) / 256, 65536)), dim3(256), 0, A, lda, m, n, Qout, rows)));
-    ctx->want_rinv = cutoff > 0.0;
-    const int qst = qr_impl<T>(ctx, rows, k, Qout, rows, Rout, k);
-    ctx->want_rinv = false;
-    QIL_TRY(qst);
+    bool known = false;
+    void* rinv = nullptr;                                        // R^-1 from CholeskyQR2 for the certificate
+    QIL_TRY(qr_impl<T>(ctx, rows, k, Qout, rows, Rout, k, &known, cutoff > 0.0 ? &rinv : nullptr));
     bool ok = true;
-    QIL_TRY(qr_reorthogonalise<T>(ctx, rows, k, Qout, rows, Rout, k, false, &ok));
+    QIL_TRY(qr_reorthogonalise<T>(ctx, rows, k, Qout, rows, Rout, k, known, &rinv, false, &ok));
     *certified = false;
     if (!ok) {
-        if (ctx->rinv) qil_ctx_free(ctx, ctx->rinv);
-        ctx->rinv = nullptr;
-        ctx->rinv_for = nullptr;
+        if (rinv) qil_ctx_free(ctx, rinv);
         return QIL_OK;
     }
-    return certify_no_truncation<T>(ctx, Rout, k, (int)k, cutoff, certified);
+    return certify_no_truncation<T>(ctx, Rout, k, (int)k, cutoff, rinv, certified);
 }
 int qil_dev_set_identity(qil_context* ctx, int dtype, void* V, int64_t ldv, int64_t n) {
     const unsigned g = (unsigned)std::min<long long>((n * n + 255) / 256, 65536);
@@ -4703,12 +4697,13 @@ int qil_dev_diag_abs2(qil_context* ctx, int dtype, const void* R, int64_t ldr, i
 int qil_dev_qr_positive(qil_context* ctx, int dtype, int64_t m, int64_t n, void* A, int64_t lda, void* R,
                         int64_t ldr, bool orthonormal) {
     QIL_REQUIRE(m >= n, QIL_EINVAL_ARG, "qr: needs m >= n (got %lld x %lld)", (long long)m, (long long)n);
+    bool known = false;
     if (dtype == QIL_C64) {
-        QIL_TRY(qr_impl<c64>(ctx, m, n, (c64*)A, lda, (c64*)R, ldr));
-        return orthonormal ? qr_reorthogonalise<c64>(ctx, m, n, (c64*)A, lda, (c64*)R, ldr, false) : QIL_OK;
+        QIL_TRY(qr_impl<c64>(ctx, m, n, (c64*)A, lda, (c64*)R, ldr, &known));
+        return orthonormal ? qr_reorthogonalise<c64>(ctx, m, n, (c64*)A, lda, (c64*)R, ldr, known, nullptr, false) : QIL_OK;
     }
-    QIL_TRY(qr_impl<double>(ctx, m, n, (double*)A, lda, (double*)R, ldr));
-    return orthonormal ? qr_reorthogonalise<double>(ctx, m, n, (double*)A, lda, (double*)R, ldr, false) : QIL_OK;
+    QIL_TRY(qr_impl<double>(ctx, m, n, (double*)A, lda, (double*)R, ldr, &known));
+    return orthonormal ? qr_reorthogonalise<double>(ctx, m, n, (double*)A, lda, (double*)R, ldr, known, nullptr, false) : QIL_OK;
 }
 
 int64_t qil_truncation_rank(const double* S, int64_t n, double cutoff, bool use_cutoff, int64_t maxdim,

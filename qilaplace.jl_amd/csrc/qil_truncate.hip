@@ -228,23 +228,20 @@ int svd_trunc_dev(qil_context* ctx, int dtype, int64_t m, int64_t n, void* A, in
     // Gauge sweeps keep ONE factor as the site (isometric) and multiply the other into the neighbour: the mid-size path
     // that accumulates no rotation matrix (qil_dev_svd_left) serves them; everything else takes the general SVD.
     int handled = 0;
-    struct deflate_scope {                                       // the one-factor SVD may drop 1e-6 of what the cutoff allows
-        qil_context* c;
-        ~deflate_scope() { c->svd_deflate = 0.0; }
-    } dscope{ctx};
+    // the one-factor SVD may drop 1e-6 of what the cutoff allows with the negligible rows of its triangular factor
     // (the weight w the one-factor SVD may drop costs sqrt(w) in amplitude.  Measured on the exact compress! of the bond-1008 zT
     // product, w = 1e-3 / 1e-5 / 1e-6 / 1e-8 of the cutoff: 253-260 / 282 / 266-273 / 270 ms (295 without), state against the
     // CPU oracle's compress! 1.2e-7 / 1.6e-9 / 4e-10 / 3e-10 (1e-11 without; the algorithm's own error there is 1.8e-5))
-    ctx->svd_deflate = (use_cutoff && cutoff > 0.0) ? 1e-6 * cutoff : 0.0;
+    const double deflate = (use_cutoff && cutoff > 0.0) ? 1e-6 * cutoff : 0.0;
     if (absorb == 2) {            // U isometric, S Vh absorbed
-        QIL_TRY(qil_dev_svd_left(ctx, dtype, m, n, A, lda, U, m, S.data(), Vh, r0, negl_rel, &handled, cert_cutoff));
+        QIL_TRY(qil_dev_svd_left(ctx, dtype, m, n, A, lda, U, m, S.data(), Vh, r0, negl_rel, &handled, cert_cutoff, deflate));
     } else if (absorb == 1) {     // Vh isometric, U S absorbed: the same problem on A^H
         void *At = nullptr, *Vi = nullptr, *SU = nullptr;
         QIL_TRY(qil_ctx_alloc(ctx, (size_t)(m * n) * e, &At));
         QIL_TRY(qil_dev_transpose(ctx, dtype, 1, m, n, A, lda, At, n));                         // A^H (n x m)
         QIL_TRY(qil_ctx_alloc(ctx, (size_t)(n * r0) * e, &Vi));
         QIL_TRY(qil_ctx_alloc(ctx, (size_t)(r0 * m) * e, &SU));
-        QIL_TRY(qil_dev_svd_left(ctx, dtype, n, m, At, n, Vi, n, S.data(), SU, r0, negl_rel, &handled, cert_cutoff));
+        QIL_TRY(qil_dev_svd_left(ctx, dtype, n, m, At, n, Vi, n, S.data(), SU, r0, negl_rel, &handled, cert_cutoff, deflate));
         if (handled) {
             QIL_TRY(qil_dev_transpose(ctx, dtype, 1, n, r0, Vi, n, Vh, r0));                    // Vh = V^H   (r0 x n)
             QIL_TRY(qil_dev_transpose(ctx, dtype, 1, r0, m, SU, r0, U, m));                     // U S = (S U^H)^H
