@@ -207,6 +207,27 @@ QIL_API int qil_norm(const qil_mps* psi, double* out);
  * Bonds <= 64 (f64) / 32 (c64) take one fused f64-MFMA kernel per site, larger ones GEMMs and a reduce-and-choose kernel. */
 QIL_API int qil_sample(const qil_mps* psi, int64_t nb, uint64_t seed, const double* uniforms, uint8_t* bits_out,
                        double* prob_out);
+/* Top-k coefficient search: the k configurations x with the largest |psi_x|, and a bound on what the search may have missed.
+ * A beam search over prefixes x_1..x_i ranked by their marginal weight w(prefix) = sum over completions of |psi_x|^2, which
+ * bounds every completion: |psi_x|^2 <= w(prefix).
+ *   Right environments as in qil_sample, with their normalisation kept as a cumulative log-scale (log |psi|^2).
+ *   The frontier starts as one empty prefix, v = [1].  At site i every prefix yields two children, T_s = v A_i[:, s, :] with
+ *   weight Re(T_s R_i T_s^H); the at most `beam` children of largest weight are kept (ties: the lower parent row, then bit 0),
+ *   rescaled with a per-row log-scale; the largest weight dropped is recorded.  After the last site the frontier holds
+ *   complete configurations with their exact values.
+ * bits_out: host, k x n_tensors bytes, the layout of qil_coefficient_batch's bits.  val_out: host, k complex (re, im), the
+ * numbers qil_coefficient_batch gives on those rows (amplitude included), in descending |value| (equal magnitudes: the order
+ * of the candidates).  bound_out: sqrt(largest weight dropped before the last site), on the scale of the values (amplitude
+ * included), 0 if nothing was dropped.  The result is certified to be the exact top-k when bound < |value_k| (1 - 1e-10):
+ * the slack covers the rounding of the weights (relative ~1e-15 per site).
+ * Bit-identical from run to run; nothing is chunked.  Limits: beam <= min(2^29, 2^30 / (3 chi s + 4 n + 64)), chi = the largest
+ * bond, s = 8 (f64) / 16 (c64), n = n_tensors: the frontier, both children and the per-row bookkeeping fit in 1 GiB (T_s R
+ * adds 2 chi s bytes per row).  At n = 24 paired, chi = 64, c64 the cap is 322638.
+ * Errors, before the context is activated: QIL_EINVAL_ARG for a null psi, k < 0, beam < k, beam above the cap,
+ * k > 2^n_tensors (n_tensors <= 62) or, when k > 0, a null output.  QIL_EDOMAIN for a state of norm 0.  k = 0 is a no-op.
+ * Route: qil_dev_gemm for T = V A and T_s R at any bond size, a scoring kernel for both children, a radix select and a
+ * prefix-scan compaction on the device. */
+QIL_API int qil_top_k(const qil_mps* psi, int64_t k, int64_t beam, uint8_t* bits_out, double* val_out, double* bound_out);
 
 /* ------------------------------------------------------------------ overlaps (ITensors' inner on device chains) */
 /* <phi|psi> = amp_phi * amp_psi * sum_x conj(phi_x) psi_x

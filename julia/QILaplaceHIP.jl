@@ -18,7 +18,7 @@ using ..ApplyMPO: _as_single_site_mpo
 
 export DeviceMPS, DeviceMPO, to_device, to_host, signal_mps_device, marginal, mps_block, apply_compress,
     compress_mpo!, build_dt_mpo_batch, build_qft_mpo_device, build_zt_qft_chain_device, apply_coefficient_sweep, apply!, rsvd_device, svd_device,
-    Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm, sample
+    Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm, sample, top_k
 
 const LIB = get(ENV, "QILHIP_LIB", "libqilhip.so")
 
@@ -247,6 +247,18 @@ function sample(psi::DeviceMPS, nsamples::Integer; seed::Integer=1234)
     check(ccall((:qil_sample, LIB), Cint, (Ptr{Cvoid}, Int64, UInt64, Ptr{Cdouble}, Ptr{UInt8}, Ptr{Cdouble}),
                 psi.h, nsamples, UInt64(seed), C_NULL, b, p))
     return Matrix{UInt8}(permutedims(b)), p
+end
+# top-k coefficient search: the k bit rows with the largest |psi_x| (k x length(psi), as coefficient takes them), their values
+# (amplitude included, descending |value|), the bound on what the beam search dropped, and whether the result is certified
+# exact (bound < |value_k| (1 - 1e-10))
+function top_k(psi::DeviceMPS, k::Integer; beam::Integer=4096)
+    n = length(psi)
+    b = Matrix{UInt8}(undef, n, k)                                              # the ABI's row-major k x n
+    v = Vector{ComplexF64}(undef, k)
+    bound = Ref{Cdouble}(0.0)
+    check(ccall((:qil_top_k, LIB), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{UInt8}, Ptr{Cvoid}, Ref{Cdouble}),
+                psi.h, k, beam, b, v, bound))
+    return Matrix{UInt8}(permutedims(b)), v, bound[], k == 0 || bound[] < abs(v[end]) * (1 - 1e-10)
 end
 function mps_to_vector(psi::DeviceMPS; reverse::Bool=false)                                        # mps.jl:716
     d = Ref{Cint}(0)

@@ -253,6 +253,12 @@ struct qil_call_scope {
     qil_call_scope& operator=(const qil_call_scope&) = delete;
 };
 
+// (qil_sample.hip) the trace-normalised right environments of qil_sample: R_n = [1], R_{i-1} = sum_s A_i[:, s, :] R_i A_i[:, s, :]^H
+// scaled by 1 / Re tr, in one pool block (*Rall, bond b's chi_b x chi_b matrix at element roff[b]).  log_norm2 (nullable,
+// host) receives the sum of the log traces, log |psi|^2 without the amplitude.  QIL_EDOMAIN ("<verb>: the state has zero norm")
+// for a state of norm 0.
+int qil_dev_right_envs(const struct qil_mps* psi, const char* verb, void** Rall, std::vector<long long>& roff, double* log_norm2);
+
 // ---------------------------------------------------------------- device linear algebra (qil_linalg.hip)
 // All matrices column-major on the device, dtype QIL_F64/QIL_C64.
 // C[m x n] = opA(A) * opB(B); op: 0 = N, 1 = T, 2 = H, 3 = conj (no transpose).  alpha = 1, beta = 0.

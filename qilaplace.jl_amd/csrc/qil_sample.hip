@@ -2,7 +2,8 @@
 // environment pass and one left-to-right conditional sweep per batch of samples.  Nothing crosses to the host between sites.
 //
 //   environments   R_n = [1],  R_{i-1} = sum_s A_i[:, s, :] R_i A_i[:, s, :]^H      (two GEMMs per site, right to left)
-//                  each R_i scaled by 1 / trace on the device (only ratios matter)
+//                  each R_i scaled by 1 / trace on the device (only ratios matter); qil_top_k builds the same environments
+//                  (qil_dev_right_envs) and also sums the log traces, the log of |psi|^2
 //   sweep          per sample r: v = [1];  at site i  w_s = v A_i[:, s, :],  q_s = Re(w_s R_i w_s^H),
 //                  s = 0 iff u_{r,i} (q_0 + q_1) < q_0,  v <- w_s / sqrt(q_s),  p_r *= q_s / (q_0 + q_1)
 //
@@ -71,14 +72,18 @@ __global__ void start_rows(T* __restrict__ V, double* __restrict__ prob, long lo
         prob[t] = 1.0;
     }
 }
-// inv[0] = 1 / Re tr(R) (R m x m), or 1 when the trace is not positive (a zero environment stays zero)
+// inv[0] = 1 / Re tr(R) (R m x m), or 1 when the trace is not positive (a zero environment stays zero); logsum (nullable)
+// accumulates log tr(R) over the sites, so that the unnormalised environment is R e^logsum
 template <class T>
-__global__ __launch_bounds__(256) void env_trace(const T* __restrict__ R, int m, double* __restrict__ inv) {
+__global__ __launch_bounds__(256) void env_trace(const T* __restrict__ R, int m, double* __restrict__ inv, double* __restrict__ logsum) {
     __shared__ double lds[4];
     double v[1] = {0.0};
     for (int j = threadIdx.x; j < m; j += 256) v[0] += re_of(R[j + (long long)m * j]);
     block_sum<1>(v, lds);
-    if (threadIdx.x == 0) inv[0] = v[0] > 0.0 ? 1.0 / v[0] : 1.0;
+    if (threadIdx.x == 0) {
+        inv[0] = v[0] > 0.0 ? 1.0 / v[0] : 1.0;
+        if (logsum && v[0] > 0.0) logsum[0] += log(v[0]);
+    }
 }
 template <class T>
 __global__ void env_scale(T* __restrict__ R, long long total, const double* __restrict__ inv) {
@@ -290,6 +295,53 @@ __global__ __launch_bounds__(kChooseRows* kChooseGroups) void gemm_choose(const 
             Vn[row + rows * (long long)beta] = scale_t(Tm[row + rows * (ssel[r] + 2LL * beta)], sscl[r]);
 }
 
+// ---- right environments (shared with qil_top_k) -------------------------------------------------------------------
+template <class T>
+static int right_envs(const qil_mps* psi, const char* verb, void** Rall, std::vector<long long>& roff, double* log_norm2) {
+    qil_context* ctx = psi->ctx;
+    const int dt = psi->dtype;
+    const size_t e = sizeof(T);
+    const int64_t n = psi->n();
+    const std::vector<int64_t>& d = psi->dims;
+    long long maxT = 1, envsum = 0;
+    roff.assign((size_t)n + 1, 0);
+    for (int64_t b = 0; b <= n; ++b) {
+        roff[(size_t)b] = envsum;
+        envsum += d[(size_t)b] * d[(size_t)b];
+    }
+    for (int64_t i = 0; i < n; ++i) maxT = std::max<long long>(maxT, 2 * d[(size_t)i] * d[(size_t)i + 1]);
+    void *Tenv = nullptr, *inv = nullptr;
+    QIL_TRY(qil_ctx_alloc(ctx, (size_t)envsum * e, Rall));
+    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxT * e, &Tenv));
+    QIL_TRY(qil_ctx_alloc(ctx, log_norm2 ? 16 : 8, &inv));
+    T* Rb = static_cast<T*>(*Rall);
+    double* logsum = log_norm2 ? static_cast<double*>(inv) + 1 : nullptr;
+    if (logsum) QIL_HIP(hipMemsetAsync(logsum, 0, 8, qil_stream(ctx)));
+    hipLaunchKernelGGL(set_one<T>, dim3(1), dim3(64), 0, qil_stream(ctx), Rb + roff[(size_t)n]);
+    QIL_HIP(hipGetLastError());
+    for (int64_t i = n - 1; i >= 0; --i) {
+        const int64_t cl = d[(size_t)i], cr = d[(size_t)i + 1];
+        const void* A = psi->site[(size_t)i];
+        // T (2 chi_l x chi_r) = A (rows alpha + chi_l s) R_{i+1};  R_i (chi_l x chi_l) = T (chi_l x 2 chi_r) A^H
+        QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, 2 * cl, cr, cr, A, 2 * cl, Rb + roff[(size_t)i + 1], cr, Tenv, 2 * cl));
+        QIL_TRY(qil_dev_gemm(ctx, dt, 0, 2, cl, cl, 2 * cr, Tenv, cl, A, cl, Rb + roff[(size_t)i], cl));
+        hipLaunchKernelGGL(env_trace<T>, dim3(1), dim3(256), 0, qil_stream(ctx), (const T*)(Rb + roff[(size_t)i]), (int)cl, (double*)inv,
+                           logsum);
+        hipLaunchKernelGGL(env_scale<T>, dim3(grid_for(cl * cl)), dim3(256), 0, qil_stream(ctx), Rb + roff[(size_t)i], (long long)(cl * cl),
+                           (const double*)inv);
+        QIL_HIP(hipGetLastError());
+    }
+    {
+        double h[2] = {0.0, 0.0};
+        QIL_TRY(qil_read_back(ctx, h, Rb + roff[0], e));
+        QIL_REQUIRE(h[0] > 0.0, QIL_EDOMAIN, "%s: the state has zero norm", verb);
+        if (logsum) QIL_TRY(qil_read_back(ctx, log_norm2, logsum, 8));
+    }
+    qil_ctx_free(ctx, Tenv);
+    qil_ctx_free(ctx, inv);
+    return QIL_OK;
+}
+
 // ---- the call -----------------------------------------------------------------------------------------------------
 template <class T>
 static int sample_impl(const qil_mps* psi, int64_t nb, uint64_t seed, const double* uniforms, uint8_t* bits_out, double* prob_out) {
@@ -298,17 +350,12 @@ static int sample_impl(const qil_mps* psi, int64_t nb, uint64_t seed, const doub
     const size_t e = sizeof(T);
     const int64_t n = psi->n();
     const std::vector<int64_t>& d = psi->dims;
-    long long maxchi = 1, maxT = 1, sitesum = 0, envsum = 0;
-    std::vector<long long> roff((size_t)n + 1), soff((size_t)n);
-    for (int64_t b = 0; b <= n; ++b) {
-        roff[(size_t)b] = envsum;
-        envsum += d[(size_t)b] * d[(size_t)b];
-        maxchi = std::max<long long>(maxchi, d[(size_t)b]);
-    }
+    long long maxchi = 1, sitesum = 0;
+    std::vector<long long> roff, soff((size_t)n);
+    for (int64_t b = 0; b <= n; ++b) maxchi = std::max<long long>(maxchi, d[(size_t)b]);
     for (int64_t i = 0; i < n; ++i) {
         soff[(size_t)i] = sitesum;
         sitesum += 2 * d[(size_t)i] * d[(size_t)i + 1];
-        maxT = std::max<long long>(maxT, 2 * d[(size_t)i] * d[(size_t)i + 1]);
     }
     // route: the fused kernel holds chi_r <= 128 in LDS.  Measured crossover (n = 24 paired, nb = 2^16, median of 10; MEASUREMENTS
     // section 7): f64 fused 4.9 vs GEMM 5.9 ms at chi 64, 25.1 vs 12.8 at 128; c64 3.4 vs 6.0 at chi 32, 11.0 vs 10.7 at 64 (and
@@ -321,31 +368,9 @@ static int sample_impl(const qil_mps* psi, int64_t nb, uint64_t seed, const doub
     else if (route && !strcmp(route, "gemm")) fused = false;
 
     // ---- environments, right to left
-    void *Rall = nullptr, *Tenv = nullptr, *inv = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)envsum * e, &Rall));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxT * e, &Tenv));
-    QIL_TRY(qil_ctx_alloc(ctx, 8, &inv));
+    void* Rall = nullptr;
+    QIL_TRY(right_envs<T>(psi, "sample", &Rall, roff, nullptr));
     T* Rb = static_cast<T*>(Rall);
-    hipLaunchKernelGGL(set_one<T>, dim3(1), dim3(64), 0, qil_stream(ctx), Rb + roff[(size_t)n]);
-    QIL_HIP(hipGetLastError());
-    for (int64_t i = n - 1; i >= 0; --i) {
-        const int64_t cl = d[(size_t)i], cr = d[(size_t)i + 1];
-        const void* A = psi->site[(size_t)i];
-        // T (2 chi_l x chi_r) = A (rows alpha + chi_l s) R_{i+1};  R_i (chi_l x chi_l) = T (chi_l x 2 chi_r) A^H
-        QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, 2 * cl, cr, cr, A, 2 * cl, Rb + roff[(size_t)i + 1], cr, Tenv, 2 * cl));
-        QIL_TRY(qil_dev_gemm(ctx, dt, 0, 2, cl, cl, 2 * cr, Tenv, cl, A, cl, Rb + roff[(size_t)i], cl));
-        hipLaunchKernelGGL(env_trace<T>, dim3(1), dim3(256), 0, qil_stream(ctx), (const T*)(Rb + roff[(size_t)i]), (int)cl, (double*)inv);
-        hipLaunchKernelGGL(env_scale<T>, dim3(grid_for(cl * cl)), dim3(256), 0, qil_stream(ctx), Rb + roff[(size_t)i], (long long)(cl * cl),
-                           (const double*)inv);
-        QIL_HIP(hipGetLastError());
-    }
-    {
-        double h[2] = {0.0, 0.0};
-        QIL_TRY(qil_read_back(ctx, h, Rb + roff[0], e));
-        QIL_REQUIRE(h[0] > 0.0, QIL_EDOMAIN, "sample: the state has zero norm");
-    }
-    qil_ctx_free(ctx, Tenv);
-    qil_ctx_free(ctx, inv);
 
     // ---- the sweep, in chunks of rows (row buffers ~1 GB)
     const long long per_row = (long long)(fused ? 2 : 6) * maxchi * (long long)e + n + 8 + (uniforms ? 8 * n : 0);
@@ -405,6 +430,11 @@ static int sample_impl(const qil_mps* psi, int64_t nb, uint64_t seed, const doub
 }
 
 }  // namespace
+
+int qil_dev_right_envs(const qil_mps* psi, const char* verb, void** Rall, std::vector<long long>& roff, double* log_norm2) {
+    if (psi->dtype == QIL_C64) return right_envs<c64>(psi, verb, Rall, roff, log_norm2);
+    return right_envs<double>(psi, verb, Rall, roff, log_norm2);
+}
 
 extern "C" int qil_sample(const qil_mps* psi, int64_t nb, uint64_t seed, const double* uniforms, uint8_t* bits_out, double* prob_out) {
     QIL_REQUIRE(psi, QIL_EINVAL_ARG, "sample: null argument");

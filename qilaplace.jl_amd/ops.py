@@ -6,6 +6,7 @@
   norm               src/mps.jl:754-771
   inner              ITensors' inner(phi, psi) / inner(phi, W, psi) on device chains (no reference counterpart)
   sample             ITensors' sample(::MPS) on device chains (no reference counterpart)
+  top_k              the k largest |psi_x| by a certified beam search (no reference counterpart: replaces argmax over grid scans)
   canonicalize       src/mps.jl:787-847, 866-901   (Julia: canonicalize!)
   compress           src/mps.jl:913-999            (Julia: compress!)
   signal_mps         src/signals/SignalConverters.jl:228-233
@@ -396,13 +397,60 @@ def sample(psi, nsamples, seed=1234, uniforms=None, bits=False):
     probs = np.zeros(nb, dtype=np.float64)
     L.check(L.lib.qil_sample(psi.handle, nb, int(seed) & 0xFFFFFFFFFFFFFFFF, u_ptr, out.ctypes.data_as(C.POINTER(C.c_uint8)),
                              probs.ctypes.data_as(C.POINTER(C.c_double))))
+    return _decode_rows(out, paired, bits), probs
+
+
+def _decode_rows(out, paired, bits):
+    """(nb, n) bit rows -> the configurations `sample` and `top_k` return: the rows themselves (bits=True), (k, l) pairs for a
+    ZTMPS (lsb(k) on the main sites, lsb(l) on the copy sites), big-endian indices (site 1 = MSB) otherwise."""
     if bits:
-        return out, probs
+        return out
+    n = out.shape[1]
     if paired:
         w = np.int64(1) << np.arange(n // 2, dtype=np.int64)
-        return (out[:, 0::2].astype(np.int64) @ w, out[:, 1::2].astype(np.int64) @ w), probs
+        return out[:, 0::2].astype(np.int64) @ w, out[:, 1::2].astype(np.int64) @ w
     w = np.int64(1) << np.arange(n - 1, -1, -1, dtype=np.int64)
-    return out.astype(np.int64) @ w, probs
+    return out.astype(np.int64) @ w
+
+
+# ---------------------------------------------------------------- top-k search
+TOP_K_SLACK = 1e-10
+
+
+def top_k(psi, k=1, beam=4096, bits=False):
+    """The k configurations x with the largest |psi_x| (amplitude included), by a beam search over prefixes ranked by their
+    marginal weight on the device (include/qilaplace_hip.h, qil_top_k).
+
+    Returns (configs, values, bound, certified).  configs are decoded as `sample` decodes them (big-endian indices for a
+    SignalMPS, (k, l) pairs for a ZTMPS, the raw (k, n) uint8 rows with bits=True).  values: descending |value|, the numbers
+    `coefficient_batch` gives on those rows (float for a real state, complex otherwise).  bound: the square root of the largest
+    prefix weight the search dropped, on the scale of the values; 0 when nothing was dropped.  certified: bound <
+    |values[-1]| (1 - 1e-10), in which case the result is the exact top-k.  beam = 2**n_tensors (when it fits the cap
+    documented in the header) never drops anything."""
+    if not isinstance(psi, SignalMPS):
+        raise TypeError("top_k: unsupported operand types")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or isinstance(beam, bool) or not isinstance(beam, (int, np.integer)):
+        raise TypeError("top_k: k and beam must be integers")
+    k, beam = int(k), int(beam)
+    if k < 0:
+        raise ValueError("top_k: k must be non-negative")
+    if beam < k:
+        raise ValueError(f"top_k: beam ({beam}) must be at least k ({k})")
+    n = _ntensors(psi)
+    paired = isinstance(psi, ZTMPS)
+    if n <= 62 and k > (1 << n):
+        raise ValueError(f"top_k: k ({k}) exceeds the 2^{n} configurations")
+    if not bits and (n if not paired else n // 2) > 62:
+        raise ValueError(f"top_k: {n} sites do not fit an integer index; use bits=True")
+    out = np.zeros((k, n), dtype=np.uint8)
+    vals = np.zeros(k, dtype=np.complex128)
+    bound = C.c_double(0.0)
+    L.check(L.lib.qil_top_k(psi.handle, k, beam, out.ctypes.data_as(C.POINTER(C.c_uint8)),
+                            vals.ctypes.data_as(C.POINTER(C.c_double)), C.byref(bound)))
+    bound = float(bound.value)
+    certified = k == 0 or bound < abs(vals[-1]) * (1.0 - TOP_K_SLACK)
+    values = vals if psi.dtype == np.complex128 else vals.real.copy()
+    return _decode_rows(out, paired, bits), values, bound, bool(certified)
 
 
 # ---------------------------------------------------------------- truncation
