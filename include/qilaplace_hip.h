@@ -243,6 +243,32 @@ QIL_API int qil_apply_inner(const qil_mps* phi, const qil_mpo* W, const qil_mps*
  * (without amplitude, as qil_norm / mps.jl:754-771).  (W, psi) pass the checks of qil_apply.              */
 QIL_API int qil_apply_norm(const qil_mpo* W, const qil_mps* psi, double* out);
 
+/* ------------------------------------------------------------------ element-wise products, adjoints (no reference counterpart) */
+/* The element-wise (Hadamard) product out_x = (conj?)(phi_x) psi_x, materialised: amplitude amp_phi * amp_psi, dtype
+ * promote(phi, psi), psi's site ids and paired flag, bonds chi_phi * chi_psi.  Site tensors in the fused layout of qil_apply
+ * with phi in the operator's place,
+ *   C_i[(a, alpha), s, (b, beta)] = phi_i[a, s, b] psi_i[alpha, s, beta],   row = alpha + chi_l a,  col = beta + chi_r b,
+ * element for element what qil_apply(qil_mpo_diagonal(phi), psi) writes (for amp_phi = 1, which the diagonal operator folds
+ * into its first tensor).  conj_phi != 0 conjugates phi.  One grouped launch for all sites, HBM-store bound.
+ * phi and psi: same context, same paired flag (QIL_EINVAL_ARG), same number of sites (QIL_EINVAL_LENGTH), same site ids
+ * (QIL_EINVAL_SITES), all checked before the context is activated; bonds and dtypes (f64 / c64) are free.            */
+QIL_API int qil_hadamard(const qil_mps* phi, int conj_phi, const qil_mps* psi, qil_mps** out);
+/* diag(phi) as an MPO with phi's bonds, site ids, paired flag and dtype: W_i[a, s', s, b] = delta_{s s'} (conj?)(phi_i[a, s, b]),
+ * the amplitude multiplied into the first tensor (MPOs carry none).  The door from states to every verb that takes an
+ * operator: qil_apply_compress(diag(phi), psi) is the truncated product that never forms the (chi_phi chi_psi)^2 tensors;
+ * qil_apply_coefficient_batch, qil_apply_inner and qil_apply_norm read phi (.) psi without forming it.  One launch.   */
+QIL_API int qil_mpo_diagonal(const qil_mps* phi, int conj_phi, qil_mpo** out);
+/* W^dagger: out_i[a, s', s, b] = conj(W_i[a, s, s', b]); same bonds, site ids, paired flag and dtype.  Only moves and sign
+ * flips, so the result is exact and the adjoint of the adjoint is W bit for bit.  The adjoint of the QFT MPO is the inverse
+ * transform (to the unitarity its build cutoff leaves: 3e-9 ... 3e-7 at cutoff = 1e-14, n = 6 ... 10).  One launch.    */
+QIL_API int qil_mpo_adjoint(const qil_mpo* W, qil_mpo** out);
+/* compress!(phi (.) psi; maxdim, tol, sweeps) without the product tensors: bit-identical to
+ * qil_apply_compress(qil_mpo_diagonal(phi, conj_phi), psi, maxdim, tol, sweeps, zip_maxdim), with the diagonal operator a
+ * temporary of the call (nothing but the result outlives it, also when an allocation fails midway).  Operand checks as
+ * qil_hadamard, then the error codes of qil_apply_compress.                                                            */
+QIL_API int qil_hadamard_compress(const qil_mps* phi, int conj_phi, const qil_mps* psi, int64_t maxdim, double tol, int sweeps,
+                          int64_t zip_maxdim, qil_mps** out);
+
 /* ------------------------------------------------------------------ truncation (K1, K2) */
 /* canonicalize!(psi, direction; center, cutoff=1e-12, maxdim) src/mps.jl:787-847.
  * center = 0 selects the default (N for :right, 1 for :left); 1-based otherwise.    */

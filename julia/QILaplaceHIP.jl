@@ -9,7 +9,7 @@ module QILaplaceHIP
 using ITensors
 import ITensors: apply, inner, sample
 import Base: *, getindex, length
-import LinearAlgebra: norm
+import LinearAlgebra: norm, adjoint
 import ..Mps
 import ..Mps: coefficient, compress!, canonicalize!, mps_to_vector      # extended below with device methods
 using ..Mps: SignalMPS, ZTMPS, _as_signal_2n, _writeback_signal_2n
@@ -18,7 +18,8 @@ using ..ApplyMPO: _as_single_site_mpo
 
 export DeviceMPS, DeviceMPO, to_device, to_host, signal_mps_device, marginal, mps_block, apply_compress,
     compress_mpo!, build_dt_mpo_batch, build_qft_mpo_device, build_zt_qft_chain_device, apply_coefficient_sweep, apply!, rsvd_device, svd_device,
-    Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm, sample, top_k
+    Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm, sample, top_k,
+    hadamard, hadamard_compress, diagonal_mpo
 
 const LIB = get(ENV, "QILHIP_LIB", "libqilhip.so")
 
@@ -259,6 +260,33 @@ function top_k(psi::DeviceMPS, k::Integer; beam::Integer=4096)
     check(ccall((:qil_top_k, LIB), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{UInt8}, Ptr{Cvoid}, Ref{Cdouble}),
                 psi.h, k, beam, b, v, bound))
     return Matrix{UInt8}(permutedims(b)), v, bound[], k == 0 || bound[] < abs(v[end]) * (1 - 1e-10)
+end
+# element-wise products of states and W^dagger (no reference counterpart).  hadamard: out_x = (conj?)(phi_x) psi_x with bonds
+# chi_phi chi_psi, from a kernel of its own; diagonal_mpo: diag(phi) as an operator, the door to apply_compress / inner /
+# apply_norm / coefficient on phi (.) psi without forming it; adjoint (also W'): W^dagger, exact -- the inverse QFT when W is
+# the QFT MPO; hadamard_compress: compress!(phi (.) psi) through apply_compress on the temporary diag(phi)
+function hadamard(phi::DeviceMPS, psi::DeviceMPS; conj::Bool=false)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:qil_hadamard, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), phi.h, conj, psi.h, r))
+    return finalizer(_free!, DeviceMPS(r[], copy(psi.sites), psi.paired))
+end
+function hadamard_compress(phi::DeviceMPS, psi::DeviceMPS; conj::Bool=false, maxdim::Int=typemax(Int), tol::Float64=1e-12,
+                           sweeps::Int=1, zip_maxdim::Int=0)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:qil_hadamard_compress, LIB), Cint,
+                (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Cdouble, Cint, Int64, Ref{Ptr{Cvoid}}),
+                phi.h, conj, psi.h, maxdim == typemax(Int) ? 0 : maxdim, tol, sweeps, zip_maxdim, r))
+    return finalizer(_free!, DeviceMPS(r[], copy(psi.sites), psi.paired))
+end
+function diagonal_mpo(phi::DeviceMPS; conj::Bool=false)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:qil_mpo_diagonal, LIB), Cint, (Ptr{Cvoid}, Cint, Ref{Ptr{Cvoid}}), phi.h, conj, r))
+    return finalizer(_free!, DeviceMPO(r[], copy(phi.sites), phi.paired))
+end
+function adjoint(W::DeviceMPO)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:qil_mpo_adjoint, LIB), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), W.h, r))
+    return finalizer(_free!, DeviceMPO(r[], copy(W.sites), W.paired))
 end
 function mps_to_vector(psi::DeviceMPS; reverse::Bool=false)                                        # mps.jl:716
     d = Ref{Cint}(0)

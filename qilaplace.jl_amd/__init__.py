@@ -16,7 +16,8 @@ from .containers import (Context, default_context, set_default_context, device_c
                          SignalMPS, ZTMPS, SingleSiteMPO, PairedSiteMPO)
 from .ops import (apply, apply_compress, apply_compress_batch, mpo_compress, compress_batch, mpo_compress_batch, mps_block, coefficient, coefficient_batch, apply_coefficient_batch, apply_coefficient_sweep,  # noqa: F401
                   marginal_batch, coefficient_grid, laplace_values,
-                  mps_to_vector, norm, inner, apply_norm, distance, apply_distance, sample, top_k, canonicalize, compress, signal_mps, signal_ztmps, signal_mps_batch,
+                  mps_to_vector, norm, inner, apply_norm, distance, apply_distance, sample, top_k, hadamard, hadamard_compress, diagonal_mpo, adjoint, convolve, correlate,
+                  power_spectrum, canonicalize, compress, signal_mps, signal_ztmps, signal_mps_batch,
                   signal_ztmps_batch, rsvd,
                   svd_trunc, gemm, gemm_device_time, qr_positive)
 from .builders import (build_qft_mpo, build_dt_mpo, build_zt_mpo, qft_mpo_tensors,  # noqa: F401
@@ -30,6 +31,7 @@ __all__ = [
     "SignalMPS", "ZTMPS", "SingleSiteMPO", "PairedSiteMPO",
     "apply", "apply_compress", "apply_compress_batch", "coefficient", "coefficient_batch", "apply_coefficient_batch", "apply_coefficient_sweep", "marginal_batch", "coefficient_grid", "laplace_values", "mps_to_vector", "norm",
     "inner", "apply_norm", "distance", "apply_distance", "sample", "top_k",
+    "hadamard", "hadamard_compress", "diagonal_mpo", "adjoint", "convolve", "correlate", "power_spectrum",
     "canonicalize", "compress", "signal_mps", "signal_ztmps", "signal_mps_batch", "signal_ztmps_batch", "rsvd", "svd_trunc", "gemm",
     "build_qft_mpo", "build_dt_mpo", "build_zt_mpo", "qft_mpo_tensors", "dt_mpo_tensors", "zt_mpo_tensors",
     "dt_mpo_tensors_many", "build_dt_mpo_batch", "build_zt_mpo_batch", "zt_qft_chain_tensors", "qft_mpo_device", "zt_qft_chain_device", "mpo_compress", "compress_batch", "mpo_compress_batch", "mps_block",

@@ -122,6 +122,10 @@ PROTOTYPES = {
     "qil_apply_norm": [_vp, _vp, _pdbl],
     "qil_sample": [_vp, _i64, _u64, _pdbl, _pu8, _pdbl],
     "qil_top_k": [_vp, _i64, _i64, _pu8, _pdbl, _pdbl],
+    "qil_hadamard": [_vp, _int, _vp, _pvp],
+    "qil_mpo_diagonal": [_vp, _int, _pvp],
+    "qil_mpo_adjoint": [_vp, _pvp],
+    "qil_hadamard_compress": [_vp, _int, _vp, _i64, _dbl, _int, _i64, _pvp],
     "qil_canonicalize": [_vp, _int, _i64, _dbl, _i64],
     "qil_compress": [_vp, _i64, _dbl, _int],
     "qil_mpo_compress": [_vp, _int, _dbl, _i64],

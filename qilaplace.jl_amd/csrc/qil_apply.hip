@@ -51,15 +51,6 @@ struct is_complex<c64> {
     static constexpr bool value = true;
 };
 
-template <class TW, class TA>
-struct out_type {
-    using type = c64;
-};
-template <>
-struct out_type<double, double> {
-    using type = double;
-};
-
 __device__ __forceinline__ double mad2(double w0, double a0, double w1, double a1) {
     return fma(w1, a1, w0 * a0);
 }
@@ -79,31 +70,6 @@ __device__ __forceinline__ c64 mad2(c64 w0, c64 a0, c64 w1, c64 a1) {
     im = fma(w1.re, a1.im, im);
     im = fma(w1.im, a1.re, im);
     return c64{re, im};
-}
-
-template <bool NT>
-__device__ __forceinline__ void store_out(double* p, double v) {
-    if (NT) __builtin_nontemporal_store(v, p); else *p = v;
-}
-template <bool NT>
-__device__ __forceinline__ void store_out(c64* p, c64 v) {
-    typedef double d2 __attribute__((ext_vector_type(2)));
-    d2 t = {v.re, v.im};
-    if (NT) __builtin_nontemporal_store(t, reinterpret_cast<d2*>(p)); else *reinterpret_cast<d2*>(p) = t;
-}
-
-// RPL = output rows per lane: 1 for complex results (one 16-B store per element), 2 for real results (two
-// adjacent rows packed into one 16-B store), so every wave-level store is 1 KiB contiguous either way.
-template <class TO>
-struct rows_per_lane {
-    static constexpr int value = sizeof(TO) == 16 ? 1 : 2;
-};
-
-template <bool NT>
-__device__ __forceinline__ void store_pair(double* p, double v0, double v1) {
-    typedef double d2 __attribute__((ext_vector_type(2)));
-    d2 t = {v0, v1};
-    if (NT) __builtin_nontemporal_store(t, reinterpret_cast<d2*>(p)); else *reinterpret_cast<d2*>(p) = t;
 }
 
 template <class TW, class TA, bool NT, int NBV, bool WLDS>

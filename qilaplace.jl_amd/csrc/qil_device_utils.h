@@ -418,4 +418,40 @@ __device__ __forceinline__ void jacobi_sweeps_nov(T* A, int lda, int m, int n, d
 }
 
 
+// ---- the store side of the fused-layout product kernels (site_apply_grouped, site_hadamard_grouped)
+// result dtype of a product: real only when both operands are
+template <class TW, class TA>
+struct out_type {
+    using type = c64;
+};
+template <>
+struct out_type<double, double> {
+    using type = double;
+};
+
+template <bool NT>
+__device__ __forceinline__ void store_out(double* p, double v) {
+    if (NT) __builtin_nontemporal_store(v, p); else *p = v;
+}
+template <bool NT>
+__device__ __forceinline__ void store_out(c64* p, c64 v) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    d2 t = {v.re, v.im};
+    if (NT) __builtin_nontemporal_store(t, reinterpret_cast<d2*>(p)); else *reinterpret_cast<d2*>(p) = t;
+}
+
+// RPL = output rows per lane: 1 for complex results (one 16-B store per element), 2 for real results (two
+// adjacent rows packed into one 16-B store), so every wave-level store is 1 KiB contiguous either way.
+template <class TO>
+struct rows_per_lane {
+    static constexpr int value = sizeof(TO) == 16 ? 1 : 2;
+};
+
+template <bool NT>
+__device__ __forceinline__ void store_pair(double* p, double v0, double v1) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    d2 t = {v0, v1};
+    if (NT) __builtin_nontemporal_store(t, reinterpret_cast<d2*>(p)); else *reinterpret_cast<d2*>(p) = t;
+}
+
 }  // namespace qil_dev

@@ -7,6 +7,8 @@
   inner              ITensors' inner(phi, psi) / inner(phi, W, psi) on device chains (no reference counterpart)
   sample             ITensors' sample(::MPS) on device chains (no reference counterpart)
   top_k              the k largest |psi_x| by a certified beam search (no reference counterpart: replaces argmax over grid scans)
+  hadamard, adjoint  element-wise products of states and W^dagger; convolve / correlate / power_spectrum on top of them (no
+                     reference counterpart)
   canonicalize       src/mps.jl:787-847, 866-901   (Julia: canonicalize!)
   compress           src/mps.jl:913-999            (Julia: compress!)
   signal_mps         src/signals/SignalConverters.jl:228-233
@@ -542,6 +544,95 @@ def apply_compress(W, psi, maxdim=None, tol=1e-12, sweeps=1, zip_maxdim=None):
     L.check(L.lib.qil_apply_compress(W.handle, psi.handle, _maxdim(maxdim), float(tol), int(sweeps),
                                      0 if zip_maxdim is None else int(zip_maxdim), C.byref(h)))
     return _wrap_like(psi, h)
+
+
+# ---------------------------------------------------------------- element-wise products, adjoints
+def _require_pair(phi, psi, what):
+    """Two states, checked before any native call (register kind, length and sites are checked natively, as for `inner`)."""
+    if not (isinstance(phi, SignalMPS) and isinstance(psi, SignalMPS)):
+        raise TypeError(f"{what}: unsupported operand types")
+
+
+def hadamard(phi, psi, conj=False):
+    """The element-wise product out_x = phi_x * psi_x (conj=True: conj(phi_x) * psi_x) as a new state of psi's class: bonds
+    chi_phi * chi_psi, amplitude amp_phi * amp_psi, nothing truncated.  The same tensors as apply(diagonal_mpo(phi), psi),
+    from a kernel of its own (include/qilaplace_hip.h, qil_hadamard)."""
+    _require_pair(phi, psi, "hadamard")
+    h = C.c_void_p()
+    L.check(L.lib.qil_hadamard(phi.handle, 1 if conj else 0, psi.handle, C.byref(h)))
+    return _wrap_like(psi, h)
+
+
+def hadamard_compress(phi, psi, conj=False, maxdim=None, tol=1e-12, sweeps=1, zip_maxdim=None):
+    """compress(hadamard(phi, psi, conj), maxdim, tol, sweeps) without the (chi_phi chi_psi)^2 product tensors: bit-identical
+    to apply_compress(diagonal_mpo(phi, conj), psi, ...), the diagonal operator being a temporary of the call."""
+    _require_pair(phi, psi, "hadamard")
+    h = C.c_void_p()
+    L.check(L.lib.qil_hadamard_compress(phi.handle, 1 if conj else 0, psi.handle, _maxdim(maxdim), float(tol), int(sweeps),
+                                        0 if zip_maxdim is None else int(zip_maxdim), C.byref(h)))
+    return _wrap_like(psi, h)
+
+
+def diagonal_mpo(phi, conj=False):
+    """diag(phi) (conj=True: diag(conj(phi))) as an operator on phi's sites -- a PairedSiteMPO for a ZTMPS -- with the
+    amplitude folded into the first tensor.  Every verb that takes an operator then reads phi (.) psi without forming it:
+    apply_coefficient_batch, inner(chi, W, psi), apply_norm, apply_compress."""
+    if not isinstance(phi, SignalMPS):
+        raise TypeError("diagonal_mpo: unsupported operand types")
+    h = C.c_void_p()
+    L.check(L.lib.qil_mpo_diagonal(phi.handle, 1 if conj else 0, C.byref(h)))
+    return (PairedSiteMPO if phi._paired() else SingleSiteMPO)(ctx=phi.ctx, _handle=h)
+
+
+def adjoint(W):
+    """W^dagger, in the container class of W; exact (moves and sign flips).  adjoint(build_qft_mpo(n)) is the inverse QFT."""
+    if not isinstance(W, SingleSiteMPO):
+        raise TypeError("adjoint: unsupported operand types")
+    h = C.c_void_p()
+    L.check(L.lib.qil_mpo_adjoint(W.handle, C.byref(h)))
+    return type(W)(ctx=W.ctx, _handle=h)
+
+
+def _spectral_product(x, h, F, maxdim, tol, conj, what):
+    if not (isinstance(x, SignalMPS) and isinstance(h, SignalMPS)) or x._paired() or h._paired():
+        raise TypeError(f"{what}: unsupported operand types")
+    if F is not None and not (isinstance(F, SingleSiteMPO) and not F._paired()):
+        raise TypeError(f"{what}: unsupported operand types")
+    if len(x) != len(h):
+        raise ValueError(f"{what}: signals must have the same number of sites. Found {len(x)} and {len(h)}")
+    if F is None:
+        from .builders import build_qft_mpo
+        F = build_qft_mpo(x)
+    X = apply_compress(F, x, maxdim=maxdim, tol=tol)
+    H = apply_compress(F, h, maxdim=maxdim, tol=tol)
+    P = hadamard_compress(X, H, conj=conj, maxdim=maxdim, tol=tol)
+    y = apply_compress(adjoint(F), P, maxdim=maxdim, tol=tol)
+    y.amplitude = y.amplitude * float(np.sqrt(2.0) ** len(x))
+    return y
+
+
+def convolve(x, h, F=None, maxdim=None, tol=1e-12):
+    """Circular convolution y[m] = sum_j x[j] h[(m - j) mod N] of two SignalMPS of n sites (N = 2^n samples), in MPS form on
+    the device by the convolution theorem: y = sqrt(N) F^dagger((F x) (.) (F h)).  `F` defaults to build_qft_mpo(x); its
+    bit reversal cancels between F and F^dagger.  The four stages (F x, F h, the product, F^dagger) each go through
+    apply_compress / hadamard_compress with `maxdim` and `tol`; the sqrt(N) goes into the amplitude.
+
+    The QFT MPO at its default cutoff 1e-14 is unitary only to 3e-9 (n = 6) ... 3e-7 (n = 10) -- the cutoff acts on squared
+    singular values -- so the result matches np.fft.ifft(fft(x) * fft(h)) to about 1e-7 of max|y|, whatever `tol` is.  Pass
+    F = build_qft_mpo(x, cutoff=...) with a tighter cutoff for a tighter result."""
+    return _spectral_product(x, h, F, maxdim, tol, False, "convolve")
+
+
+def correlate(x, h, F=None, maxdim=None, tol=1e-12):
+    """Circular cross-correlation y[m] = sum_j conj(x[j]) h[(j + m) mod N] = sqrt(N) F^dagger(conj(F x) (.) (F h)): the route,
+    the stages and the 1e-7-grade accuracy of `convolve` (see there for the unitarity of the default QFT MPO)."""
+    return _spectral_product(x, h, F, maxdim, tol, True, "correlate")
+
+
+def power_spectrum(psi, maxdim=None, tol=1e-12, sweeps=1, zip_maxdim=None):
+    """|psi_x|^2 as a state: hadamard_compress(psi, psi, conj=True, ...).  Band energies are its partial sums:
+    marginal_batch with bit value 2 on the summed sites."""
+    return hadamard_compress(psi, psi, conj=True, maxdim=maxdim, tol=tol, sweeps=sweeps, zip_maxdim=zip_maxdim)
 
 
 # ---------------------------------------------------------------- encode
