@@ -40,6 +40,43 @@ QIL_API int qil_hbm_store_peak(qil_context* ctx, int64_t bytes, int reps, double
 QIL_API int qil_gemm_device_time(qil_context* ctx, int dtype, int opA, int opB, int64_t m, int64_t n, int64_t k,
                          int reps, double* ms_per_call);
 
+/* Everything the MFMA GEMM decides on the host before it launches: THE decision, not a copy of it -- the launch code
+ * switches on this struct.  (bm, bn, gkt, deep) name the kernel's output tile, K step and whether two K tiles are in
+ * flight; arc / bkc: op(A)'s row index / op(B)'s k index is the contiguous one; splits K slices of kchunk each, decided
+ * by split_rule (0 = none, 1 = few tiles and a long K, 2 = at most four tiles from K = 128, 3 = one wave of tiles and
+ * K >= 4096); col_fastest: tiles are walked along a tile row first; xcd: the XCD-aware tile permutation is applied. */
+typedef struct qil_gemm_plan_info {
+    int bm, bn, wm, wn, gkt, deep;
+    int arc, bkc;
+    int splits, split_rule;
+    int64_t kchunk;
+    int col_fastest, xcd;
+    int64_t tiles_m, tiles_n;
+    int can_split;                      /* a batch may only split K when its outputs are packed */
+} qil_gemm_plan_info;
+/* The plan of C (m x n) = op(A) op(B) for a batch of `count` products whose outputs lie c_bs elements apart (has_cmap: scattered
+ * column blocks; skinny_m: the caller's skinny hint).  Host only: no context, no GPU.  QIL_EINVAL_ARG for bad op codes, empty
+ * operands or leading dimensions smaller than the stored rows. */
+QIL_API int qil_gemm_plan(int dtype, int opA, int opB, int64_t m, int64_t n, int64_t k, int64_t lda, int64_t ldb, int64_t ldc,
+                          int64_t count, int64_t c_bs, int has_cmap, int skinny_m, qil_gemm_plan_info* plan);
+
+/* One operand of qil_gemm_batched_host: a whole host buffer of `elems` elements; the product uses base + off with leading dimension
+ * ld, batch b a further b * bs elements on. */
+typedef struct qil_gemm_host_operand {
+    void* base;
+    int64_t elems, off, ld, bs;
+} qil_gemm_host_operand;
+/* The batched and epilogue forms of the GEMM on host operands: uploads the three parent buffers whole (C included), runs the
+ * dispatch on base + off -- so the device addresses carry the offsets the internal callers produce -- and downloads the whole of
+ * C.  subtract: C <- C - op(A) op(B); skinny_m: the skinny hint; b_sel (count entries b_sel_step apart, or null): batch b reads
+ * B a further b_sel[b * b_sel_step] * b_sel_stride elements on; cmap (count * n / cmap_blk entries, or null): output column block
+ * g of batch b goes to column block cmap[b * n / cmap_blk + g] of C.  Every element the product would touch must lie inside
+ * its buffer (QIL_EINVAL_ARG otherwise). */
+QIL_API int qil_gemm_batched_host(qil_context* ctx, int dtype, int opA, int opB, int64_t m, int64_t n, int64_t k,
+                                  const qil_gemm_host_operand* A, const qil_gemm_host_operand* B, const qil_gemm_host_operand* C,
+                                  int64_t count, int subtract, int skinny_m, const uint8_t* b_sel, int64_t b_sel_step,
+                                  int64_t b_sel_stride, const int32_t* cmap, int64_t cmap_blk);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,6 +64,22 @@ _vp, _i64, _int, _dbl = C.c_void_p, C.c_int64, C.c_int, C.c_double
 _pi64, _pint, _pdbl, _pvp = C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_void_p)
 _pu8, _u64 = C.POINTER(C.c_uint8), C.c_uint64
 
+
+
+class GemmPlanInfo(C.Structure):
+    """qil_gemm_plan_info of include/qilaplace_hip_testing.h."""
+    _fields_ = [("bm", _int), ("bn", _int), ("wm", _int), ("wn", _int), ("gkt", _int), ("deep", _int),
+                ("arc", _int), ("bkc", _int), ("splits", _int), ("split_rule", _int), ("kchunk", _i64),
+                ("col_fastest", _int), ("xcd", _int), ("tiles_m", _i64), ("tiles_n", _i64), ("can_split", _int)]
+
+
+class GemmHostOperand(C.Structure):
+    """qil_gemm_host_operand of include/qilaplace_hip_testing.h."""
+    _fields_ = [("base", _vp), ("elems", _i64), ("off", _i64), ("ld", _i64), ("bs", _i64)]
+
+
+_pop = C.POINTER(GemmHostOperand)
+
 # name -> argtypes; every function returns int (qil_status) unless listed in _RET
 PROTOTYPES = {
     "qil_device_count": [_pint],
@@ -143,6 +159,9 @@ PROTOTYPES = {
     "qil_build_qft_mpo": [_vp, _i64, _dbl, _i64, _pi64, _pvp, _pint],
     "qil_build_zt_qft_chain": [_vp, _i64, _dbl, _i64, _pi64, _pvp, _pint],
     "qil_gemm": [_vp, _int, _int, _int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64],
+    "qil_gemm_plan": [_int, _int, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, C.POINTER(GemmPlanInfo)],
+    "qil_gemm_batched_host": [_vp, _int, _int, _int, _i64, _i64, _i64, _pop, _pop, _pop, _i64, _int, _int, _pu8, _i64, _i64,
+                              C.POINTER(C.c_int32), _i64],
     "qil_qr_positive": [_vp, _int, _i64, _i64, _vp, _vp, _vp],
     "qil_gemm_device_time": [_vp, _int, _int, _int, _i64, _i64, _i64, _int, _pdbl],
     "qil_hbm_store_peak": [_vp, _i64, _int, _pdbl, _pint],

@@ -90,14 +90,10 @@ __device__ __forceinline__ void gemm_mfma_body(const uint3 blockIdx, const uint3
     const int l15 = lane & 15, l4 = lane >> 4;
     // XCD-aware tile order: workgroups are dealt round-robin to the 8 XCDs (each with its own L2), so workgroup b
     // runs on XCD b % 8.  Give every XCD one CONTIGUOUS eighth of the tile sequence instead of every eighth tile:
-    // neighbouring tiles share an operand panel, and now they also share an L2.  (bit 1 of col_fastest switches it off.)
+    // neighbouring tiles share an operand panel, and now they also share an L2.  The host decides (gemm_plan: at least 64
+    // tiles and a multiple of 8 -- an exact split keeps the map a bijection without a table) and says so in bit 1 of col_fastest.
     int tile = blockIdx.x;
-    const int ntiles = tiles_m * tiles_n;
-    if (!(col_fastest & 2) && ntiles >= 64) {
-        const int per = (ntiles + 7) / 8;
-        const int t2 = (tile % 8) * per + tile / 8;
-        if ((ntiles % 8) == 0) tile = t2;          // exact split only: keeps the map a bijection without a table
-    }
+    if (col_fastest & 2) tile = (tile % 8) * (tiles_m * tiles_n / 8) + tile / 8;
     int tm, tn;
     if (col_fastest & 1) {
         tn = tile % tiles_n;
@@ -361,56 +357,140 @@ struct gemm_batch {
     int skinny_m = 0;                   // 1: the caller knows op(A) has <= 32 rows and a long n: 32 x 128 output tiles
 };
 
-template <class T, int BM, int BN, int WM, int WN, bool PIPE, int GKT = GK, int DEEP = 0>
-int gemm_launch(qil_context* ctx, long long m, long long n, long long k, const T* A, long long a_rs,
-                long long a_ks, int conjA, const T* B, long long b_ks, long long b_cs, int conjB, T* C,
-                long long ldc, const gemm_batch& bt) {
-    constexpr int NP = sizeof(T) == 16 ? 2 : 1;
-    constexpr size_t lds = (size_t)(PIPE ? 2 : 1) * NP * GKT * ((BM + GPAD) + (BN + GPAD)) * sizeof(double);
-    const bool arc = a_rs == 1, bkc = b_ks == 1;
-    const long long tiles_m = (m + BM - 1) / BM, tiles_n = (n + BN - 1) / BN;
+// The tile shapes of the family: (BM, BN, WM, WN, GKT, DEEP).  gemm_plan picks one by its index, gemm_dispatch switches on it.
+struct gemm_shape {
+    int bm, bn, wm, wn, gkt, deep;
+};
+enum { GS_32x64_DEEP, GS_48x64_DEEP, GS_32x32, GS_64x64, GS_64x144, GS_128x128, GS_128x64, GS_COUNT };
+constexpr gemm_shape GEMM_SHAPES[GS_COUNT] = {
+    {32, 64, 16, 32, GK, 1}, {48, 64, 48, 16, GK, 1}, {32, 32, 16, 16, 32, 0}, {64, 64, 32, 32, GK, 0},
+    {64, 144, 16, 144, GK, 0}, {128, 128, 64, 64, GK, 0}, {128, 64, 64, 32, GK, 0}};
+
+// which tile shape a product runs on (cx: complex elements)
+int gemm_pick_shape(bool cx, long long m, long long n, long long count, int skinny_m) {
+    // few output tiles (the 256 x 256 products of the gauge steps: 16 tiles of 64 x 64): a product that leaves most of the chip
+    // idle is bound by the K loop of ONE tile on its CU (32 MFMAs per wave and 32-deep K step at 64 x 64, 8 at 32 x 32)
+    // (measured, up to 0 / 16 / 32 / 64 tiles of 64 x 64 as 32 x 32 tiles: compress! chi 256 f64 49.5 / 46.2 / 45.6 / 46.1 ms, c64 66.2 /
+    // 61.5 / 59.6 / 61.0, chi 512 f64 122.3 / 118.0 / 115.7 / 114.5, c64 165.9 / 151.8 / 148.1 / 142.6, fused apply-and-truncate 147 / 131 / 128 / 129)
+    // skinny op(A) (the halves of a bit-sorted coefficient read-out: ~32 queries x 8192 columns x 8192 deep): the product streams
+    // its long operand ONCE, one row of tiles.  32 x 64 / 48 x 64 tiles (no rows of padding work; 51 / 59 KB of LDS: 3 / 2
+    // workgroups per CU) with TWO K tiles in flight (DEEP).  Measured per 8192 x 8192 complex slice: 64 x 64 tile, one tile ahead
+    // 0.47 ms whatever the rows (latency-bound, 2.3 TB/s); 32 x 128 / 48 x 128 one tile ahead the same; 32 x 64 DEEP 0.30 ms
+    // (3.5 TB/s), 48 x 64 DEEP 0.43-0.47 ms, 64 x 64 DEEP 0.58 ms -- now proportional to the padded rows (~42 TFLOP/s of real
+    // MFMA work, 0.54 of the matrix peak) and independent of the grid size (512 ... 1536 workgroups: equal)
+    if (skinny_m && m <= 32 && n >= 128) return GS_32x64_DEEP;
+    // ... and 33-48 rows (the larger half of 64 sorted queries is typically 33-40 rows)
+    if (skinny_m && m <= 48 && n >= 128) return GS_48x64_DEEP;
+    constexpr long long small_tiles = 64;
+    // (K step of the small tiles 16 / 32 / 64: compress! chi 256 46.5 / 45.3 / 45.2 ms, chi 512 115.1 / 111.7 / 112.1, exact route 300 / 293 / 294)
+    if (((m + 63) / 64) * ((n + 63) / 64) * count <= small_tiles && m >= 32 && n >= 32) return GS_32x32;
+    if (cx) return GS_64x64;      // pipelined: equal on big squares, 56 vs 45 TFLOP/s on 64 x 16384 x 8192
+    // 97..144 output columns (RSVD sketches with k + p = 133): one 144-wide tile reads A ONCE and pads
+    // 133 -> 144 columns instead of 192
+    // one 144-wide tile per row panel; 64 rows (one 16 x 144 strip per wave) fit 2 waves/SIMD, 128 rows do not
+    // (two K tiles in flight on this tile: 5.9 -> 6.9 ms for 32768 x 133 x 32768, r05 -- it is not latency-bound)
+    if (m >= 256 && n > 96 && n <= 144) return GS_64x144;
+    // big outputs: 128 x 128 tiles, 4 x 4 MFMA tiles per wave (two fragment reads per MFMA step pair, 64 MFMAs
+    // between barriers) at 2 waves/SIMD -- 59 vs 52 TFLOP/s for the 128 x 64 tile at 4096^3
+    {
+        const long long t128 = ((m + 127) / 128) * ((n + 127) / 128);
+        const bool fills = (double)m * (double)n >= 0.85 * 16384.0 * (double)t128;   // little padding in edge tiles
+        if (t128 * count >= 512 && fills) return GS_128x128;
+    }
+    // 128 x 64 tiles only when they still give every CU a workgroup: a product that fills a fraction of the chip is bound by
+    // the time of ONE tile on its CU, and a 64 x 64 tile takes half of it
+    {
+        constexpr long long min_tiles = 128;   // (measured, compress! chi 256 / 512: always 51.9 / 131.1 ms; from 64, 256 or 1024 tiles on: 49.4-50.4 / 123.1 ms)
+        const long long t = ((m + 127) / 128) * ((n + 63) / 64) * count;
+        if (m >= 256 && t >= min_tiles) return GS_128x64;
+    }
+    return GS_64x64;
+}
+
+// Everything the host decides about one product, from its arguments alone (no context, no device): the tile shape, the staging
+// pattern, split-K, the tile order.  gemm_dispatch / gemm_launch switch on the result and decide nothing themselves;
+// qil_gemm_plan hands the same struct to the tests.  opA / opB: 0 = N, 1 = T, 2 = H, 3 = conj.  Returns the GS_ index.
+int gemm_plan(bool cx, int opA, int opB, long long m, long long n, long long k, long long lda, long long ldb, long long ldc,
+              long long count, long long c_bs, bool has_cmap, int skinny_m, qil_gemm_plan_info* p) {
+    const int si = gemm_pick_shape(cx, m, n, count, skinny_m);
+    const gemm_shape& s = GEMM_SHAPES[si];
+    p->bm = s.bm, p->bn = s.bn, p->wm = s.wm, p->wn = s.wn, p->gkt = s.gkt, p->deep = s.deep;
+    // op(A)[r, kk] = A[r * a_rs + kk * a_ks];  op(B)[kk, c] = B[kk * b_ks + c * b_cs]
+    const bool at = opA == 1 || opA == 2, bt = opB == 1 || opB == 2;
+    p->arc = (at ? lda : 1) == 1;
+    p->bkc = (bt ? ldb : 1) == 1;
+    const long long tiles_m = (m + s.bm - 1) / s.bm, tiles_n = (n + s.bn - 1) / s.bn;
     const long long tiles = tiles_m * tiles_n;
-    const bool can_split = bt.count == 1 || (ldc == m && bt.c_bs == m * n && !bt.cmap);
+    p->tiles_m = tiles_m, p->tiles_n = tiles_n;
+    const bool can_split = count == 1 || (ldc == m && c_bs == m * n && !has_cmap);
+    p->can_split = can_split;
     // few output tiles + long K (projections Q^H P, sketches of skinny panels): split K over the chip
-    int splits = 1;
+    int splits = 1, rule = 0;
     static const long long split_min_k = 1024;   // (measured; 512: exact compress! of the bond-1008 product 572 -> 534 ms, compress! 512 -> 256 330 -> 355 ms)
     // ... and from K = 512 when the output is at most 8 tiles (the CGS2 projections Q^H P of 1008-row complex panels:
     // exact compress! of the bond-1008 product 476 -> 445 ms; splitting every K >= 512 product costs the small chains 5 %)
-    if (can_split && tiles * bt.count < 128 && (k >= split_min_k || (k >= 512 && tiles * bt.count <= 8)))
-        splits = (int)std::min<long long>(std::min<long long>(k / 256, 512 / (tiles * bt.count)), 64);
+    if (can_split && tiles * count < 128 && (k >= split_min_k || (k >= 512 && tiles * count <= 8))) {
+        splits = (int)std::min<long long>(std::min<long long>(k / 256, 512 / (tiles * count)), 64);
+        rule = 1;
+    }
     // one to four output tiles (complex: a 64 x 64 tile is 0.85 us of MFMA per 16 k on ITS ONE CU -- the projections and
     // environment products of the truncation chains spend 20-40 us there): slices of 64 k from K = 128 on
     // (measured against no slicing: fused apply-compress 263 -> 244 ms, exact route 439 -> 417 ms)
-    if (can_split && tiles * bt.count <= 4 && k >= 128)
-        splits = std::max<int>(splits, (int)std::min<long long>(k / 64, 32));
+    if (can_split && tiles * count <= 4 && k >= 128) {
+        const int s2 = (int)std::min<long long>(k / 64, 32);
+        if (s2 > splits) splits = s2, rule = 2;
+    }
     // one wave of workgroups or less and a long K (the encoder's 16384 x 133 x 16384 sketches: 256 tiles): two to four K
     // slices fill the second workgroup slot of every CU (37.7 -> see DESIGN 3.4)
-    if (splits < 2 && can_split && tiles * bt.count >= 128 && tiles * bt.count <= 384 && k >= 4096)
-        splits = (int)std::min<long long>(4, (767 / (tiles * bt.count)));
-    if (splits < 2) splits = 1;
-    long long kchunk = k, cstride = 0, c_bs = bt.c_bs;
+    if (splits < 2 && can_split && tiles * count >= 128 && tiles * count <= 384 && k >= 4096) {
+        splits = (int)std::min<long long>(4, (767 / (tiles * count)));
+        rule = 3;
+    }
+    if (splits < 2) splits = 1, rule = 0;
+    long long kchunk = k;
+    if (splits > 1) {
+        kchunk = (((k + splits - 1) / splits) + s.gkt - 1) / s.gkt * s.gkt;
+        splits = (int)((k + kchunk - 1) / kchunk);
+    }
+    p->splits = splits, p->split_rule = rule, p->kchunk = kchunk;
+    // narrow outputs: neighbouring workgroups share the same rows of A (served from L2 / Infinity Cache)
+    p->col_fastest = tiles_n <= 8 ? 1 : 0;
+    // XCD-aware tile order (see the kernel): exact split only, which keeps the map a bijection without a table
+    p->xcd = tiles >= 64 && tiles % 8 == 0;
+    return si;
+}
+
+template <class T, int SI>
+int gemm_launch(qil_context* ctx, const qil_gemm_plan_info& p, long long m, long long n, long long k, const T* A, long long a_rs,
+                long long a_ks, int conjA, const T* B, long long b_ks, long long b_cs, int conjB, T* C,
+                long long ldc, const gemm_batch& bt) {
+    constexpr gemm_shape S = GEMM_SHAPES[SI];
+    constexpr int BM = S.bm, BN = S.bn, WM = S.wm, WN = S.wn, GKT = S.gkt, DEEP = S.deep;
+    constexpr bool PIPE = true;
+    constexpr int NP = sizeof(T) == 16 ? 2 : 1;
+    constexpr size_t lds = (size_t)(PIPE ? 2 : 1) * NP * GKT * ((BM + GPAD) + (BN + GPAD)) * sizeof(double);
+    const long long tiles = p.tiles_m * p.tiles_n;
+    const int splits = p.splits;
+    long long cstride = 0, c_bs = bt.c_bs;
     T* Cout = C;
     long long ldo = ldc;
     void* wsp = nullptr;
     if (splits > 1) {
-        kchunk = (((k + splits - 1) / splits) + GKT - 1) / GKT * GKT;
-        splits = (int)((k + kchunk - 1) / kchunk);
         cstride = m * n * bt.count;
         c_bs = m * n;
         QIL_TRY(qil_ctx_alloc(ctx, (size_t)(cstride * splits) * sizeof(T), &wsp));
         Cout = static_cast<T*>(wsp);
         ldo = m;
     }
-    // narrow outputs: neighbouring workgroups share the same rows of A (served from L2 / Infinity Cache)
-    const int col_fastest = tiles_n <= 8 ? 1 : 0;
+    const int order = p.col_fastest | (p.xcd ? 2 : 0);
 #define QIL_GEMM_K(ARCv, BKCv)                                                                                               \
     QIL_TRY((qil_klaunch<gemm_mfma_k<T, BM, BN, WM, WN, PIPE, ARCv, BKCv, GKT, DEEP>>(                                                      \
         ctx, dim3((unsigned)tiles, (unsigned)bt.count, (unsigned)splits), dim3(256), lds, m, n, k, A, a_rs, a_ks, conjA, B, b_ks, \
-        b_cs, conjB, Cout, ldo, kchunk, cstride, (int)tiles_m, (int)tiles_n, col_fastest, bt.a_bs, bt.b_bs, c_bs, bt.cmap,        \
+        b_cs, conjB, Cout, ldo, (long long)p.kchunk, cstride, (int)p.tiles_m, (int)p.tiles_n, order, bt.a_bs, bt.b_bs, c_bs, bt.cmap,  \
         bt.cmap_blk, bt.b_sel, bt.b_sel_step, bt.b_sel_stride, splits > 1 ? 0 : bt.subtract)))
-    if (arc && bkc) QIL_GEMM_K(true, true);
-    else if (arc) QIL_GEMM_K(true, false);
-    else if (bkc) QIL_GEMM_K(false, true);
+    if (p.arc && p.bkc) QIL_GEMM_K(true, true);
+    else if (p.arc) QIL_GEMM_K(true, false);
+    else if (p.bkc) QIL_GEMM_K(false, true);
     else QIL_GEMM_K(false, false);
 #undef QIL_GEMM_K
     if (splits > 1) {
@@ -434,50 +514,25 @@ int gemm_dispatch(qil_context* ctx, int opA, int opB, long long m, long long n, 
     const long long b_ks = bt ? ldb : 1, b_cs = bt ? 1 : ldb;
     const int cA = (opA == 2 || opA == 3) ? 1 : 0, cB = (opB == 2 || opB == 3) ? 1 : 0;
     constexpr bool CX = sizeof(T) == 16;
-#define QIL_GEMM_GO(BM, BN, WM, WN, PIPE) \
-    return gemm_launch<T, BM, BN, WM, WN, PIPE>(ctx, m, n, k, A, a_rs, a_ks, cA, B, b_ks, b_cs, cB, C, ldc, batch)
-    // few output tiles (the 256 x 256 products of the gauge steps: 16 tiles of 64 x 64): a product that leaves most of the chip
-    // idle is bound by the K loop of ONE tile on its CU (32 MFMAs per wave and 32-deep K step at 64 x 64, 8 at 32 x 32)
-    // (measured, up to 0 / 16 / 32 / 64 tiles of 64 x 64 as 32 x 32 tiles: compress! chi 256 f64 49.5 / 46.2 / 45.6 / 46.1 ms, c64 66.2 /
-    // 61.5 / 59.6 / 61.0, chi 512 f64 122.3 / 118.0 / 115.7 / 114.5, c64 165.9 / 151.8 / 148.1 / 142.6, fused apply-and-truncate 147 / 131 / 128 / 129)
-    // skinny op(A) (the halves of a bit-sorted coefficient read-out: ~32 queries x 8192 columns x 8192 deep): the product streams
-    // its long operand ONCE, one row of tiles.  32 x 64 / 48 x 64 tiles (no rows of padding work; 51 / 59 KB of LDS: 3 / 2
-    // workgroups per CU) with TWO K tiles in flight (DEEP).  Measured per 8192 x 8192 complex slice: 64 x 64 tile, one tile ahead
-    // 0.47 ms whatever the rows (latency-bound, 2.3 TB/s); 32 x 128 / 48 x 128 one tile ahead the same; 32 x 64 DEEP 0.30 ms
-    // (3.5 TB/s), 48 x 64 DEEP 0.43-0.47 ms, 64 x 64 DEEP 0.58 ms -- now proportional to the padded rows (~42 TFLOP/s of real
-    // MFMA work, 0.54 of the matrix peak) and independent of the grid size (512 ... 1536 workgroups: equal)
-    if (batch.skinny_m && m <= 32 && n >= 128) return gemm_launch<T, 32, 64, 16, 32, true, GK, 1>(ctx, m, n, k, A, a_rs, a_ks, cA, B, b_ks, b_cs, cB, C, ldc, batch);
-    // ... and 33-48 rows (the larger half of 64 sorted queries is typically 33-40 rows)
-    if (batch.skinny_m && m <= 48 && n >= 128) return gemm_launch<T, 48, 64, 48, 16, true, GK, 1>(ctx, m, n, k, A, a_rs, a_ks, cA, B, b_ks, b_cs, cB, C, ldc, batch);
-    constexpr long long small_tiles = 64;
-    // (K step of the small tiles 16 / 32 / 64: compress! chi 256 46.5 / 45.3 / 45.2 ms, chi 512 115.1 / 111.7 / 112.1, exact route 300 / 293 / 294)
-    if (((m + 63) / 64) * ((n + 63) / 64) * batch.count <= small_tiles && m >= 32 && n >= 32)
-        return gemm_launch<T, 32, 32, 16, 16, true, 32>(ctx, m, n, k, A, a_rs, a_ks, cA, B, b_ks, b_cs, cB, C, ldc, batch);
-    if constexpr (CX) {
-        QIL_GEMM_GO(64, 64, 32, 32, true);      // pipelined: equal on big squares, 56 vs 45 TFLOP/s on 64 x 16384 x 8192
-    } else {
-        // 97..144 output columns (RSVD sketches with k + p = 133): one 144-wide tile reads A ONCE and pads
-        // 133 -> 144 columns instead of 192
-        // one 144-wide tile per row panel; 64 rows (one 16 x 144 strip per wave) fit 2 waves/SIMD, 128 rows do not
-        // (two K tiles in flight on this tile: 5.9 -> 6.9 ms for 32768 x 133 x 32768, r05 -- it is not latency-bound)
-        if (m >= 256 && n > 96 && n <= 144) QIL_GEMM_GO(64, 144, 16, 144, true);
-        // big outputs: 128 x 128 tiles, 4 x 4 MFMA tiles per wave (two fragment reads per MFMA step pair, 64 MFMAs
-        // between barriers) at 2 waves/SIMD -- 59 vs 52 TFLOP/s for the 128 x 64 tile at 4096^3
-        {
-            const long long t128 = ((m + 127) / 128) * ((n + 127) / 128);
-            const bool fills = (double)m * (double)n >= 0.85 * 16384.0 * (double)t128;   // little padding in edge tiles
-            if (t128 * batch.count >= 512 && fills) QIL_GEMM_GO(128, 128, 64, 64, true);
+    qil_gemm_plan_info p;
+    const int si = gemm_plan(CX, opA, opB, m, n, k, lda, ldb, ldc, batch.count, batch.c_bs, batch.cmap != nullptr, batch.skinny_m, &p);
+#define QIL_GEMM_GO(SI) \
+    case SI: return gemm_launch<T, SI>(ctx, p, m, n, k, A, a_rs, a_ks, cA, B, b_ks, b_cs, cB, C, ldc, batch)
+    switch (si) {
+        QIL_GEMM_GO(GS_32x64_DEEP);
+        QIL_GEMM_GO(GS_48x64_DEEP);
+        QIL_GEMM_GO(GS_32x32);
+        QIL_GEMM_GO(GS_64x64);
+    }
+    if constexpr (!CX) {            // the wide and the 128-row tiles exist for f64 only
+        switch (si) {
+            QIL_GEMM_GO(GS_64x144);
+            QIL_GEMM_GO(GS_128x128);
+            QIL_GEMM_GO(GS_128x64);
         }
-        // 128 x 64 tiles only when they still give every CU a workgroup: a product that fills a fraction of the chip is bound by
-        // the time of ONE tile on its CU, and a 64 x 64 tile takes half of it
-        {
-            constexpr long long min_tiles = 128;   // (measured, compress! chi 256 / 512: always 51.9 / 131.1 ms; from 64, 256 or 1024 tiles on: 49.4-50.4 / 123.1 ms)
-            const long long t = ((m + 127) / 128) * ((n + 63) / 64) * batch.count;
-            if (m >= 256 && t >= min_tiles) QIL_GEMM_GO(128, 64, 64, 32, true);
-        }
-        QIL_GEMM_GO(64, 64, 32, 32, true);
     }
 #undef QIL_GEMM_GO
+    return qil_fail(QIL_EINVAL_ARG, "gemm: no kernel for tile shape %d", si);
 }
 
 // ------------------------------------------------------------------ one-sided Jacobi SVD
@@ -4498,12 +4553,23 @@ int qil_dev_gemm_skinny(qil_context* ctx, int dtype, int opA, int opB, int64_t m
                                  (const double*)B, ldb, (double*)C, ldc, bt);
 }
 
+// sizes, op codes and leading dimensions of a host-facing GEMM call: a leading dimension smaller than the stored rows of its
+// operand would make the kernel read (lda, ldb) or write (ldc) outside the allocation
+static int gemm_check_args(int opA, int opB, int64_t m, int64_t n, int64_t k, int64_t lda, int64_t ldb, int64_t ldc) {
+    QIL_REQUIRE(m >= 1 && n >= 1 && k >= 1, QIL_EINVAL_ARG, "gemm: empty operand");
+    QIL_REQUIRE(opA >= 0 && opA <= 3 && opB >= 0 && opB <= 3, QIL_EINVAL_ARG, "gemm: bad op code");
+    const int64_t a_rows = (opA == 0 || opA == 3) ? m : k, b_rows = (opB == 0 || opB == 3) ? k : n;
+    QIL_REQUIRE(lda >= a_rows, QIL_EINVAL_ARG, "gemm: lda %lld is smaller than the %lld stored rows of A", (long long)lda, (long long)a_rows);
+    QIL_REQUIRE(ldb >= b_rows, QIL_EINVAL_ARG, "gemm: ldb %lld is smaller than the %lld stored rows of B", (long long)ldb, (long long)b_rows);
+    QIL_REQUIRE(ldc >= m, QIL_EINVAL_ARG, "gemm: ldc %lld is smaller than the %lld rows of C", (long long)ldc, (long long)m);
+    return QIL_OK;
+}
+
 // C = opA(A) * opB(B) on host operands (column-major): utility / test hook for the MFMA GEMM
 extern "C" int qil_gemm(qil_context* ctx, int dtype, int opA, int opB, int64_t m, int64_t n, int64_t k,
                         const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc) {
     QIL_REQUIRE(ctx && A && B && C, QIL_EINVAL_ARG, "gemm: null argument");
-    QIL_REQUIRE(m >= 1 && n >= 1 && k >= 1, QIL_EINVAL_ARG, "gemm: empty operand");
-    QIL_REQUIRE(opA >= 0 && opA <= 3 && opB >= 0 && opB <= 3, QIL_EINVAL_ARG, "gemm: bad op code");
+    QIL_TRY(gemm_check_args(opA, opB, m, n, k, lda, ldb, ldc));
     QIL_TRY(qil_ctx_activate(ctx));
     qil_call_scope call_scope(ctx);
     const size_t e = qil_elem_size(dtype);
@@ -4521,6 +4587,96 @@ extern "C" int qil_gemm(qil_context* ctx, int dtype, int opA, int opB, int64_t m
     qil_ctx_free(ctx, dA);
     qil_ctx_free(ctx, dB);
     qil_ctx_free(ctx, dC);
+    return QIL_OK;
+}
+
+// What the dispatch would decide for this product (testing hook; host only)
+extern "C" int qil_gemm_plan(int dtype, int opA, int opB, int64_t m, int64_t n, int64_t k, int64_t lda, int64_t ldb, int64_t ldc,
+                             int64_t count, int64_t c_bs, int has_cmap, int skinny_m, qil_gemm_plan_info* plan) {
+    QIL_REQUIRE(plan, QIL_EINVAL_ARG, "gemm: null argument");
+    QIL_REQUIRE(dtype == QIL_F64 || dtype == QIL_C64, QIL_EINVAL_ARG, "gemm: bad dtype %d", dtype);
+    QIL_TRY(gemm_check_args(opA, opB, m, n, k, lda, ldb, ldc));
+    QIL_REQUIRE(count >= 1 && count <= 65535, QIL_EINVAL_ARG, "gemm: batch count %lld exceeds the grid limit", (long long)count);
+    static const int real_op[4] = {0, 1, 1, 0};   // for real data H == T and conj == N
+    if (dtype == QIL_F64) opA = real_op[opA], opB = real_op[opB];
+    gemm_plan(dtype == QIL_C64, opA, opB, m, n, k, lda, ldb, ldc, count, c_bs, has_cmap != 0, skinny_m, plan);
+    return QIL_OK;
+}
+
+// The batched and epilogue forms on host operands (testing hook): whole parent buffers up, gemm_dispatch on base + off, whole C down
+extern "C" int qil_gemm_batched_host(qil_context* ctx, int dtype, int opA, int opB, int64_t m, int64_t n, int64_t k,
+                                     const qil_gemm_host_operand* A, const qil_gemm_host_operand* B, const qil_gemm_host_operand* C,
+                                     int64_t count, int subtract, int skinny_m, const uint8_t* b_sel, int64_t b_sel_step,
+                                     int64_t b_sel_stride, const int32_t* cmap, int64_t cmap_blk) {
+    QIL_REQUIRE(ctx && A && B && C && A->base && B->base && C->base, QIL_EINVAL_ARG, "gemm: null argument");
+    QIL_REQUIRE(dtype == QIL_F64 || dtype == QIL_C64, QIL_EINVAL_ARG, "gemm: bad dtype %d", dtype);
+    QIL_TRY(gemm_check_args(opA, opB, m, n, k, A->ld, B->ld, C->ld));
+    QIL_REQUIRE(count >= 1, QIL_EINVAL_ARG, "gemm: empty batch");
+    QIL_REQUIRE(count <= 65535, QIL_EINVAL_ARG, "gemm: batch count %lld exceeds the grid limit", (long long)count);
+    // every element the kernels touch lies inside its parent buffer
+    QIL_REQUIRE(A->off >= 0 && A->bs >= 0 && B->off >= 0 && B->bs >= 0 && C->off >= 0 && C->bs >= 0 && b_sel_step >= 0 && b_sel_stride >= 0,
+                QIL_EINVAL_ARG, "gemm: negative offset or stride");
+    const int64_t a_rows = (opA == 0 || opA == 3) ? m : k, a_cols = (opA == 0 || opA == 3) ? k : m;
+    const int64_t b_rows = (opB == 0 || opB == 3) ? k : n, b_cols = (opB == 0 || opB == 3) ? n : k;
+    int64_t sel_max = 0, c_cols = n;
+    if (b_sel)
+        for (int64_t b = 0; b < count; ++b) sel_max = std::max<int64_t>(sel_max, b_sel[b * b_sel_step]);
+    if (cmap) {
+        QIL_REQUIRE(cmap_blk >= 1 && n % cmap_blk == 0, QIL_EINVAL_ARG, "gemm: cmap needs n (%lld) to be a multiple of its block (%lld)",
+                    (long long)n, (long long)cmap_blk);
+        int64_t blk_max = 0;
+        for (int64_t g = 0; g < count * (n / cmap_blk); ++g) {
+            QIL_REQUIRE(cmap[g] >= 0, QIL_EINVAL_ARG, "gemm: negative cmap entry");
+            blk_max = std::max<int64_t>(blk_max, cmap[g]);
+        }
+        c_cols = (blk_max + 1) * cmap_blk;
+    }
+    QIL_REQUIRE(A->off + (count - 1) * A->bs + (a_rows - 1) + A->ld * (a_cols - 1) < A->elems, QIL_EINVAL_ARG, "gemm: A reaches beyond its buffer");
+    QIL_REQUIRE(B->off + (count - 1) * B->bs + sel_max * b_sel_stride + (b_rows - 1) + B->ld * (b_cols - 1) < B->elems, QIL_EINVAL_ARG,
+                "gemm: B reaches beyond its buffer");
+    QIL_REQUIRE(C->off + (count - 1) * C->bs + (m - 1) + C->ld * (c_cols - 1) < C->elems, QIL_EINVAL_ARG, "gemm: C reaches beyond its buffer");
+    QIL_TRY(qil_ctx_activate(ctx));
+    qil_call_scope call_scope(ctx);
+    const size_t e = qil_elem_size(dtype);
+    void *dA = nullptr, *dB = nullptr, *dC = nullptr, *dsel = nullptr, *dmap = nullptr;
+    QIL_TRY(qil_ctx_alloc(ctx, (size_t)A->elems * e, &dA));
+    QIL_TRY(qil_ctx_alloc(ctx, (size_t)B->elems * e, &dB));
+    QIL_TRY(qil_ctx_alloc(ctx, (size_t)C->elems * e, &dC));
+    QIL_HIP(hipMemcpyAsync(dA, A->base, (size_t)A->elems * e, hipMemcpyHostToDevice, qil_stream(ctx)));
+    QIL_HIP(hipMemcpyAsync(dB, B->base, (size_t)B->elems * e, hipMemcpyHostToDevice, qil_stream(ctx)));
+    QIL_HIP(hipMemcpyAsync(dC, C->base, (size_t)C->elems * e, hipMemcpyHostToDevice, qil_stream(ctx)));
+    gemm_batch bt;
+    bt.count = (int)count;
+    bt.a_bs = A->bs, bt.b_bs = B->bs, bt.c_bs = C->bs;
+    bt.subtract = subtract ? 1 : 0;
+    bt.skinny_m = skinny_m ? 1 : 0;
+    if (b_sel) {
+        const size_t nsel = (size_t)((count - 1) * b_sel_step + 1);
+        QIL_TRY(qil_ctx_alloc(ctx, nsel, &dsel));
+        QIL_HIP(hipMemcpyAsync(dsel, b_sel, nsel, hipMemcpyHostToDevice, qil_stream(ctx)));
+        bt.b_sel = static_cast<const uint8_t*>(dsel), bt.b_sel_step = b_sel_step, bt.b_sel_stride = b_sel_stride;
+    }
+    if (cmap) {
+        const size_t nmap = (size_t)(count * (n / cmap_blk)) * sizeof(int);
+        QIL_TRY(qil_ctx_alloc(ctx, nmap, &dmap));
+        QIL_HIP(hipMemcpyAsync(dmap, cmap, nmap, hipMemcpyHostToDevice, qil_stream(ctx)));
+        bt.cmap = static_cast<const int*>(dmap), bt.cmap_blk = (int)cmap_blk;
+    }
+    QIL_HIP(qil_stream_sync(ctx));
+    if (dtype == QIL_C64) {
+        QIL_TRY(gemm_dispatch<c64>(ctx, opA, opB, m, n, k, (const c64*)dA + A->off, A->ld, (const c64*)dB + B->off, B->ld,
+                                   (c64*)dC + C->off, C->ld, bt));
+    } else {
+        static const int real_op[4] = {0, 1, 1, 0};
+        QIL_TRY(gemm_dispatch<double>(ctx, real_op[opA], real_op[opB], m, n, k, (const double*)dA + A->off, A->ld,
+                                      (const double*)dB + B->off, B->ld, (double*)dC + C->off, C->ld, bt));
+    }
+    QIL_TRY(qil_read_back(ctx, C->base, dC, (size_t)C->elems * e));
+    qil_ctx_free(ctx, dA);
+    qil_ctx_free(ctx, dB);
+    qil_ctx_free(ctx, dC);
+    if (dsel) qil_ctx_free(ctx, dsel);
+    if (dmap) qil_ctx_free(ctx, dmap);
     return QIL_OK;
 }
 

@@ -786,6 +786,55 @@ def gemm(A, B, opA="N", opB="N", ctx=None):
     return Cm
 
 
+def gemm_plan(dtype, m, n, k, opA="N", opB="N", lda=None, ldb=None, ldc=None, count=1, c_bs=0, has_cmap=False,
+              skinny_m=False):
+    """What the MFMA GEMM's dispatch decides for this product (testing hook; needs no GPU): a dict of the fields of
+    qil_gemm_plan_info.  Leading dimensions default to tight ones."""
+    code = L.QIL_C64 if np.dtype(dtype) == np.complex128 else L.QIL_F64
+    lda = (m if opA in "NC" else k) if lda is None else lda
+    ldb = (k if opB in "NC" else n) if ldb is None else ldb
+    ldc = m if ldc is None else ldc
+    info = L.GemmPlanInfo()
+    L.check(L.lib.qil_gemm_plan(code, _OPS[opA], _OPS[opB], int(m), int(n), int(k), int(lda), int(ldb), int(ldc),
+                                int(count), int(c_bs), int(bool(has_cmap)), int(bool(skinny_m)), C.byref(info)))
+    return {name: int(getattr(info, name)) for name, _ in info._fields_}
+
+
+def gemm_batched(A, B, Cbuf, m, n, k, opA="N", opB="N", a=(0, None, 0), b=(0, None, 0), c=(0, None, 0), count=1,
+                 subtract=False, skinny_m=False, b_sel=None, b_sel_step=0, b_sel_stride=0, cmap=None, cmap_blk=1, ctx=None):
+    """The batched / epilogue forms of the MFMA GEMM on host buffers (testing hook).  A, B, Cbuf are flat parent buffers of one
+    dtype; a, b, c = (element offset, leading dimension, batch stride) of each operand inside its buffer.  Cbuf is uploaded whole,
+    the product of batch i is written (or, with subtract, subtracted) at c_off + i * c_bs, and the whole buffer comes back in
+    place; it is also returned."""
+    ctx = ctx or default_context()
+    code = L.QIL_C64 if Cbuf.dtype == np.complex128 else L.QIL_F64
+    dt = _np_dtype(code)
+    bufs = []
+    for x in (A, B, Cbuf):
+        if not (isinstance(x, np.ndarray) and x.ndim == 1 and x.dtype == dt and x.flags.c_contiguous):
+            raise ValueError("gemm_batched: operands are flat contiguous arrays of the output's dtype")
+        bufs.append(x)
+    tight = ((m if opA in "NC" else k), (k if opB in "NC" else n), m)
+    ops_ = []
+    for x, (off, ld, bs), t in zip(bufs, (a, b, c), tight):
+        ops_.append(L.GemmHostOperand(x.ctypes.data, x.size, int(off), int(t if ld is None else ld), int(bs)))
+    sel = mp = None
+    if b_sel is not None:
+        sel = np.ascontiguousarray(b_sel, dtype=np.uint8)
+        if sel.size < (count - 1) * b_sel_step + 1:
+            raise ValueError("gemm_batched: b_sel is shorter than (count - 1) * b_sel_step + 1")
+    if cmap is not None:
+        mp = np.ascontiguousarray(cmap, dtype=np.int32)
+        if cmap_blk < 1 or mp.size < count * (n // cmap_blk):
+            raise ValueError("gemm_batched: cmap is shorter than count * n / cmap_blk")
+    L.check(L.lib.qil_gemm_batched_host(
+        ctx.handle, code, _OPS[opA], _OPS[opB], int(m), int(n), int(k), C.byref(ops_[0]), C.byref(ops_[1]), C.byref(ops_[2]),
+        int(count), int(bool(subtract)), int(bool(skinny_m)),
+        sel.ctypes.data_as(C.POINTER(C.c_uint8)) if sel is not None else None, int(b_sel_step), int(b_sel_stride),
+        mp.ctypes.data_as(C.POINTER(C.c_int32)) if mp is not None else None, int(cmap_blk)))
+    return Cbuf
+
+
 def gemm_device_time(m, n, k, dtype=np.float64, opA="N", opB="N", reps=10, ctx=None):
     """ms per call of the device-resident MFMA GEMM (diagnostic)."""
     ctx = ctx or default_context()
