@@ -269,6 +269,46 @@ QIL_API int qil_mpo_adjoint(const qil_mpo* W, qil_mpo** out);
 QIL_API int qil_hadamard_compress(const qil_mps* phi, int conj_phi, const qil_mps* psi, int64_t maxdim, double tol, int sweeps,
                           int64_t zip_maxdim, qil_mps** out);
 
+/* ------------------------------------------------------------------ linear combinations (no reference counterpart) */
+/* out = sum_j c_j terms[j], materialised as the direct sum of the chains; nothing is truncated.
+ *   coeffs    host memory, nb complex values as interleaved (re, im) doubles; null = all ones.
+ *   terms     entries may repeat (psi + psi); repeated and zero-weight terms keep their block, so the structure of the result
+ *             depends on the operands' shapes only.
+ *   dtype     promote(terms); c64 as well when any coefficient has a non-zero imaginary part.
+ *   metadata  site ids and paired flag of terms[0]; amplitude 1.0: the weights w_j = c_j * amplitude_j are multiplied into the
+ *             first tensor's blocks (the way qil_mpo_diagonal folds its amplitude).
+ *   bonds     every internal bond is sum_j chi_j.
+ *   layout    term j occupies rows [off_l(j), off_l(j) + chi_l(j)) and columns [off_r(j), off_r(j) + chi_r(j)), offsets in
+ *             term order: the first tensor is the row [w_1 A^1 | w_2 A^2 | ...] (1 x 2 x sum chi), the last tensor the column
+ *             stack (sum chi x 2 x 1); for n = 1 the single tensor is sum_j w_j A^j.
+ *   exactness interior and last tensors are copies: block entries equal the operand's bit for bit (a real operand of a c64
+ *             result is widened with imaginary part +0.0), every off-block entry is exactly +0.0; only the first tensor
+ *             carries one rounding, from the multiply by w_j.
+ * One grouped launch writes all sites, every output element exactly once, zeros included: HBM-store bound like qil_hadamard.
+ * Errors, all returned before the context is activated: QIL_EINVAL_ARG for a null terms / out / entry ("mps_sum: null
+ * argument"), nb < 1, a non-finite coefficient, terms of different contexts or mixed paired flags; QIL_EINVAL_LENGTH for
+ * different numbers of sites; QIL_EINVAL_SITES for different site ids (each term against terms[0], in that order).       */
+QIL_API int qil_mps_sum(const qil_mps* const* terms, int64_t nb, const double* coeffs, qil_mps** out);
+/* compress!(sum_j c_j terms[j]; maxdim, tol, sweeps); with a cap (maxdim) below sum chi, without the direct-sum tensors of
+ * size (sum chi)^2: the terms are copied
+ * and brought to right-canonical gauge by exact QRs, a zip-up sweep carries one environment per term (stored concatenated) and
+ * builds a basis per bond with intermediate cap zip_maxdim (<= 0: the default of qil_apply_compress, max(maxdim + 16, maxdim +
+ * ceil(maxdim / 8)); sketched on capped bonds), ONE variational sweep replaces every site by the best tensor given the others
+ * (re-gauged at canonicalize!'s cutoff 1e-12: it stands in for the gauge pass compress! opens with), then the exact-gauge
+ * compress! runs.  Where a concatenated bond fits under zip_maxdim the sweep takes the exact route's gauge step literally (the SVD
+ * of the stacked operand at cutoff 1e-12); when every bond does -- small sums, calls without a cap -- the operands are read as
+ * they are, no copy, no zip-up, and the bonds are those of qil_mps_sum + qil_compress.  Such a call saves the (sum chi)^2 site
+ * tensors but not the work: its stacked operands are sum chi x 2 r' with r' up to sum chi, so an uncapped sum costs what
+ * qil_mps_sum + qil_compress costs.  Two departures from a plain zip-up + QR-gauged sweep, both so that the bonds are those of
+ * the exact route on decaying spectra too: this literal step, and the 1e-12 cutoff of the sweep.  The result has the post-conditions of compress!: bonds by the ITensors rule with cutoff
+ * = tol^2 / ((N - 1) sweeps), unit-norm tensors, the norm in `amplitude`.  The per-term products of a step run in one grouped
+ * f64-MFMA launch while every term's bond is <= 64 and the carried bond of the step <= 128, through the GEMM per term above that.  Nothing but the result outlives
+ * the call, also when an allocation fails midway.  Operand checks as qil_mps_sum under the name "mps_sum_compress", then the
+ * error codes of qil_apply_compress (QIL_EDOMAIN for n < 2, sweeps >= 1).  Accuracy against qil_mps_sum + qil_compress (the
+ * exact route): identical bonds and a state error <= 2x the truncation's own on random operands (tests/test_gpu_sum.py).   */
+QIL_API int qil_mps_sum_compress(const qil_mps* const* terms, int64_t nb, const double* coeffs, int64_t maxdim, double tol,
+                                 int sweeps, int64_t zip_maxdim, qil_mps** out);
+
 /* ------------------------------------------------------------------ truncation (K1, K2) */
 /* canonicalize!(psi, direction; center, cutoff=1e-12, maxdim) src/mps.jl:787-847.
  * center = 0 selects the default (N for :right, 1 for :left); 1-based otherwise.    */

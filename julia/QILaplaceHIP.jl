@@ -19,7 +19,7 @@ using ..ApplyMPO: _as_single_site_mpo
 export DeviceMPS, DeviceMPO, to_device, to_host, signal_mps_device, marginal, mps_block, apply_compress,
     compress_mpo!, build_dt_mpo_batch, build_qft_mpo_device, build_zt_qft_chain_device, apply_coefficient_sweep, apply!, rsvd_device, svd_device,
     Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm, sample, top_k,
-    hadamard, hadamard_compress, diagonal_mpo
+    hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress
 
 const LIB = get(ENV, "QILHIP_LIB", "libqilhip.so")
 
@@ -288,6 +288,36 @@ function adjoint(W::DeviceMPO)
     check(ccall((:qil_mpo_adjoint, LIB), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), W.h, r))
     return finalizer(_free!, DeviceMPO(r[], copy(W.sites), W.paired))
 end
+# linear combinations of states (no reference counterpart).  linear_combination: sum_j c_j terms[j] as the direct sum of the
+# chains (bonds add, amplitude 1, one grouped launch); linear_combination_compress: compress!(that sum) without the direct-sum
+# tensors (zip-up over per-term environments + one variational sweep); phi + psi, phi - psi on top of the first
+function _coeff_pairs(coeffs, nb::Int)
+    coeffs === nothing && return C_NULL
+    length(coeffs) == nb || throw(ArgumentError("linear_combination: $(length(coeffs)) coefficients for $nb terms"))
+    return collect(reinterpret(Float64, ComplexF64.(coeffs)))
+end
+function linear_combination(terms::Vector{<:DeviceMPS}, coeffs=nothing)
+    isempty(terms) && throw(ArgumentError("linear_combination: needs at least one term"))
+    hs = Ptr{Cvoid}[t.h for t in terms]
+    c = _coeff_pairs(coeffs, length(terms))
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve terms c check(ccall((:qil_mps_sum, LIB), Cint, (Ptr{Ptr{Cvoid}}, Int64, Ptr{Cdouble}, Ref{Ptr{Cvoid}}),
+                                     hs, length(terms), c, r))
+    return finalizer(_free!, DeviceMPS(r[], copy(terms[1].sites), terms[1].paired))
+end
+function linear_combination_compress(terms::Vector{<:DeviceMPS}, coeffs=nothing; maxdim::Int=typemax(Int), tol::Float64=1e-12,
+                                     sweeps::Int=1, zip_maxdim::Int=0)
+    isempty(terms) && throw(ArgumentError("linear_combination: needs at least one term"))
+    hs = Ptr{Cvoid}[t.h for t in terms]
+    c = _coeff_pairs(coeffs, length(terms))
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve terms c check(ccall((:qil_mps_sum_compress, LIB), Cint,
+                                     (Ptr{Ptr{Cvoid}}, Int64, Ptr{Cdouble}, Int64, Cdouble, Cint, Int64, Ref{Ptr{Cvoid}}),
+                                     hs, length(terms), c, maxdim == typemax(Int) ? 0 : maxdim, tol, sweeps, zip_maxdim, r))
+    return finalizer(_free!, DeviceMPS(r[], copy(terms[1].sites), terms[1].paired))
+end
+Base.:+(phi::DeviceMPS, psi::DeviceMPS) = linear_combination([phi, psi], [1.0, 1.0])
+Base.:-(phi::DeviceMPS, psi::DeviceMPS) = linear_combination([phi, psi], [1.0, -1.0])
 function mps_to_vector(psi::DeviceMPS; reverse::Bool=false)                                        # mps.jl:716
     d = Ref{Cint}(0)
     check(ccall((:qil_mps_dtype, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}), psi.h, d))

@@ -258,6 +258,24 @@ class SignalMPS(_Chain):
         L.check(L.lib.qil_mps_clone(self.handle, C.byref(h)))
         return type(self)(ctx=self.ctx, _handle=h)
 
+    # psi + phi, psi - phi, -psi: the vector-space operations (ops.linear_combination / ops.scale).  A ZTMPS combines only with
+    # a ZTMPS.  `*` is deliberately absent here: it stays the operator application W * psi.
+    def __add__(self, other):
+        if not isinstance(other, SignalMPS) or self._paired() != other._paired():
+            return NotImplemented
+        from .ops import add
+        return add(self, other)
+
+    def __sub__(self, other):
+        if not isinstance(other, SignalMPS) or self._paired() != other._paired():
+            return NotImplemented
+        from .ops import sub
+        return sub(self, other)
+
+    def __neg__(self):
+        from .ops import scale
+        return scale(self, -1.0)
+
     def __getitem__(self, bits):
         """psi[b1, b2, ...] == coefficient(psi, (b1, b2, ...))  (src/mps.jl:692-693)."""
         from .ops import coefficient

@@ -318,6 +318,8 @@ int make_diagonal(const qil_mps* phi, int conj_phi, qil_mpo** out) {
 
 }  // namespace
 
+int qil_check_pair(const char* verb, const qil_mps* phi, const qil_mps* psi) { return check_pair(verb, phi, psi); }
+
 extern "C" int qil_hadamard(const qil_mps* phi, int conj_phi, const qil_mps* psi, qil_mps** out) {
     QIL_REQUIRE(phi && psi && out, QIL_EINVAL_ARG, "hadamard: null argument");
     QIL_TRY(check_pair("hadamard", phi, psi));

@@ -280,6 +280,28 @@ struct qil_gemm_batch {
 int qil_dev_gemm_batched(qil_context* ctx, int dtype, int opA, int opB, int64_t m, int64_t n, int64_t k,
                          const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
                          const qil_gemm_batch* batch);
+// A table of SMALL independent products in ONE launch (qil_sum.hip): C (m x n, ldc) = A (m x k, lda) * B (k x n, ldb), all of
+// one dtype, one 16 x 16 f64-MFMA tile per wave, no LDS.  For steps that would otherwise
+// cost one ~4 us dispatch per operand for a microsecond of work (the per-term products of qil_mps_sum_compress); tile_begin is
+// filled in by the call.  qil_dev_gemm_grouped_fits: the table fits one descriptor slot.
+struct qil_gemm_problem {
+    const void* A;
+    const void* B;
+    void* C;
+    int m, n, k;
+    int lda, ldb, ldc;
+    int tile_begin;
+    int pad;
+};
+int qil_dev_gemm_grouped(qil_context* ctx, int dtype, std::vector<qil_gemm_problem>& probs);
+bool qil_dev_gemm_grouped_fits(size_t nproblems);
+// (qil_hadamard.hip) phi against psi under `verb`: context, paired flag (QIL_EINVAL_ARG), length (QIL_EINVAL_LENGTH), site ids
+// (QIL_EINVAL_SITES), in that order; touches no device
+int qil_check_pair(const char* verb, const struct qil_mps* phi, const struct qil_mps* psi);
+// (qil_truncate.hip) the fused sum-and-truncate behind qil_mps_sum_compress: operands checked, context active, call scope open;
+// w = nb (re, im) weights with the amplitudes folded in, odt = result dtype
+int qil_sum_compress_impl(qil_context* ctx, const struct qil_mps* const* terms, int64_t nb, const double* w, int odt,
+                          int64_t maxdim, double tol, int sweeps, int64_t zip_maxdim, struct qil_mps** out);
 // |r_jj|^2 (j < n <= 1024) of a triangular factor on the device, to the host
 int qil_dev_diag_abs2(qil_context* ctx, int dtype, const void* R, int64_t ldr, int64_t n, double* host_out);
 // At (n x m, ldt) = A^T (conj = 0) or A^H (conj = 1)

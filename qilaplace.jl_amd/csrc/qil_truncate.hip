@@ -1279,6 +1279,279 @@ extern "C" int qil_apply_compress_batch(const qil_mpo* const* Ws, const qil_mps*
     return st;
 }
 
+// Fused sum-and-truncate: compress!(sum_j w_j psi_j; maxdim, tol, sweeps) WITHOUT the direct-sum tensors of size (sum chi)^2.
+// The structure of apply_compress_on with the terms in the operator's place:
+//   1. every (distinct) term is copied and brought to right-canonical gauge by exact thin QRs; the weights are the 1 x 1
+//      environments the zip-up starts from, so no term tensor is touched for them;
+//   2. zip-up left to right: term j carries C_j (r x chi_j), all of them stored concatenated as ONE r x sum(chi) array; per site
+//          theta = [C_1 A^1 | C_2 A^2 | ...]     (2r x sum(chi_right), each product into its own column slice)
+//      an orthonormal basis U of its column space (sketched on capped bonds, truncated SVD at cutoff * 1e-2 otherwise) is the
+//      provisional site and C' = U^H theta the next concatenated environment;
+//   3. one variational sweep right to left with the kept C's and right environments R_j (chi_j x r', stacked by rows):
+//          site_i = [C_1 ... C_nb] * rowstack(A^j R_j)        ONE GEMM over the concatenated inner dimension
+//      re-gauged by an SVD at canonicalize!'s cutoff 1e-12 (this sweep stands in for the gauge pass compress! opens with), then
+//      R_j <- (A^j R_j) conj(site), again one GEMM on the stacked operand;
+//   4. compress_impl on the right-canonical result.
+// The per-term products C_j A^j (r x chi x 2 chi) and A^j R_j (chi x chi x r') go through the grouped small GEMM (one launch per
+// step for ALL terms) while every term's bond is <= kSumGroupedMaxBond and the carried side r resp. r' of the step is
+// <= kSumGroupedMaxSide: a product of at most 128 x 128 x 64.  The kernel is one 16 x 16 tile per wave without LDS reuse, made
+// for steps whose cost is the dispatch; larger products go to qil_dev_gemm's tiling, one call per term.  Both bounds were
+// chosen by that argument, not by a sweep (MEASUREMENTS section 10 records the launch counts and what was not measured).
+constexpr int64_t kSumGroupedMaxBond = 64;
+constexpr int64_t kSumGroupedMaxSide = 128;
+
+int qil_sum_compress_impl(qil_context* ctx, const qil_mps* const* terms, int64_t nb, const double* w, int odt, int64_t maxdim,
+                          double tol, int sweeps, int64_t zip_maxdim, qil_mps** out) {
+    const int64_t N = terms[0]->n();
+    if (maxdim <= 0) maxdim = kNoCap;
+    const int64_t zip_over = 16;                     // the oversampling of apply_compress_on (see there for the evidence)
+    if (zip_maxdim <= 0) zip_maxdim = maxdim > kNoCap / 2 ? kNoCap : std::max(maxdim + zip_over, maxdim + (maxdim + 7) / 8);
+    const double cutoff = tol * tol / ((double)(N - 1) * sweeps);
+    const double zip_cutoff = cutoff * 1e-2;
+    const size_t e = qil_elem_size(odt);
+    std::vector<qil_mps*> own;                       // the distinct right-canonical copies (handles: destroyed explicitly)
+    std::vector<const qil_mps*> seen;
+    std::vector<const qil_mps*> phi((size_t)nb, nullptr);
+    qil_mps* res = nullptr;
+    std::vector<void*> tmp;                          // every pool block this call owns outside a handle
+    auto cleanup = [&](int code) {
+        for (void* p : tmp) qil_ctx_free(ctx, p);
+        tmp.clear();
+        for (qil_mps* c : own) qil_mps_destroy(c);
+        own.clear();
+        if (code != QIL_OK && res) {
+            qil_mps_destroy(res);
+            res = nullptr;
+        }
+        return code;
+    };
+    auto take = [&](size_t bytes, void** p) {
+        int s = qil_ctx_alloc(ctx, bytes, p);
+        if (s == QIL_OK) tmp.push_back(*p);
+        return s;
+    };
+    auto forget = [&](void* p) {
+        for (size_t t = tmp.size(); t-- > 0;)
+            if (tmp[t] == p) {
+                tmp.erase(tmp.begin() + (long)t);
+                break;
+            }
+    };
+    auto drop = [&](void* p) {
+        forget(p);
+        qil_ctx_free(ctx, p);
+    };
+    int st = QIL_OK;
+    // `literal`: every concatenated bond of the operands fits under the cap.  Then the sweep of step 3 takes the exact route's
+    // gauge step at every site (see there), which needs neither the zip-up nor gauged terms: the operands are read as they are,
+    // and the decisions are those of compress! on the direct sum, bond for bond.
+    bool literal = true;
+    for (int64_t i = 1; i < N && literal; ++i) {
+        int64_t sc = 0;
+        for (int64_t j = 0; j < nb; ++j) sc += terms[j]->dims[(size_t)i];
+        literal = sc <= zip_maxdim;
+    }
+    // ---- 1. gauge (a repeated handle is copied once)
+    for (int64_t j = 0; j < nb; ++j) {
+        if (literal && (odt == QIL_F64 || terms[j]->dtype == QIL_C64)) {
+            phi[(size_t)j] = terms[j];
+            continue;
+        }
+        for (size_t t = 0; t < seen.size(); ++t)
+            if (seen[t] == terms[j]) phi[(size_t)j] = own[t];
+        if (phi[(size_t)j]) continue;
+        qil_mps* c = nullptr;
+        if ((st = qil_mps_clone_to(ctx, terms[j], &c)) != QIL_OK) {
+            if (c) qil_mps_destroy(c);
+            return cleanup(st);
+        }
+        own.push_back(c);
+        seen.push_back(terms[j]);
+        phi[(size_t)j] = c;
+        if (!literal && (st = canonicalize_impl(c, QIL_DIR_LEFT, 0, 0.0, kNoCap, true)) != QIL_OK) return cleanup(st);
+        if (odt == QIL_C64 && c->dtype == QIL_F64) {           // a real term of a complex sum is widened once: KB..MB
+            for (int64_t i = 0; i < N; ++i) {
+                const long long ne = c->site_elems(i);
+                void* p = nullptr;
+                if ((st = qil_ctx_alloc(ctx, (size_t)ne * e, &p)) != QIL_OK) return cleanup(st);
+                st = qil_klaunch<widen_f64_k>(ctx, dim3(nblk(ne)), dim3(256), 0, (const double*)c->site[(size_t)i], (c64*)p, ne);
+                if (st == QIL_OK) st = qil_chain_set_site(c, i, p, c->dims[(size_t)i], c->dims[(size_t)i + 1]);
+                if (st != QIL_OK) return cleanup(st);
+            }
+            c->dtype = QIL_C64;
+        }
+    }
+    // offsets of the terms inside every concatenated bond (the edge bonds included: nb entries of 1)
+    std::vector<std::vector<int64_t>> off((size_t)N + 1, std::vector<int64_t>((size_t)nb + 1, 0));
+    int64_t maxbond = 1, om_ld = 1;
+    for (int64_t i = 0; i <= N; ++i) {
+        for (int64_t j = 0; j < nb; ++j) {
+            off[(size_t)i][(size_t)j + 1] = off[(size_t)i][(size_t)j] + phi[(size_t)j]->dims[(size_t)i];
+            maxbond = std::max(maxbond, phi[(size_t)j]->dims[(size_t)i]);
+        }
+        if (i >= 1 && i < N) om_ld = std::max(om_ld, off[(size_t)i][(size_t)nb]);
+    }
+    auto sig = [&](int64_t i) { return off[(size_t)i][(size_t)nb]; };
+    // QIL_SUM_NO_GROUPED: the per-term GEMMs everywhere (A/B of the grouped kernel, tools/_sum_time.py)
+    const bool grouped = maxbond <= kSumGroupedMaxBond && qil_dev_gemm_grouped_fits((size_t)(2 * nb)) && !getenv("QIL_SUM_NO_GROUPED");
+    auto at = [&](const void* base, int64_t elems) { return (void*)((char*)base + (size_t)elems * e); };
+    std::vector<qil_gemm_problem> probs;
+    auto run_products = [&](int64_t side) {          // one launch for all terms, or one GEMM per term
+        if (grouped && side <= kSumGroupedMaxSide) return qil_dev_gemm_grouped(ctx, odt, probs);
+        for (const qil_gemm_problem& p : probs)
+            QIL_TRY(qil_dev_gemm(ctx, odt, 0, 0, p.m, p.n, p.k, p.A, p.lda, p.B, p.ldb, p.C, p.ldc));
+        return (int)QIL_OK;
+    };
+    auto upload = [&](const std::vector<double>& host, void** p) {     // nb small numbers; the source dies with this frame
+        int s2 = take(host.size() * sizeof(double), p);
+        if (s2 == QIL_OK && hipMemcpyAsync(*p, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, qil_stream(ctx)) != hipSuccess)
+            s2 = qil_fail(QIL_EHIP, "mps_sum_compress: upload failed");
+        if (s2 == QIL_OK && qil_stream_sync(ctx) != hipSuccess) s2 = qil_fail(QIL_EHIP, "mps_sum_compress: sync failed");
+        return s2;
+    };
+    res = new qil_mps();
+    qil_chain_bind(res, ctx);
+    res->dtype = odt;
+    res->paired = terms[0]->paired;
+    res->phys_rank = 1;
+    res->dims.assign((size_t)N + 1, 1);
+    res->site.assign((size_t)N, nullptr);
+    res->site_ids = terms[0]->site_ids;
+    res->amplitude = 1.0;                            // the weights carry the amplitudes
+    // sketch matrix for capped bonds (one for the whole call: any sub-block of a Gaussian matrix is Gaussian)
+    void* Om = nullptr;
+    if (zip_maxdim < om_ld) {
+        if ((st = take((size_t)(om_ld * zip_maxdim) * e, &Om)) != QIL_OK) return cleanup(st);
+        if ((st = qil_dev_fill_normal(ctx, odt, Om, om_ld * zip_maxdim, 0x51b0e7c5ull, 1.0)) != QIL_OK) return cleanup(st);
+    }
+    // ---- 2. zip-up, keeping the concatenated environments C_i (Rdim[i] x sig(i)); C_0 = the row of weights
+    std::vector<void*> Ckeep((size_t)N, nullptr);
+    std::vector<int64_t> Rdim((size_t)N + 1, 1);
+    {
+        std::vector<double> h((size_t)nb * (odt == QIL_C64 ? 2 : 1));
+        for (int64_t j = 0; j < nb; ++j) {
+            if (odt == QIL_C64) {
+                h[(size_t)(2 * j)] = w[2 * j];
+                h[(size_t)(2 * j + 1)] = w[2 * j + 1];
+            } else {
+                h[(size_t)j] = w[2 * j];
+            }
+        }
+        if ((st = upload(h, &Ckeep[0])) != QIL_OK) return cleanup(st);
+    }
+    for (int64_t i = 0; i + 1 < N && !literal; ++i) {   // the last site is formed by the variational sweep
+        const int64_t R = Rdim[(size_t)i], rows = 2 * R, Pc = sig(i + 1);
+        void* theta = nullptr;
+        if ((st = take((size_t)(rows * Pc) * e, &theta)) != QIL_OK) return cleanup(st);
+        probs.clear();
+        for (int64_t j = 0; j < nb; ++j) {           // theta[:, slice j] = C_j (R x chi_l) A^j (chi_l x 2 chi_r), layout [r, s, beta]
+            const qil_mps* t = phi[(size_t)j];
+            const int64_t cl = t->dims[(size_t)i], cr = t->dims[(size_t)i + 1];
+            probs.push_back(qil_gemm_problem{at(Ckeep[(size_t)i], R * off[(size_t)i][(size_t)j]), t->site[(size_t)i],
+                                             at(theta, rows * off[(size_t)i + 1][(size_t)j]), (int)R, (int)(2 * cr), (int)cl,
+                                             (int)R, (int)cl, (int)R, 0, 0});
+        }
+        if ((st = run_products(R)) != QIL_OK) return cleanup(st);
+        int64_t r = 0;
+        void *U = nullptr, *SV = nullptr;
+        if (zip_maxdim < std::min(rows, Pc)) {       // capped bond: orthonormal basis of theta Omega (see apply_compress_on)
+            r = zip_maxdim;
+            void* Y = nullptr;
+            if ((st = qil_ctx_alloc(ctx, (size_t)(rows * r) * e, &Y)) != QIL_OK) return cleanup(st);
+            st = qil_dev_gemm(ctx, odt, 0, 0, rows, r, Pc, theta, rows, Om, om_ld, Y, rows);
+            if (st == QIL_OK) st = qil_dev_qr_positive(ctx, odt, rows, r, Y, rows, nullptr, 0, true);
+            if (st == QIL_OK) st = qil_ctx_alloc(ctx, (size_t)(r * Pc) * e, &SV);
+            if (st == QIL_OK) st = qil_dev_gemm(ctx, odt, odt == QIL_C64 ? 2 : 1, 0, r, Pc, rows, Y, rows, theta, rows, SV, r);
+            if (st != QIL_OK) return cleanup(st);
+            U = Y;
+        } else {
+            st = svd_trunc_dev(ctx, odt, rows, Pc, theta, rows, zip_cutoff, true, zip_maxdim, 1, 2, &r, &U, &SV, nullptr);
+            if (st != QIL_OK) return cleanup(st);
+        }
+        drop(theta);
+        qil_chain_adopt(res, i, U);                  // [R, s, r]
+        res->dims[(size_t)i] = R;
+        res->dims[(size_t)i + 1] = r;
+        tmp.push_back(SV);
+        Ckeep[(size_t)i + 1] = SV;                   // [r, sig(i + 1)]: the C_j of the next site, concatenated
+        Rdim[(size_t)i + 1] = r;
+    }
+    // ---- 3. variational sweep right to left; Rcat = row stack of the R_j (sig(i + 1) x rp)
+    void* Rcat = nullptr;
+    int64_t rp = 1;
+    {
+        std::vector<double> h((size_t)nb * (odt == QIL_C64 ? 2 : 1), 0.0);
+        for (int64_t j = 0; j < nb; ++j) h[(size_t)(odt == QIL_C64 ? 2 * j : j)] = 1.0;
+        if ((st = upload(h, &Rcat)) != QIL_OK) return cleanup(st);
+    }
+    for (int64_t i = N - 1; i >= 0; --i) {
+        const int64_t R = Rdim[(size_t)i], Sl = sig(i), Sr = sig(i + 1);
+        void *AR = nullptr, *T = nullptr;
+        if ((st = take((size_t)(Sl * 2 * rp) * e, &AR)) != QIL_OK) return cleanup(st);
+        probs.clear();
+        for (int64_t j = 0; j < nb; ++j) {           // AR[rows of j, (s, r')] = A^j[:, s, :] (chi_l x chi_r) R_j (chi_r x rp)
+            const qil_mps* t = phi[(size_t)j];
+            const int64_t cl = t->dims[(size_t)i], cr = t->dims[(size_t)i + 1];
+            for (int s = 0; s < 2; ++s)
+                probs.push_back(qil_gemm_problem{at(t->site[(size_t)i], cl * s), at(Rcat, off[(size_t)i + 1][(size_t)j]),
+                                                 at(AR, off[(size_t)i][(size_t)j] + Sl * s), (int)cl, (int)rp, (int)cr,
+                                                 (int)(2 * cl), (int)Sr, (int)(2 * Sl), 0, 0});
+        }
+        if ((st = run_products(rp)) != QIL_OK) return cleanup(st);
+        if (i > 0 && Sl <= zip_maxdim) {
+            // The stacked operand is no larger than a capped site: take the gauge step of the exact route literally.  AR IS the
+            // matrix canonicalize!(:left) factors at this bond of the direct sum (rows: the concatenated left bond, columns: an
+            // orthonormal basis of everything to the right), so its SVD at that pass's cutoff 1e-12 makes the same decision:
+            // site_i = V^H, and U S is the stack of the new R_j.  Uncapped calls and small sums run entirely through here.
+            int64_t K = 0;
+            void *US = nullptr, *Vh = nullptr;
+            if ((st = svd_trunc_dev(ctx, odt, Sl, 2 * rp, AR, Sl, 1e-12, true, kNoCap, 1, 1, &K, &US, &Vh, nullptr)) != QIL_OK)
+                return cleanup(st);
+            tmp.push_back(US);
+            if ((st = qil_chain_set_site(res, i, Vh, K, rp)) != QIL_OK) return cleanup(st);
+            drop(AR);
+            drop(Rcat);
+            drop(Ckeep[(size_t)i]);
+            Ckeep[(size_t)i] = nullptr;
+            Rcat = US;
+            rp = K;
+            continue;
+        }
+        if ((st = take((size_t)(2 * R * rp) * e, &T)) != QIL_OK) return cleanup(st);
+        st = qil_dev_gemm(ctx, odt, 0, 0, R, 2 * rp, Sl, Ckeep[(size_t)i], R, AR, Sl, T, R);
+        if (st != QIL_OK) return cleanup(st);
+        forget(T);
+        if ((st = qil_chain_set_site(res, i, T, R, rp)) != QIL_OK) return cleanup(st);
+        if (i == 0) break;
+        // This sweep is the right-to-left gauge pass compress! opens with (mps.jl:923, canonicalize!(:left) at its fixed cutoff
+        // 1e-12), so it carries that cutoff: site i is the orthogonality centre here, its singular values are the bond's
+        // Schmidt values, and what the exact route's gauge pass drops from the direct sum is dropped here too.  compress_impl
+        // below is then told the state is right-canonical and skips the pass.
+        if ((st = gauge_site_left(res, i, 1e-12, kNoCap, false)) != QIL_OK) return cleanup(st);
+        const int64_t K = res->dims[(size_t)i];
+        void* Rn = nullptr;
+        if ((st = take((size_t)(Sl * K) * e, &Rn)) != QIL_OK) return cleanup(st);
+        // R_j'[alpha, k] = sum_{s, r'} AR[alpha, (s, r')] conj(site_i[k, (s, r')]) for all terms at once
+        st = qil_dev_gemm(ctx, odt, 0, 2, Sl, K, 2 * rp, AR, Sl, res->site[(size_t)i], K, Rn, Sl);
+        if (st != QIL_OK) return cleanup(st);
+        drop(AR);
+        drop(Rcat);
+        drop(Ckeep[(size_t)i]);
+        Ckeep[(size_t)i] = nullptr;
+        Rcat = Rn;
+        rp = K;
+    }
+    (void)cleanup(QIL_OK);
+    // ---- 4. exact-gauge truncation
+    st = compress_impl(res, maxdim, tol, sweeps, true);        // the variational sweep left res right-canonical
+    if (st != QIL_OK) {
+        qil_mps_destroy(res);
+        return st;
+    }
+    *out = res;
+    return QIL_OK;
+}
+
 static int compress_impl(qil_mps* psi, int64_t maxdim, double tol, int sweeps, bool right_canonical);
 
 extern "C" int qil_compress(qil_mps* psi, int64_t maxdim, double tol, int sweeps) {

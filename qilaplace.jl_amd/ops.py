@@ -635,6 +635,151 @@ def power_spectrum(psi, maxdim=None, tol=1e-12, sweeps=1, zip_maxdim=None):
     return hadamard_compress(psi, psi, conj=True, maxdim=maxdim, tol=tol, sweeps=sweeps, zip_maxdim=zip_maxdim)
 
 
+# ---------------------------------------------------------------- linear combinations
+def _require_terms(terms, coeffs, what="linear_combination"):
+    """A non-empty sequence of states of one register kind and their coefficients as nb x (re, im) doubles (None: all ones),
+    checked before any native call (context, length and sites are checked natively, as for `hadamard`)."""
+    if isinstance(terms, SignalMPS) or not isinstance(terms, (list, tuple)):
+        raise TypeError(f"{what}: unsupported operand types (expected a list of SignalMPS / ZTMPS)")
+    terms = list(terms)
+    if not terms or not all(isinstance(t, SignalMPS) for t in terms):
+        raise TypeError(f"{what}: unsupported operand types (expected a non-empty list of SignalMPS / ZTMPS)")
+    if any(t._paired() != terms[0]._paired() for t in terms):
+        raise TypeError(f"{what}: unsupported operand types (ZTMPS combines only with ZTMPS)")
+    if coeffs is None:
+        return terms, None
+    try:
+        c = np.asarray(coeffs, dtype=np.complex128).reshape(-1)
+    except (TypeError, ValueError):
+        raise TypeError(f"{what}: unsupported operand types (coefficients must be numbers)") from None
+    if c.size != len(terms):
+        raise ValueError(f"{what}: {c.size} coefficients for {len(terms)} terms")
+    return terms, np.ascontiguousarray(c).view(np.float64)
+
+
+def linear_combination(terms, coeffs=None):
+    """sum_j coeffs[j] * terms[j] as a new state of terms[0]'s class, materialised as the direct sum of the chains: every bond
+    is the sum of the terms' bonds, nothing is truncated, the amplitude is 1 (weights and amplitudes sit in the first tensor).
+    `coeffs` may be complex (the result is then complex); None means all ones.  Terms may repeat.  One grouped launch
+    (include/qilaplace_hip.h, qil_mps_sum)."""
+    terms, c = _require_terms(terms, coeffs)
+    _, arr = _handle_array(terms)
+    h = C.c_void_p()
+    L.check(L.lib.qil_mps_sum(arr, len(terms), None if c is None else c.ctypes.data_as(L._pdbl), C.byref(h)))
+    return _wrap_like(terms[0], h)
+
+
+def linear_combination_compress(terms, coeffs=None, maxdim=None, tol=1e-12, sweeps=1, zip_maxdim=None):
+    """compress(linear_combination(terms, coeffs), maxdim, tol, sweeps) without the direct-sum tensors of size (sum chi)^2: the
+    terms are gauged, a zip-up sweep and one variational sweep build the sum at bond <= zip_maxdim (default maxdim + 16), then
+    the exact-gauge compress runs (include/qilaplace_hip.h, qil_mps_sum_compress).  Same bonds as the exact route and at most
+    twice its truncation error on random operands.  What it saves is the (sum chi)^2 tensors and SVDs of that size, so it pays
+    when sum(chi) is well above `maxdim`; without `maxdim` (or with sum(chi) <= maxdim + 16) it is the exact route in stacked
+    form and costs what linear_combination + compress costs.  MEASUREMENTS.md section 10 has the timings that exist."""
+    terms, c = _require_terms(terms, coeffs)
+    _, arr = _handle_array(terms)
+    h = C.c_void_p()
+    L.check(L.lib.qil_mps_sum_compress(arr, len(terms), None if c is None else c.ctypes.data_as(L._pdbl), _maxdim(maxdim),
+                                       float(tol), int(sweeps), 0 if zip_maxdim is None else int(zip_maxdim), C.byref(h)))
+    return _wrap_like(terms[0], h)
+
+
+def add(phi, psi):
+    """phi + psi (linear_combination of the two with unit coefficients)."""
+    return linear_combination([phi, psi], [1.0, 1.0])
+
+
+def sub(phi, psi):
+    """phi - psi."""
+    return linear_combination([phi, psi], [1.0, -1.0])
+
+
+def scale(psi, c):
+    """c * psi as a new state: a real `c` gives a copy with its amplitude scaled, a complex one the one-term sum."""
+    _require_terms([psi], None)
+    if isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, float, complex, np.number)):
+        raise TypeError("linear_combination: unsupported operand types (the factor must be a number)")
+    if np.imag(c) == 0:
+        out = psi.copy()
+        out.amplitude = psi.amplitude * float(np.real(c))
+        return out
+    return linear_combination([psi], [c])
+
+
+def _dyadic_powers(z, n):
+    """z^(2^k), k = 0 .. n-1, each correctly rounded to double: repeated squaring in 256-bit fixed point with a running binary
+    exponent (squaring in double loses a bit per step: 2^39 eps = 6e-5 at n = 40).  Overflow gives inf, underflow 0."""
+    import math
+    z = complex(z)
+    if not (math.isfinite(z.real) and math.isfinite(z.imag)):
+        raise ValueError("exponential_mps: z must be finite")
+    (mr, er), (mi, ei) = math.frexp(z.real), math.frexp(z.imag)
+    ex = min(er, ei) - 53
+    re, im = int(math.ldexp(mr, 53)) << (er - 53 - ex), int(math.ldexp(mi, 53)) << (ei - 53 - ex)
+    out = []
+
+    def to_float(v, e2):
+        try:
+            return math.ldexp(float(v), e2)
+        except OverflowError:
+            return math.copysign(math.inf, v)
+
+    for _ in range(n):
+        out.append(complex(to_float(re, ex), to_float(im, ex)))
+        re, im, ex = re * re - im * im, 2 * re * im, 2 * ex
+        sh = max(re.bit_length(), im.bit_length()) - 256
+        if sh > 0:
+            re, im, ex = re >> sh, im >> sh, ex + sh
+        ex = max(min(ex, 1 << 40), -(1 << 40))               # far outside double's range either way: keep the integers small
+    return out
+
+
+def exponential_tensors(z, n):
+    """(Public because it is the part of `exponential_mps` that needs no device: callers that only want the tensors -- to save
+    them, or to check them on a machine without a GPU -- get them here.)  Host tensors of the bond-1 state x_j = z^j, j < 2^n (site 1 = most significant bit): site i holds [1, z^(2^(n-i))].
+    complex128 unless z is real."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("exponential_mps: n must be >= 1")
+    pw = _dyadic_powers(z, n)
+    real = np.imag(z) == 0
+    data = []
+    for i in range(1, n + 1):
+        A = np.ones((1, 2, 1), dtype=np.float64 if real else np.complex128)
+        A[0, 1, 0] = pw[n - i].real if real else pw[n - i]
+        data.append(A)
+    return data
+
+
+def exponential_mps(z, n, amplitude=1.0, ctx=None):
+    """The complex exponential x_j = amplitude * z^j, j < 2^n, as an exact SignalMPS of bond 1, built on the host from n numbers
+    (no dense vector).  complex128 unless z is real."""
+    return SignalMPS(exponential_tensors(z, n), amplitude=float(amplitude), ctx=ctx)
+
+
+def exponential_sum(amps, zs, n, maxdim=None, tol=1e-12):
+    """x_j = sum_k amps[k] * zs[k]^j, j < 2^n, as a SignalMPS of bond <= K without touching 2^n numbers: the K bond-1 states of
+    `exponential_mps` summed by linear_combination_compress(maxdim, tol) -- or by linear_combination, untruncated at bond K,
+    when both `maxdim` and `tol` are None.
+
+    A mode with |z| > 1 overflows for large n (z^(2^(n-1)) leaves double's range near |z|^(2^n) > 1e308), one with |z| < 1
+    underflows to zero in its upper sites, which is then the value of those samples.  A real damped sinusoid
+    A exp(-g j) cos(w j + p) is TWO conjugate modes: z = exp(-g +- i w) with amps (A / 2) exp(+- i p); the result is complex
+    with an imaginary part at rounding level.
+
+    The truncating route is `compress`: its gauge pass drops whatever carries less than 1e-12 of the squared norm, so a mode
+    that decays within a few samples of a long record (weight ~ 2^-n of the rest) is truncated away; keep such modes with
+    maxdim=None, tol=None."""
+    zs = list(np.atleast_1d(zs))
+    amps = list(np.atleast_1d(amps))
+    if len(zs) != len(amps) or not zs:
+        raise ValueError(f"exponential_sum: {len(amps)} amplitudes for {len(zs)} modes")
+    terms = [exponential_mps(z, n) for z in zs]
+    if maxdim is None and tol is None:
+        return linear_combination(terms, amps)
+    return linear_combination_compress(terms, amps, maxdim=maxdim, tol=1e-12 if tol is None else tol)
+
+
 # ---------------------------------------------------------------- encode
 def _encode(fn, cls, x, method, cutoff, maxdim, k, p, q, random_seed, mindim, ctx):
     if method not in ("svd", "rsvd"):
