@@ -309,6 +309,36 @@ QIL_API int qil_mps_sum(const qil_mps* const* terms, int64_t nb, const double* c
 QIL_API int qil_mps_sum_compress(const qil_mps* const* terms, int64_t nb, const double* coeffs, int64_t maxdim, double tol,
                                  int sweeps, int64_t zip_maxdim, qil_mps** out);
 
+/* ------------------------------------------------------------------ restriction (no reference counterpart) */
+/* The MPS-valued counterpart of qil_mps_block: spec (host, n_tensors bytes, the vocabulary and layout of qil_mps_block's spec)
+ * fixes a site's bit (0 / 1), sums the site (2) or keeps it (3); out is the chain of the KEPT tensors, in order -- one damping
+ * row or frequency column of a z-plane, a zoom window (high bits fixed), a decimated signal (low bits fixed), the copy-register
+ * marginal -- ready for every verb that takes a state, at sizes where no dense block fits.
+ *   removed   a fixed site contributes S_i = A_i[:, b, :], a summed site S_i = A_i[:, 0, :] + A_i[:, 1, :] (slice 0 + slice 1);
+ *             a maximal run p..q of removed sites contributes M = S_p ... S_q (chi_{p-1} x chi_q).
+ *   absorbed  into the kept tensor on the run's right, A'_k = M A_k with A_k viewed as chi_l x 2 chi_r.  A leading run is a row
+ *             vector.  A trailing run (no kept tensor on its right) is a column vector c and goes into the last kept tensor
+ *             from the right, A'_k[:, s] = A_k[:, s, :] c.
+ *   order     (it fixes the rounding) M = ((S_p S_p+1) S_p+2) ..., left to right, leading runs included; c = S_p (S_p+1 (... S_q)),
+ *             right to left; a last kept tensor that takes both is M (A_k c).  A run of length 1 is not formed: its slice is
+ *             read in place from the removed site's tensor, the sum of a summed site made in the operand load.
+ *   result    psi's dtype and amplitude (tensors are not renormalised: qil_norm(out) * amplitude is the 2-norm of the slice), the
+ *             kept sites' ids; internal bonds = the parent's right bonds of the kept sites but the last.  paired = 1 iff psi is
+ *             paired and the kept tensors are whole (main_i, copy_i) pairs, otherwise a plain chain.
+ *   exactness a kept tensor that absorbs nothing is a bit-for-bit copy (spec all 3: a bit-identical clone); results are
+ *             bit-identical from run to run.
+ * One grouped f64-MFMA launch writes all kept sites, copies included, every output element once.  Runs of length >= 2 and
+ * trailing runs are multiplied in one further launch, one workgroup per run with the running product in LDS, while every bond
+ * the run touches is <= 96 (f64) / 64 (c64): two buffers of chi^2 elements within the 160 KiB of a CU; wider runs go through the
+ * GEMM with summed sites materialised, as in qil_mps_block.  One call may mix the routes; their roundings differ.
+ * Nothing but the result outlives the call, also when an allocation fails midway.
+ * Errors: QIL_EINVAL_ARG ("mps_restrict: null argument") for a null psi, spec or out, before the context is activated; then
+ * QIL_EINVAL_CONFIG for a spec value above 3 and for a spec that keeps no site (that number is what qil_coefficient_batch /
+ * qil_coefficient_marginal_batch return).
+ * Deliberately not here: the lazy form (a slice of W psi without forming it), a batch of specs in one call, Born marginals
+ * (tracing a site in |psi|^2).                                                                                            */
+QIL_API int qil_mps_restrict(const qil_mps* psi, const uint8_t* spec, qil_mps** out);
+
 /* ------------------------------------------------------------------ truncation (K1, K2) */
 /* canonicalize!(psi, direction; center, cutoff=1e-12, maxdim) src/mps.jl:787-847.
  * center = 0 selects the default (N for :right, 1 for :left); 1-based otherwise.    */

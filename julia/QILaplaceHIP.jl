@@ -19,7 +19,7 @@ using ..ApplyMPO: _as_single_site_mpo
 export DeviceMPS, DeviceMPO, to_device, to_host, signal_mps_device, marginal, mps_block, apply_compress,
     compress_mpo!, build_dt_mpo_batch, build_qft_mpo_device, build_zt_qft_chain_device, apply_coefficient_sweep, apply!, rsvd_device, svd_device,
     Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm, sample, top_k,
-    hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress
+    hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress, restrict
 
 const LIB = get(ENV, "QILHIP_LIB", "libqilhip.so")
 
@@ -318,6 +318,19 @@ function linear_combination_compress(terms::Vector{<:DeviceMPS}, coeffs=nothing;
 end
 Base.:+(phi::DeviceMPS, psi::DeviceMPS) = linear_combination([phi, psi], [1.0, 1.0])
 Base.:-(phi::DeviceMPS, psi::DeviceMPS) = linear_combination([phi, psi], [1.0, -1.0])
+# restriction (no reference counterpart; by hand it is psi[i] * onehot(s => b)).  spec: one UInt8 per tensor, 0 / 1 fixes the
+# site's bit, 2 sums the site, 3 keeps it (mps_block's vocabulary); the result is the chain of the kept tensors with the
+# parent's dtype and amplitude, paired when whole (main, copy) pairs are kept
+function restrict(psi::DeviceMPS, spec::AbstractVector{<:Integer})
+    length(spec) == length(psi.sites) || throw(ArgumentError("coefficient: expected $(length(psi.sites)) entries, got $(length(spec))"))
+    all(s -> 0 <= s <= 3, spec) || throw(ArgumentError("coefficient: spec value outside [0,3]"))
+    sp = Vector{UInt8}(spec)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve sp check(ccall((:qil_mps_restrict, LIB), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Ref{Ptr{Cvoid}}), psi.h, sp, r))
+    p = Ref{Cint}(0)
+    check(ccall((:qil_mps_is_paired, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}), r[], p))
+    return finalizer(_free!, DeviceMPS(r[], psi.sites[findall(==(3), sp)], p[] != 0))
+end
 function mps_to_vector(psi::DeviceMPS; reverse::Bool=false)                                        # mps.jl:716
     d = Ref{Cint}(0)
     check(ccall((:qil_mps_dtype, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}), psi.h, d))

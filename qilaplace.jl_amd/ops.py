@@ -266,6 +266,65 @@ def mps_block(psi, spec, reverse=False):
     return out
 
 
+def restrict(psi, spec):
+    """The part of `psi` that agrees with `spec`, as a state of its own (qil_mps_restrict): spec[i] = FIX0 / FIX1 fixes tensor
+    i's bit, SUM sums the site, FREE keeps it -- the vocabulary of `mps_block`, but the kept sites stay site tensors, so the
+    result works at any size with every verb that takes a state (`norm`, `top_k`, `sample`, `inner`, `hadamard`, ...).
+
+    The result has psi's dtype and amplitude (`norm(out) * out.amplitude` is the 2-norm of the slice), the kept sites' ids and
+    no bond larger than the parent's.  It is a ZTMPS when psi is one and whole (main_i, copy_i) pairs are kept, a SignalMPS
+    otherwise.  A spec that keeps no site is a number: `coefficient` / `marginal_batch` return it."""
+    if not isinstance(psi, SignalMPS):
+        raise TypeError("restrict: unsupported operand types")
+    n = _ntensors(psi)
+    sp = np.ascontiguousarray(np.asarray(spec), dtype=np.uint8)
+    if sp.shape != (n,):
+        raise ValueError(f"coefficient: expected {n} entries, got {sp.shape}")
+    if sp.size and sp.max() > 3:
+        raise ValueError(f"coefficient: spec value {int(sp.max())} outside [0,3]")
+    h = C.c_void_p()
+    L.check(L.lib.qil_mps_restrict(psi.handle, sp.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(h)))
+    paired = C.c_int()
+    L.lib.qil_mps_is_paired(h, C.byref(paired))
+    return (ZTMPS if paired.value else SignalMPS)(ctx=psi.ctx, _handle=h)
+
+
+def _register_spec(psi, what, fixed_offset, value, summed=False):
+    """spec of a ZTMPS with one register (0 = main, 1 = copy) set to the lsb-first bits of `value` (or to SUM) and the other
+    register kept"""
+    if not isinstance(psi, ZTMPS):
+        raise TypeError(f"{what}: needs a ZTMPS")
+    n = len(psi)
+    spec = np.full(2 * n, FREE, dtype=np.uint8)
+    if summed:
+        spec[fixed_offset::2] = SUM
+        return spec
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+        raise TypeError(f"{what}: the index must be an integer")
+    if not 0 <= int(value) < 2 ** n:
+        raise ValueError(f"{what}: index {int(value)} outside [0, 2^{n})")
+    spec[fixed_offset::2] = [(int(value) >> i) & 1 for i in range(n)]
+    return spec
+
+
+def zt_row(psi, l):
+    """Row l of a transformed ZTMPS's (k, l) grid as an n-site SignalMPS over k: the copy sites fixed to the bits of l, so that
+    coefficient_batch(zt_row(psi, l), _lsb_bits([k], n)) == coefficient_grid(psi, [k], [l]) for every k."""
+    return restrict(psi, _register_spec(psi, "zt_row", 1, l))
+
+
+def zt_column(psi, k):
+    """Column k of a transformed ZTMPS's (k, l) grid as an n-site SignalMPS over l: the main sites fixed to the bits of k, so
+    that coefficient_batch(zt_column(psi, k), _lsb_bits([l], n)) == coefficient_grid(psi, [k], [l]) for every l."""
+    return restrict(psi, _register_spec(psi, "zt_column", 0, k))
+
+
+def copy_marginal(psi):
+    """The copy register of a damping-transformed ZTMPS summed out; the coefficients of the n-site result are the Laplace
+    values: laplace_values(psi, ks, dt) == dt * sqrt(2**n) * coefficient_batch(copy_marginal(psi), _lsb_bits(ks, n))."""
+    return restrict(psi, _register_spec(psi, "copy_marginal", 1, None, summed=True))
+
+
 def _bit_block_range(v):
     """(s, a) if v == arange(2^a) << s -- every pattern of bits s .. s+a-1, all other bits zero -- else None."""
     v = np.asarray(v, dtype=np.int64)
