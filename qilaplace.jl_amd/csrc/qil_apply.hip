@@ -405,6 +405,13 @@ static int apply_mpo_mpo_impl(const qil_mpo* W1, const qil_mpo* W2, qil_mpo** ou
     const int odt = (W1->dtype == QIL_C64 || W2->dtype == QIL_C64) ? QIL_C64 : QIL_F64;
     qil_mpo* res = nullptr;
     QIL_TRY(qil_mpo_alloc(ctx, nb, odt, base->paired, dims.data() + 1, base->site_ids.data(), &res));
+    // the sites belong to the handle from here on (the call scope reclaims temporaries only): an early return below destroys it
+    struct result_guard {
+        qil_mpo* p;
+        ~result_guard() {
+            if (p) qil_mpo_destroy(p);
+        }
+    } guard{res};
     for (int64_t i = 0; i < nb; ++i) {
         const int64_t w = i - base_start;
         if (w >= 0 && w < match) {
@@ -444,6 +451,7 @@ static int apply_mpo_mpo_impl(const qil_mpo* W1, const qil_mpo* W2, qil_mpo** ou
         }
     }
     QIL_HIP(hipGetLastError());
+    guard.p = nullptr;
     *out = res;
     return QIL_OK;
 }

@@ -232,7 +232,10 @@ int svd_trunc_dev(qil_context* ctx, int dtype, int64_t m, int64_t n, void* A, in
     // (the weight w the one-factor SVD may drop costs sqrt(w) in amplitude.  Measured on the exact compress! of the bond-1008 zT
     // product, w = 1e-3 / 1e-5 / 1e-6 / 1e-8 of the cutoff: 253-260 / 282 / 266-273 / 270 ms (295 without), state against the
     // CPU oracle's compress! 1.2e-7 / 1.6e-9 / 4e-10 / 3e-10 (1e-11 without; the algorithm's own error there is 1.8e-5))
-    const double deflate = (use_cutoff && cutoff > 0.0) ? 1e-6 * cutoff : 0.0;
+    // ... and never more than 1e-18 of the total, sqrt(w) = 1e-9 in amplitude, the figure device and oracle truncations are held to:
+    // at cutoff 1e-8 the plain 1e-6 left the compressed 7-site MPO of tests/mpo_cases.py (bond 70 of rank 64) 1.2e-9 from the oracle's.
+    // Cutoffs up to 1e-12 (every compress! tolerance, the builders' 1e-14) are below the cap and unchanged.
+    const double deflate = (use_cutoff && cutoff > 0.0) ? std::min(1e-6 * cutoff, 1e-18) : 0.0;
     if (absorb == 2) {            // U isometric, S Vh absorbed
         QIL_TRY(qil_dev_svd_left(ctx, dtype, m, n, A, lda, U, m, S.data(), Vh, r0, negl_rel, &handled, cert_cutoff, deflate));
     } else if (absorb == 1) {     // Vh isometric, U S absorbed: the same problem on A^H
@@ -277,17 +280,26 @@ int svd_trunc_dev(qil_context* ctx, int dtype, int64_t m, int64_t n, void* A, in
 // Exact gauge sweep by thin QR (no truncation): the first pass of zip_to_compress_mpo (dt_transformer.jl:190, :237
 // use `qr`, only the return pass uses `svd`).  Same site layouts as canonicalize_impl below; a site whose matrix is
 // wider than tall has no thin QR that shrinks nothing, so it takes the SVD route with cutoff 0.
+// Every gauge step here and below factors a COPY of site i and replaces the two sites only when nothing can fail any more: a
+// call that runs out of memory half way leaves the chain, and the operator or state it stands for, as the last finished step left it.
+static int site_copy(qil_chain* psi, int64_t i, void** out) {
+    QIL_TRY(qil_ctx_alloc(psi->ctx, psi->site_bytes(i), out));
+    return qil_dev_copy(psi->ctx, *out, psi->site[(size_t)i], psi->site_bytes(i));
+}
+
 static int gauge_qr_site_right(qil_chain* psi, int64_t i, int64_t pd) {
     qil_context* ctx = psi->ctx;
     const int dt = psi->dtype;
     const size_t e = qil_elem_size(dt);
     const int64_t cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1], cr2 = psi->dims[(size_t)i + 2];
-    void *Rf = nullptr, *next = nullptr;
+    void *Q = nullptr, *Rf = nullptr, *next = nullptr;
+    QIL_TRY(site_copy(psi, i, &Q));
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)(cr * cr) * e, &Rf));
-    QIL_TRY(qil_dev_qr_positive(ctx, dt, pd * cl, cr, psi->site[(size_t)i], pd * cl, Rf, cr, true));   // Q in place
+    QIL_TRY(qil_dev_qr_positive(ctx, dt, pd * cl, cr, Q, pd * cl, Rf, cr, true));   // Q in place of the copy
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)(cr * pd * cr2) * e, &next));
     QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, cr, pd * cr2, cr, Rf, cr, psi->site[(size_t)i + 1], cr, next, cr));
     qil_ctx_free(ctx, Rf);
+    QIL_TRY(qil_chain_set_site(psi, i, Q, cl, cr));
     QIL_TRY(qil_chain_set_site(psi, i + 1, next, cr, cr2));
     return QIL_OK;
 }
@@ -298,16 +310,18 @@ static int gauge_qr_site_left(qil_chain* psi, int64_t i, int64_t pd) {
     const size_t e = qil_elem_size(dt);
     const int64_t cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1], cl0 = psi->dims[(size_t)i - 1];
     // A (cl x pd cr) = L Q with orthonormal rows of Q:  A^H = Qt Rt  =>  Q = Qt^H, L = Rt^H
-    void *Ah = nullptr, *Rt = nullptr, *prev = nullptr;
+    void *Ah = nullptr, *Rt = nullptr, *prev = nullptr, *Q = nullptr;
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)(pd * cr * cl) * e, &Ah));
     QIL_TRY(qil_dev_transpose(ctx, dt, 1, cl, pd * cr, psi->site[(size_t)i], cl, Ah, pd * cr));
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)(cl * cl) * e, &Rt));
     QIL_TRY(qil_dev_qr_positive(ctx, dt, pd * cr, cl, Ah, pd * cr, Rt, cl, true));
-    QIL_TRY(qil_dev_transpose(ctx, dt, 1, pd * cr, cl, Ah, pd * cr, psi->site[(size_t)i], cl));
+    QIL_TRY(qil_ctx_alloc(ctx, psi->site_bytes(i), &Q));
+    QIL_TRY(qil_dev_transpose(ctx, dt, 1, pd * cr, cl, Ah, pd * cr, Q, cl));
     qil_ctx_free(ctx, Ah);
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)(cl0 * pd * cl) * e, &prev));
     QIL_TRY(qil_dev_gemm(ctx, dt, 0, 2, pd * cl0, cl, cl, psi->site[(size_t)i - 1], pd * cl0, Rt, cl, prev, pd * cl0));
     qil_ctx_free(ctx, Rt);
+    QIL_TRY(qil_chain_set_site(psi, i, Q, cl, cr));
     QIL_TRY(qil_chain_set_site(psi, i - 1, prev, cl0, cl));
     return QIL_OK;
 }
@@ -324,10 +338,11 @@ static int gauge_site_left(qil_chain* psi, int64_t i, double cutoff, int64_t max
     const int64_t cl0 = psi->dims[(size_t)i - 1];
     if (gauge_qr && pd * cr >= cl) return gauge_qr_site_left(psi, i, pd);
     int64_t r = 0;
-    void *US = nullptr, *Vh = nullptr;
+    void *A = nullptr, *US = nullptr, *Vh = nullptr;
     // rows alpha | cols (s, beta)
-    QIL_TRY(svd_trunc_dev(ctx, dt, cl, pd * cr, psi->site[(size_t)i], cl, cutoff, true, maxdim, 1, 1, &r, &US, &Vh,
-                          nullptr));
+    QIL_TRY(site_copy(psi, i, &A));
+    QIL_TRY(svd_trunc_dev(ctx, dt, cl, pd * cr, A, cl, cutoff, true, maxdim, 1, 1, &r, &US, &Vh, nullptr));
+    qil_ctx_free(ctx, A);
     void* prev = nullptr;
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)(cl0 * pd * r) * e, &prev));
     QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, pd * cl0, r, cl, psi->site[(size_t)i - 1], pd * cl0, US, cl, prev, pd * cl0));
@@ -356,10 +371,11 @@ int canonicalize_impl(qil_chain* psi, int direction, int64_t center, double cuto
                 continue;
             }
             int64_t r = 0;
-            void *U = nullptr, *SV = nullptr;
+            void *A = nullptr, *U = nullptr, *SV = nullptr;
             // rows (alpha, s) | cols beta : the site buffer as it lies
-            QIL_TRY(svd_trunc_dev(ctx, dt, pd * cl, cr, psi->site[(size_t)i], pd * cl, cutoff, true, maxdim, 1, 2, &r,
-                                  &U, &SV, nullptr));
+            QIL_TRY(site_copy(psi, i, &A));
+            QIL_TRY(svd_trunc_dev(ctx, dt, pd * cl, cr, A, pd * cl, cutoff, true, maxdim, 1, 2, &r, &U, &SV, nullptr));
+            qil_ctx_free(ctx, A);
             void* next = nullptr;
             QIL_TRY(qil_ctx_alloc(ctx, (size_t)(r * pd * cr2) * e, &next));
             QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, r, pd * cr2, cr, SV, r, psi->site[(size_t)i + 1], cr, next, r));
