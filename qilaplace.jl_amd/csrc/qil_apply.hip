@@ -25,19 +25,6 @@ namespace {
 
 using namespace qil_dev;
 
-struct ApplySite {
-    const void* W;
-    const void* A;
-    void* B;
-    int Dl, Dr, cl, cr;
-    long long R;           // Dl * cl   (rows)
-    int row_tiles;         // ceil(R / ROWS)
-    int beta_tiles;        // ceil(cr / TB)
-    int b_chunks;          // ceil(Dr / NB)
-    int pad;
-    long long block_begin; // first workgroup of this site in the grouped grid
-};
-
 constexpr int kRows = 256;  // rows per workgroup = threads per workgroup
 constexpr int kTB = 8;      // beta values cached in registers per lane
 constexpr int kNB = 16;     // MPO right-bond values streamed per workgroup
@@ -72,19 +59,15 @@ __device__ __forceinline__ c64 mad2(c64 w0, c64 a0, c64 w1, c64 a1) {
     return c64{re, im};
 }
 
-template <class TW, class TA, bool NT, int NBV, bool WLDS>
-__global__ __launch_bounds__(kRows) void site_apply_grouped(const ApplySite* __restrict__ sites, int nsites) {
+// The one shipped shape: MPO slab staged in LDS, non-temporal stores, kNB = 16 b per workgroup.  Measured against it in r02 and
+// removed: plain stores -3 %, 32-wide b chunks -3 %, MPO entries straight from L1/L2 -1.5 %, 8-wide chunks -2 %.
+template <class TW, class TA>
+__global__ __launch_bounds__(kRows) void site_apply_grouped(const ProductSite* __restrict__ sites, int nsites) {
     using TO = typename out_type<TW, TA>::type;
     constexpr int RPL = rows_per_lane<TO>::value;
     constexpr int kTileRows = kRows * RPL;
-    // ---- block -> site (wave-uniform binary search over the prefix table)
     const long long blk = blockIdx.x;
-    int lo = 0, hi = nsites - 1;
-    while (lo < hi) {
-        int mid = (lo + hi + 1) >> 1;
-        if (sites[mid].block_begin <= blk) lo = mid; else hi = mid - 1;
-    }
-    const ApplySite S = sites[lo];
+    const ProductSite S = sites[last_entry_le<&ProductSite::block_begin>(sites, nsites, blk)];   // block -> site
     long long local = blk - S.block_begin;
     // row tile fastest: concurrently resident workgroups cover whole output columns
     const int row_tile = (int)(local % S.row_tiles);
@@ -95,12 +78,11 @@ __global__ __launch_bounds__(kRows) void site_apply_grouped(const ApplySite* __r
     const long long R = S.R;
     const long long r_first = (long long)row_tile * kTileRows + (long long)threadIdx.x * RPL;
     const bool valid = r_first < R;
-    if (!WLDS && !valid) return;
     long long rr[RPL];
     int a[RPL], alpha[RPL];
 #pragma unroll
     for (int k = 0; k < RPL; ++k) {
-        rr[k] = min(r_first + k, R - 1);   // clamped: idle lanes (WLDS) and the odd last row stay on a real row
+        rr[k] = min(r_first + k, R - 1);   // clamped: idle lanes and the odd last row stay on a real row
         a[k] = (int)(rr[k] / S.cl);
         alpha[k] = (int)(rr[k] - (long long)a[k] * S.cl);
     }
@@ -108,12 +90,12 @@ __global__ __launch_bounds__(kRows) void site_apply_grouped(const ApplySite* __r
     const bool packed = RPL == 2 && second && (R & 1) == 0;       // 16-B aligned pair for every column
     const int beta0 = beta_tile * kTB;
     const int nbeta = min(kTB, S.cr - beta0);
-    const int b0 = b_chunk * NBV;
-    const int b1 = min(b0 + NBV, S.Dr);
+    const int b0 = b_chunk * kNB;
+    const int b1 = min(b0 + kNB, S.Dr);
 
     const TA* __restrict__ A = static_cast<const TA*>(S.A);
-    const TW* __restrict__ W = static_cast<const TW*>(S.W);
-    TO* __restrict__ B = static_cast<TO*>(S.B);
+    const TW* __restrict__ W = static_cast<const TW*>(S.L);
+    TO* __restrict__ B = static_cast<TO*>(S.C);
 
     // ---- this lane's slice of the MPS site: A[alpha, s', beta0 .. beta0+TB)
     TA A0[RPL][kTB], A1[RPL][kTB];
@@ -132,22 +114,20 @@ __global__ __launch_bounds__(kRows) void site_apply_grouped(const ApplySite* __r
         }
 
     const long long wstride = (long long)S.Dl;  // W[a, si, so, b]: a + Dl*(si + 2*(so + 2*b))
-    // ---- WLDS: stage this workgroup's slab of the MPO site, W[a_lo..a_hi, :, :, b0..b1), in LDS once
+    // ---- stage this workgroup's slab of the MPO site, W[a_lo..a_hi, :, :, b0..b1), in LDS once
     constexpr int kWCap = 16384 / (int)sizeof(TW);
-    __shared__ TW wtile[WLDS ? kWCap : 1];
+    __shared__ TW wtile[kWCap];
     const int a_lo = (int)(((long long)row_tile * kTileRows) / S.cl);
     const int a_hi = (int)(min((long long)row_tile * kTileRows + kTileRows - 1, R - 1) / S.cl);
     const int na = a_hi - a_lo + 1;
-    const bool staged = WLDS && na * 4 * (b1 - b0) <= kWCap;
-    if (WLDS) {
-        if (staged)
-            for (int idx = threadIdx.x; idx < na * 4 * (b1 - b0); idx += kRows) {
-                const int al = idx % na, q = (idx / na) & 3, bl = idx / (4 * na);
-                wtile[idx] = W[(a_lo + al) + wstride * (q + 4LL * (b0 + bl))];
-            }
-        __syncthreads();
-        if (!valid) return;
-    }
+    const bool staged = na * 4 * (b1 - b0) <= kWCap;
+    if (staged)
+        for (int idx = threadIdx.x; idx < na * 4 * (b1 - b0); idx += kRows) {
+            const int al = idx % na, q = (idx / na) & 3, bl = idx / (4 * na);
+            wtile[idx] = W[(a_lo + al) + wstride * (q + 4LL * (b0 + bl))];
+        }
+    __syncthreads();
+    if (!valid) return;
     for (int b = b0; b < b1; ++b) {
         TW w00[RPL], w10[RPL], w01[RPL], w11[RPL];
 #pragma unroll
@@ -176,19 +156,19 @@ __global__ __launch_bounds__(kRows) void site_apply_grouped(const ApplySite* __r
                     const TO u0 = mad2(w00[1], A0[1][t], w10[1], A1[1][t]);
                     const TO u1 = mad2(w01[1], A0[1][t], w11[1], A1[1][t]);
                     if (packed) {
-                        store_pair<NT>(bp, v0, u0);
-                        store_pair<NT>(bp + R, v1, u1);
+                        store_pair(bp, v0, u0);
+                        store_pair(bp + R, v1, u1);
                     } else {
-                        store_out<NT>(bp, v0);
-                        store_out<NT>(bp + R, v1);
+                        store_out<true>(bp, v0);
+                        store_out<true>(bp + R, v1);
                         if (second) {
-                            store_out<NT>(bp + 1, u0);
-                            store_out<NT>(bp + R + 1, u1);
+                            store_out<true>(bp + 1, u0);
+                            store_out<true>(bp + R + 1, u1);
                         }
                     }
                 } else {
-                    store_out<NT>(bp, v0);
-                    store_out<NT>(bp + R, v1);
+                    store_out<true>(bp, v0);
+                    store_out<true>(bp + R, v1);
                 }
             }
             bp += 2 * R;
@@ -252,43 +232,19 @@ int check_apply_operands(const qil_mpo* W, const qil_mps* psi, bool shared_state
 int launch_apply(const qil_mpo* W, const qil_mps* psi, qil_mps* out) {
     qil_context* ctx = W->ctx;
     const int64_t n = W->n();
-    // the one shipped shape: MPO slab staged in LDS, non-temporal stores, 16 b per workgroup (measured against it in r02 and
-    // removed: plain stores -3 %, 32-wide b chunks -3 %, MPO entries straight from L1/L2 -1.5 %, 8-wide chunks -2 %)
-    const int nbv = kNB;
     // real x real results pack two rows per lane (16-B stores): 512-row tiles
     const int tile_rows = (W->dtype == QIL_F64 && psi->dtype == QIL_F64) ? 2 * kRows : kRows;
-    std::vector<ApplySite> tab((size_t)n);
-    long long blocks = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        ApplySite& s = tab[(size_t)i];
-        s.W = W->site[(size_t)i];
-        s.A = psi->site[(size_t)i];
-        s.B = out->site[(size_t)i];
-        s.Dl = (int)W->dims[(size_t)i];
-        s.Dr = (int)W->dims[(size_t)i + 1];
-        s.cl = (int)psi->dims[(size_t)i];
-        s.cr = (int)psi->dims[(size_t)i + 1];
-        s.R = (long long)s.Dl * s.cl;
-        s.row_tiles = (int)((s.R + tile_rows - 1) / tile_rows);
-        s.beta_tiles = (s.cr + kTB - 1) / kTB;
-        s.b_chunks = (s.Dr + nbv - 1) / nbv;
-        s.pad = 0;
-        s.block_begin = blocks;
-        blocks += (long long)s.row_tiles * s.beta_tiles * s.b_chunks;
-    }
+    std::vector<ProductSite> tab;
+    const long long blocks = qil_product_sites(W, psi, out, tile_rows, kTB, kNB, tab);
     QIL_REQUIRE(blocks < (1LL << 31), QIL_EINVAL_ARG, "apply: grid too large (%lld workgroups)", blocks);
-    const size_t bytes = tab.size() * sizeof(ApplySite);
-    void *pin = nullptr, *dev = nullptr;
-    int slot = 0;
-    QIL_TRY(qil_ctx_desc_acquire(ctx, bytes, &pin, &dev, &slot));
-    memcpy(pin, tab.data(), bytes);
-    QIL_HIP(hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, qil_stream(ctx)));
+    qil_dev_table dev(ctx);
+    QIL_TRY(dev.upload(tab.data(), tab.size() * sizeof(ProductSite)));
     QIL_TRY(qil_ctx_prof_begin(ctx));
-    const ApplySite* dtab = static_cast<const ApplySite*>(dev);
+    const ProductSite* dtab = dev.as<ProductSite>();
     const dim3 grid((unsigned)blocks), block(kRows);
     const bool wc = W->dtype == QIL_C64, ac = psi->dtype == QIL_C64;
 #define QIL_APPLY_LAUNCH(TW, TA) \
-    hipLaunchKernelGGL((site_apply_grouped<TW, TA, true, 16, true>), grid, block, 0, qil_stream(ctx), dtab, (int)n)
+    hipLaunchKernelGGL((site_apply_grouped<TW, TA>), grid, block, 0, qil_stream(ctx), dtab, (int)n)
     if (wc && ac) QIL_APPLY_LAUNCH(c64, c64);
     else if (wc) QIL_APPLY_LAUNCH(c64, double);
     else if (ac) QIL_APPLY_LAUNCH(double, c64);
@@ -296,10 +252,35 @@ int launch_apply(const qil_mpo* W, const qil_mps* psi, qil_mps* out) {
 #undef QIL_APPLY_LAUNCH
     QIL_HIP(hipGetLastError());
     QIL_TRY(qil_ctx_prof_end(ctx));
-    return qil_ctx_desc_commit(ctx, slot);
+    return dev.release();
 }
 
 }  // namespace
+
+long long qil_product_sites(const qil_chain* left, const qil_chain* right, const qil_chain* out, int tile_rows, int tb, int nb,
+                            std::vector<ProductSite>& tab) {
+    const int64_t n = right->n();
+    tab.resize((size_t)n);
+    long long blocks = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        ProductSite& s = tab[(size_t)i];
+        s.L = left->site[(size_t)i];
+        s.A = right->site[(size_t)i];
+        s.C = out->site[(size_t)i];
+        s.Dl = (int)left->dims[(size_t)i];
+        s.Dr = (int)left->dims[(size_t)i + 1];
+        s.cl = (int)right->dims[(size_t)i];
+        s.cr = (int)right->dims[(size_t)i + 1];
+        s.R = (long long)s.Dl * s.cl;
+        s.row_tiles = (int)((s.R + tile_rows - 1) / tile_rows);
+        s.beta_tiles = (s.cr + tb - 1) / tb;
+        s.b_chunks = (s.Dr + nb - 1) / nb;
+        s.pad = 0;
+        s.block_begin = blocks;
+        blocks += (long long)s.row_tiles * s.beta_tiles * s.b_chunks;
+    }
+    return blocks;
+}
 
 int qil_check_apply_operands(const qil_mpo* W, const qil_mps* psi) { return check_apply_operands(W, psi); }
 
@@ -340,12 +321,9 @@ static int apply_new(const qil_mpo* W, const qil_mps* psi, qil_mps** out, bool s
     const int odt = (W->dtype == QIL_C64 || psi->dtype == QIL_C64) ? QIL_C64 : QIL_F64;
     qil_mps* res = nullptr;
     QIL_TRY(qil_mps_alloc(W->ctx, n, odt, psi->paired, bonds.data(), psi->site_ids.data(), psi->amplitude, &res));
-    int s = launch_apply(W, psi, res);
-    if (s != QIL_OK) {
-        qil_mps_destroy(res);
-        return s;
-    }
-    *out = res;
+    qil_result_guard<qil_mps> guard(res);
+    QIL_TRY(launch_apply(W, psi, res));
+    *out = guard.release();
     return QIL_OK;
 }
 
@@ -405,13 +383,7 @@ static int apply_mpo_mpo_impl(const qil_mpo* W1, const qil_mpo* W2, qil_mpo** ou
     const int odt = (W1->dtype == QIL_C64 || W2->dtype == QIL_C64) ? QIL_C64 : QIL_F64;
     qil_mpo* res = nullptr;
     QIL_TRY(qil_mpo_alloc(ctx, nb, odt, base->paired, dims.data() + 1, base->site_ids.data(), &res));
-    // the sites belong to the handle from here on (the call scope reclaims temporaries only): an early return below destroys it
-    struct result_guard {
-        qil_mpo* p;
-        ~result_guard() {
-            if (p) qil_mpo_destroy(p);
-        }
-    } guard{res};
+    qil_result_guard<qil_mpo> guard(res);
     for (int64_t i = 0; i < nb; ++i) {
         const int64_t w = i - base_start;
         if (w >= 0 && w < match) {
@@ -451,7 +423,6 @@ static int apply_mpo_mpo_impl(const qil_mpo* W1, const qil_mpo* W2, qil_mpo** ou
         }
     }
     QIL_HIP(hipGetLastError());
-    guard.p = nullptr;
-    *out = res;
+    *out = guard.release();
     return QIL_OK;
 }

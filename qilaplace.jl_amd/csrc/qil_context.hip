@@ -308,7 +308,9 @@ int qil_ctx_dev_scratch(qil_context* ctx, size_t bytes, void** out) {
     return QIL_OK;
 }
 
-int qil_ctx_desc_acquire(qil_context* ctx, size_t bytes, void** host, void** dev, int* slot) {
+// acquire a descriptor slot (host staging + device copy target); desc_commit after enqueueing the last kernel that reads the
+// device side
+static int desc_acquire(qil_context* ctx, size_t bytes, void** host, void** dev, int* slot) {
     QIL_REQUIRE(bytes <= qil_context::kDescSlotBytes, QIL_EINVAL_ARG,
                 "descriptor table of %zu bytes exceeds the slot size", bytes);
     if (!ctx->desc_host) {
@@ -327,10 +329,37 @@ int qil_ctx_desc_acquire(qil_context* ctx, size_t bytes, void** host, void** dev
     return QIL_OK;
 }
 
-int qil_ctx_desc_commit(qil_context* ctx, int slot) {
+static int desc_commit(qil_context* ctx, int slot) {
     QIL_HIP(hipEventRecord(ctx->desc_event[slot], qil_stream(ctx)));
     ctx->desc_used[slot] = true;
     return QIL_OK;
+}
+
+int qil_dev_table::upload(const void* src, size_t bytes, const void* src2, size_t bytes2) {
+    const size_t total = bytes + bytes2;
+    if (total <= qil_context::kDescSlotBytes) {
+        void* pin = nullptr;
+        QIL_TRY(desc_acquire(ctx, total, &pin, &dev, &slot));
+        memcpy(pin, src, bytes);
+        if (bytes2) memcpy(static_cast<char*>(pin) + bytes, src2, bytes2);
+        QIL_HIP(hipMemcpyAsync(dev, pin, total, hipMemcpyHostToDevice, qil_stream(ctx)));
+    } else {
+        QIL_TRY(qil_ctx_alloc(ctx, total, &block));
+        dev = block;
+        QIL_HIP(hipMemcpyAsync(dev, src, bytes, hipMemcpyHostToDevice, qil_stream(ctx)));
+        if (bytes2) QIL_HIP(hipMemcpyAsync(static_cast<char*>(dev) + bytes, src2, bytes2, hipMemcpyHostToDevice, qil_stream(ctx)));
+        QIL_HIP(qil_stream_sync(ctx));                 // pageable sources that die with the caller's frame
+    }
+    return QIL_OK;
+}
+
+int qil_dev_table::release() {
+    int st = QIL_OK;
+    if (block) st = qil_ctx_free(ctx, block);
+    else if (slot >= 0) st = desc_commit(ctx, slot);
+    block = nullptr;
+    slot = -1;
+    return st;
 }
 
 

@@ -1,7 +1,8 @@
 // Device-side helpers shared by the dense linear algebra (qil_linalg.hip), the MPO builders (qil_build*.hip), the
 // apply (qil_apply.hip), the read-outs (qil_readout.hip), the overlaps (qil_inner.hip), the sampler (qil_sample.hip) and
 // the truncation (qil_truncate.hip): the complex scalar type and its arithmetic, the splitmix64 hash, DPP cross-lane sums,
-// Jacobi rotations and the in-workgroup one-sided Jacobi sweep loop.  gfx950 only.
+// Jacobi rotations, the in-workgroup one-sided Jacobi sweep loop, and the site table, site lookup and stores of the grouped
+// launches.  gfx950 only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -447,11 +448,41 @@ struct rows_per_lane {
     static constexpr int value = sizeof(TO) == 16 ? 1 : 2;
 };
 
-template <bool NT>
+// two adjacent rows of a real result in one non-temporal 16-B store
 __device__ __forceinline__ void store_pair(double* p, double v0, double v1) {
     typedef double d2 __attribute__((ext_vector_type(2)));
     d2 t = {v0, v1};
-    if (NT) __builtin_nontemporal_store(t, reinterpret_cast<d2*>(p)); else *reinterpret_cast<d2*>(p) = t;
+    __builtin_nontemporal_store(t, reinterpret_cast<d2*>(p));
 }
+
+// ---- grouped launches: one grid for all sites of a chain, the table entries carry the prefix sum of their share of it
+// The index of the last of the n >= 1 entries of `tab` whose prefix field Begin (&Entry::block_begin, ...) is <= v: block -> site.
+// A binary search, wave-uniform where v is.  The loop is written in its rotated form (guard + do-while) on purpose: inlined,
+// that compiles to the instruction stream of the `while (lo < hi)` search spelled out in the kernel, which is what
+// site_apply_grouped was measured with.
+template <auto Begin, class Entry, class V>
+__device__ __forceinline__ int last_entry_le(const Entry* tab, int n, V v) {
+    int lo = 0, hi = n - 1;
+    if (lo < hi) do {
+        int mid = (lo + hi + 1) >> 1;
+        if (tab[mid].*Begin <= v) lo = mid; else hi = mid - 1;
+    } while (lo < hi);
+    return lo;
+}
+
+// One site of the fused-layout products (site_apply_grouped: L = the MPO site W[Dl, 2, 2, Dr]; site_hadamard_grouped: L = the
+// phi site [Dl, 2, Dr]); filled by qil_product_sites (qil_apply.hip)
+struct ProductSite {
+    const void* L;         // left operand site
+    const void* A;         // psi site  [cl, 2, cr]
+    void* C;               // result    [Dl cl, 2, Dr cr]
+    int Dl, Dr, cl, cr;
+    long long R;           // Dl * cl   (rows)
+    int row_tiles;         // ceil(R / tile rows)
+    int beta_tiles;        // ceil(cr / TB)
+    int b_chunks;          // ceil(Dr / NB)
+    int pad;
+    long long block_begin; // first workgroup of this site in the grouped grid
+};
 
 }  // namespace qil_dev

@@ -19,19 +19,6 @@ namespace {
 
 using namespace qil_dev;
 
-struct HadSite {
-    const void* P;         // phi site  [Dl, 2, Dr]
-    const void* A;         // psi site  [cl, 2, cr]
-    void* C;               // result    [Dl cl, 2, Dr cr]
-    int Dl, Dr, cl, cr;
-    long long R;           // Dl * cl   (rows)
-    int row_tiles;         // ceil(R / tile rows)
-    int beta_tiles;        // ceil(cr / kTB)
-    int b_chunks;          // ceil(Dr / kNB)
-    int pad;
-    long long block_begin; // first workgroup of this site in the grouped grid
-};
-
 constexpr int kRows = 256;  // lanes per workgroup
 constexpr int kTB = 8;      // beta values cached in registers per lane
 constexpr int kNB = 16;     // phi right-bond values streamed per workgroup
@@ -45,18 +32,12 @@ __device__ __forceinline__ c64 mul1(c64 p, c64 a) {
 }
 
 template <class TP, class TA, bool CONJ>
-__global__ __launch_bounds__(kRows) void site_hadamard_grouped(const HadSite* __restrict__ sites, int nsites) {
+__global__ __launch_bounds__(kRows) void site_hadamard_grouped(const ProductSite* __restrict__ sites, int nsites) {
     using TO = typename out_type<TP, TA>::type;
     constexpr int RPL = rows_per_lane<TO>::value;
     constexpr int kTileRows = kRows * RPL;
-    // ---- block -> site (wave-uniform binary search over the prefix table)
     const long long blk = blockIdx.x;
-    int lo = 0, hi = nsites - 1;
-    while (lo < hi) {
-        int mid = (lo + hi + 1) >> 1;
-        if (sites[mid].block_begin <= blk) lo = mid; else hi = mid - 1;
-    }
-    const HadSite S = sites[lo];
+    const ProductSite S = sites[last_entry_le<&ProductSite::block_begin>(sites, nsites, blk)];   // block -> site
     long long local = blk - S.block_begin;
     // row tile fastest: concurrently resident workgroups cover whole output columns
     const int row_tile = (int)(local % S.row_tiles);
@@ -83,7 +64,7 @@ __global__ __launch_bounds__(kRows) void site_hadamard_grouped(const HadSite* __
     const int b1 = min(b0 + kNB, S.Dr);
 
     const TA* __restrict__ A = static_cast<const TA*>(S.A);
-    const TP* __restrict__ P = static_cast<const TP*>(S.P);
+    const TP* __restrict__ P = static_cast<const TP*>(S.L);
     TO* __restrict__ C = static_cast<TO*>(S.C);
 
     // ---- this lane's slice of psi's site: A[alpha, s, beta0 .. beta0+TB)
@@ -142,8 +123,8 @@ __global__ __launch_bounds__(kRows) void site_hadamard_grouped(const HadSite* __
                     const TO u0 = mul1(p0[1], A0[1][t]);
                     const TO u1 = mul1(p1[1], A1[1][t]);
                     if (packed) {
-                        store_pair<true>(cp, v0, u0);
-                        store_pair<true>(cp + R, v1, u1);
+                        store_pair(cp, v0, u0);
+                        store_pair(cp + R, v1, u1);
                     } else {
                         store_out<true>(cp, v0);
                         store_out<true>(cp + R, v1);
@@ -176,6 +157,8 @@ template <class T, bool ADJ>
 __global__ void chain_move_sites(const MoveSite* __restrict__ sites, int nsites, long long total, int conj) {
     for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total;
          idx += (long long)gridDim.x * blockDim.x) {
+        // element -> site, spelled out: inside this grid-stride loop qil_dev::last_entry_le is scheduled differently, and the
+        // kernels of this file keep the instruction streams they were measured with
         int lo = 0, hi = nsites - 1;
         while (lo < hi) {
             int mid = (lo + hi + 1) >> 1;
@@ -218,34 +201,13 @@ int launch_hadamard(const qil_mps* phi, int conj_phi, const qil_mps* psi, qil_mp
     const int64_t n = psi->n();
     // real x real results pack two rows per lane (16-B stores): 512-row tiles
     const int tile_rows = (phi->dtype == QIL_F64 && psi->dtype == QIL_F64) ? 2 * kRows : kRows;
-    std::vector<HadSite> tab((size_t)n);
-    long long blocks = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        HadSite& s = tab[(size_t)i];
-        s.P = phi->site[(size_t)i];
-        s.A = psi->site[(size_t)i];
-        s.C = out->site[(size_t)i];
-        s.Dl = (int)phi->dims[(size_t)i];
-        s.Dr = (int)phi->dims[(size_t)i + 1];
-        s.cl = (int)psi->dims[(size_t)i];
-        s.cr = (int)psi->dims[(size_t)i + 1];
-        s.R = (long long)s.Dl * s.cl;
-        s.row_tiles = (int)((s.R + tile_rows - 1) / tile_rows);
-        s.beta_tiles = (s.cr + kTB - 1) / kTB;
-        s.b_chunks = (s.Dr + kNB - 1) / kNB;
-        s.pad = 0;
-        s.block_begin = blocks;
-        blocks += (long long)s.row_tiles * s.beta_tiles * s.b_chunks;
-    }
+    std::vector<ProductSite> tab;
+    const long long blocks = qil_product_sites(phi, psi, out, tile_rows, kTB, kNB, tab);
     QIL_REQUIRE(blocks < (1LL << 31), QIL_EINVAL_ARG, "hadamard: grid too large (%lld workgroups)", blocks);
-    const size_t bytes = tab.size() * sizeof(HadSite);
-    void *pin = nullptr, *dev = nullptr;
-    int slot = 0;
-    QIL_TRY(qil_ctx_desc_acquire(ctx, bytes, &pin, &dev, &slot));
-    memcpy(pin, tab.data(), bytes);
-    QIL_HIP(hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, qil_stream(ctx)));
+    qil_dev_table dev(ctx);
+    QIL_TRY(dev.upload(tab.data(), tab.size() * sizeof(ProductSite)));
     QIL_TRY(qil_ctx_prof_begin(ctx));
-    const HadSite* dtab = static_cast<const HadSite*>(dev);
+    const ProductSite* dtab = dev.as<ProductSite>();
     const dim3 grid((unsigned)blocks), block(kRows);
     const bool pc = phi->dtype == QIL_C64, ac = psi->dtype == QIL_C64;
 #define QIL_HADAMARD_LAUNCH(TP, TA, CJ) \
@@ -262,7 +224,7 @@ int launch_hadamard(const qil_mps* phi, int conj_phi, const qil_mps* psi, qil_mp
 #undef QIL_HADAMARD_LAUNCH
     QIL_HIP(hipGetLastError());
     QIL_TRY(qil_ctx_prof_end(ctx));
-    return qil_ctx_desc_commit(ctx, slot);
+    return dev.release();
 }
 
 // one launch of chain_move_sites over the whole chain: src (MPS for the diagonal, MPO for the adjoint) -> the MPO dst
@@ -281,13 +243,9 @@ int launch_move(const qil_chain* src, qil_mpo* dst, bool adjoint, int conj, doub
         s.elem_begin = total;
         total += dst->site_elems(i);
     }
-    const size_t bytes = tab.size() * sizeof(MoveSite);
-    void *pin = nullptr, *dev = nullptr;
-    int slot = 0;
-    QIL_TRY(qil_ctx_desc_acquire(ctx, bytes, &pin, &dev, &slot));
-    memcpy(pin, tab.data(), bytes);
-    QIL_HIP(hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, qil_stream(ctx)));
-    const MoveSite* dtab = static_cast<const MoveSite*>(dev);
+    qil_dev_table dev(ctx);
+    QIL_TRY(dev.upload(tab.data(), tab.size() * sizeof(MoveSite)));
+    const MoveSite* dtab = dev.as<MoveSite>();
     const long long want = (total + 255) / 256;
     const dim3 grid((unsigned)std::min<long long>(want, 64LL * ctx->num_cus)), block(256);
     const bool cx = src->dtype == QIL_C64;
@@ -300,19 +258,16 @@ int launch_move(const qil_chain* src, qil_mpo* dst, bool adjoint, int conj, doub
     }
 #undef QIL_MOVE_LAUNCH
     QIL_HIP(hipGetLastError());
-    return qil_ctx_desc_commit(ctx, slot);
+    return dev.release();
 }
 
 // diag(phi) as a new MPO handle (the caller has activated the context and opened its call scope)
 int make_diagonal(const qil_mps* phi, int conj_phi, qil_mpo** out) {
     qil_mpo* D = nullptr;
     QIL_TRY(qil_mpo_alloc(phi->ctx, phi->n(), phi->dtype, phi->paired, phi->dims.data() + 1, phi->site_ids.data(), &D));
-    const int st = launch_move(phi, D, false, conj_phi, phi->amplitude);
-    if (st != QIL_OK) {
-        qil_mpo_destroy(D);
-        return st;
-    }
-    *out = D;
+    qil_result_guard<qil_mpo> guard(D);
+    QIL_TRY(launch_move(phi, D, false, conj_phi, phi->amplitude));
+    *out = guard.release();
     return QIL_OK;
 }
 
@@ -332,12 +287,9 @@ extern "C" int qil_hadamard(const qil_mps* phi, int conj_phi, const qil_mps* psi
     const int odt = (phi->dtype == QIL_C64 || psi->dtype == QIL_C64) ? QIL_C64 : QIL_F64;
     qil_mps* res = nullptr;
     QIL_TRY(qil_mps_alloc(ctx, n, odt, psi->paired, bonds.data(), psi->site_ids.data(), phi->amplitude * psi->amplitude, &res));
-    const int st = launch_hadamard(phi, conj_phi, psi, res);
-    if (st != QIL_OK) {
-        qil_mps_destroy(res);
-        return st;
-    }
-    *out = res;
+    qil_result_guard<qil_mps> guard(res);
+    QIL_TRY(launch_hadamard(phi, conj_phi, psi, res));
+    *out = guard.release();
     return QIL_OK;
 }
 
@@ -354,12 +306,9 @@ extern "C" int qil_mpo_adjoint(const qil_mpo* W, qil_mpo** out) {
     qil_call_scope call_scope(W->ctx);
     qil_mpo* res = nullptr;
     QIL_TRY(qil_mpo_alloc(W->ctx, W->n(), W->dtype, W->paired, W->dims.data() + 1, W->site_ids.data(), &res));
-    const int st = launch_move(W, res, true, 1, 1.0);
-    if (st != QIL_OK) {
-        qil_mpo_destroy(res);
-        return st;
-    }
-    *out = res;
+    qil_result_guard<qil_mpo> guard(res);
+    QIL_TRY(launch_move(W, res, true, 1, 1.0));
+    *out = guard.release();
     return QIL_OK;
 }
 

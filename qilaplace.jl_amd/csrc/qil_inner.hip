@@ -181,21 +181,19 @@ static int inner_chain_route(const qil_mps* phi, const qil_mps* psi, double h[2]
     for (int64_t i = 0; i < n; ++i)
         tab[(size_t)i] = InnerSite{phi->site[(size_t)i], psi->site[(size_t)i], (int)phi->dims[(size_t)i], (int)phi->dims[(size_t)i + 1],
                                    (int)psi->dims[(size_t)i], (int)psi->dims[(size_t)i + 1]};
-    void *pin = nullptr, *dtab = nullptr, *dout = nullptr;
-    int slot = 0;
+    void* dout = nullptr;
     QIL_TRY(qil_ctx_alloc(ctx, 16, &dout));
-    QIL_TRY(qil_ctx_desc_acquire(ctx, tab.size() * sizeof(InnerSite), &pin, &dtab, &slot));
-    memcpy(pin, tab.data(), tab.size() * sizeof(InnerSite));
-    QIL_HIP(hipMemcpyAsync(dtab, pin, tab.size() * sizeof(InnerSite), hipMemcpyHostToDevice, qil_stream(ctx)));
+    qil_dev_table dtab(ctx);
+    QIL_TRY(dtab.upload(tab.data(), tab.size() * sizeof(InnerSite)));
     const double amp = phi->amplitude * psi->amplitude;
     const bool pc = phi->dtype == QIL_C64, sc = psi->dtype == QIL_C64;
-    const InnerSite* t = static_cast<const InnerSite*>(dtab);
+    const InnerSite* t = dtab.as<InnerSite>();
     c64* o = static_cast<c64*>(dout);
     if (pc && sc) QIL_TRY((launch_inner_chain<c64, c64, c64>(ctx, t, (int)n, amp, o)));
     else if (pc) QIL_TRY((launch_inner_chain<c64, double, c64>(ctx, t, (int)n, amp, o)));
     else if (sc) QIL_TRY((launch_inner_chain<double, c64, c64>(ctx, t, (int)n, amp, o)));
     else QIL_TRY((launch_inner_chain<double, double, double>(ctx, t, (int)n, amp, o)));
-    QIL_TRY(qil_ctx_desc_commit(ctx, slot));
+    QIL_TRY(dtab.release());
     QIL_TRY(qil_read_back(ctx, h, dout, 16));
     qil_ctx_free(ctx, dout);
     return QIL_OK;
@@ -272,7 +270,7 @@ extern "C" int qil_inner(const qil_mps* phi, const qil_mps* psi, double* out) {
     qil_call_scope call_scope(ctx);
     const char* route = getenv("QIL_INNER_ROUTE");
     const long long mb = std::max(max_bond(phi), max_bond(psi));
-    const bool fits = mb <= kChainMax && (size_t)psi->n() * sizeof(InnerSite) <= qil_context::kDescSlotBytes;
+    const bool fits = mb <= kChainMax;
     bool chain = fits && mb <= kChainAutoMax;
     if (route && !strcmp(route, "chain")) chain = fits;
     else if (route && !strcmp(route, "gemm")) chain = false;

@@ -158,10 +158,27 @@ int qil_ctx_alloc(qil_context* ctx, size_t bytes, void** out);
 int qil_ctx_free(qil_context* ctx, void* p);
 int qil_ctx_pinned(qil_context* ctx, size_t bytes, void** out);       // grows, stream-synchronising
 int qil_ctx_dev_scratch(qil_context* ctx, size_t bytes, void** out);  // grows
-// acquire a descriptor slot (host staging + device copy target); call qil_ctx_desc_commit after
-// enqueueing the last kernel that reads the device side
-int qil_ctx_desc_acquire(qil_context* ctx, size_t bytes, void** host, void** dev, int* slot);
-int qil_ctx_desc_commit(qil_context* ctx, int slot);
+// A host table on the device for one grouped launch -- what every grouped launch goes through.  upload() takes the descriptor
+// ring where the table fits a slot, a pool block otherwise (filled from the pageable source and stream-synchronised); a second
+// span, if given, lands right behind the first (at dev + bytes).  release() hands the slot back committed behind whatever was
+// enqueued, or the block to the pool, which recycles in stream order; call it after the last consumer launch.  The destructor
+// releases what an early return left, so a failing launch can never strand a slot without its event.
+struct qil_dev_table {
+    qil_context* ctx;
+    void* dev = nullptr;
+    void* block = nullptr;
+    int slot = -1;
+    explicit qil_dev_table(qil_context* c) : ctx(c) {}
+    ~qil_dev_table() { release(); }
+    qil_dev_table(const qil_dev_table&) = delete;
+    qil_dev_table& operator=(const qil_dev_table&) = delete;
+    int upload(const void* src, size_t bytes, const void* src2 = nullptr, size_t bytes2 = 0);
+    int release();
+    template <class T>
+    const T* as(size_t byte_offset = 0) const {
+        return reinterpret_cast<const T*>(static_cast<const char*>(dev) + byte_offset);
+    }
+};
 int qil_ctx_event(qil_context* ctx, hipEvent_t* e);            // from the context's event pool
 void qil_ctx_event_release(qil_context* ctx, hipEvent_t e);
 // `bytes` (a multiple of 4, 4-byte aligned source) of device memory to the host, ordered after everything this context has
@@ -237,6 +254,25 @@ void qil_chain_bind(qil_chain* c, qil_context* ctx);
 int qil_chain_set_site(qil_chain* c, int64_t i, void* p, int64_t dl, int64_t dr);
 // attach a pool block to an EMPTY site slot of a chain under construction (ownership moves to the chain)
 void qil_chain_adopt(qil_chain* c, int64_t i, void* p);
+// Owns a result handle (qil_mps or qil_mpo) while the call that allocated it can still fail: the sites belong to the handle, not
+// to the call scope, so every early return destroys it; release() hands it to the caller on success.
+inline void qil_handle_destroy(qil_mps* p) { qil_mps_destroy(p); }
+inline void qil_handle_destroy(qil_mpo* p) { qil_mpo_destroy(p); }
+template <class H>
+struct qil_result_guard {
+    H* p = nullptr;
+    explicit qil_result_guard(H* h) : p(h) {}
+    ~qil_result_guard() {
+        if (p) qil_handle_destroy(p);
+    }
+    qil_result_guard(const qil_result_guard&) = delete;
+    qil_result_guard& operator=(const qil_result_guard&) = delete;
+    H* release() {
+        H* h = p;
+        p = nullptr;
+        return h;
+    }
+};
 
 // Error-path reclamation.  Every C entry point opens one of these; temporaries come from the context pool and
 // are released explicitly on the success path.  If the call FAILS (qil_fail ran on this thread while the scope
@@ -283,7 +319,7 @@ int qil_dev_gemm_batched(qil_context* ctx, int dtype, int opA, int opB, int64_t 
 // A table of SMALL independent products in ONE launch (qil_sum.hip): C (m x n, ldc) = A (m x k, lda) * B (k x n, ldb), all of
 // one dtype, one 16 x 16 f64-MFMA tile per wave, no LDS.  For steps that would otherwise
 // cost one ~4 us dispatch per operand for a microsecond of work (the per-term products of qil_mps_sum_compress); tile_begin is
-// filled in by the call.  qil_dev_gemm_grouped_fits: the table fits one descriptor slot.
+// filled in by the call.  qil_dev_gemm_grouped_fits: the table fits one descriptor slot (what qil_sum_compress_impl routes by).
 struct qil_gemm_problem {
     const void* A;
     const void* B;
@@ -298,6 +334,14 @@ bool qil_dev_gemm_grouped_fits(size_t nproblems);
 // (qil_hadamard.hip) phi against psi under `verb`: context, paired flag (QIL_EINVAL_ARG), length (QIL_EINVAL_LENGTH), site ids
 // (QIL_EINVAL_SITES), in that order; touches no device
 int qil_check_pair(const char* verb, const struct qil_mps* phi, const struct qil_mps* psi);
+// (qil_apply.hip) the site table of the two fused-layout product kernels, site_apply_grouped and site_hadamard_grouped
+// (qil_dev::ProductSite, qil_device_utils.h): result site i = left site i x right site i in row tiles of tile_rows, beta tiles of
+// tb and left-bond chunks of nb.  Returns the workgroup count of the grouped grid.
+namespace qil_dev {
+struct ProductSite;
+}
+long long qil_product_sites(const qil_chain* left, const qil_chain* right, const qil_chain* out, int tile_rows, int tb, int nb,
+                            std::vector<qil_dev::ProductSite>& tab);
 // (qil_truncate.hip) the fused sum-and-truncate behind qil_mps_sum_compress: operands checked, context active, call scope open;
 // w = nb (re, im) weights with the amplitudes folded in, odt = result dtype
 int qil_sum_compress_impl(qil_context* ctx, const struct qil_mps* const* terms, int64_t nb, const double* w, int odt,

@@ -536,22 +536,20 @@ static int coefficient_enqueue(const qil_mps* psi, int64_t nb, const uint8_t* db
         qil_ctx_free(ctx, Tm);
         return QIL_OK;
     }
-    void *scratch = nullptr, *pin = nullptr, *dtab = nullptr;
-    int slot = 0;
+    void* scratch = nullptr;
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)(2 * nb * maxchi) * esz, &scratch));
-    QIL_TRY(qil_ctx_desc_acquire(ctx, tab.size() * sizeof(ChainSite), &pin, &dtab, &slot));
-    memcpy(pin, tab.data(), tab.size() * sizeof(ChainSite));
-    QIL_HIP(hipMemcpyAsync(dtab, pin, tab.size() * sizeof(ChainSite), hipMemcpyHostToDevice, qil_stream(ctx)));
+    qil_dev_table dtab(ctx);
+    QIL_TRY(dtab.upload(tab.data(), tab.size() * sizeof(ChainSite)));
     if (psi->dtype == QIL_C64)
         hipLaunchKernelGGL(coefficient_chain<c64>, dim3((unsigned)nb), dim3(kThreads), 0, qil_stream(ctx),
-                           (const ChainSite*)dtab, (int)n, dbits, (c64*)scratch, maxchi, (c64*)dout,
+                           dtab.as<ChainSite>(), (int)n, dbits, (c64*)scratch, maxchi, (c64*)dout,
                            psi->amplitude);
     else
         hipLaunchKernelGGL(coefficient_chain<double>, dim3((unsigned)nb), dim3(kThreads), 0, qil_stream(ctx),
-                           (const ChainSite*)dtab, (int)n, dbits, (double*)scratch, maxchi, (c64*)dout,
+                           dtab.as<ChainSite>(), (int)n, dbits, (double*)scratch, maxchi, (c64*)dout,
                            psi->amplitude);
     QIL_HIP(hipGetLastError());
-    QIL_TRY(qil_ctx_desc_commit(ctx, slot));
+    QIL_TRY(dtab.release());
     qil_ctx_free(ctx, scratch);
     return QIL_OK;
 }
@@ -666,8 +664,7 @@ extern "C" int qil_apply_coefficient_batch(const qil_mpo* W, const qil_mps* psi,
     }
     uint8_t* dbits = nullptr;
     QIL_TRY(upload_bits(ctx, nb, n, bits, &dbits));
-    void *scratch = nullptr, *dout = nullptr, *pin = nullptr, *dtab = nullptr;
-    int slot = 0;
+    void *scratch = nullptr, *dout = nullptr;
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)nb * 16, &dout));
     // Many queries on a wide product bond: the per-query chains (one workgroup each, vector ALU) give way to
     // batched MFMA GEMMs.  Tuning aid: QIL_LAZY_GEMM_MIN = smallest chi * D that takes the GEMM form.
@@ -682,20 +679,19 @@ extern "C" int qil_apply_coefficient_batch(const qil_mpo* W, const qil_mps* psi,
         return st;
     }
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)(4 * nb * msz) * 16, &scratch));
-    QIL_TRY(qil_ctx_desc_acquire(ctx, tab.size() * sizeof(ChainSite), &pin, &dtab, &slot));
-    memcpy(pin, tab.data(), tab.size() * sizeof(ChainSite));
-    QIL_HIP(hipMemcpyAsync(dtab, pin, tab.size() * sizeof(ChainSite), hipMemcpyHostToDevice, qil_stream(ctx)));
+    qil_dev_table dtab(ctx);
+    QIL_TRY(dtab.upload(tab.data(), tab.size() * sizeof(ChainSite)));
     const bool wc = W->dtype == QIL_C64, ac = psi->dtype == QIL_C64;
 #define LAUNCH_LAZY(TW, TA)                                                                             \
     hipLaunchKernelGGL((lazy_coefficient_chain<TW, TA>), dim3((unsigned)nb), dim3(kThreads), 0, qil_stream(ctx), \
-                       (const ChainSite*)dtab, (int)n, dbits, (c64*)scratch, msz, (c64*)dout, psi->amplitude)
+                       dtab.as<ChainSite>(), (int)n, dbits, (c64*)scratch, msz, (c64*)dout, psi->amplitude)
     if (wc && ac) LAUNCH_LAZY(c64, c64);
     else if (wc) LAUNCH_LAZY(c64, double);
     else if (ac) LAUNCH_LAZY(double, c64);
     else LAUNCH_LAZY(double, double);
 #undef LAUNCH_LAZY
     QIL_HIP(hipGetLastError());
-    QIL_TRY(qil_ctx_desc_commit(ctx, slot));
+    QIL_TRY(dtab.release());
     QIL_HIP(hipMemcpyAsync(out, dout, (size_t)nb * 16, hipMemcpyDeviceToHost, qil_stream(ctx)));
     QIL_HIP(qil_stream_sync(ctx));
     qil_ctx_free(ctx, scratch);

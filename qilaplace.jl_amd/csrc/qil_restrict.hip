@@ -84,12 +84,7 @@ struct AbsorbSite {
 template <class T>
 __global__ __launch_bounds__(kThreads) void restrict_absorb_grouped(const AbsorbSite* __restrict__ sites, int nsites) {
     const long long blk = blockIdx.x;
-    int lo = 0, hi = nsites - 1;
-    while (lo < hi) {                                  // block -> site (wave-uniform binary search over the prefix table)
-        int mid = (lo + hi + 1) >> 1;
-        if (sites[mid].block_begin <= blk) lo = mid; else hi = mid - 1;
-    }
-    const AbsorbSite S = sites[lo];
+    const AbsorbSite S = sites[last_entry_le<&AbsorbSite::block_begin>(sites, nsites, blk)];   // block -> site
     const long long local = blk - S.block_begin;
     if (!S.M) {                                        // nothing absorbed: a bit-for-bit copy, 16 bytes per lane and step
         const long long units = (long long)S.R * S.ncols * (long long)sizeof(T) / 16;   // ncols is even
@@ -195,38 +190,6 @@ __global__ void restrict_factor(const T* __restrict__ A, long long cl, long long
     for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x)
         out[t] = load_factor(A, t % cl + 2 * cl * (t / cl), cl);
 }
-
-// A host table on the device for one grouped launch: the descriptor ring where it fits a slot, a pool block otherwise.  release()
-// hands the slot or the block back (the slot committed behind whatever was enqueued, the block recycled in stream order).
-struct DevTable {
-    qil_context* ctx;
-    void* dev = nullptr;
-    void* block = nullptr;
-    int slot = -1;
-    explicit DevTable(qil_context* c) : ctx(c) {}
-    int upload(const void* src, size_t bytes) {
-        if (bytes <= qil_context::kDescSlotBytes) {
-            void* pin = nullptr;
-            QIL_TRY(qil_ctx_desc_acquire(ctx, bytes, &pin, &dev, &slot));
-            memcpy(pin, src, bytes);
-            QIL_HIP(hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, qil_stream(ctx)));
-        } else {
-            QIL_TRY(qil_ctx_alloc(ctx, bytes, &block));
-            dev = block;
-            QIL_HIP(hipMemcpyAsync(dev, src, bytes, hipMemcpyHostToDevice, qil_stream(ctx)));
-            QIL_HIP(qil_stream_sync(ctx));             // a pageable source that dies with the caller's frame
-        }
-        return QIL_OK;
-    }
-    int release() {
-        int st = QIL_OK;
-        if (block) st = qil_ctx_free(ctx, block);
-        else if (slot >= 0) st = qil_ctx_desc_commit(ctx, slot);
-        block = nullptr;
-        slot = -1;
-        return st;
-    }
-};
 
 enum { kLeading = 0, kInterior = 1, kTrailing = 2 };
 struct RunPlan {
@@ -366,31 +329,23 @@ int Restriction::launch_runs_lds(const std::vector<const RunPlan*>& sel) {
         run.nsteps = (int)stab.size() - run.step_begin;
         rtab.push_back(run);
     }
-    const size_t rbytes = rtab.size() * sizeof(Run), sbytes = stab.size() * sizeof(RunStep);
-    std::vector<char> host(rbytes + sbytes);
-    memcpy(host.data(), rtab.data(), rbytes);
-    memcpy(host.data() + rbytes, stab.data(), sbytes);
+    const size_t rbytes = rtab.size() * sizeof(Run);
     const size_t lds = 2 * (size_t)half * e;                    // <= 144 KiB by kRunLdsMaxBond
-    DevTable tab(ctx);
-    auto body = [&]() -> int {
-        QIL_TRY(tab.upload(host.data(), host.size()));
-        const Run* druns = static_cast<const Run*>(tab.dev);
-        const RunStep* dsteps = reinterpret_cast<const RunStep*>(static_cast<const char*>(tab.dev) + rbytes);
-        const dim3 grid((unsigned)rtab.size()), block(kThreads);
-        static qil_lds_grant grant_r, grant_c;                  // per device (qil_internal.h)
-        if (dt == QIL_C64) {
-            QIL_HIP(grant_c.ensure(ctx->device, reinterpret_cast<const void*>(&restrict_runs_lds<c64>), lds));
-            hipLaunchKernelGGL(restrict_runs_lds<c64>, grid, block, lds, qil_stream(ctx), druns, dsteps, (int)half);
-        } else {
-            QIL_HIP(grant_r.ensure(ctx->device, reinterpret_cast<const void*>(&restrict_runs_lds<double>), lds));
-            hipLaunchKernelGGL(restrict_runs_lds<double>, grid, block, lds, qil_stream(ctx), druns, dsteps, (int)half);
-        }
-        QIL_HIP(hipGetLastError());
-        return QIL_OK;
-    };
-    const int st = body();
-    const int rel = tab.release();
-    return st != QIL_OK ? st : rel;
+    qil_dev_table tab(ctx);
+    QIL_TRY(tab.upload(rtab.data(), rbytes, stab.data(), stab.size() * sizeof(RunStep)));
+    const Run* druns = tab.as<Run>();
+    const RunStep* dsteps = tab.as<RunStep>(rbytes);
+    const dim3 grid((unsigned)rtab.size()), block(kThreads);
+    static qil_lds_grant grant_r, grant_c;                      // per device (qil_internal.h)
+    if (dt == QIL_C64) {
+        QIL_HIP(grant_c.ensure(ctx->device, reinterpret_cast<const void*>(&restrict_runs_lds<c64>), lds));
+        hipLaunchKernelGGL(restrict_runs_lds<c64>, grid, block, lds, qil_stream(ctx), druns, dsteps, (int)half);
+    } else {
+        QIL_HIP(grant_r.ensure(ctx->device, reinterpret_cast<const void*>(&restrict_runs_lds<double>), lds));
+        hipLaunchKernelGGL(restrict_runs_lds<double>, grid, block, lds, qil_stream(ctx), druns, dsteps, (int)half);
+    }
+    QIL_HIP(hipGetLastError());
+    return tab.release();
 }
 
 int Restriction::launch_absorb(qil_mps* res) {
@@ -434,19 +389,14 @@ int Restriction::launch_absorb(qil_mps* res) {
         }
     }
     QIL_REQUIRE(blocks < (1LL << 31), QIL_EINVAL_ARG, "mps_restrict: grid too large (%lld workgroups)", blocks);
-    DevTable dtab(ctx);
-    auto body = [&]() -> int {
-        QIL_TRY(dtab.upload(tab.data(), tab.size() * sizeof(AbsorbSite)));
-        const AbsorbSite* dsites = static_cast<const AbsorbSite*>(dtab.dev);
-        const dim3 grid((unsigned)blocks), block(kThreads);
-        if (dt == QIL_C64) hipLaunchKernelGGL(restrict_absorb_grouped<c64>, grid, block, 0, qil_stream(ctx), dsites, (int)m);
-        else hipLaunchKernelGGL(restrict_absorb_grouped<double>, grid, block, 0, qil_stream(ctx), dsites, (int)m);
-        QIL_HIP(hipGetLastError());
-        return QIL_OK;
-    };
-    const int st = body();
-    const int rel = dtab.release();
-    return st != QIL_OK ? st : rel;
+    qil_dev_table dtab(ctx);
+    QIL_TRY(dtab.upload(tab.data(), tab.size() * sizeof(AbsorbSite)));
+    const AbsorbSite* dsites = dtab.as<AbsorbSite>();
+    const dim3 grid((unsigned)blocks), block(kThreads);
+    if (dt == QIL_C64) hipLaunchKernelGGL(restrict_absorb_grouped<c64>, grid, block, 0, qil_stream(ctx), dsites, (int)m);
+    else hipLaunchKernelGGL(restrict_absorb_grouped<double>, grid, block, 0, qil_stream(ctx), dsites, (int)m);
+    QIL_HIP(hipGetLastError());
+    return dtab.release();
 }
 
 }  // namespace
@@ -487,27 +437,20 @@ extern "C" int qil_mps_restrict(const qil_mps* psi, const uint8_t* spec, qil_mps
     }
     qil_mps* res = nullptr;
     QIL_TRY(qil_mps_alloc(ctx, m, psi->dtype, paired, bonds.data(), ids.data(), psi->amplitude, &res));
-    auto body = [&]() -> int {
-        std::vector<const RunPlan*> in_lds;
-        for (RunPlan& r : rs.runs) {
-            if (!rs.forms_product(r)) continue;
-            const int64_t k = rs.kept[(size_t)r.kept];
-            const int64_t elems = r.kind == kTrailing ? 2 * rs.cl(k) : (r.kind == kLeading ? 1 : rs.cl(r.p)) * rs.cr(r.q);
-            QIL_TRY(rs.alloc((size_t)elems, &r.out));
-            if (rs.fits_lds(r)) in_lds.push_back(&r);
-        }
-        QIL_TRY(rs.launch_runs_lds(in_lds));
-        for (const RunPlan& r : rs.runs)
-            if (rs.forms_product(r) && !rs.fits_lds(r)) QIL_TRY(rs.run_by_gemm(r));
-        QIL_TRY(rs.launch_absorb(res));
-        for (void* t : rs.temps) QIL_TRY(qil_ctx_free(ctx, t));
-        return QIL_OK;
-    };
-    const int st = body();
-    if (st != QIL_OK) {                       // the call scope returns the temporaries; the result is a handle of its own
-        qil_mps_destroy(res);
-        return st;
+    qil_result_guard<qil_mps> guard(res);     // the call scope returns the temporaries; the result is a handle of its own
+    std::vector<const RunPlan*> in_lds;
+    for (RunPlan& r : rs.runs) {
+        if (!rs.forms_product(r)) continue;
+        const int64_t k = rs.kept[(size_t)r.kept];
+        const int64_t elems = r.kind == kTrailing ? 2 * rs.cl(k) : (r.kind == kLeading ? 1 : rs.cl(r.p)) * rs.cr(r.q);
+        QIL_TRY(rs.alloc((size_t)elems, &r.out));
+        if (rs.fits_lds(r)) in_lds.push_back(&r);
     }
-    *out = res;
+    QIL_TRY(rs.launch_runs_lds(in_lds));
+    for (const RunPlan& r : rs.runs)
+        if (rs.forms_product(r) && !rs.fits_lds(r)) QIL_TRY(rs.run_by_gemm(r));
+    QIL_TRY(rs.launch_absorb(res));
+    for (void* t : rs.temps) QIL_TRY(qil_ctx_free(ctx, t));
+    *out = guard.release();
     return QIL_OK;
 }

@@ -74,14 +74,8 @@ __global__ __launch_bounds__(kRows) void site_sum_grouped(const SumSite* __restr
     constexpr int RPL = rows_per_lane<TO>::value;
     constexpr int kTileRows = kRows * RPL;
     __shared__ SumTerm st[kNC];
-    // ---- block -> site (wave-uniform binary search over the prefix table)
     const long long blk = blockIdx.x;
-    int lo = 0, hi = nsites - 1;
-    while (lo < hi) {
-        int mid = (lo + hi + 1) >> 1;
-        if (sites[mid].block_begin <= blk) lo = mid; else hi = mid - 1;
-    }
-    const SumSite S = sites[lo];
+    const SumSite S = sites[last_entry_le<&SumSite::block_begin>(sites, nsites, blk)];   // block -> site
     const SumTerm* __restrict__ T = terms + S.term_begin;
     TO* __restrict__ C = static_cast<TO*>(S.C);
     const long long R = S.R;
@@ -157,7 +151,7 @@ __global__ __launch_bounds__(kRows) void site_sum_grouped(const SumSite* __restr
             }
             if constexpr (RPL == 2) {
                 if (packed) {
-                    store_pair<true>(cp + R * s, v[0], v[1]);
+                    store_pair(cp + R * s, v[0], v[1]);
                 } else {
                     store_out<true>(cp + R * s, v[0]);
                     if (second) store_out<true>(cp + R * s + 1, v[1]);
@@ -184,12 +178,7 @@ template <class T>
 __global__ __launch_bounds__(64) void gemm_grouped_small(const qil_gemm_problem* __restrict__ probs, int count) {
     constexpr bool CX = sizeof(T) == 16;
     const int blk = (int)blockIdx.x;
-    int lo = 0, hi = count - 1;
-    while (lo < hi) {
-        int mid = (lo + hi + 1) >> 1;
-        if (probs[mid].tile_begin <= blk) lo = mid; else hi = mid - 1;
-    }
-    const qil_gemm_problem P = probs[lo];
+    const qil_gemm_problem P = probs[last_entry_le<&qil_gemm_problem::tile_begin>(probs, count, blk)];   // tile -> problem
     const int t = blk - P.tile_begin, tm = (P.m + 15) >> 4;
     const int ti = t % tm, tj = t / tm;
     const int lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
@@ -280,44 +269,26 @@ int launch_sum(const qil_mps* const* terms, int64_t nb, const std::vector<double
         }
     }
     QIL_REQUIRE(blocks < (1LL << 31), QIL_EINVAL_ARG, "mps_sum: grid too large (%lld workgroups)", blocks);
-    // both tables in one upload: the descriptor ring where they fit a slot, a pool block otherwise (64 terms x 48 sites)
-    const size_t sbytes = stab.size() * sizeof(SumSite), tbytes = ttab.size() * sizeof(SumTerm), bytes = sbytes + tbytes;
-    void *pin = nullptr, *dev = nullptr, *blockp = nullptr;
-    int slot = -1;
-    if (bytes <= qil_context::kDescSlotBytes) QIL_TRY(qil_ctx_desc_acquire(ctx, bytes, &pin, &dev, &slot));
-    else QIL_TRY(qil_ctx_alloc(ctx, bytes, &blockp));
-    // from here on every path hands the slot or the block back: the slot is committed (an event behind whatever was enqueued),
-    // the block returns to the pool, which recycles in stream order
-    auto body = [&]() -> int {
-        if (blockp) {
-            dev = blockp;
-            QIL_HIP(hipMemcpyAsync(dev, stab.data(), sbytes, hipMemcpyHostToDevice, qil_stream(ctx)));
-            QIL_HIP(hipMemcpyAsync(static_cast<char*>(dev) + sbytes, ttab.data(), tbytes, hipMemcpyHostToDevice, qil_stream(ctx)));
-            QIL_HIP(qil_stream_sync(ctx));               // pageable sources that die with this frame
-        } else {
-            memcpy(pin, stab.data(), sbytes);
-            memcpy(static_cast<char*>(pin) + sbytes, ttab.data(), tbytes);
-            QIL_HIP(hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, qil_stream(ctx)));
-        }
-        QIL_TRY(qil_ctx_prof_begin(ctx));
-        const SumSite* dsites = static_cast<const SumSite*>(dev);
-        const SumTerm* dterms = reinterpret_cast<const SumTerm*>(static_cast<const char*>(dev) + sbytes);
-        const dim3 grid((unsigned)blocks), block(kRows);
-        bool any_c = false, any_r = false;
-        for (int64_t j = 0; j < nb; ++j) (terms[j]->dtype == QIL_C64 ? any_c : any_r) = true;
+    // both tables in one upload, the terms behind the sites (64 terms x 48 sites is past a descriptor slot)
+    const size_t sbytes = stab.size() * sizeof(SumSite);
+    qil_dev_table dev(ctx);
+    QIL_TRY(dev.upload(stab.data(), sbytes, ttab.data(), ttab.size() * sizeof(SumTerm)));
+    QIL_TRY(qil_ctx_prof_begin(ctx));
+    const SumSite* dsites = dev.as<SumSite>();
+    const SumTerm* dterms = dev.as<SumTerm>(sbytes);
+    const dim3 grid((unsigned)blocks), block(kRows);
+    bool any_c = false, any_r = false;
+    for (int64_t j = 0; j < nb; ++j) (terms[j]->dtype == QIL_C64 ? any_c : any_r) = true;
 #define QIL_SUM_LAUNCH(TA, TO, MIXED) \
     hipLaunchKernelGGL((site_sum_grouped<TA, TO, MIXED>), grid, block, 0, qil_stream(ctx), dsites, dterms, (int)n)
-        if (out->dtype == QIL_F64) QIL_SUM_LAUNCH(double, double, false);
-        else if (any_c && any_r) QIL_SUM_LAUNCH(double, c64, true);
-        else if (any_c) QIL_SUM_LAUNCH(c64, c64, false);
-        else QIL_SUM_LAUNCH(double, c64, false);
+    if (out->dtype == QIL_F64) QIL_SUM_LAUNCH(double, double, false);
+    else if (any_c && any_r) QIL_SUM_LAUNCH(double, c64, true);
+    else if (any_c) QIL_SUM_LAUNCH(c64, c64, false);
+    else QIL_SUM_LAUNCH(double, c64, false);
 #undef QIL_SUM_LAUNCH
-        QIL_HIP(hipGetLastError());
-        return qil_ctx_prof_end(ctx);
-    };
-    const int st = body();
-    const int rel = blockp ? qil_ctx_free(ctx, blockp) : qil_ctx_desc_commit(ctx, slot);
-    return st != QIL_OK ? st : rel;
+    QIL_HIP(hipGetLastError());
+    QIL_TRY(qil_ctx_prof_end(ctx));
+    return dev.release();
 }
 
 }  // namespace
@@ -329,26 +300,16 @@ int qil_dev_gemm_grouped(qil_context* ctx, int dtype, std::vector<qil_gemm_probl
         p.tile_begin = (int)tiles;
         tiles += (long long)((p.m + 15) / 16) * ((p.n + 15) / 16);
     }
-    const size_t bytes = probs.size() * sizeof(qil_gemm_problem);
-    QIL_REQUIRE(tiles < (1LL << 31) && bytes <= qil_context::kDescSlotBytes, QIL_EINVAL_ARG,
-                "gemm_grouped: table too large (%zu problems)", probs.size());
-    void *pin = nullptr, *dev = nullptr;
-    int slot = 0;
-    QIL_TRY(qil_ctx_desc_acquire(ctx, bytes, &pin, &dev, &slot));
-    memcpy(pin, probs.data(), bytes);
-    auto body = [&]() -> int {
-        QIL_HIP(hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, qil_stream(ctx)));
-        const qil_gemm_problem* dtab = static_cast<const qil_gemm_problem*>(dev);
-        if (dtype == QIL_C64)
-            hipLaunchKernelGGL((gemm_grouped_small<c64>), dim3((unsigned)tiles), dim3(64), 0, qil_stream(ctx), dtab, (int)probs.size());
-        else
-            hipLaunchKernelGGL((gemm_grouped_small<double>), dim3((unsigned)tiles), dim3(64), 0, qil_stream(ctx), dtab, (int)probs.size());
-        QIL_HIP(hipGetLastError());
-        return QIL_OK;
-    };
-    const int st = body();
-    const int rel = qil_ctx_desc_commit(ctx, slot);      // also on failure: the slot is handed back either way
-    return st != QIL_OK ? st : rel;
+    QIL_REQUIRE(tiles < (1LL << 31), QIL_EINVAL_ARG, "gemm_grouped: table too large (%zu problems)", probs.size());
+    qil_dev_table dev(ctx);
+    QIL_TRY(dev.upload(probs.data(), probs.size() * sizeof(qil_gemm_problem)));
+    const qil_gemm_problem* dtab = dev.as<qil_gemm_problem>();
+    if (dtype == QIL_C64)
+        hipLaunchKernelGGL((gemm_grouped_small<c64>), dim3((unsigned)tiles), dim3(64), 0, qil_stream(ctx), dtab, (int)probs.size());
+    else
+        hipLaunchKernelGGL((gemm_grouped_small<double>), dim3((unsigned)tiles), dim3(64), 0, qil_stream(ctx), dtab, (int)probs.size());
+    QIL_HIP(hipGetLastError());
+    return dev.release();
 }
 
 bool qil_dev_gemm_grouped_fits(size_t nproblems) { return nproblems * sizeof(qil_gemm_problem) <= qil_context::kDescSlotBytes; }
@@ -366,12 +327,9 @@ extern "C" int qil_mps_sum(const qil_mps* const* terms, int64_t nb, const double
         for (int64_t j = 0; j < nb; ++j) bonds[(size_t)i] += terms[j]->dims[(size_t)i + 1];
     qil_mps* res = nullptr;
     QIL_TRY(qil_mps_alloc(ctx, n, odt, terms[0]->paired, bonds.data(), terms[0]->site_ids.data(), 1.0, &res));
-    const int st = launch_sum(terms, nb, w, res);
-    if (st != QIL_OK) {
-        qil_mps_destroy(res);
-        return st;
-    }
-    *out = res;
+    qil_result_guard<qil_mps> guard(res);
+    QIL_TRY(launch_sum(terms, nb, w, res));
+    *out = guard.release();
     return QIL_OK;
 }
 

@@ -1078,7 +1078,6 @@ static int apply_compress_on(qil_context* ctx, const qil_mpo* W, const qil_mps* 
     auto cleanup = [&](int code) {
         for (void* p : tmp) qil_ctx_free(ctx, p);
         if (phi) qil_mps_destroy(phi);
-        if (code != QIL_OK && res) qil_mps_destroy(res);
         return code;
     };
     auto take = [&](size_t bytes, void** p) {
@@ -1143,6 +1142,7 @@ static int apply_compress_on(qil_context* ctx, const qil_mpo* W, const qil_mps* 
         return s2;
     };
     res = new qil_mps();
+    qil_result_guard<qil_mps> guard(res);            // a failing return below destroys the result
     qil_chain_bind(res, ctx);
     res->dtype = odt;
     res->paired = psi->paired;
@@ -1260,11 +1260,8 @@ static int apply_compress_on(qil_context* ctx, const qil_mpo* W, const qil_mps* 
     // ---- 3. exact-gauge truncation
     st = compress_impl(res, maxdim, tol, sweeps, true);        // the variational sweep left res right-canonical
     lap("compress!");
-    if (st != QIL_OK) {
-        qil_mps_destroy(res);
-        return st;
-    }
-    *out = res;
+    if (st != QIL_OK) return st;
+    *out = guard.release();
     return QIL_OK;
 }
 
@@ -1335,10 +1332,6 @@ int qil_sum_compress_impl(qil_context* ctx, const qil_mps* const* terms, int64_t
         tmp.clear();
         for (qil_mps* c : own) qil_mps_destroy(c);
         own.clear();
-        if (code != QIL_OK && res) {
-            qil_mps_destroy(res);
-            res = nullptr;
-        }
         return code;
     };
     auto take = [&](size_t bytes, void** p) {
@@ -1426,6 +1419,7 @@ int qil_sum_compress_impl(qil_context* ctx, const qil_mps* const* terms, int64_t
         return s2;
     };
     res = new qil_mps();
+    qil_result_guard<qil_mps> guard(res);            // a failing return below destroys the result
     qil_chain_bind(res, ctx);
     res->dtype = odt;
     res->paired = terms[0]->paired;
@@ -1559,12 +1553,8 @@ int qil_sum_compress_impl(qil_context* ctx, const qil_mps* const* terms, int64_t
     }
     (void)cleanup(QIL_OK);
     // ---- 4. exact-gauge truncation
-    st = compress_impl(res, maxdim, tol, sweeps, true);        // the variational sweep left res right-canonical
-    if (st != QIL_OK) {
-        qil_mps_destroy(res);
-        return st;
-    }
-    *out = res;
+    QIL_TRY(compress_impl(res, maxdim, tol, sweeps, true));    // the variational sweep left res right-canonical
+    *out = guard.release();
     return QIL_OK;
 }
 
