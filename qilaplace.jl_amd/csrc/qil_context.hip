@@ -535,6 +535,20 @@ int qil_chain_alloc(qil_context* ctx, qil_chain* c, int64_t n, int dtype, int pa
     return QIL_OK;
 }
 
+qil_mps* qil_mps_empty(qil_context* ctx, int64_t n, int dtype, int paired, const int64_t* site_ids, double amplitude) {
+    qil_mps* h = new qil_mps();
+    qil_chain_bind(h, ctx);
+    h->dtype = dtype;
+    h->paired = paired;
+    h->phys_rank = 1;
+    h->dims.assign((size_t)n + 1, 1);
+    h->site.assign((size_t)n, nullptr);
+    h->site_ids.resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) h->site_ids[(size_t)i] = site_ids ? site_ids[i] : i + 1;
+    h->amplitude = amplitude;
+    return h;
+}
+
 // ---------------------------------------------------------------- batches of independent chains
 static void chain_move(qil_chain* c, qil_context* to);
 

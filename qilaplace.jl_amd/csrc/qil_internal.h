@@ -179,6 +179,42 @@ struct qil_dev_table {
         return reinterpret_cast<const T*>(static_cast<const char*>(dev) + byte_offset);
     }
 };
+// The pool temporaries of one call that live outside a handle.  alloc() takes a block from the context pool, own() takes in one
+// that a callee returned (svd_trunc_dev's factors); free() returns one early, so the peak is what the algorithm needs; give() hands
+// one to a handle (qil_chain_adopt, qil_chain_set_site) or to the caller.  The destructor frees what is left, on every return path.
+// A block is listed at most once and leaves the list when it is freed or given, so none is freed twice: a second qil_ctx_free of
+// an address puts an error behind a successful call (or, once the pool has handed the address out again, frees a stranger's
+// block).  Declare it after the call's qil_call_scope: a failed call then frees these first and the scope reclaims the rest.
+struct qil_scratch {
+    qil_context* ctx;
+    std::vector<void*> blocks;
+    explicit qil_scratch(qil_context* c) : ctx(c) {}
+    ~qil_scratch() {
+        for (void* p : blocks) qil_ctx_free(ctx, p);
+    }
+    qil_scratch(const qil_scratch&) = delete;
+    qil_scratch& operator=(const qil_scratch&) = delete;
+    int alloc(size_t bytes, void** out) {
+        const int s = qil_ctx_alloc(ctx, bytes, out);
+        if (s == QIL_OK) blocks.push_back(*out);
+        return s;
+    }
+    void* own(void* p) {
+        blocks.push_back(p);
+        return p;
+    }
+    void* give(void* p) {                      // the latest blocks leave first: search from the back
+        for (size_t t = blocks.size(); t-- > 0;)
+            if (blocks[t] == p) {
+                blocks.erase(blocks.begin() + (long)t);
+                return p;
+            }
+        return nullptr;                        // not ours (any more): nothing to hand over, nothing to free
+    }
+    void free(void* p) {
+        if (give(p)) qil_ctx_free(ctx, p);
+    }
+};
 int qil_ctx_event(qil_context* ctx, hipEvent_t* e);            // from the context's event pool
 void qil_ctx_event_release(qil_context* ctx, hipEvent_t e);
 // `bytes` (a multiple of 4, 4-byte aligned source) of device memory to the host, ordered after everything this context has
@@ -248,6 +284,9 @@ struct qil_mpo : qil_chain {};
 int qil_chain_alloc(qil_context* ctx, qil_chain* c, int64_t n, int dtype, int paired, int phys_rank,
                     const int64_t* bond_dims, const int64_t* site_ids);
 int qil_chain_release(qil_chain* c);
+// a bound MPS of n empty site slots with all bonds 1, for a result built site by site (qil_chain_adopt / qil_chain_set_site);
+// site_ids = nullptr numbers the sites 1..n.  Allocates nothing on the device.
+struct qil_mps* qil_mps_empty(qil_context* ctx, int64_t n, int dtype, int paired, const int64_t* site_ids, double amplitude);
 // tie a handle to its context (registers it for orphaning on context destruction)
 void qil_chain_bind(qil_chain* c, qil_context* ctx);
 // replace site i's buffer (takes ownership of `p`), updating the bond dims
@@ -267,6 +306,7 @@ struct qil_result_guard {
     }
     qil_result_guard(const qil_result_guard&) = delete;
     qil_result_guard& operator=(const qil_result_guard&) = delete;
+    qil_result_guard(qil_result_guard&& o) noexcept : p(o.release()) {}     // for a std::vector of guards
     H* release() {
         H* h = p;
         p = nullptr;

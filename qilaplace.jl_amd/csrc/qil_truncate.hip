@@ -101,26 +101,23 @@ static int svd_trunc_lowrank(qil_context* ctx, int dtype, int64_t m, int64_t n, 
     for (int64_t k : {(int64_t)128, (int64_t)256}) {
         if (k * 3 > r0) break;
         void *Om = nullptr, *Y = nullptr, *Z = nullptr, *B = nullptr, *D = nullptr, *part = nullptr;
-        auto release = [&]() {
-            for (void* b : {Om, Y, Z, B, D, part})
-                if (b) qil_ctx_free(ctx, b);
-        };
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(n * k) * e, &Om));
+        qil_scratch scratch(ctx);                        // this attempt's blocks: freed when it ends, whichever way
+        QIL_TRY(scratch.alloc((size_t)(n * k) * e, &Om));
         QIL_TRY(qil_dev_fill_normal(ctx, dtype, Om, n * k, 0x10a4c0deull + (uint64_t)k, 1.0));
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(m * k) * e, &Y));
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(n * k) * e, &Z));
+        QIL_TRY(scratch.alloc((size_t)(m * k) * e, &Y));
+        QIL_TRY(scratch.alloc((size_t)(n * k) * e, &Z));
         QIL_TRY(qil_dev_gemm(ctx, dtype, 0, 0, m, k, n, A, lda, Om, n, Y, m));                       // Y = A Omega
         QIL_TRY(qil_dev_qr_positive(ctx, dtype, m, k, Y, m, nullptr, 0, false));
         QIL_TRY(qil_dev_gemm(ctx, dtype, cj, 0, n, k, m, A, lda, Y, m, Z, n));                       // Z = A^H Y
         QIL_TRY(qil_dev_qr_positive(ctx, dtype, n, k, Z, n, nullptr, 0, false));
         QIL_TRY(qil_dev_gemm(ctx, dtype, 0, 0, m, k, n, A, lda, Z, n, Y, m));                        // Y = A Z
         QIL_TRY(qil_dev_qr_positive(ctx, dtype, m, k, Y, m, nullptr, 0, true));                      // Q (orthonormal)
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(k * n) * e, &B));
+        QIL_TRY(scratch.alloc((size_t)(k * n) * e, &B));
         QIL_TRY(qil_dev_gemm(ctx, dtype, cj, 0, k, n, m, Y, m, A, lda, B, k));                       // B = Q^H A
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(m * n) * e, &D));
+        QIL_TRY(scratch.alloc((size_t)(m * n) * e, &D));
         QIL_TRY(qil_dev_gemm(ctx, dtype, 0, 0, m, n, k, Y, m, B, k, D, m));                          // D = Q B
         const unsigned nblk_ = (unsigned)std::min<long long>((m * n * nre + 255) / 256, 1024);
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)nblk_ * 2 * sizeof(double), &part));
+        QIL_TRY(scratch.alloc((size_t)nblk_ * 2 * sizeof(double), &part));
         QIL_TRY((qil_klaunch<residual_sumsq_k>(ctx, dim3(nblk_), dim3(256), 0, (const double*)A, (long long)lda, (const double*)D, (long long)m, (long long)m, (long long)n, nre, (double*)part)));
         std::vector<double> hp((size_t)nblk_ * 2);
         QIL_TRY(qil_read_back(ctx, hp.data(), part, hp.size() * sizeof(double)));
@@ -132,7 +129,6 @@ static int svd_trunc_lowrank(qil_context* ctx, int dtype, int64_t m, int64_t n, 
         if (getenv("QIL_SVD_DEBUG")) fprintf(stderr, "[svd-lowrank] %lld x %lld, k = %lld: residual^2 / total = %.3e (cutoff %.1e)\n",
                                              (long long)m, (long long)n, (long long)k, tot > 0 ? rho / tot : 0.0, cutoff);
         if (!(rho <= 1e-8 * cutoff * tot)) {
-            release();
             // a sketch twice as wide cannot help an operand that is nowhere near low rank (flat spectra leave > 50 % of
             // the weight outside 128 columns): only residuals that are already small earn the second attempt
             if (rho > 1e-4 * tot) break;
@@ -141,13 +137,11 @@ static int svd_trunc_lowrank(qil_context* ctx, int dtype, int64_t m, int64_t n, 
         int64_t r = 0;
         void *Ub = nullptr, *Vh = nullptr;
         std::vector<double> S;
-        int st = svd_trunc_dev(ctx, dtype, k, n, B, k, cutoff, true, maxdim, mindim, absorb, &r, &Ub, &Vh, &S);
-        if (st != QIL_OK) return st;
+        QIL_TRY(svd_trunc_dev(ctx, dtype, k, n, B, k, cutoff, true, maxdim, mindim, absorb, &r, &Ub, &Vh, &S));
         void* U = nullptr;
         QIL_TRY(qil_ctx_alloc(ctx, (size_t)(m * std::min(m, n)) * e, &U));     // callers index U with ld m only
         QIL_TRY(qil_dev_gemm(ctx, dtype, 0, 0, m, r, k, Y, m, Ub, k, U, m));                         // U = Q U_B
         qil_ctx_free(ctx, Ub);
-        release();
         *rank = r;
         *U_out = U;
         *Vh_out = Vh;
@@ -326,9 +320,34 @@ static int gauge_qr_site_left(qil_chain* psi, int64_t i, int64_t pd) {
     return QIL_OK;
 }
 
-// One step of the right-to-left gauge sweep (mps.jl:822-837): site i becomes a right isometry (rows alpha | cols
-// (phys, beta)), its left factor is multiplied into site i-1.  gauge_qr: exact thin QR where the site is wide enough,
+// One step of the left-to-right gauge sweep (mps.jl:802-817): site i becomes a left isometry (rows (alpha, phys) | cols
+// beta), its right factor is multiplied into site i+1.  gauge_qr: exact thin QR where the site is tall enough,
 // truncated SVD otherwise (and always when gauge_qr is off).
+static int gauge_site_right(qil_chain* psi, int64_t i, double cutoff, int64_t maxdim, bool gauge_qr) {
+    const int64_t pd = psi->phys_rank == 1 ? 2 : 4;
+    qil_context* ctx = psi->ctx;
+    const int dt = psi->dtype;
+    const size_t e = qil_elem_size(dt);
+    const int64_t cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1];
+    const int64_t cr2 = psi->dims[(size_t)i + 2];
+    if (gauge_qr && pd * cl >= cr) return gauge_qr_site_right(psi, i, pd);
+    int64_t r = 0;
+    void *A = nullptr, *U = nullptr, *SV = nullptr;
+    // rows (alpha, s) | cols beta : the site buffer as it lies
+    QIL_TRY(site_copy(psi, i, &A));
+    QIL_TRY(svd_trunc_dev(ctx, dt, pd * cl, cr, A, pd * cl, cutoff, true, maxdim, 1, 2, &r, &U, &SV, nullptr));
+    qil_ctx_free(ctx, A);
+    void* next = nullptr;
+    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(r * pd * cr2) * e, &next));
+    QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, r, pd * cr2, cr, SV, r, psi->site[(size_t)i + 1], cr, next, r));
+    qil_ctx_free(ctx, SV);
+    QIL_TRY(qil_chain_set_site(psi, i, U, cl, r));
+    QIL_TRY(qil_chain_set_site(psi, i + 1, next, r, cr2));
+    return QIL_OK;
+}
+
+// The mirror step of the right-to-left sweep (mps.jl:822-837): site i becomes a right isometry (rows alpha | cols
+// (phys, beta)), its left factor is multiplied into site i-1.
 static int gauge_site_left(qil_chain* psi, int64_t i, double cutoff, int64_t maxdim, bool gauge_qr) {
     const int64_t pd = psi->phys_rank == 1 ? 2 : 4;
     qil_context* ctx = psi->ctx;
@@ -354,34 +373,14 @@ static int gauge_site_left(qil_chain* psi, int64_t i, double cutoff, int64_t max
 
 int canonicalize_impl(qil_chain* psi, int direction, int64_t center, double cutoff, int64_t maxdim,
                       bool gauge_qr = false) {
-    const int64_t pd = psi->phys_rank == 1 ? 2 : 4;
     qil_context* ctx = psi->ctx;
     const int64_t N = psi->n();
-    const int dt = psi->dtype;
-    const size_t e = qil_elem_size(dt);
     if (direction == QIL_DIR_RIGHT) {
         const int64_t c = center == 0 ? N : center;
         QIL_REQUIRE(c >= 1 && c <= N, QIL_EDOMAIN, "Center out of range [1,%lld]", (long long)N);
         for (int64_t i = 0; i + 1 < c; ++i) {  // mps.jl:802-817
             qil_progress_step(ctx, i == 0, i);                                  // lock-step batches: where this chain is
-            const int64_t cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1];
-            const int64_t cr2 = psi->dims[(size_t)i + 2];
-            if (gauge_qr && pd * cl >= cr) {
-                QIL_TRY(gauge_qr_site_right(psi, i, pd));
-                continue;
-            }
-            int64_t r = 0;
-            void *A = nullptr, *U = nullptr, *SV = nullptr;
-            // rows (alpha, s) | cols beta : the site buffer as it lies
-            QIL_TRY(site_copy(psi, i, &A));
-            QIL_TRY(svd_trunc_dev(ctx, dt, pd * cl, cr, A, pd * cl, cutoff, true, maxdim, 1, 2, &r, &U, &SV, nullptr));
-            qil_ctx_free(ctx, A);
-            void* next = nullptr;
-            QIL_TRY(qil_ctx_alloc(ctx, (size_t)(r * pd * cr2) * e, &next));
-            QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, r, pd * cr2, cr, SV, r, psi->site[(size_t)i + 1], cr, next, r));
-            qil_ctx_free(ctx, SV);
-            QIL_TRY(qil_chain_set_site(psi, i, U, cl, r));
-            QIL_TRY(qil_chain_set_site(psi, i + 1, next, r, cr2));
+            QIL_TRY(gauge_site_right(psi, i, cutoff, maxdim, gauge_qr));
         }
     } else if (direction == QIL_DIR_LEFT) {
         const int64_t c = center == 0 ? 1 : center;
@@ -861,17 +860,9 @@ int signal_mps_impl(qil_context* ctx, const void* x, int64_t len, int dtype, con
             if (p) qil_ctx_free(ctx, p);
         return s;
     }
-    qil_mps* psi = new qil_mps();
-    qil_chain_bind(psi, ctx);
-    psi->dtype = dtype;
-    psi->paired = 0;
-    psi->phys_rank = 1;
+    qil_mps* psi = qil_mps_empty(ctx, n, dtype, 0, nullptr, amp);
     psi->dims = dims;
-    psi->site.assign(sites.size(), nullptr);
     for (size_t i = 0; i < sites.size(); ++i) qil_chain_adopt(psi, (int64_t)i, sites[i]);
-    psi->site_ids.resize((size_t)n);
-    for (int64_t i = 0; i < n; ++i) psi->site_ids[(size_t)i] = i + 1;
-    psi->amplitude = amp;
     *out = psi;
     return QIL_OK;
 }
@@ -1018,7 +1009,103 @@ extern "C" int qil_canonicalize(qil_mps* psi, int direction, int64_t center, dou
     return canonicalize_impl(psi, direction, center, cutoff, maxdim);
 }
 
-static int compress_impl(qil_mps* psi, int64_t maxdim, double tol, int sweeps, bool right_canonical);
+// right_canonical: the caller guarantees every site but the first is a right isometry (the fused apply-and-truncate
+// after its variational sweep).  canonicalize!(:left) of such a state can neither truncate nor change anything but the
+// gauge (all its singular values are 1), so it is not run.
+static int compress_impl(qil_mps* psi, int64_t maxdim, double tol, int sweeps, bool right_canonical) {
+    QIL_REQUIRE(psi, QIL_EINVAL_ARG, "compress!: null handle");
+    const int64_t N = psi->n();
+    QIL_REQUIRE(N >= 2, QIL_EDOMAIN, "SignalMPS must have at least 2 sites.");   // mps.jl:918
+    QIL_REQUIRE(sweeps >= 1, QIL_EINVAL_ARG, "compress!: sweeps must be >= 1");
+    qil_context* ctx = psi->ctx;
+    QIL_TRY(qil_ctx_activate(ctx));
+    qil_call_scope call_scope(ctx);
+    const int dt = psi->dtype;
+    const double cutoff = tol * tol / ((double)(N - 1) * sweeps);               // mps.jl:920
+    if (!right_canonical) QIL_TRY(canonicalize_impl(psi, QIL_DIR_LEFT, 0, 1e-12, kNoCap));            // mps.jl:923
+    // The reference truncates the two-site tensor psi[j] psi[j+1] (mps.jl:929, :946).  In canonical gauge --
+    // which every step of the sweep maintains -- that tensor has the same singular values and the same kept
+    // subspace as the single site next to the orthogonality centre (its neighbour is an isometry), so each
+    // sweep is run as a truncating gauge sweep on one-site matrices: (2 chi_l x chi) instead of
+    // (2 chi_l x 2 chi_r), no theta product, and the Jacobi SVD rotates half as many columns.
+    for (int sw = 0; sw < sweeps; ++sw) {
+        QIL_TRY(canonicalize_impl(psi, QIL_DIR_RIGHT, 0, cutoff, maxdim));      // L -> R: U | S V   (mps.jl:927-942)
+        QIL_TRY(canonicalize_impl(psi, QIL_DIR_LEFT, 0, cutoff, maxdim));       // R -> L: U S | V   (mps.jl:944-959)
+    }
+    // mps.jl:963 re-gauges once more (canonicalize!(:left), cutoff 1e-12).  The sweep that just ended left every site
+    // but the first an isometry (all its singular values are 1), so that pass can neither truncate nor change anything
+    // but the gauge -- it is not run.
+    double nrm = 0;
+    QIL_TRY(qil_norm(psi, &nrm));                                               // mps.jl:967-971
+    if (nrm != 0) {
+        psi->amplitude *= nrm;
+        const double inv = 1.0 / nrm;
+        std::vector<double> s((size_t)psi->dims[1], inv);
+        QIL_TRY(qil_dev_scale(ctx, dt, 1, 2 * psi->dims[0], psi->dims[1], psi->site[0], 2 * psi->dims[0], s.data()));
+    }
+    return QIL_OK;
+}
+
+extern "C" int qil_compress(qil_mps* psi, int64_t maxdim, double tol, int sweeps) {
+    return compress_impl(psi, maxdim, tol, sweeps, false);
+}
+
+// ---------------------------------------------------------------- steps the fused routes share
+// Default intermediate bond cap of the zip-up and the variational sweep: maxdim + 16.  With the variational sweep behind it the zip-up
+// only has to deliver a basis that contains the kept space: an oversampling of 16 columns gives the same verdicts as 2 maxdim
+// (r01), max(1.5 maxdim, maxdim + 16) (r02/r03) -- 200 random flat-spectrum products with maxdim 8 ... 128 each, 0 bad
+// (tools/_fuzz_product_compress.py, QIL_FUZZ_ZIP=plus16) -- and the oracle tests, while an oversampling of 4 (1.5 maxdim at
+// maxdim = 8) fails 2 of 200.  Bench product, maxdim 64: cap 96 117 ms, cap 80 108.6 ms (MEASUREMENTS R04.7).
+// The evidence covers maxdim <= 128 with flat spectra only: beyond that a relative floor of 1.125 maxdim
+// keeps the oversampling proportional (maxdim 256: 288, 512: 576) until a slowly-decaying case at that size is fuzzed.
+static int64_t zip_default_cap(int64_t maxdim) {
+    const int64_t zip_over = 16;
+    return maxdim > kNoCap / 2 ? kNoCap : std::max(maxdim + zip_over, maxdim + (maxdim + 7) / 8);
+}
+
+// Sketch matrix for capped bonds (om_ld x zip_maxdim; one for the whole call: any sub-block of a Gaussian matrix is Gaussian);
+// *Om stays null when no bond of the call (the widest is om_ld) exceeds the cap.
+static int zip_sketch(qil_scratch& scratch, int dt, int64_t om_ld, int64_t zip_maxdim, void** Om) {
+    *Om = nullptr;
+    if (zip_maxdim >= om_ld) return QIL_OK;
+    QIL_TRY(scratch.alloc((size_t)(om_ld * zip_maxdim) * qil_elem_size(dt), Om));
+    return qil_dev_fill_normal(scratch.ctx, dt, *Om, om_ld * zip_maxdim, 0x51b0e7c5ull, 1.0);
+}
+
+// One zip-up step: theta (rows x Pc, left intact) -> the provisional site U (rows x r, orthonormal columns) and the next
+// environment SV = U^H theta (r x Pc), both fresh pool blocks the caller owns.
+// Capped bond: an orthonormal basis of theta Omega (Omega: Pc x zip_maxdim, seeded Gaussian) instead of theta's truncated
+// SVD -- the variational sweep re-optimises every site anyway, and with it the sketched zip-up reproduces the oracle's
+// compress!(apply) on all 24 random products exactly as the SVD one does (numpy prototype, then tests); one GEMM + one thin QR +
+// one GEMM instead of a 2r x D chi SVD.  Otherwise: the truncated SVD at zip_cutoff.
+static int zip_step(qil_context* ctx, int dt, int64_t rows, int64_t Pc, void* theta, int64_t zip_maxdim, double zip_cutoff,
+                    const void* Om, int64_t om_ld, int64_t* r, void** U, void** SV) {
+    if (zip_maxdim >= std::min(rows, Pc))
+        return svd_trunc_dev(ctx, dt, rows, Pc, theta, rows, zip_cutoff, true, zip_maxdim, 1, 2, r, U, SV, nullptr);
+    const size_t e = qil_elem_size(dt);
+    const int64_t k = zip_maxdim;
+    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(rows * k) * e, U));
+    QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, rows, k, Pc, theta, rows, Om, om_ld, *U, rows));
+    QIL_TRY(qil_dev_qr_positive(ctx, dt, rows, k, *U, rows, nullptr, 0, true));
+    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(k * Pc) * e, SV));
+    QIL_TRY(qil_dev_gemm(ctx, dt, dt == QIL_C64 ? 2 : 1, 0, k, Pc, rows, *U, rows, theta, rows, *SV, k));
+    *r = k;
+    return QIL_OK;
+}
+
+// *out = a fresh block with the ne real numbers at src as c64 (a real operand of a complex result is widened once: KB..MB)
+static int widen_site(qil_context* ctx, const void* src, long long ne, void** out) {
+    QIL_TRY(qil_ctx_alloc(ctx, (size_t)ne * sizeof(c64), out));
+    return qil_klaunch<widen_f64_k>(ctx, dim3(nblk(ne)), dim3(256), 0, (const double*)src, (c64*)*out, ne);
+}
+
+// a few doubles to a fresh block owned by `scratch`, complete on return (the source may die with the caller's frame)
+static int upload_small(qil_scratch& scratch, const double* host, size_t n, void** p) {
+    QIL_TRY(scratch.alloc(n * sizeof(double), p));
+    QIL_HIP(hipMemcpyAsync(*p, host, n * sizeof(double), hipMemcpyHostToDevice, qil_stream(scratch.ctx)));
+    QIL_HIP(qil_stream_sync(scratch.ctx));
+    return QIL_OK;
+}
 
 // Fused apply-and-truncate: compress!(apply(W, psi); maxdim, tol, sweeps) WITHOUT ever writing the
 // (D chi)^2 product tensors.
@@ -1054,103 +1141,12 @@ static int apply_compress_on(qil_context* ctx, const qil_mpo* W, const qil_mps* 
     QIL_TRY(qil_ctx_activate(ctx));
     qil_call_scope call_scope(ctx);
     if (maxdim <= 0) maxdim = kNoCap;
-    // intermediate bond cap of the zip-up and the variational sweep: maxdim + 16.  With the variational sweep behind it the zip-up
-    // only has to deliver a basis that contains the kept space: an oversampling of 16 columns gives the same verdicts as 2 maxdim
-    // (r01), max(1.5 maxdim, maxdim + 16) (r02/r03) -- 200 random flat-spectrum products with maxdim 8 ... 128 each, 0 bad
-    // (tools/_fuzz_product_compress.py, QIL_FUZZ_ZIP=plus16) -- and the oracle tests, while an oversampling of 4 (1.5 maxdim at
-    // maxdim = 8) fails 2 of 200.  Bench product, maxdim 64: cap 96 117 ms, cap 80 108.6 ms (MEASUREMENTS R04.7).
-    // The evidence covers maxdim <= 128 with flat spectra only: beyond that a relative floor of 1.125 maxdim
-    // keeps the oversampling proportional (maxdim 256: 288, 512: 576) until a slowly-decaying case at that size is fuzzed.
-    const int64_t zip_over = 16;
-    if (zip_maxdim <= 0) zip_maxdim = maxdim > kNoCap / 2 ? kNoCap : std::max(maxdim + zip_over, maxdim + (maxdim + 7) / 8);
+    if (zip_maxdim <= 0) zip_maxdim = zip_default_cap(maxdim);
     const double cutoff = tol * tol / ((double)(N - 1) * sweeps);
     const double zip_cutoff = cutoff * 1e-2;
     const bool wc = W->dtype == QIL_C64, ac = psi->dtype == QIL_C64;
     const int odt = (wc || ac) ? QIL_C64 : QIL_F64;
     const size_t e = qil_elem_size(odt);
-    // right-canonical copy of psi: the zip's truncations then see (nearly) orthonormal environments
-    qil_mps* phi = nullptr;
-    QIL_TRY(qil_mps_clone_to(ctx, psi, &phi));
-    qil_mps* res = nullptr;
-    std::vector<void*> tmp;                          // every pool block this call owns outside a handle
-    std::vector<void*> Asite((size_t)N), Wsite((size_t)N), Lenv((size_t)N, nullptr);
-    std::vector<int> Rdim((size_t)N + 1, 1);
-    auto cleanup = [&](int code) {
-        for (void* p : tmp) qil_ctx_free(ctx, p);
-        if (phi) qil_mps_destroy(phi);
-        return code;
-    };
-    auto take = [&](size_t bytes, void** p) {
-        int s = qil_ctx_alloc(ctx, bytes, p);
-        if (s == QIL_OK) tmp.push_back(*p);
-        return s;
-    };
-    auto drop = [&](void* p) {
-        for (size_t t = tmp.size(); t-- > 0;)
-            if (tmp[t] == p) {
-                tmp.erase(tmp.begin() + (long)t);
-                break;
-            }
-        qil_ctx_free(ctx, p);
-    };
-    auto forget = [&](void* p) {                     // ownership moved into a handle
-        for (size_t t = tmp.size(); t-- > 0;)
-            if (tmp[t] == p) {
-                tmp.erase(tmp.begin() + (long)t);
-                break;
-            }
-    };
-    int st = canonicalize_impl(phi, QIL_DIR_LEFT, 0, 0.0, kNoCap, true);      // exact thin-QR gauge: psi loses nothing
-    if (st != QIL_OK) return cleanup(st);
-    // operands in the output dtype (a real operand of a complex product is widened once: KB..MB)
-    for (int64_t i = 0; i < N && st == QIL_OK; ++i) {
-        Asite[(size_t)i] = phi->site[(size_t)i];
-        Wsite[(size_t)i] = W->site[(size_t)i];
-        if (odt == QIL_C64 && !ac) {
-            const long long ne = phi->site_elems(i);
-            void* p = nullptr;
-            if ((st = take((size_t)ne * e, &p)) != QIL_OK) break;
-            QIL_TRY((qil_klaunch<widen_f64_k>(ctx, dim3(nblk(ne)), dim3(256), 0, (const double*)phi->site[(size_t)i], (c64*)p, ne)));
-            Asite[(size_t)i] = p;
-        }
-        if (odt == QIL_C64 && !wc) {
-            const long long ne = W->site_elems(i);
-            void* p = nullptr;
-            if ((st = take((size_t)ne * e, &p)) != QIL_OK) break;
-            QIL_TRY((qil_klaunch<widen_f64_k>(ctx, dim3(nblk(ne)), dim3(256), 0, (const double*)W->site[(size_t)i], (c64*)p, ne)));
-            Wsite[(size_t)i] = p;
-        }
-    }
-    if (st != QIL_OK) return cleanup(st);
-    auto theta_of = [&](int64_t i, void** theta) {
-        const int Dl = (int)W->dims[(size_t)i], Dr = (int)W->dims[(size_t)i + 1];
-        const int cl = (int)phi->dims[(size_t)i], cr = (int)phi->dims[(size_t)i + 1];
-        int s2 = odt == QIL_F64
-                     ? zip_theta<double, double, double>(ctx, Lenv[(size_t)i], Wsite[(size_t)i], Asite[(size_t)i],
-                                                         Rdim[(size_t)i], Dl, Dr, cl, cr, theta)
-                     : zip_theta<c64, c64, c64>(ctx, Lenv[(size_t)i], Wsite[(size_t)i], Asite[(size_t)i], Rdim[(size_t)i], Dl,
-                                                Dr, cl, cr, theta);
-        if (s2 == QIL_OK) tmp.push_back(*theta);
-        return s2;
-    };
-    auto one = [&](void** p) {                       // 1 x 1 environment
-        int s2 = take(e, p);
-        const double v[2] = {1.0, 0.0};
-        if (s2 == QIL_OK && hipMemcpyAsync(*p, v, e, hipMemcpyHostToDevice, qil_stream(ctx)) != hipSuccess)
-            s2 = qil_fail(QIL_EHIP, "apply_compress: upload failed");
-        if (s2 == QIL_OK && qil_stream_sync(ctx) != hipSuccess) s2 = qil_fail(QIL_EHIP, "sync failed");
-        return s2;
-    };
-    res = new qil_mps();
-    qil_result_guard<qil_mps> guard(res);            // a failing return below destroys the result
-    qil_chain_bind(res, ctx);
-    res->dtype = odt;
-    res->paired = psi->paired;
-    res->phys_rank = 1;
-    res->dims.assign((size_t)N + 1, 1);
-    res->site.assign((size_t)N, nullptr);
-    res->site_ids = psi->site_ids;
-    res->amplitude = psi->amplitude;
     const bool fdbg = getenv("QIL_FUSED_DEBUG") != nullptr;
     auto t_prev = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
@@ -1160,108 +1156,110 @@ static int apply_compress_on(qil_context* ctx, const qil_mpo* W, const qil_mps* 
         fprintf(stderr, "[apply_compress] %s %.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
         t_prev = now;
     };
-    // sketch matrix for capped bonds (one for the whole call: any sub-block of a Gaussian matrix is Gaussian)
-    void* Om = nullptr;
-    int64_t om_ld = 1;
-    if (zip_maxdim < kNoCap / 2) {
+    qil_result_guard<qil_mps> res_own(qil_mps_empty(ctx, N, odt, psi->paired, psi->site_ids.data(), psi->amplitude));
+    qil_mps* const res = res_own.p;
+    {   // steps 1 and 2; the gauged copy and every temporary are gone before step 3
+        // right-canonical copy of psi: the zip's truncations then see (nearly) orthonormal environments
+        qil_result_guard<qil_mps> phi_own(nullptr);
+        QIL_TRY(qil_mps_clone_to(ctx, psi, &phi_own.p));
+        qil_mps* const phi = phi_own.p;
+        qil_scratch scratch(ctx);                            // every pool block this call owns outside a handle
+        QIL_TRY(canonicalize_impl(phi, QIL_DIR_LEFT, 0, 0.0, kNoCap, true));      // exact thin-QR gauge: psi loses nothing
+        // operands in the output dtype
+        std::vector<void*> Asite(phi->site), Wsite(W->site), Lenv((size_t)N, nullptr);
+        std::vector<int> Rdim((size_t)N + 1, 1);
+        for (int64_t i = 0; i < N; ++i) {
+            if (odt == QIL_C64 && !ac) {
+                QIL_TRY(widen_site(ctx, phi->site[(size_t)i], phi->site_elems(i), &Asite[(size_t)i]));
+                scratch.own(Asite[(size_t)i]);
+            }
+            if (odt == QIL_C64 && !wc) {
+                QIL_TRY(widen_site(ctx, W->site[(size_t)i], W->site_elems(i), &Wsite[(size_t)i]));
+                scratch.own(Wsite[(size_t)i]);
+            }
+        }
+        auto theta_of = [&](int64_t i, void** theta) -> int {
+            const int Dl = (int)W->dims[(size_t)i], Dr = (int)W->dims[(size_t)i + 1];
+            const int cl = (int)phi->dims[(size_t)i], cr = (int)phi->dims[(size_t)i + 1];
+            if (odt == QIL_F64)
+                QIL_TRY((zip_theta<double, double, double>(ctx, Lenv[(size_t)i], Wsite[(size_t)i], Asite[(size_t)i], Rdim[(size_t)i],
+                                                           Dl, Dr, cl, cr, theta)));
+            else
+                QIL_TRY((zip_theta<c64, c64, c64>(ctx, Lenv[(size_t)i], Wsite[(size_t)i], Asite[(size_t)i], Rdim[(size_t)i], Dl, Dr,
+                                                  cl, cr, theta)));
+            scratch.own(*theta);
+            return QIL_OK;
+        };
+        void* Om = nullptr;
+        int64_t om_ld = 1;
         for (int64_t i = 0; i + 1 < N; ++i) om_ld = std::max<int64_t>(om_ld, phi->dims[(size_t)i + 1] * W->dims[(size_t)i + 1]);
-        if (zip_maxdim < om_ld) {
-            if ((st = take((size_t)(om_ld * zip_maxdim) * e, &Om)) != QIL_OK) return cleanup(st);
-            if ((st = qil_dev_fill_normal(ctx, odt, Om, om_ld * zip_maxdim, 0x51b0e7c5ull, 1.0)) != QIL_OK) return cleanup(st);
-        }
-    }
-    // ---- 1. zip-up, keeping the left environments
-    if ((st = one(&Lenv[0])) != QIL_OK) return cleanup(st);
-    for (int64_t i = 0; i < N; ++i) {
-        const int Dr = (int)W->dims[(size_t)i + 1], cr = (int)phi->dims[(size_t)i + 1];
-        const int R = Rdim[(size_t)i];
-        void* theta = nullptr;
-        if ((st = theta_of(i, &theta)) != QIL_OK) return cleanup(st);
-        if (i + 1 == N) {                       // last site: theta is (R, 2, 1)
-            forget(theta);
-            qil_chain_adopt(res, i, theta);
+        QIL_TRY(zip_sketch(scratch, odt, om_ld, zip_maxdim, &Om));
+        const double one[2] = {1.0, 0.0};                // the 1 x 1 environments at both ends
+        // ---- 1. zip-up, keeping the left environments
+        QIL_TRY(upload_small(scratch, one, e / sizeof(double), &Lenv[0]));
+        for (int64_t i = 0; i < N; ++i) {
+            const int Dr = (int)W->dims[(size_t)i + 1], cr = (int)phi->dims[(size_t)i + 1];
+            const int R = Rdim[(size_t)i];
+            void* theta = nullptr;
+            QIL_TRY(theta_of(i, &theta));
+            if (i + 1 == N) {                       // last site: theta is (R, 2, 1)
+                qil_chain_adopt(res, i, scratch.give(theta));
+                res->dims[(size_t)i] = R;
+                break;
+            }
+            int64_t r = 0;
+            void *U = nullptr, *SV = nullptr;
+            QIL_TRY(zip_step(ctx, odt, 2LL * R, (int64_t)cr * Dr, theta, zip_maxdim, zip_cutoff, Om, om_ld, &r, &U, &SV));
+            scratch.free(theta);
+            qil_chain_adopt(res, i, U);             // [R, s, r]
             res->dims[(size_t)i] = R;
-            break;
+            res->dims[(size_t)i + 1] = r;
+            Lenv[(size_t)i + 1] = scratch.own(SV);      // [r, (beta, b)] == L[r, alpha, a] of the next site
+            Rdim[(size_t)i + 1] = (int)r;
         }
-        int64_t r = 0;
-        void *U = nullptr, *SV = nullptr;
-        const int64_t rows = 2LL * R, Pc = (int64_t)cr * Dr;
-        if (zip_maxdim < std::min(rows, Pc)) {
-            // capped bond: an orthonormal basis of theta Omega (Omega: Pc x zip_maxdim, seeded Gaussian) instead of
-            // theta's truncated SVD -- the variational sweep below re-optimises every site anyway, and with it the
-            // sketched zip-up reproduces the oracle's compress!(apply) on all 24 random products exactly as the SVD one
-            // does (numpy prototype, then tests); one GEMM + one thin QR + one GEMM instead of a 2r x D chi SVD
-            r = zip_maxdim;
-            void* Y = nullptr;
-            if ((st = qil_ctx_alloc(ctx, (size_t)(rows * r) * e, &Y)) != QIL_OK) return cleanup(st);
-            st = qil_dev_gemm(ctx, odt, 0, 0, rows, r, Pc, theta, rows, Om, om_ld, Y, rows);
-            if (st == QIL_OK) st = qil_dev_qr_positive(ctx, odt, rows, r, Y, rows, nullptr, 0, true);
-            if (st == QIL_OK) st = qil_ctx_alloc(ctx, (size_t)(r * Pc) * e, &SV);
-            if (st == QIL_OK) st = qil_dev_gemm(ctx, odt, odt == QIL_C64 ? 2 : 1, 0, r, Pc, rows, Y, rows, theta, rows, SV, r);
-            if (st != QIL_OK) return cleanup(st);
-            U = Y;
-        } else {
-            st = svd_trunc_dev(ctx, odt, rows, Pc, theta, rows, zip_cutoff, true, zip_maxdim, 1, 2, &r, &U, &SV, nullptr);
-            if (st != QIL_OK) return cleanup(st);
+        lap("gauge + zip-up");
+        // ---- 2. variational sweep right to left
+        void* Renv = nullptr;                       // [(beta, b), r']
+        int rp = 1;
+        QIL_TRY(upload_small(scratch, one, e / sizeof(double), &Renv));
+        for (int64_t i = N - 1; i >= 0; --i) {
+            const int Dl = (int)W->dims[(size_t)i], Dr = (int)W->dims[(size_t)i + 1];
+            const int cl = (int)phi->dims[(size_t)i], cr = (int)phi->dims[(size_t)i + 1];
+            const int R = Rdim[(size_t)i];
+            void *theta = nullptr, *T = nullptr;
+            QIL_TRY(theta_of(i, &theta));
+            QIL_TRY(scratch.alloc((size_t)2 * R * rp * e, &T));
+            QIL_TRY(qil_dev_gemm(ctx, odt, 0, 0, 2LL * R, rp, (int64_t)cr * Dr, theta, 2LL * R, Renv, (int64_t)cr * Dr, T, 2LL * R));
+            scratch.free(theta);
+            QIL_TRY(qil_chain_set_site(res, i, scratch.give(T), R, rp));
+            if (i == 0) break;
+            QIL_TRY(gauge_site_left(res, i, 0.0, kNoCap, true));
+            const int K = (int)res->dims[(size_t)i];
+            void *Y = nullptr, *Z = nullptr, *Rn = nullptr;
+            QIL_TRY(scratch.alloc((size_t)2 * cl * Dr * rp * e, &Y));
+            QIL_TRY(qil_dev_gemm(ctx, odt, 0, 0, 2LL * cl, (int64_t)Dr * rp, cr, Asite[(size_t)i], 2LL * cl, Renv, cr, Y, 2LL * cl));
+            QIL_TRY(scratch.alloc((size_t)cl * Dl * 2 * rp * e, &Z));
+            if (odt == QIL_F64)
+                QIL_TRY((qil_klaunch<fit_env_stage_k<double>>(ctx, dim3(nblk((long long)cl * Dl * 2 * rp)), dim3(256), 0, (const double*)Y, (const double*)Wsite[(size_t)i], (double*)Z, cl, Dl, Dr, rp)));
+            else
+                QIL_TRY((qil_klaunch<fit_env_stage_k<c64>>(ctx, dim3(nblk((long long)cl * Dl * 2 * rp)), dim3(256), 0, (const c64*)Y, (const c64*)Wsite[(size_t)i], (c64*)Z, cl, Dl, Dr, rp)));
+            QIL_TRY(scratch.alloc((size_t)cl * Dl * K * e, &Rn));
+            // R_{i-1}[(alpha, a), k] = sum_{s, r'} Z[(alpha, a), (s, r')] conj(phi_i[k, (s, r')])
+            QIL_TRY(qil_dev_gemm(ctx, odt, 0, 2, (int64_t)cl * Dl, K, 2LL * rp, Z, (int64_t)cl * Dl, res->site[(size_t)i], K, Rn,
+                                 (int64_t)cl * Dl));
+            scratch.free(Y);
+            scratch.free(Z);
+            scratch.free(Renv);
+            Renv = Rn;
+            rp = K;
         }
-        drop(theta);
-        qil_chain_adopt(res, i, U);             // [R, s, r]
-        res->dims[(size_t)i] = R;
-        res->dims[(size_t)i + 1] = r;
-        tmp.push_back(SV);
-        Lenv[(size_t)i + 1] = SV;               // [r, (beta, b)] == L[r, alpha, a] of the next site
-        Rdim[(size_t)i + 1] = (int)r;
+        lap("variational sweep");
     }
-    lap("gauge + zip-up");
-    // ---- 2. variational sweep right to left
-    void* Renv = nullptr;                       // [(beta, b), r']
-    int rp = 1;
-    if ((st = one(&Renv)) != QIL_OK) return cleanup(st);
-    for (int64_t i = N - 1; i >= 0; --i) {
-        const int Dl = (int)W->dims[(size_t)i], Dr = (int)W->dims[(size_t)i + 1];
-        const int cl = (int)phi->dims[(size_t)i], cr = (int)phi->dims[(size_t)i + 1];
-        const int R = Rdim[(size_t)i];
-        void *theta = nullptr, *T = nullptr;
-        if ((st = theta_of(i, &theta)) != QIL_OK) return cleanup(st);
-        if ((st = take((size_t)2 * R * rp * e, &T)) != QIL_OK) return cleanup(st);
-        st = qil_dev_gemm(ctx, odt, 0, 0, 2LL * R, rp, (int64_t)cr * Dr, theta, 2LL * R, Renv, (int64_t)cr * Dr, T, 2LL * R);
-        if (st != QIL_OK) return cleanup(st);
-        drop(theta);
-        forget(T);
-        if ((st = qil_chain_set_site(res, i, T, R, rp)) != QIL_OK) return cleanup(st);
-        if (i == 0) break;
-        if ((st = gauge_site_left(res, i, 0.0, kNoCap, true)) != QIL_OK) return cleanup(st);
-        const int K = (int)res->dims[(size_t)i];
-        void *Y = nullptr, *Z = nullptr, *Rn = nullptr;
-        if ((st = take((size_t)2 * cl * Dr * rp * e, &Y)) != QIL_OK) return cleanup(st);
-        st = qil_dev_gemm(ctx, odt, 0, 0, 2LL * cl, (int64_t)Dr * rp, cr, Asite[(size_t)i], 2LL * cl, Renv, cr, Y, 2LL * cl);
-        if (st != QIL_OK) return cleanup(st);
-        if ((st = take((size_t)cl * Dl * 2 * rp * e, &Z)) != QIL_OK) return cleanup(st);
-        if (odt == QIL_F64)
-            QIL_TRY((qil_klaunch<fit_env_stage_k<double>>(ctx, dim3(nblk((long long)cl * Dl * 2 * rp)), dim3(256), 0, (const double*)Y, (const double*)Wsite[(size_t)i], (double*)Z, cl, Dl, Dr, rp)));
-        else
-            QIL_TRY((qil_klaunch<fit_env_stage_k<c64>>(ctx, dim3(nblk((long long)cl * Dl * 2 * rp)), dim3(256), 0, (const c64*)Y, (const c64*)Wsite[(size_t)i], (c64*)Z, cl, Dl, Dr, rp)));
-        if (hipGetLastError() != hipSuccess) return cleanup(qil_fail(QIL_EHIP, "apply_compress: launch failed"));
-        if ((st = take((size_t)cl * Dl * K * e, &Rn)) != QIL_OK) return cleanup(st);
-        // R_{i-1}[(alpha, a), k] = sum_{s, r'} Z[(alpha, a), (s, r')] conj(phi_i[k, (s, r')])
-        st = qil_dev_gemm(ctx, odt, 0, 2, (int64_t)cl * Dl, K, 2LL * rp, Z, (int64_t)cl * Dl, res->site[(size_t)i], K, Rn,
-                          (int64_t)cl * Dl);
-        if (st != QIL_OK) return cleanup(st);
-        drop(Y);
-        drop(Z);
-        drop(Renv);
-        Renv = Rn;
-        rp = K;
-    }
-    lap("variational sweep");
-    (void)cleanup(QIL_OK);
-    phi = nullptr;
-    tmp.clear();
     // ---- 3. exact-gauge truncation
-    st = compress_impl(res, maxdim, tol, sweeps, true);        // the variational sweep left res right-canonical
+    const int st = compress_impl(res, maxdim, tol, sweeps, true);    // the variational sweep left res right-canonical
     lap("compress!");
-    if (st != QIL_OK) return st;
-    *out = guard.release();
+    QIL_TRY(st);
+    *out = res_own.release();
     return QIL_OK;
 }
 
@@ -1293,13 +1291,12 @@ extern "C" int qil_apply_compress_batch(const qil_mpo* const* Ws, const qil_mps*
 }
 
 // Fused sum-and-truncate: compress!(sum_j w_j psi_j; maxdim, tol, sweeps) WITHOUT the direct-sum tensors of size (sum chi)^2.
-// The structure of apply_compress_on with the terms in the operator's place:
+// The structure of apply_compress_on with the terms in the operator's place, on the same steps (zip_default_cap, zip_sketch, zip_step):
 //   1. every (distinct) term is copied and brought to right-canonical gauge by exact thin QRs; the weights are the 1 x 1
 //      environments the zip-up starts from, so no term tensor is touched for them;
 //   2. zip-up left to right: term j carries C_j (r x chi_j), all of them stored concatenated as ONE r x sum(chi) array; per site
 //          theta = [C_1 A^1 | C_2 A^2 | ...]     (2r x sum(chi_right), each product into its own column slice)
-//      an orthonormal basis U of its column space (sketched on capped bonds, truncated SVD at cutoff * 1e-2 otherwise) is the
-//      provisional site and C' = U^H theta the next concatenated environment;
+//      zip_step gives the provisional site U and the next concatenated environment C' = U^H theta;
 //   3. one variational sweep right to left with the kept C's and right environments R_j (chi_j x r', stacked by rows):
 //          site_i = [C_1 ... C_nb] * rowstack(A^j R_j)        ONE GEMM over the concatenated inner dimension
 //      re-gauged by an SVD at canonicalize!'s cutoff 1e-12 (this sweep stands in for the gauge pass compress! opens with), then
@@ -1317,287 +1314,166 @@ int qil_sum_compress_impl(qil_context* ctx, const qil_mps* const* terms, int64_t
                           double tol, int sweeps, int64_t zip_maxdim, qil_mps** out) {
     const int64_t N = terms[0]->n();
     if (maxdim <= 0) maxdim = kNoCap;
-    const int64_t zip_over = 16;                     // the oversampling of apply_compress_on (see there for the evidence)
-    if (zip_maxdim <= 0) zip_maxdim = maxdim > kNoCap / 2 ? kNoCap : std::max(maxdim + zip_over, maxdim + (maxdim + 7) / 8);
+    if (zip_maxdim <= 0) zip_maxdim = zip_default_cap(maxdim);
     const double cutoff = tol * tol / ((double)(N - 1) * sweeps);
     const double zip_cutoff = cutoff * 1e-2;
     const size_t e = qil_elem_size(odt);
-    std::vector<qil_mps*> own;                       // the distinct right-canonical copies (handles: destroyed explicitly)
-    std::vector<const qil_mps*> seen;
-    std::vector<const qil_mps*> phi((size_t)nb, nullptr);
-    qil_mps* res = nullptr;
-    std::vector<void*> tmp;                          // every pool block this call owns outside a handle
-    auto cleanup = [&](int code) {
-        for (void* p : tmp) qil_ctx_free(ctx, p);
-        tmp.clear();
-        for (qil_mps* c : own) qil_mps_destroy(c);
-        own.clear();
-        return code;
-    };
-    auto take = [&](size_t bytes, void** p) {
-        int s = qil_ctx_alloc(ctx, bytes, p);
-        if (s == QIL_OK) tmp.push_back(*p);
-        return s;
-    };
-    auto forget = [&](void* p) {
-        for (size_t t = tmp.size(); t-- > 0;)
-            if (tmp[t] == p) {
-                tmp.erase(tmp.begin() + (long)t);
-                break;
-            }
-    };
-    auto drop = [&](void* p) {
-        forget(p);
-        qil_ctx_free(ctx, p);
-    };
-    int st = QIL_OK;
-    // `literal`: every concatenated bond of the operands fits under the cap.  Then the sweep of step 3 takes the exact route's
-    // gauge step at every site (see there), which needs neither the zip-up nor gauged terms: the operands are read as they are,
-    // and the decisions are those of compress! on the direct sum, bond for bond.
-    bool literal = true;
-    for (int64_t i = 1; i < N && literal; ++i) {
-        int64_t sc = 0;
-        for (int64_t j = 0; j < nb; ++j) sc += terms[j]->dims[(size_t)i];
-        literal = sc <= zip_maxdim;
-    }
-    // ---- 1. gauge (a repeated handle is copied once)
-    for (int64_t j = 0; j < nb; ++j) {
-        if (literal && (odt == QIL_F64 || terms[j]->dtype == QIL_C64)) {
-            phi[(size_t)j] = terms[j];
-            continue;
+    const int nre = odt == QIL_C64 ? 2 : 1;          // doubles per element
+    // the weights carry the amplitudes
+    qil_result_guard<qil_mps> res_own(qil_mps_empty(ctx, N, odt, terms[0]->paired, terms[0]->site_ids.data(), 1.0));
+    qil_mps* const res = res_own.p;
+    {   // steps 1 to 3; the gauged copies and every temporary are gone before step 4
+        std::vector<qil_result_guard<qil_mps>> own;      // the distinct right-canonical copies
+        std::vector<const qil_mps*> seen;
+        std::vector<const qil_mps*> phi((size_t)nb, nullptr);
+        qil_scratch scratch(ctx);                            // every pool block this call owns outside a handle
+        // `literal`: every concatenated bond of the operands fits under the cap.  Then the sweep of step 3 takes the exact route's
+        // gauge step at every site (see there), which needs neither the zip-up nor gauged terms: the operands are read as they are,
+        // and the decisions are those of compress! on the direct sum, bond for bond.
+        bool literal = true;
+        for (int64_t i = 1; i < N && literal; ++i) {
+            int64_t sc = 0;
+            for (int64_t j = 0; j < nb; ++j) sc += terms[j]->dims[(size_t)i];
+            literal = sc <= zip_maxdim;
         }
-        for (size_t t = 0; t < seen.size(); ++t)
-            if (seen[t] == terms[j]) phi[(size_t)j] = own[t];
-        if (phi[(size_t)j]) continue;
-        qil_mps* c = nullptr;
-        if ((st = qil_mps_clone_to(ctx, terms[j], &c)) != QIL_OK) {
-            if (c) qil_mps_destroy(c);
-            return cleanup(st);
-        }
-        own.push_back(c);
-        seen.push_back(terms[j]);
-        phi[(size_t)j] = c;
-        if (!literal && (st = canonicalize_impl(c, QIL_DIR_LEFT, 0, 0.0, kNoCap, true)) != QIL_OK) return cleanup(st);
-        if (odt == QIL_C64 && c->dtype == QIL_F64) {           // a real term of a complex sum is widened once: KB..MB
-            for (int64_t i = 0; i < N; ++i) {
-                const long long ne = c->site_elems(i);
-                void* p = nullptr;
-                if ((st = qil_ctx_alloc(ctx, (size_t)ne * e, &p)) != QIL_OK) return cleanup(st);
-                st = qil_klaunch<widen_f64_k>(ctx, dim3(nblk(ne)), dim3(256), 0, (const double*)c->site[(size_t)i], (c64*)p, ne);
-                if (st == QIL_OK) st = qil_chain_set_site(c, i, p, c->dims[(size_t)i], c->dims[(size_t)i + 1]);
-                if (st != QIL_OK) return cleanup(st);
-            }
-            c->dtype = QIL_C64;
-        }
-    }
-    // offsets of the terms inside every concatenated bond (the edge bonds included: nb entries of 1)
-    std::vector<std::vector<int64_t>> off((size_t)N + 1, std::vector<int64_t>((size_t)nb + 1, 0));
-    int64_t maxbond = 1, om_ld = 1;
-    for (int64_t i = 0; i <= N; ++i) {
+        // ---- 1. gauge (a repeated handle is copied once)
         for (int64_t j = 0; j < nb; ++j) {
-            off[(size_t)i][(size_t)j + 1] = off[(size_t)i][(size_t)j] + phi[(size_t)j]->dims[(size_t)i];
-            maxbond = std::max(maxbond, phi[(size_t)j]->dims[(size_t)i]);
-        }
-        if (i >= 1 && i < N) om_ld = std::max(om_ld, off[(size_t)i][(size_t)nb]);
-    }
-    auto sig = [&](int64_t i) { return off[(size_t)i][(size_t)nb]; };
-    // QIL_SUM_NO_GROUPED: the per-term GEMMs everywhere (A/B of the grouped kernel, tools/_sum_time.py)
-    const bool grouped = maxbond <= kSumGroupedMaxBond && qil_dev_gemm_grouped_fits((size_t)(2 * nb)) && !getenv("QIL_SUM_NO_GROUPED");
-    auto at = [&](const void* base, int64_t elems) { return (void*)((char*)base + (size_t)elems * e); };
-    std::vector<qil_gemm_problem> probs;
-    auto run_products = [&](int64_t side) {          // one launch for all terms, or one GEMM per term
-        if (grouped && side <= kSumGroupedMaxSide) return qil_dev_gemm_grouped(ctx, odt, probs);
-        for (const qil_gemm_problem& p : probs)
-            QIL_TRY(qil_dev_gemm(ctx, odt, 0, 0, p.m, p.n, p.k, p.A, p.lda, p.B, p.ldb, p.C, p.ldc));
-        return (int)QIL_OK;
-    };
-    auto upload = [&](const std::vector<double>& host, void** p) {     // nb small numbers; the source dies with this frame
-        int s2 = take(host.size() * sizeof(double), p);
-        if (s2 == QIL_OK && hipMemcpyAsync(*p, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, qil_stream(ctx)) != hipSuccess)
-            s2 = qil_fail(QIL_EHIP, "mps_sum_compress: upload failed");
-        if (s2 == QIL_OK && qil_stream_sync(ctx) != hipSuccess) s2 = qil_fail(QIL_EHIP, "mps_sum_compress: sync failed");
-        return s2;
-    };
-    res = new qil_mps();
-    qil_result_guard<qil_mps> guard(res);            // a failing return below destroys the result
-    qil_chain_bind(res, ctx);
-    res->dtype = odt;
-    res->paired = terms[0]->paired;
-    res->phys_rank = 1;
-    res->dims.assign((size_t)N + 1, 1);
-    res->site.assign((size_t)N, nullptr);
-    res->site_ids = terms[0]->site_ids;
-    res->amplitude = 1.0;                            // the weights carry the amplitudes
-    // sketch matrix for capped bonds (one for the whole call: any sub-block of a Gaussian matrix is Gaussian)
-    void* Om = nullptr;
-    if (zip_maxdim < om_ld) {
-        if ((st = take((size_t)(om_ld * zip_maxdim) * e, &Om)) != QIL_OK) return cleanup(st);
-        if ((st = qil_dev_fill_normal(ctx, odt, Om, om_ld * zip_maxdim, 0x51b0e7c5ull, 1.0)) != QIL_OK) return cleanup(st);
-    }
-    // ---- 2. zip-up, keeping the concatenated environments C_i (Rdim[i] x sig(i)); C_0 = the row of weights
-    std::vector<void*> Ckeep((size_t)N, nullptr);
-    std::vector<int64_t> Rdim((size_t)N + 1, 1);
-    {
-        std::vector<double> h((size_t)nb * (odt == QIL_C64 ? 2 : 1));
-        for (int64_t j = 0; j < nb; ++j) {
-            if (odt == QIL_C64) {
-                h[(size_t)(2 * j)] = w[2 * j];
-                h[(size_t)(2 * j + 1)] = w[2 * j + 1];
-            } else {
-                h[(size_t)j] = w[2 * j];
+            if (literal && (odt == QIL_F64 || terms[j]->dtype == QIL_C64)) {
+                phi[(size_t)j] = terms[j];
+                continue;
+            }
+            for (size_t t = 0; t < seen.size(); ++t)
+                if (seen[t] == terms[j]) phi[(size_t)j] = own[t].p;
+            if (phi[(size_t)j]) continue;
+            own.emplace_back(nullptr);
+            QIL_TRY(qil_mps_clone_to(ctx, terms[j], &own.back().p));
+            qil_mps* const c = own.back().p;
+            seen.push_back(terms[j]);
+            phi[(size_t)j] = c;
+            if (!literal) QIL_TRY(canonicalize_impl(c, QIL_DIR_LEFT, 0, 0.0, kNoCap, true));
+            if (odt == QIL_C64 && c->dtype == QIL_F64) {
+                for (int64_t i = 0; i < N; ++i) {
+                    void* p = nullptr;
+                    QIL_TRY(widen_site(ctx, c->site[(size_t)i], c->site_elems(i), &p));
+                    QIL_TRY(qil_chain_set_site(c, i, p, c->dims[(size_t)i], c->dims[(size_t)i + 1]));
+                }
+                c->dtype = QIL_C64;
             }
         }
-        if ((st = upload(h, &Ckeep[0])) != QIL_OK) return cleanup(st);
-    }
-    for (int64_t i = 0; i + 1 < N && !literal; ++i) {   // the last site is formed by the variational sweep
-        const int64_t R = Rdim[(size_t)i], rows = 2 * R, Pc = sig(i + 1);
-        void* theta = nullptr;
-        if ((st = take((size_t)(rows * Pc) * e, &theta)) != QIL_OK) return cleanup(st);
-        probs.clear();
-        for (int64_t j = 0; j < nb; ++j) {           // theta[:, slice j] = C_j (R x chi_l) A^j (chi_l x 2 chi_r), layout [r, s, beta]
-            const qil_mps* t = phi[(size_t)j];
-            const int64_t cl = t->dims[(size_t)i], cr = t->dims[(size_t)i + 1];
-            probs.push_back(qil_gemm_problem{at(Ckeep[(size_t)i], R * off[(size_t)i][(size_t)j]), t->site[(size_t)i],
-                                             at(theta, rows * off[(size_t)i + 1][(size_t)j]), (int)R, (int)(2 * cr), (int)cl,
-                                             (int)R, (int)cl, (int)R, 0, 0});
+        // offsets of the terms inside every concatenated bond (the edge bonds included: nb entries of 1)
+        std::vector<std::vector<int64_t>> off((size_t)N + 1, std::vector<int64_t>((size_t)nb + 1, 0));
+        int64_t maxbond = 1, om_ld = 1;
+        for (int64_t i = 0; i <= N; ++i) {
+            for (int64_t j = 0; j < nb; ++j) {
+                off[(size_t)i][(size_t)j + 1] = off[(size_t)i][(size_t)j] + phi[(size_t)j]->dims[(size_t)i];
+                maxbond = std::max(maxbond, phi[(size_t)j]->dims[(size_t)i]);
+            }
+            if (i >= 1 && i < N) om_ld = std::max(om_ld, off[(size_t)i][(size_t)nb]);
         }
-        if ((st = run_products(R)) != QIL_OK) return cleanup(st);
-        int64_t r = 0;
-        void *U = nullptr, *SV = nullptr;
-        if (zip_maxdim < std::min(rows, Pc)) {       // capped bond: orthonormal basis of theta Omega (see apply_compress_on)
-            r = zip_maxdim;
-            void* Y = nullptr;
-            if ((st = qil_ctx_alloc(ctx, (size_t)(rows * r) * e, &Y)) != QIL_OK) return cleanup(st);
-            st = qil_dev_gemm(ctx, odt, 0, 0, rows, r, Pc, theta, rows, Om, om_ld, Y, rows);
-            if (st == QIL_OK) st = qil_dev_qr_positive(ctx, odt, rows, r, Y, rows, nullptr, 0, true);
-            if (st == QIL_OK) st = qil_ctx_alloc(ctx, (size_t)(r * Pc) * e, &SV);
-            if (st == QIL_OK) st = qil_dev_gemm(ctx, odt, odt == QIL_C64 ? 2 : 1, 0, r, Pc, rows, Y, rows, theta, rows, SV, r);
-            if (st != QIL_OK) return cleanup(st);
-            U = Y;
-        } else {
-            st = svd_trunc_dev(ctx, odt, rows, Pc, theta, rows, zip_cutoff, true, zip_maxdim, 1, 2, &r, &U, &SV, nullptr);
-            if (st != QIL_OK) return cleanup(st);
+        auto sig = [&](int64_t i) { return off[(size_t)i][(size_t)nb]; };
+        // QIL_SUM_NO_GROUPED: the per-term GEMMs everywhere (A/B of the grouped kernel, tools/_sum_time.py)
+        const bool grouped = maxbond <= kSumGroupedMaxBond && qil_dev_gemm_grouped_fits((size_t)(2 * nb)) && !getenv("QIL_SUM_NO_GROUPED");
+        auto at = [&](const void* base, int64_t elems) { return (void*)((char*)base + (size_t)elems * e); };
+        std::vector<qil_gemm_problem> probs;
+        auto run_products = [&](int64_t side) -> int {   // one launch for all terms, or one GEMM per term
+            if (grouped && side <= kSumGroupedMaxSide) return qil_dev_gemm_grouped(ctx, odt, probs);
+            for (const qil_gemm_problem& p : probs)
+                QIL_TRY(qil_dev_gemm(ctx, odt, 0, 0, p.m, p.n, p.k, p.A, p.lda, p.B, p.ldb, p.C, p.ldc));
+            return QIL_OK;
+        };
+        void* Om = nullptr;
+        QIL_TRY(zip_sketch(scratch, odt, om_ld, zip_maxdim, &Om));
+        // ---- 2. zip-up, keeping the concatenated environments C_i (Rdim[i] x sig(i)); C_0 = the row of weights
+        std::vector<void*> Ckeep((size_t)N, nullptr);
+        std::vector<int64_t> Rdim((size_t)N + 1, 1);
+        {
+            std::vector<double> h((size_t)(nb * nre));
+            for (int64_t j = 0; j < nb; ++j)
+                for (int c = 0; c < nre; ++c) h[(size_t)(nre * j + c)] = w[2 * j + c];
+            QIL_TRY(upload_small(scratch, h.data(), h.size(), &Ckeep[0]));
         }
-        drop(theta);
-        qil_chain_adopt(res, i, U);                  // [R, s, r]
-        res->dims[(size_t)i] = R;
-        res->dims[(size_t)i + 1] = r;
-        tmp.push_back(SV);
-        Ckeep[(size_t)i + 1] = SV;                   // [r, sig(i + 1)]: the C_j of the next site, concatenated
-        Rdim[(size_t)i + 1] = r;
-    }
-    // ---- 3. variational sweep right to left; Rcat = row stack of the R_j (sig(i + 1) x rp)
-    void* Rcat = nullptr;
-    int64_t rp = 1;
-    {
-        std::vector<double> h((size_t)nb * (odt == QIL_C64 ? 2 : 1), 0.0);
-        for (int64_t j = 0; j < nb; ++j) h[(size_t)(odt == QIL_C64 ? 2 * j : j)] = 1.0;
-        if ((st = upload(h, &Rcat)) != QIL_OK) return cleanup(st);
-    }
-    for (int64_t i = N - 1; i >= 0; --i) {
-        const int64_t R = Rdim[(size_t)i], Sl = sig(i), Sr = sig(i + 1);
-        void *AR = nullptr, *T = nullptr;
-        if ((st = take((size_t)(Sl * 2 * rp) * e, &AR)) != QIL_OK) return cleanup(st);
-        probs.clear();
-        for (int64_t j = 0; j < nb; ++j) {           // AR[rows of j, (s, r')] = A^j[:, s, :] (chi_l x chi_r) R_j (chi_r x rp)
-            const qil_mps* t = phi[(size_t)j];
-            const int64_t cl = t->dims[(size_t)i], cr = t->dims[(size_t)i + 1];
-            for (int s = 0; s < 2; ++s)
-                probs.push_back(qil_gemm_problem{at(t->site[(size_t)i], cl * s), at(Rcat, off[(size_t)i + 1][(size_t)j]),
-                                                 at(AR, off[(size_t)i][(size_t)j] + Sl * s), (int)cl, (int)rp, (int)cr,
-                                                 (int)(2 * cl), (int)Sr, (int)(2 * Sl), 0, 0});
+        for (int64_t i = 0; i + 1 < N && !literal; ++i) {   // the last site is formed by the variational sweep
+            const int64_t R = Rdim[(size_t)i], rows = 2 * R, Pc = sig(i + 1);
+            void* theta = nullptr;
+            QIL_TRY(scratch.alloc((size_t)(rows * Pc) * e, &theta));
+            probs.clear();
+            for (int64_t j = 0; j < nb; ++j) {           // theta[:, slice j] = C_j (R x chi_l) A^j (chi_l x 2 chi_r), layout [r, s, beta]
+                const qil_mps* t = phi[(size_t)j];
+                const int64_t cl = t->dims[(size_t)i], cr = t->dims[(size_t)i + 1];
+                probs.push_back(qil_gemm_problem{at(Ckeep[(size_t)i], R * off[(size_t)i][(size_t)j]), t->site[(size_t)i],
+                                                 at(theta, rows * off[(size_t)i + 1][(size_t)j]), (int)R, (int)(2 * cr), (int)cl,
+                                                 (int)R, (int)cl, (int)R, 0, 0});
+            }
+            QIL_TRY(run_products(R));
+            int64_t r = 0;
+            void *U = nullptr, *SV = nullptr;
+            QIL_TRY(zip_step(ctx, odt, rows, Pc, theta, zip_maxdim, zip_cutoff, Om, om_ld, &r, &U, &SV));
+            scratch.free(theta);
+            qil_chain_adopt(res, i, U);                  // [R, s, r]
+            res->dims[(size_t)i] = R;
+            res->dims[(size_t)i + 1] = r;
+            Ckeep[(size_t)i + 1] = scratch.own(SV);          // [r, sig(i + 1)]: the C_j of the next site, concatenated
+            Rdim[(size_t)i + 1] = r;
         }
-        if ((st = run_products(rp)) != QIL_OK) return cleanup(st);
-        if (i > 0 && Sl <= zip_maxdim) {
-            // The stacked operand is no larger than a capped site: take the gauge step of the exact route literally.  AR IS the
-            // matrix canonicalize!(:left) factors at this bond of the direct sum (rows: the concatenated left bond, columns: an
-            // orthonormal basis of everything to the right), so its SVD at that pass's cutoff 1e-12 makes the same decision:
-            // site_i = V^H, and U S is the stack of the new R_j.  Uncapped calls and small sums run entirely through here.
+        // ---- 3. variational sweep right to left; Rcat = row stack of the R_j (sig(i + 1) x rp)
+        void* Rcat = nullptr;
+        int64_t rp = 1;
+        {
+            std::vector<double> h((size_t)(nb * nre), 0.0);
+            for (int64_t j = 0; j < nb; ++j) h[(size_t)(nre * j)] = 1.0;
+            QIL_TRY(upload_small(scratch, h.data(), h.size(), &Rcat));
+        }
+        for (int64_t i = N - 1; i >= 0; --i) {
+            const int64_t R = Rdim[(size_t)i], Sl = sig(i), Sr = sig(i + 1);
+            void *AR = nullptr, *T = nullptr;
+            QIL_TRY(scratch.alloc((size_t)(Sl * 2 * rp) * e, &AR));
+            probs.clear();
+            for (int64_t j = 0; j < nb; ++j) {           // AR[rows of j, (s, r')] = A^j[:, s, :] (chi_l x chi_r) R_j (chi_r x rp)
+                const qil_mps* t = phi[(size_t)j];
+                const int64_t cl = t->dims[(size_t)i], cr = t->dims[(size_t)i + 1];
+                for (int s = 0; s < 2; ++s)
+                    probs.push_back(qil_gemm_problem{at(t->site[(size_t)i], cl * s), at(Rcat, off[(size_t)i + 1][(size_t)j]),
+                                                     at(AR, off[(size_t)i][(size_t)j] + Sl * s), (int)cl, (int)rp, (int)cr,
+                                                     (int)(2 * cl), (int)Sr, (int)(2 * Sl), 0, 0});
+            }
+            QIL_TRY(run_products(rp));
+            void* Rn = nullptr;                          // the stack of the new R_j
             int64_t K = 0;
-            void *US = nullptr, *Vh = nullptr;
-            if ((st = svd_trunc_dev(ctx, odt, Sl, 2 * rp, AR, Sl, 1e-12, true, kNoCap, 1, 1, &K, &US, &Vh, nullptr)) != QIL_OK)
-                return cleanup(st);
-            tmp.push_back(US);
-            if ((st = qil_chain_set_site(res, i, Vh, K, rp)) != QIL_OK) return cleanup(st);
-            drop(AR);
-            drop(Rcat);
-            drop(Ckeep[(size_t)i]);
+            if (i > 0 && Sl <= zip_maxdim) {
+                // The stacked operand is no larger than a capped site: take the gauge step of the exact route literally.  AR IS the
+                // matrix canonicalize!(:left) factors at this bond of the direct sum (rows: the concatenated left bond, columns: an
+                // orthonormal basis of everything to the right), so its SVD at that pass's cutoff 1e-12 makes the same decision:
+                // site_i = V^H, and U S is the stack of the new R_j.  Uncapped calls and small sums run entirely through here.
+                void* Vh = nullptr;
+                QIL_TRY(svd_trunc_dev(ctx, odt, Sl, 2 * rp, AR, Sl, 1e-12, true, kNoCap, 1, 1, &K, &Rn, &Vh, nullptr));
+                scratch.own(Rn);
+                QIL_TRY(qil_chain_set_site(res, i, Vh, K, rp));
+            } else {
+                QIL_TRY(scratch.alloc((size_t)(2 * R * rp) * e, &T));
+                QIL_TRY(qil_dev_gemm(ctx, odt, 0, 0, R, 2 * rp, Sl, Ckeep[(size_t)i], R, AR, Sl, T, R));
+                QIL_TRY(qil_chain_set_site(res, i, scratch.give(T), R, rp));
+                if (i == 0) break;
+                // This sweep is the right-to-left gauge pass compress! opens with (mps.jl:923, canonicalize!(:left) at its fixed
+                // cutoff 1e-12), so it carries that cutoff: site i is the orthogonality centre here, its singular values are the
+                // bond's Schmidt values, and what the exact route's gauge pass drops from the direct sum is dropped here too.
+                // compress_impl below is then told the state is right-canonical and skips the pass.
+                QIL_TRY(gauge_site_left(res, i, 1e-12, kNoCap, false));
+                K = res->dims[(size_t)i];
+                QIL_TRY(scratch.alloc((size_t)(Sl * K) * e, &Rn));
+                // R_j'[alpha, k] = sum_{s, r'} AR[alpha, (s, r')] conj(site_i[k, (s, r')]) for all terms at once
+                QIL_TRY(qil_dev_gemm(ctx, odt, 0, 2, Sl, K, 2 * rp, AR, Sl, res->site[(size_t)i], K, Rn, Sl));
+            }
+            scratch.free(AR);
+            scratch.free(Rcat);
+            scratch.free(Ckeep[(size_t)i]);                  // (none on the literal route past site 0)
             Ckeep[(size_t)i] = nullptr;
-            Rcat = US;
+            Rcat = Rn;
             rp = K;
-            continue;
         }
-        if ((st = take((size_t)(2 * R * rp) * e, &T)) != QIL_OK) return cleanup(st);
-        st = qil_dev_gemm(ctx, odt, 0, 0, R, 2 * rp, Sl, Ckeep[(size_t)i], R, AR, Sl, T, R);
-        if (st != QIL_OK) return cleanup(st);
-        forget(T);
-        if ((st = qil_chain_set_site(res, i, T, R, rp)) != QIL_OK) return cleanup(st);
-        if (i == 0) break;
-        // This sweep is the right-to-left gauge pass compress! opens with (mps.jl:923, canonicalize!(:left) at its fixed cutoff
-        // 1e-12), so it carries that cutoff: site i is the orthogonality centre here, its singular values are the bond's
-        // Schmidt values, and what the exact route's gauge pass drops from the direct sum is dropped here too.  compress_impl
-        // below is then told the state is right-canonical and skips the pass.
-        if ((st = gauge_site_left(res, i, 1e-12, kNoCap, false)) != QIL_OK) return cleanup(st);
-        const int64_t K = res->dims[(size_t)i];
-        void* Rn = nullptr;
-        if ((st = take((size_t)(Sl * K) * e, &Rn)) != QIL_OK) return cleanup(st);
-        // R_j'[alpha, k] = sum_{s, r'} AR[alpha, (s, r')] conj(site_i[k, (s, r')]) for all terms at once
-        st = qil_dev_gemm(ctx, odt, 0, 2, Sl, K, 2 * rp, AR, Sl, res->site[(size_t)i], K, Rn, Sl);
-        if (st != QIL_OK) return cleanup(st);
-        drop(AR);
-        drop(Rcat);
-        drop(Ckeep[(size_t)i]);
-        Ckeep[(size_t)i] = nullptr;
-        Rcat = Rn;
-        rp = K;
     }
-    (void)cleanup(QIL_OK);
     // ---- 4. exact-gauge truncation
     QIL_TRY(compress_impl(res, maxdim, tol, sweeps, true));    // the variational sweep left res right-canonical
-    *out = guard.release();
-    return QIL_OK;
-}
-
-static int compress_impl(qil_mps* psi, int64_t maxdim, double tol, int sweeps, bool right_canonical);
-
-extern "C" int qil_compress(qil_mps* psi, int64_t maxdim, double tol, int sweeps) {
-    return compress_impl(psi, maxdim, tol, sweeps, false);
-}
-
-// right_canonical: the caller guarantees every site but the first is a right isometry (the fused apply-and-truncate
-// after its variational sweep).  canonicalize!(:left) of such a state can neither truncate nor change anything but the
-// gauge (all its singular values are 1), so it is not run.
-static int compress_impl(qil_mps* psi, int64_t maxdim, double tol, int sweeps, bool right_canonical) {
-    QIL_REQUIRE(psi, QIL_EINVAL_ARG, "compress!: null handle");
-    const int64_t N = psi->n();
-    QIL_REQUIRE(N >= 2, QIL_EDOMAIN, "SignalMPS must have at least 2 sites.");   // mps.jl:918
-    QIL_REQUIRE(sweeps >= 1, QIL_EINVAL_ARG, "compress!: sweeps must be >= 1");
-    qil_context* ctx = psi->ctx;
-    QIL_TRY(qil_ctx_activate(ctx));
-    qil_call_scope call_scope(ctx);
-    const int dt = psi->dtype;
-    const double cutoff = tol * tol / ((double)(N - 1) * sweeps);               // mps.jl:920
-    if (!right_canonical) QIL_TRY(canonicalize_impl(psi, QIL_DIR_LEFT, 0, 1e-12, kNoCap));            // mps.jl:923
-    // The reference truncates the two-site tensor psi[j] psi[j+1] (mps.jl:929, :946).  In canonical gauge --
-    // which every step of the sweep maintains -- that tensor has the same singular values and the same kept
-    // subspace as the single site next to the orthogonality centre (its neighbour is an isometry), so each
-    // sweep is run as a truncating gauge sweep on one-site matrices: (2 chi_l x chi) instead of
-    // (2 chi_l x 2 chi_r), no theta product, and the Jacobi SVD rotates half as many columns.
-    for (int sw = 0; sw < sweeps; ++sw) {
-        QIL_TRY(canonicalize_impl(psi, QIL_DIR_RIGHT, 0, cutoff, maxdim));      // L -> R: U | S V   (mps.jl:927-942)
-        QIL_TRY(canonicalize_impl(psi, QIL_DIR_LEFT, 0, cutoff, maxdim));       // R -> L: U S | V   (mps.jl:944-959)
-    }
-    // mps.jl:963 re-gauges once more (canonicalize!(:left), cutoff 1e-12).  The sweep that just ended left every site
-    // but the first an isometry (all its singular values are 1), so that pass can neither truncate nor change anything
-    // but the gauge -- it is not run.
-    double nrm = 0;
-    QIL_TRY(qil_norm(psi, &nrm));                                               // mps.jl:967-971
-    if (nrm != 0) {
-        psi->amplitude *= nrm;
-        const double inv = 1.0 / nrm;
-        std::vector<double> s((size_t)psi->dims[1], inv);
-        QIL_TRY(qil_dev_scale(ctx, dt, 1, 2 * psi->dims[0], psi->dims[1], psi->site[0], 2 * psi->dims[0], s.data()));
-    }
+    *out = res_own.release();
     return QIL_OK;
 }
 
@@ -1724,48 +1600,32 @@ extern "C" int qil_signal_ztmps(qil_context* ctx, const void* x, int64_t len, in
     QIL_REQUIRE(ctx && out, QIL_EINVAL_ARG, "signal_ztmps: null argument");
     qil_call_scope call_scope(ctx);
     EncodeParams P{method, cutoff, maxdim <= 0 ? kNoCap : maxdim, k, p, q, seed, mindim < 1 ? 1 : mindim};
-    qil_mps* sig = nullptr;
-    QIL_TRY(signal_mps_impl(ctx, x, len, dtype, P, &sig));                        // SignalConverters.jl:251
+    qil_result_guard<qil_mps> sig_own(nullptr);       // gone on every return: only zt leaves the call
+    QIL_TRY(signal_mps_impl(ctx, x, len, dtype, P, &sig_own.p));                  // SignalConverters.jl:251
+    const qil_mps* const sig = sig_own.p;
     const int64_t n = sig->n();
     const size_t e = qil_elem_size(dtype);
-    qil_mps* zt = new qil_mps();
-    qil_chain_bind(zt, ctx);
-    zt->dtype = dtype;
-    zt->paired = 1;
-    zt->phys_rank = 1;
-    zt->dims.assign((size_t)(2 * n) + 1, 1);
-    zt->site.assign((size_t)(2 * n), nullptr);
-    zt->site_ids.resize((size_t)(2 * n));
-    for (int64_t i = 0; i < 2 * n; ++i) zt->site_ids[(size_t)i] = i + 1;
-    zt->amplitude = sig->amplitude;
-    int status = QIL_OK;
-    for (int64_t i = 0; i < n && status == QIL_OK; ++i) {                          // :261-276
+    qil_result_guard<qil_mps> zt_own(qil_mps_empty(ctx, 2 * n, dtype, 1, nullptr, sig->amplitude));
+    qil_mps* const zt = zt_own.p;
+    for (int64_t i = 0; i < n; ++i) {                                             // :261-276
         const int64_t cl = sig->dims[(size_t)i], cr = sig->dims[(size_t)i + 1];
         void* T = nullptr;
-        status = qil_ctx_alloc(ctx, (size_t)(4 * cl * cr) * e, &T);
-        if (status != QIL_OK) break;
+        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(4 * cl * cr) * e, &T));
         if (dtype == QIL_C64)
             QIL_TRY((qil_klaunch<fuse_delta_k<c64>>(ctx, dim3(nblk(4 * cl * cr)), dim3(256), 0, (const c64*)sig->site[(size_t)i], (int)cl, (int)cr, (c64*)T)));
         else
             QIL_TRY((qil_klaunch<fuse_delta_k<double>>(ctx, dim3(nblk(4 * cl * cr)), dim3(256), 0, (const double*)sig->site[(size_t)i], (int)cl, (int)cr, (double*)T)));
         int64_t r = 0;
         void *U = nullptr, *SV = nullptr;
-        status = svd_trunc_dev(ctx, dtype, 2 * cl, 2 * cr, T, 2 * cl, P.cutoff, true, P.maxdim, 1, 2, &r, &U, &SV,
-                               nullptr);
+        QIL_TRY(svd_trunc_dev(ctx, dtype, 2 * cl, 2 * cr, T, 2 * cl, P.cutoff, true, P.maxdim, 1, 2, &r, &U, &SV, nullptr));
         qil_ctx_free(ctx, T);
-        if (status != QIL_OK) break;
         qil_chain_adopt(zt, 2 * i, U);        // core_main [b_{i-1}, s_main, c]
         qil_chain_adopt(zt, 2 * i + 1, SV);   // core_copy [c, s_copy, b_i]
         zt->dims[(size_t)(2 * i)] = cl;
         zt->dims[(size_t)(2 * i + 1)] = r;
         zt->dims[(size_t)(2 * i + 2)] = cr;
     }
-    qil_mps_destroy(sig);
-    if (status != QIL_OK) {
-        qil_mps_destroy(zt);
-        return status;
-    }
-    *out = zt;
+    *out = zt_own.release();
     return QIL_OK;
 }
 
