@@ -339,6 +339,33 @@ QIL_API int qil_mps_sum_compress(const qil_mps* const* terms, int64_t nb, const 
  * (tracing a site in |psi|^2).                                                                                            */
 QIL_API int qil_mps_restrict(const qil_mps* psi, const uint8_t* spec, qil_mps** out);
 
+/* ------------------------------------------------------------------ Born weights (no reference counterpart) */
+/* Energy read-out: out[r] = amplitude^2 * sum over the configurations x that match row r of |psi_x|^2 -- the power in a
+ * frequency band, the energy of one damping row of a z-plane, the probability that a bit is set.  spec (host, nb x n_tensors
+ * bytes, row-major, the layout of qil_coefficient_marginal_batch's bits): 0 / 1 fixes the tensor's bit, 2 TRACES the site in
+ * |psi|^2 (qil_coefficient_marginal_batch's 2 sums amplitudes; this sums their squares).  out: host, nb doubles.
+ *   chain     rho_0 = [1]; a fixed site with bit b gives rho_i = A_b^H rho_{i-1} A_b with A_b = A_i[:, b, :]; a traced site
+ *             rho_i = A_0^H rho_{i-1} A_0 + A_1^H rho_{i-1} A_1, the slice-0 term first; the result is amplitude^2 * Re rho_n.
+ *   order     (it fixes the rounding) each term is A_s^H (rho A_s).  A leading run of fixed sites keeps rho at rank one: the row
+ *             vector v <- v A_b is carried through it, as the coefficient chain does, and rho = v^H v is formed at the first
+ *             traced site.  A row with no traced site gives |coefficient|^2, a row of all 2 gives (amplitude * norm)^2.  Nothing
+ *             is rescaled along the way and the result is not clamped at 0.
+ *   rows      row r depends on (psi, row r) only, not on nb or on the other rows.
+ * Two routes, chosen from the state's bonds alone (never from the spec), so a given state always takes one route.  While every
+ * bond is <= 80 (f64) / 48 (c64) one launch serves the batch, one workgroup per row, with rho, rho A_s and the next rho in LDS
+ * and both products per slice on the f64 MFMA: three buffers of ld^2 elements and two vectors within the 160 KiB of a CU, ld =
+ * 80 (f64: 154 880 B; = 16 mod 32 against bank conflicts of the 8-byte operand reads) or 48 (c64: 112 128 B; = 0 mod 16 for the
+ * 16-byte reads); the next admissible ld, 112 / 64, does not fit.  On this route a row's result is bit-identical whether it is
+ * computed alone or in any batch, and from run to run.  Wider states go through strided-batch GEMMs with rho per row in pool
+ * memory, in chunks of rows under 64 MiB of temporaries; that route starts from rho_0 = [1] without the vector phase (the same
+ * number in exact arithmetic) and its rounding may depend on the chunk.
+ * Nothing but `out` outlives the call, also when an allocation fails midway.
+ * Errors, all before the context is activated: QIL_EINVAL_ARG ("weight_batch: null argument") for a null psi or, when nb > 0, a
+ * null spec or out; QIL_EINVAL_ARG for nb < 0; QIL_EINVAL_CONFIG for a spec value above 2 (a kept site makes no number).
+ * nb = 0 is a no-op (out is not touched); a state of norm 0 gives zeros.
+ * Left out: the lazy form on W psi (weights of W psi without forming it), weights of operators, a device-resident out.     */
+QIL_API int qil_weight_batch(const qil_mps* psi, int64_t nb, const uint8_t* spec, double* out);
+
 /* ------------------------------------------------------------------ truncation (K1, K2) */
 /* canonicalize!(psi, direction; center, cutoff=1e-12, maxdim) src/mps.jl:787-847.
  * center = 0 selects the default (N for :right, 1 for :left); 1-based otherwise.    */

@@ -19,7 +19,7 @@ using ..ApplyMPO: _as_single_site_mpo
 export DeviceMPS, DeviceMPO, to_device, to_host, signal_mps_device, marginal, mps_block, apply_compress,
     compress_mpo!, build_dt_mpo_batch, build_qft_mpo_device, build_zt_qft_chain_device, apply_coefficient_sweep, apply!, rsvd_device, svd_device,
     Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm, sample, top_k,
-    hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress, restrict
+    hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress, restrict, weight_batch
 
 const LIB = get(ENV, "QILHIP_LIB", "libqilhip.so")
 
@@ -330,6 +330,18 @@ function restrict(psi::DeviceMPS, spec::AbstractVector{<:Integer})
     p = Ref{Cint}(0)
     check(ccall((:qil_mps_is_paired, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}), r[], p))
     return finalizer(_free!, DeviceMPS(r[], psi.sites[findall(==(3), sp)], p[] != 0))
+end
+# Born weights (no reference counterpart).  specs: nb x n_tensors, 0 / 1 fixes the tensor's bit, 2 traces the site in |psi|^2;
+# returns amplitude^2 * sum |psi_x|^2 over the configurations that match each row (band power, row energy, bit probability)
+function weight_batch(psi::DeviceMPS, specs::AbstractMatrix{<:Integer})
+    nb, n = size(specs)
+    n == length(psi.sites) || throw(ArgumentError("coefficient: expected $(length(psi.sites)) entries, got $n"))
+    all(s -> 0 <= s <= 2, specs) || throw(ArgumentError("coefficient: spec value outside [0,2]"))
+    sp = Matrix{UInt8}(permutedims(specs))                                     # the ABI's row-major nb x n
+    out = Vector{Float64}(undef, nb)
+    nb == 0 && return out
+    GC.@preserve sp check(ccall((:qil_weight_batch, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{Cdouble}), psi.h, nb, sp, out))
+    return out
 end
 function mps_to_vector(psi::DeviceMPS; reverse::Bool=false)                                        # mps.jl:716
     d = Ref{Cint}(0)

@@ -18,7 +18,8 @@ from .ops import (apply, apply_compress, apply_compress_batch, mpo_compress, com
                   marginal_batch, coefficient_grid, laplace_values,
                   mps_to_vector, norm, inner, apply_norm, distance, apply_distance, sample, top_k, hadamard, hadamard_compress, diagonal_mpo, adjoint, convolve, correlate,
                   power_spectrum, linear_combination, linear_combination_compress, add, sub, scale, exponential_tensors,
-                  exponential_mps, exponential_sum, restrict, zt_row, zt_column, copy_marginal, canonicalize, compress, signal_mps, signal_ztmps, signal_mps_batch,
+                  exponential_mps, exponential_sum, restrict, zt_row, zt_column, copy_marginal, weight_batch, weight, bit_probabilities,
+                  range_weight, weight_quantiles, zt_row_weights, zt_column_weights, canonicalize, compress, signal_mps, signal_ztmps, signal_mps_batch,
                   signal_ztmps_batch, rsvd,
                   svd_trunc, gemm, gemm_plan, gemm_batched, gemm_device_time, qr_positive)
 from .builders import (build_qft_mpo, build_dt_mpo, build_zt_mpo, qft_mpo_tensors,  # noqa: F401
@@ -35,6 +36,7 @@ __all__ = [
     "hadamard", "hadamard_compress", "diagonal_mpo", "adjoint", "convolve", "correlate", "power_spectrum",
     "linear_combination", "linear_combination_compress", "add", "sub", "scale", "exponential_tensors", "exponential_mps",
     "exponential_sum", "restrict", "zt_row", "zt_column", "copy_marginal",
+    "weight_batch", "weight", "bit_probabilities", "range_weight", "weight_quantiles", "zt_row_weights", "zt_column_weights",
     "canonicalize", "compress", "signal_mps", "signal_ztmps", "signal_mps_batch", "signal_ztmps_batch", "rsvd", "svd_trunc", "gemm",
     "build_qft_mpo", "build_dt_mpo", "build_zt_mpo", "qft_mpo_tensors", "dt_mpo_tensors", "zt_mpo_tensors",
     "dt_mpo_tensors_many", "build_dt_mpo_batch", "build_zt_mpo_batch", "zt_qft_chain_tensors", "qft_mpo_device", "zt_qft_chain_device", "mpo_compress", "compress_batch", "mpo_compress_batch", "mps_block",

@@ -325,6 +325,133 @@ def copy_marginal(psi):
     return restrict(psi, _register_spec(psi, "copy_marginal", 1, None, summed=True))
 
 
+# ---------------------------------------------------------------- Born weights
+TRACE = 2
+
+
+def _weight_specs(psi, specs):
+    if not isinstance(psi, SignalMPS):
+        raise TypeError("weight: unsupported operand types")
+    n = _ntensors(psi)
+    sp = np.asarray(specs)
+    if sp.ndim != 2 or sp.shape[1] != n:
+        got = sp.shape[1] if sp.ndim == 2 else sp.shape
+        raise ValueError(f"coefficient: expected {n} entries, got {got}")
+    if sp.size and (sp.min() < 0 or sp.max() > TRACE):
+        bad = int(sp[(sp < 0) | (sp > TRACE)][0])
+        raise ValueError(f"coefficient: spec value {bad} outside [0,2]")
+    return np.ascontiguousarray(sp, dtype=np.uint8)
+
+
+def weight_batch(psi, specs):
+    """Born weights (qil_weight_batch): specs is (nb, n_tensors) of FIX0 / FIX1 / TRACE; returns the (nb,) float64 array
+    amplitude^2 * sum |psi_x|^2 over the configurations x that agree with each row on its fixed tensors -- TRACE sums a site in
+    |psi|^2, where `marginal_batch`'s 2 sums amplitudes.  A row without TRACE is abs(coefficient)^2, a row of all TRACE is
+    (amplitude * norm)^2."""
+    sp = _weight_specs(psi, specs)
+    out = np.zeros(sp.shape[0], dtype=np.float64)
+    if sp.shape[0]:
+        L.check(L.lib.qil_weight_batch(psi.handle, sp.shape[0], sp.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                       out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def weight(psi, spec):
+    """`weight_batch` of one spec, as a float."""
+    return float(weight_batch(psi, np.asarray(spec)[None])[0])
+
+
+def bit_probabilities(psi):
+    """P(bit i = 1) under |psi|^2 for every tensor i, from one call: n rows all traced but one FIX1, and the all-traced row
+    as the divisor."""
+    if not isinstance(psi, SignalMPS):
+        raise TypeError("weight: unsupported operand types")
+    n = _ntensors(psi)
+    sp = np.full((n + 1, n), TRACE, dtype=np.uint8)
+    sp[np.arange(n), np.arange(n)] = FIX1
+    w = weight_batch(psi, sp)
+    return w[:n] / w[n]
+
+
+def _dyadic_blocks(lo, hi, n):
+    """[lo, hi) as at most 2n aligned blocks (start, log2 size), in ascending order"""
+    blocks = []
+    while lo < hi:
+        k = min((lo & -lo).bit_length() - 1 if lo else n, (hi - lo).bit_length() - 1)
+        blocks.append((lo, k))
+        lo += 1 << k
+    return blocks
+
+
+def range_weight(psi, lo, hi, reverse=False):
+    """sum of |psi_x|^2 (times amplitude^2) over lo <= x < hi, x the big-endian integer of `coefficient(psi, int)` and `sample`:
+    the power in a band of a spectrum.  [lo, hi) splits into at most 2n dyadic blocks -- a fixed prefix, the rest traced --
+    whose weights come from one call.  At any n: nothing dense is formed.  reverse=True reads x with the first tensor as the
+    LEAST significant bit, the order in which a QFT output holds its bin index (as `mps_to_vector(..., reverse=True)`)."""
+    if not isinstance(psi, SignalMPS):
+        raise TypeError("weight: unsupported operand types")
+    for v in (lo, hi):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError("range_weight: the bounds must be integers")
+    n = _ntensors(psi)
+    lo, hi = int(lo), int(hi)
+    if not 0 <= lo <= hi <= 2 ** n:
+        raise ValueError(f"range_weight: need 0 <= lo <= hi <= 2^{n}, got [{lo}, {hi})")
+    if lo == hi:
+        return 0.0
+    blocks = _dyadic_blocks(lo, hi, n)
+    sp = np.full((len(blocks), n), TRACE, dtype=np.uint8)
+    for r, (start, k) in enumerate(blocks):
+        sp[r, :n - k] = [(start >> (n - 1 - i)) & 1 for i in range(n - k)]
+    return float(np.sum(weight_batch(psi, sp[:, ::-1] if reverse else sp)))
+
+
+def weight_quantiles(psi, qs, reverse=False):
+    """For every q of `qs` (each in [0, 1]) the smallest x, in the big-endian integer convention of `range_weight`, with
+    sum_{y <= x} |psi_y|^2 >= q * total: q = 0.5 is the median frequency of a spectrum, 0.95 its 95 % edge.  The bits of all
+    quantiles are found together from the top, one `weight_batch` call of len(qs) rows per tensor after one for the total.
+    reverse=True as in `range_weight`: the first tensor is the least significant bit."""
+    if not isinstance(psi, SignalMPS):
+        raise TypeError("weight: unsupported operand types")
+    q = np.atleast_1d(np.asarray(qs, dtype=np.float64))
+    if q.ndim != 1 or (q.size and not (np.all(q >= 0.0) and np.all(q <= 1.0))):
+        raise ValueError("weight_quantiles: every q must lie in [0, 1]")
+    n = _ntensors(psi)
+    if not q.size:
+        return np.zeros(0, dtype=np.int64 if n <= 62 else object)
+    target = q * weight(psi, np.full(n, TRACE, dtype=np.uint8))
+    below = np.zeros(len(q))                           # the weight of everything under the prefix found so far
+    sp = np.full((len(q), n), TRACE, dtype=np.uint8)
+    for i in (range(n - 1, -1, -1) if reverse else range(n)):
+        sp[:, i] = FIX0
+        w0 = weight_batch(psi, sp)
+        up = below + w0 < target                       # the low half does not reach the target: the bit is 1
+        sp[up, i] = FIX1
+        below[up] += w0[up]
+    xs = [int("".join(map(str, row[::-1] if reverse else row)), 2) for row in sp]
+    return np.array(xs, dtype=np.int64 if n <= 62 else object)
+
+
+def _register_weights(psi, what, fixed_offset, values):
+    if not isinstance(psi, ZTMPS):
+        raise TypeError(f"{what}: needs a ZTMPS")
+    vals = list(np.atleast_1d(np.asarray(values, dtype=object)))
+    sp = np.array([_register_spec(psi, what, fixed_offset, v) for v in vals], dtype=np.uint8).reshape(len(vals), 2 * len(psi))
+    sp[sp == FREE] = TRACE
+    return weight_batch(psi, sp)
+
+
+def zt_row_weights(psi, ls):
+    """sum_k |Z(k, l)|^2 for every l of `ls`: the energy of damping rows of a transformed ZTMPS's (k, l) grid, in one call (the
+    copy register fixed to the lsb-first bits of l as in `zt_row`, the main register traced)."""
+    return _register_weights(psi, "zt_row_weights", 1, ls)
+
+
+def zt_column_weights(psi, ks):
+    """sum_l |Z(k, l)|^2 for every k of `ks`: the energy of frequency columns, the main register fixed as in `zt_column`."""
+    return _register_weights(psi, "zt_column_weights", 0, ks)
+
+
 def _bit_block_range(v):
     """(s, a) if v == arange(2^a) << s -- every pattern of bits s .. s+a-1, all other bits zero -- else None."""
     v = np.asarray(v, dtype=np.int64)
