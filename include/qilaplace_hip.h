@@ -363,8 +363,40 @@ QIL_API int qil_mps_restrict(const qil_mps* psi, const uint8_t* spec, qil_mps** 
  * Errors, all before the context is activated: QIL_EINVAL_ARG ("weight_batch: null argument") for a null psi or, when nb > 0, a
  * null spec or out; QIL_EINVAL_ARG for nb < 0; QIL_EINVAL_CONFIG for a spec value above 2 (a kept site makes no number).
  * nb = 0 is a no-op (out is not touched); a state of norm 0 gives zeros.
- * Left out: the lazy form on W psi (weights of W psi without forming it), weights of operators, a device-resident out.     */
+ * Left out: weights of operators, a device-resident out.  The lazy form on W psi is qil_apply_weight_batch, below.        */
 QIL_API int qil_weight_batch(const qil_mps* psi, int64_t nb, const uint8_t* spec, double* out);
+/* The same read-out on a transformed state, without forming it: out[r] = amplitude^2 * sum over the configurations x that
+ * match row r of |(W psi)_x|^2, in exact arithmetic qil_weight_batch(qil_apply(W, psi), nb, spec, out).  spec and its values
+ * 0 / 1 / 2 are qil_weight_batch's; amplitude is psi's.  The operand checks are qil_apply's; the contraction runs in c64 if
+ * either operand is c64, a real operand being widened per site.  Every row has three parts, and its route through them
+ * depends on the row's spec and the operands' shapes only:
+ *   lead      the leading run of fixed sites carries the lazy row vector of qil_apply_coefficient_batch,
+ *             M'[beta, b] = sum W[a, s', bit, b] M[alpha, a] A[alpha, s', beta], two strided-batch products per site.
+ *   middle    at the row's first traced site E[alpha', a', a, alpha] = conj(M[alpha', a']) M[alpha, a]; every further site up
+ *             to the tail runs the four products of qil_apply_norm (T1 = E A, T2 = T1 W, T3 = T2 conj(W), E' = A^H T3) for
+ *             all rows of a chunk at once, with the s_out != bit half of T2 zeroed where the row fixes the site (ket and bra
+ *             share the output leg, so one side carries the projector).
+ *   tail      R_k[alpha', a', a, alpha], the right environment of |W psi|^2 with the sites k+1 .. n all traced (R_n = [1]),
+ *             does not depend on the row: one right-to-left pass per call, the four products mirrored.  Kept are the R_k at
+ *             which some row's trailing run of traced sites starts, from the right, while their total stays within 256 MiB
+ *             (QIL_APPLY_WEIGHT_RENV_BYTES overrides the figure, read on each call; 0 keeps none); the pass itself holds two
+ *             more buffers of the size of its largest intermediate.  A row stops at the first kept R_k of its trailing run and
+ *             gives amplitude^2 Re sum E o R_k -- Re(m R_k m^H), m = vec(M), when it has no middle, so a prefix-fixed row (the
+ *             blocks of a range, the steps of a quantile search) is a vector phase and one quadratic form.  A row with no kept
+ *             R_k walks to the end as middle and gives Re E[0]; a row with no traced site gives |M|^2.  Each result is a
+ *             fixed-order sum of one workgroup, without atomics.
+ * Rows are processed in chunks under 64 MiB of per-row temporaries:
+ *   chunk = max(1, min(nb, 32768, 64 MiB / ((2 maxMid + 2 maxM + maxX) e))),  e = 8 (f64) or 16 (c64) bytes, and over the sites
+ *   (chi_l, chi_r the bonds of psi, D_l, D_r those of W)
+ *   maxMid = max(chi_l^2 D_l^2, 2 chi_l D_l^2 chi_r, 2 chi_l D_l D_r chi_r, 2 chi_l D_r^2 chi_r, chi_r^2 D_r^2),
+ *   maxM = max(chi_l D_l, chi_r D_r),  maxX = 2 chi_l D_r.
+ * A result is bit-identical from run to run.  Its rounding may differ between chunkings (hence with nb and the other rows)
+ * and between kept and not-kept R_k.  Nothing but `out` outlives the call, also when an allocation fails midway.
+ * Errors, all before the context is activated: QIL_EINVAL_ARG ("apply_weight_batch: null argument") for a null W or psi or,
+ * when nb > 0, a null spec or out; QIL_EINVAL_ARG for nb < 0; the operand errors of qil_apply; QIL_EINVAL_CONFIG for a spec
+ * value above 2.  nb = 0 is a no-op (out is not touched).
+ * Left out: weights of operators, a device-resident out.                                                                   */
+QIL_API int qil_apply_weight_batch(const qil_mpo* W, const qil_mps* psi, int64_t nb, const uint8_t* spec, double* out);
 
 /* ------------------------------------------------------------------ truncation (K1, K2) */
 /* canonicalize!(psi, direction; center, cutoff=1e-12, maxdim) src/mps.jl:787-847.

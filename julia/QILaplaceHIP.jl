@@ -19,7 +19,7 @@ using ..ApplyMPO: _as_single_site_mpo
 export DeviceMPS, DeviceMPO, to_device, to_host, signal_mps_device, marginal, mps_block, apply_compress,
     compress_mpo!, build_dt_mpo_batch, build_qft_mpo_device, build_zt_qft_chain_device, apply_coefficient_sweep, apply!, rsvd_device, svd_device,
     Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm, sample, top_k,
-    hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress, restrict, weight_batch
+    hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress, restrict, weight_batch, apply_weight_batch
 
 const LIB = get(ENV, "QILHIP_LIB", "libqilhip.so")
 
@@ -341,6 +341,19 @@ function weight_batch(psi::DeviceMPS, specs::AbstractMatrix{<:Integer})
     out = Vector{Float64}(undef, nb)
     nb == 0 && return out
     GC.@preserve sp check(ccall((:qil_weight_batch, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{Cdouble}), psi.h, nb, sp, out))
+    return out
+end
+# the same weights of W * psi without the product (lazy: row vector through the leading fixed sites, density walk, shared right
+# environments)
+function apply_weight_batch(W::DeviceMPO, psi::DeviceMPS, specs::AbstractMatrix{<:Integer})
+    nb, n = size(specs)
+    n == length(psi.sites) || throw(ArgumentError("coefficient: expected $(length(psi.sites)) entries, got $n"))
+    all(s -> 0 <= s <= 2, specs) || throw(ArgumentError("coefficient: spec value outside [0,2]"))
+    sp = Matrix{UInt8}(permutedims(specs))                                     # the ABI's row-major nb x n
+    out = Vector{Float64}(undef, nb)
+    nb == 0 && return out
+    GC.@preserve sp check(ccall((:qil_apply_weight_batch, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{Cdouble}),
+                                W.h, psi.h, nb, sp, out))
     return out
 end
 function mps_to_vector(psi::DeviceMPS; reverse::Bool=false)                                        # mps.jl:716

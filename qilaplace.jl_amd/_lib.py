@@ -146,6 +146,7 @@ PROTOTYPES = {
     "qil_mps_sum_compress": [_pvp, _i64, _pdbl, _i64, _dbl, _int, _i64, _pvp],
     "qil_mps_restrict": [_vp, _pu8, _pvp],
     "qil_weight_batch": [_vp, _i64, _pu8, _pdbl],
+    "qil_apply_weight_batch": [_vp, _vp, _i64, _pu8, _pdbl],
     "qil_canonicalize": [_vp, _int, _i64, _dbl, _i64],
     "qil_compress": [_vp, _i64, _dbl, _int],
     "qil_mpo_compress": [_vp, _int, _dbl, _i64],

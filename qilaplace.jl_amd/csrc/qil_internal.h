@@ -371,6 +371,12 @@ struct qil_gemm_problem {
 };
 int qil_dev_gemm_grouped(qil_context* ctx, int dtype, std::vector<qil_gemm_problem>& probs);
 bool qil_dev_gemm_grouped_fits(size_t nproblems);
+// (qil_readout.hip) one site of the lazy row vector M_q[alpha, a] of <bits| W psi>, for nq rows packed per site:
+//   X_q = M_q W[.. | s_out = sel[q * sel_step]] (chi_l x D_l) (D_l x 2 D_r),   M'_q = A^T X_q (chi_r x 2 chi_l) (2 chi_l x D_r)
+// as two strided-batch GEMMs.  Wc / Ac are the call's scratch for the re-laid MPO site and the widened MPS site (Ac null when
+// psi has the contraction dtype), X holds nq * chi_l 2 D_r elements.
+int qil_lazy_row_step(qil_context* ctx, int dt, const struct qil_mpo* W, const struct qil_mps* psi, int64_t i, const void* Mc,
+                      void* Mn, void* X, void* Wc, void* Ac, int64_t nq, const uint8_t* sel, int64_t sel_step);
 // (qil_hadamard.hip) phi against psi under `verb`: context, paired flag (QIL_EINVAL_ARG), length (QIL_EINVAL_LENGTH), site ids
 // (QIL_EINVAL_SITES), in that order; touches no device
 int qil_check_pair(const char* verb, const struct qil_mps* phi, const struct qil_mps* psi);

@@ -331,40 +331,7 @@ int lazy_gemm_path(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64
         else hipLaunchKernelGGL(fill_ones<double>, dim3(g1), dim3(256), 0, qil_stream(ctx), (double*)M0, (long long)nq);
         void *Mc = M0, *Mn = M1;
         for (int64_t i = 0; i < n && st == QIL_OK; ++i) {
-            const long long cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1];
-            const long long Dl = W->dims[(size_t)i], Dr = W->dims[(size_t)i + 1];
-            const void* Ap = psi->site[(size_t)i];
-            {
-                const unsigned g = (unsigned)std::min<long long>((Dl * 4 * Dr + 255) / 256, 4096);
-                const void* Ws = W->site[(size_t)i];
-                if (dt == QIL_F64)
-                    hipLaunchKernelGGL((mpo_site_bit_major<double, double>), dim3(g), dim3(256), 0, qil_stream(ctx),
-                                       (const double*)Ws, (double*)Wc, (int)Dl, (int)Dr);
-                else if (wc)
-                    hipLaunchKernelGGL((mpo_site_bit_major<c64, c64>), dim3(g), dim3(256), 0, qil_stream(ctx), (const c64*)Ws,
-                                       (c64*)Wc, (int)Dl, (int)Dr);
-                else
-                    hipLaunchKernelGGL((mpo_site_bit_major<double, c64>), dim3(g), dim3(256), 0, qil_stream(ctx),
-                                       (const double*)Ws, (c64*)Wc, (int)Dl, (int)Dr);
-            }
-            if (Ac) {
-                hipLaunchKernelGGL(widen_to_c64<double>, dim3((unsigned)std::min<long long>((cl * 2 * cr + 255) / 256, 4096)),
-                                   dim3(256), 0, qil_stream(ctx), (const double*)Ap, (c64*)Ac, cl * 2 * cr);
-                Ap = Ac;
-            }
-            qil_gemm_batch b1, b2;
-            b1.count = nq;
-            b1.a_bs = cl * Dl;
-            b1.c_bs = cl * 2 * Dr;
-            b1.b_sel = dbits + q0 * n + i;
-            b1.b_sel_step = n;
-            b1.b_sel_stride = Dl * 2 * Dr;
-            st = qil_dev_gemm_batched(ctx, dt, 0, 0, cl, 2 * Dr, Dl, Mc, cl, Wc, Dl, X, cl, &b1);
-            if (st != QIL_OK) break;
-            b2.count = nq;
-            b2.b_bs = cl * 2 * Dr;
-            b2.c_bs = cr * Dr;
-            st = qil_dev_gemm_batched(ctx, dt, 1, 0, cr, Dr, 2 * cl, Ap, 2 * cl, X, 2 * cl, Mn, cr, &b2);
+            st = qil_lazy_row_step(ctx, dt, W, psi, i, Mc, Mn, X, Wc, Ac, nq, dbits + q0 * n + i, n);
             std::swap(Mc, Mn);
         }
         if (st != QIL_OK) break;
@@ -401,6 +368,48 @@ int upload_bits(qil_context* ctx, int64_t nb, int64_t n, const uint8_t* bits, ui
 }
 
 }  // namespace
+
+// One site of the lazy row vector, shared by lazy_gemm_path above and the lead phase of qil_apply_weight_batch
+// (qil_apply_weight.hip): Mn_q = the two products in front of lazy_gemm_path for the nq rows whose output bit at this site is
+// sel[q * sel_step] (0 / 1).  Wc (D_l 4 D_r elements of dt) receives the re-laid MPO site, Ac (chi_l 2 chi_r c64, or null when psi
+// needs no widening) the widened MPS site, X is nq * chi_l 2 D_r elements; Mc / Mn are packed per row (chi_l D_l and chi_r D_r).
+int qil_lazy_row_step(qil_context* ctx, int dt, const qil_mpo* W, const qil_mps* psi, int64_t i, const void* Mc, void* Mn, void* X,
+                      void* Wc, void* Ac, int64_t nq, const uint8_t* sel, int64_t sel_step) {
+    const bool wc = W->dtype == QIL_C64;
+    const long long cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1];
+    const long long Dl = W->dims[(size_t)i], Dr = W->dims[(size_t)i + 1];
+    const void* Ap = psi->site[(size_t)i];
+    {
+        const unsigned g = (unsigned)std::min<long long>((Dl * 4 * Dr + 255) / 256, 4096);
+        const void* Ws = W->site[(size_t)i];
+        if (dt == QIL_F64)
+            hipLaunchKernelGGL((mpo_site_bit_major<double, double>), dim3(g), dim3(256), 0, qil_stream(ctx),
+                               (const double*)Ws, (double*)Wc, (int)Dl, (int)Dr);
+        else if (wc)
+            hipLaunchKernelGGL((mpo_site_bit_major<c64, c64>), dim3(g), dim3(256), 0, qil_stream(ctx), (const c64*)Ws,
+                               (c64*)Wc, (int)Dl, (int)Dr);
+        else
+            hipLaunchKernelGGL((mpo_site_bit_major<double, c64>), dim3(g), dim3(256), 0, qil_stream(ctx),
+                               (const double*)Ws, (c64*)Wc, (int)Dl, (int)Dr);
+    }
+    if (Ac) {
+        hipLaunchKernelGGL(widen_to_c64<double>, dim3((unsigned)std::min<long long>((cl * 2 * cr + 255) / 256, 4096)),
+                           dim3(256), 0, qil_stream(ctx), (const double*)Ap, (c64*)Ac, cl * 2 * cr);
+        Ap = Ac;
+    }
+    qil_gemm_batch b1, b2;
+    b1.count = nq;
+    b1.a_bs = cl * Dl;
+    b1.c_bs = cl * 2 * Dr;
+    b1.b_sel = sel;
+    b1.b_sel_step = sel_step;
+    b1.b_sel_stride = Dl * 2 * Dr;
+    QIL_TRY(qil_dev_gemm_batched(ctx, dt, 0, 0, cl, 2 * Dr, Dl, Mc, cl, Wc, Dl, X, cl, &b1));
+    b2.count = nq;
+    b2.b_bs = cl * 2 * Dr;
+    b2.c_bs = cr * Dr;
+    return qil_dev_gemm_batched(ctx, dt, 1, 0, cr, Dr, 2 * cl, Ap, 2 * cl, X, 2 * cl, Mn, cr, &b2);
+}
 
 static int coefficient_impl(const qil_mps* psi, int64_t nb, const uint8_t* bits, double* out, int max_bit);
 

@@ -20,7 +20,7 @@
 // groups that take rows 0-3 and 12-15 of one column and rows 4-11 of the next) the columns must start on the same bank: ld = 0 mod
 // 16.  f64: ld = 80 -> 154 880 B (ld = 112 does not fit), so every bond <= 80; c64: ld = 48 -> 112 128 B (ld = 64 -> 198 656 B does
 // not fit), so every bond <= 48.  A state with a wider bond anywhere takes the GEMM route for every row.
-// Left out: the lazy form on W psi, weights of operators, a device-resident result.
+// Left out: weights of operators, a device-resident result (the lazy form on W psi is qil_apply_weight.hip).
 #include <algorithm>
 #include <cstdlib>
 #include <vector>

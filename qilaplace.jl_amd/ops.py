@@ -348,7 +348,11 @@ def weight_batch(psi, specs):
     amplitude^2 * sum |psi_x|^2 over the configurations x that agree with each row on its fixed tensors -- TRACE sums a site in
     |psi|^2, where `marginal_batch`'s 2 sums amplitudes.  A row without TRACE is abs(coefficient)^2, a row of all TRACE is
     (amplitude * norm)^2."""
-    sp = _weight_specs(psi, specs)
+    return _weigh(psi, specs, _native_weights)
+
+
+def _native_weights(psi, sp):
+    """the weigher of a state held on the device: qil_weight_batch on checked specs"""
     out = np.zeros(sp.shape[0], dtype=np.float64)
     if sp.shape[0]:
         L.check(L.lib.qil_weight_batch(psi.handle, sp.shape[0], sp.ctypes.data_as(C.POINTER(C.c_uint8)),
@@ -356,20 +360,45 @@ def weight_batch(psi, specs):
     return out
 
 
+def _lazy_weights(W):
+    """the weigher of W psi, never formed: qil_apply_weight_batch on checked specs"""
+    def weigher(psi, sp):
+        out = np.zeros(sp.shape[0], dtype=np.float64)
+        if sp.shape[0]:
+            L.check(L.lib.qil_apply_weight_batch(W.handle, psi.handle, sp.shape[0], sp.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                 out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+    return weigher
+
+
+def _weigh(psi, specs, weigher):
+    """Every front-end below ends here: the spec checks of `weight_batch`, then the weigher -- `_native_weights` for the state
+    itself, `_lazy_weights(W)` for W psi."""
+    return weigher(psi, _weight_specs(psi, specs))
+
+
 def weight(psi, spec):
     """`weight_batch` of one spec, as a float."""
-    return float(weight_batch(psi, np.asarray(spec)[None])[0])
+    return _weight(psi, spec, _native_weights)
+
+
+def _weight(psi, spec, weigher):
+    return float(_weigh(psi, np.asarray(spec)[None], weigher)[0])
 
 
 def bit_probabilities(psi):
     """P(bit i = 1) under |psi|^2 for every tensor i, from one call: n rows all traced but one FIX1, and the all-traced row
     as the divisor."""
+    return _bit_probabilities(psi, _native_weights)
+
+
+def _bit_probabilities(psi, weigher):
     if not isinstance(psi, SignalMPS):
         raise TypeError("weight: unsupported operand types")
     n = _ntensors(psi)
     sp = np.full((n + 1, n), TRACE, dtype=np.uint8)
     sp[np.arange(n), np.arange(n)] = FIX1
-    w = weight_batch(psi, sp)
+    w = _weigh(psi, sp, weigher)
     return w[:n] / w[n]
 
 
@@ -388,6 +417,10 @@ def range_weight(psi, lo, hi, reverse=False):
     the power in a band of a spectrum.  [lo, hi) splits into at most 2n dyadic blocks -- a fixed prefix, the rest traced --
     whose weights come from one call.  At any n: nothing dense is formed.  reverse=True reads x with the first tensor as the
     LEAST significant bit, the order in which a QFT output holds its bin index (as `mps_to_vector(..., reverse=True)`)."""
+    return _range_weight(psi, lo, hi, reverse, _native_weights)
+
+
+def _range_weight(psi, lo, hi, reverse, weigher):
     if not isinstance(psi, SignalMPS):
         raise TypeError("weight: unsupported operand types")
     for v in (lo, hi):
@@ -403,7 +436,7 @@ def range_weight(psi, lo, hi, reverse=False):
     sp = np.full((len(blocks), n), TRACE, dtype=np.uint8)
     for r, (start, k) in enumerate(blocks):
         sp[r, :n - k] = [(start >> (n - 1 - i)) & 1 for i in range(n - k)]
-    return float(np.sum(weight_batch(psi, sp[:, ::-1] if reverse else sp)))
+    return float(np.sum(_weigh(psi, sp[:, ::-1] if reverse else sp, weigher)))
 
 
 def weight_quantiles(psi, qs, reverse=False):
@@ -411,6 +444,10 @@ def weight_quantiles(psi, qs, reverse=False):
     sum_{y <= x} |psi_y|^2 >= q * total: q = 0.5 is the median frequency of a spectrum, 0.95 its 95 % edge.  The bits of all
     quantiles are found together from the top, one `weight_batch` call of len(qs) rows per tensor after one for the total.
     reverse=True as in `range_weight`: the first tensor is the least significant bit."""
+    return _weight_quantiles(psi, qs, reverse, _native_weights)
+
+
+def _weight_quantiles(psi, qs, reverse, weigher):
     if not isinstance(psi, SignalMPS):
         raise TypeError("weight: unsupported operand types")
     q = np.atleast_1d(np.asarray(qs, dtype=np.float64))
@@ -419,12 +456,12 @@ def weight_quantiles(psi, qs, reverse=False):
     n = _ntensors(psi)
     if not q.size:
         return np.zeros(0, dtype=np.int64 if n <= 62 else object)
-    target = q * weight(psi, np.full(n, TRACE, dtype=np.uint8))
+    target = q * _weight(psi, np.full(n, TRACE, dtype=np.uint8), weigher)
     below = np.zeros(len(q))                           # the weight of everything under the prefix found so far
     sp = np.full((len(q), n), TRACE, dtype=np.uint8)
     for i in (range(n - 1, -1, -1) if reverse else range(n)):
         sp[:, i] = FIX0
-        w0 = weight_batch(psi, sp)
+        w0 = _weigh(psi, sp, weigher)
         up = below + w0 < target                       # the low half does not reach the target: the bit is 1
         sp[up, i] = FIX1
         below[up] += w0[up]
@@ -432,13 +469,13 @@ def weight_quantiles(psi, qs, reverse=False):
     return np.array(xs, dtype=np.int64 if n <= 62 else object)
 
 
-def _register_weights(psi, what, fixed_offset, values):
+def _register_weights(psi, what, fixed_offset, values, weigher=_native_weights):
     if not isinstance(psi, ZTMPS):
         raise TypeError(f"{what}: needs a ZTMPS")
     vals = list(np.atleast_1d(np.asarray(values, dtype=object)))
     sp = np.array([_register_spec(psi, what, fixed_offset, v) for v in vals], dtype=np.uint8).reshape(len(vals), 2 * len(psi))
     sp[sp == FREE] = TRACE
-    return weight_batch(psi, sp)
+    return _weigh(psi, sp, weigher)
 
 
 def zt_row_weights(psi, ls):
@@ -450,6 +487,58 @@ def zt_row_weights(psi, ls):
 def zt_column_weights(psi, ks):
     """sum_l |Z(k, l)|^2 for every k of `ks`: the energy of frequency columns, the main register fixed as in `zt_column`."""
     return _register_weights(psi, "zt_column_weights", 0, ks)
+
+
+# ---- the same read-outs of W psi, which is never formed (qil_apply_weight_batch): the bodies above with the lazy weigher
+def apply_weight_batch(W, psi, specs):
+    """`weight_batch(apply(W, psi), specs)` without the product: amplitude^2 * sum |(W psi)_x|^2 over the configurations that
+    agree with each row, for operands whose product does not fit (the product's bond is chi * D).  A leading run of fixed
+    tensors costs a lazy coefficient step per tensor, a trailing run of traced ones one quadratic form with a right environment
+    shared by all rows, everything between the four products of `apply_norm` per tensor and row.  The rounding may depend on
+    the other rows of the call (they decide the chunking); two identical calls give identical bits.
+    Which to call (one MI355X, MEASUREMENTS section 16): where the product fits and the rows trace from the first tensor on, the
+    lazy form is SLOWER -- 64 row energies of a natural zT operand at n = 20 (chi <= 8, D <= 80) take 119 ms here against 81 ms
+    for `weight_batch(apply(W, psi))`.  It is faster for prefix-fixed rows (a 45-block band of the same operand: 9.9 against
+    58 ms) and for wide bonds (chi 32, D 64: 48 against 319 ms for 8 rows), and it is the only exact way when the product does
+    not fit."""
+    _require_operator(W, psi)
+    return _weigh(psi, specs, _lazy_weights(W))
+
+
+def apply_weight(W, psi, spec):
+    """`apply_weight_batch` of one spec, as a float."""
+    _require_operator(W, psi)
+    return _weight(psi, spec, _lazy_weights(W))
+
+
+def apply_bit_probabilities(W, psi):
+    """`bit_probabilities(apply(W, psi))` without the product."""
+    _require_operator(W, psi)
+    return _bit_probabilities(psi, _lazy_weights(W))
+
+
+def apply_range_weight(W, psi, lo, hi, reverse=False):
+    """`range_weight(apply(W, psi), lo, hi, reverse)` without the product: the power of a transformed signal in a band."""
+    _require_operator(W, psi)
+    return _range_weight(psi, lo, hi, reverse, _lazy_weights(W))
+
+
+def apply_weight_quantiles(W, psi, qs, reverse=False):
+    """`weight_quantiles(apply(W, psi), qs, reverse)` without the product."""
+    _require_operator(W, psi)
+    return _weight_quantiles(psi, qs, reverse, _lazy_weights(W))
+
+
+def apply_zt_row_weights(W, psi, ls):
+    """`zt_row_weights(apply(W, psi), ls)` without the product: psi a ZTMPS, W a PairedSiteMPO."""
+    _require_operator(W, psi)
+    return _register_weights(psi, "zt_row_weights", 1, ls, _lazy_weights(W))
+
+
+def apply_zt_column_weights(W, psi, ks):
+    """`zt_column_weights(apply(W, psi), ks)` without the product."""
+    _require_operator(W, psi)
+    return _register_weights(psi, "zt_column_weights", 0, ks, _lazy_weights(W))
 
 
 def _bit_block_range(v):
