@@ -6,14 +6,15 @@
 //            length of that run, longest first, so the rows still in the lead at a site are a prefix of their chunk.
 //   middle   at the row's first traced site apply_weight_seed forms E[alpha', a', a, alpha] = conj(M[alpha', a']) M[alpha, a], the
 //            layout of qil_apply_norm; every further site up to the row's tail runs its four products (T1 = E A, T2 = T1 W,
-//            T3 = T2 conj(Wr), E' = A^H T3) for all rows in the middle at once.  The buffers are packed per site -- row slot j's
+//            T3 = T2 conj(Wr), E' = A^H T3: qil_norm_env_ket / qil_norm_env_bra, qil_contract.hip) for all rows in the middle at once.  The buffers are packed per site -- row slot j's
 //            block sits at j * (block size of this site) -- so the row index and the batch index of each product collapse into
 //            one strided batch, and E' is ONE product.  Between T2 and T3 apply_weight_mask zeroes the s_out != bit half of T2 for
 //            the rows whose site is fixed: ket and bra share the output leg, so masking one side is the projector.  Rows enter
 //            at the end of the slot list (seeded in place); rows that leave are dropped from its end, and only when a row leaves
 //            from the inside apply_weight_gather copies the survivors' blocks into the other buffer.
 //   tail     R_k[alpha', a', a, alpha], the right environment of |W psi|^2 with the sites k+1 .. n all traced, is shared by all
-//            rows: ONE right-to-left pass per call (the four products mirrored, R_n = [1]) from n down to the leftmost R_k kept.
+//            rows: ONE right-to-left pass per call (the same step with left and right exchanged, R_n = [1]) from n down to the
+//            leftmost R_k kept.
 //            Kept are the R_k at which some row's trailing run of traced sites starts, from the right, while their total stays
 //            within kRightEnvBudget bytes (QIL_APPLY_WEIGHT_RENV_BYTES overrides it, read on each call).  A row stops at the first
 //            kept R_k inside its trailing run (t_r); with none kept it walks to the end as middle.
@@ -47,49 +48,6 @@ enum { kNoTrace = 0, kDensity = 1, kVector = 2 };   // how a row finishes
 
 __device__ __forceinline__ double re_mul(double a, double b) { return a * b; }
 __device__ __forceinline__ double re_mul(c64 a, c64 b) { return a.re * b.re - a.im * b.im; }
-__device__ __forceinline__ double re_part(double v) { return v; }
-__device__ __forceinline__ double re_part(c64 v) { return v.re; }
-
-template <class T>
-__global__ void apply_weight_fill_one(T* __restrict__ v, long long n) {
-    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x)
-        v[t] = cast_elem<T>(1.0);
-}
-
-// A[s, sigma, beta] -> Ap (cast to TD): mode 0 as it lies (a widened copy), mode 1 reversed, Ap[beta, sigma, s]
-template <class TS, class TD>
-__global__ void apply_weight_mps_site(const TS* __restrict__ A, TD* __restrict__ Ap, int cl, int cr, int mode) {
-    const long long total = 2LL * cl * cr;
-    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
-        long long src = t;
-        if (mode == 1) {
-            const long long be = t % cr, u = t / cr;
-            src = (u >> 1) + (long long)cl * ((u & 1) + 2 * be);
-        }
-        Ap[t] = cast_elem<TD>(A[src]);
-    }
-}
-// W[a, s_in, s_out, b] -> Wp (cast to TD):
-//   mode 0  as it lies                       the ket operand of T2
-//   mode 1  Wp[a, s_out, s_in, b]            the bra operand of T3 (qil_apply_norm's Wr)
-//   mode 2  Wp[b, s_in, s_out, a]            the ket operand of the mirrored pass
-//   mode 3  Wp[b, s_out, s_in, a]            the bra operand of the mirrored pass
-template <class TS, class TD>
-__global__ void apply_weight_mpo_site(const TS* __restrict__ W, TD* __restrict__ Wp, int Dl, int Dr, int mode) {
-    const long long total = 4LL * Dl * Dr;
-    const int d0 = mode >= 2 ? Dr : Dl;              // the fastest index of the target
-    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
-        const long long x = t % d0;
-        long long u = t / d0;
-        const int p = (int)(u & 1);
-        u >>= 1;
-        const int q = (int)(u & 1);
-        const long long y = u >> 1;
-        const long long a = mode >= 2 ? y : x, b = mode >= 2 ? x : y;
-        const int si = (mode == 0 || mode == 2) ? p : q, so = (mode == 0 || mode == 2) ? q : p;
-        Wp[t] = cast_elem<TD>(W[a + (long long)Dl * (si + 2 * (so + 2 * b))]);
-    }
-}
 
 // E_slot[alpha', a', a, alpha] = conj(M_j[alpha', a']) M_j[alpha, a] for the slots first .. first + count - 1, j = act[slot] the
 // row's place in the chunk (its M block, P = cl Dl elements, M_j[alpha, a] at alpha + cl a)
@@ -146,7 +104,7 @@ __global__ __launch_bounds__(kFinishThreads) void apply_weight_finish(const int*
         if (tid == 0) acc = abs2_t(M[slot * P]);
     } else if (kind == kDensity) {
         const T* __restrict__ Er = E + slot * P * P;
-        for (long long idx = tid; idx < P * P; idx += kFinishThreads) acc += R ? re_mul(Er[idx], R[idx]) : re_part(Er[idx]);
+        for (long long idx = tid; idx < P * P; idx += kFinishThreads) acc += R ? re_mul(Er[idx], R[idx]) : re_of(Er[idx]);
     } else {
         const T* __restrict__ m = M + slot * P;
         for (long long q = tid; q < P; q += kFinishThreads) {
@@ -163,57 +121,6 @@ __global__ __launch_bounds__(kFinishThreads) void apply_weight_finish(const int*
         __syncthreads();
     }
     if (tid == 0) out[e[0]] = amp2 * red[0];
-}
-
-unsigned grid_for(long long work) { return (unsigned)std::min<long long>(std::max<long long>((work + 255) / 256, 1), 4096); }
-
-// the strided batch in grid-sized pieces (the batch is the grid's y dimension)
-int gemm_batched_all(qil_context* ctx, int dt, int opA, int opB, int64_t m, int64_t n, int64_t k, const void* A, int64_t lda,
-                     const void* B, int64_t ldb, void* C, int64_t ldc, int64_t count, int64_t a_bs, int64_t b_bs, int64_t c_bs) {
-    const size_t e = qil_elem_size(dt);
-    for (int64_t b0 = 0; b0 < count; b0 += 65535) {
-        qil_gemm_batch bt;
-        bt.count = std::min<int64_t>(65535, count - b0);
-        bt.a_bs = a_bs;
-        bt.b_bs = b_bs;
-        bt.c_bs = c_bs;
-        QIL_TRY(qil_dev_gemm_batched(ctx, dt, opA, opB, m, n, k, static_cast<const char*>(A) + (size_t)(b0 * a_bs) * e, lda,
-                                     static_cast<const char*>(B) + (size_t)(b0 * b_bs) * e, ldb,
-                                     static_cast<char*>(C) + (size_t)(b0 * c_bs) * e, ldc, &bt));
-    }
-    return QIL_OK;
-}
-
-// site tensors in the contraction dtype T and the layout a product reads
-template <class T>
-int put_mps_site(qil_context* ctx, const qil_mps* psi, int64_t i, int mode, T* dst) {
-    const int cl = (int)psi->dims[(size_t)i], cr = (int)psi->dims[(size_t)i + 1];
-    const unsigned g = grid_for(2LL * cl * cr);
-    if (psi->dtype == QIL_C64) {
-        if constexpr (sizeof(T) == 16)
-            hipLaunchKernelGGL((apply_weight_mps_site<c64, c64>), dim3(g), dim3(256), 0, qil_stream(ctx),
-                               (const c64*)psi->site[(size_t)i], dst, cl, cr, mode);
-    } else {
-        hipLaunchKernelGGL((apply_weight_mps_site<double, T>), dim3(g), dim3(256), 0, qil_stream(ctx),
-                           (const double*)psi->site[(size_t)i], dst, cl, cr, mode);
-    }
-    QIL_HIP(hipGetLastError());
-    return QIL_OK;
-}
-template <class T>
-int put_mpo_site(qil_context* ctx, const qil_mpo* W, int64_t i, int mode, T* dst) {
-    const int Dl = (int)W->dims[(size_t)i], Dr = (int)W->dims[(size_t)i + 1];
-    const unsigned g = grid_for(4LL * Dl * Dr);
-    if (W->dtype == QIL_C64) {
-        if constexpr (sizeof(T) == 16)
-            hipLaunchKernelGGL((apply_weight_mpo_site<c64, c64>), dim3(g), dim3(256), 0, qil_stream(ctx),
-                               (const c64*)W->site[(size_t)i], dst, Dl, Dr, mode);
-    } else {
-        hipLaunchKernelGGL((apply_weight_mpo_site<double, T>), dim3(g), dim3(256), 0, qil_stream(ctx),
-                           (const double*)W->site[(size_t)i], dst, Dl, Dr, mode);
-    }
-    QIL_HIP(hipGetLastError());
-    return QIL_OK;
 }
 
 struct RowPlan {
@@ -235,26 +142,15 @@ int right_environments(qil_context* ctx, int dt, const qil_mpo* W, const qil_mps
                        const SiteScratch<T>& sc, T* X, T* Y) {
     const int64_t n = psi->n();
     const T* cur = X;                                  // R_n = [1] (never kept: a row that reaches bond n reads Re E[0])
-    hipLaunchKernelGGL(apply_weight_fill_one<T>, dim3(1), dim3(64), 0, qil_stream(ctx), X, 1LL);
-    QIL_HIP(hipGetLastError());
+    QIL_TRY(qil_dev_fill_ones(ctx, dt, X, 1));
     for (int64_t i = n - 1; i >= kmin; --i) {
-        const int64_t cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1];
-        const int64_t Dl = W->dims[(size_t)i], Dr = W->dims[(size_t)i + 1];
-        QIL_TRY(put_mps_site<T>(ctx, psi, i, 1, sc.At));                                  // At[beta, sigma, s]
-        QIL_TRY(put_mpo_site<T>(ctx, W, i, 2, sc.Wd));                                    // Wk[b, sigma, tau, a]
-        QIL_TRY(put_mpo_site<T>(ctx, W, i, 3, sc.Wr));                                    // Wb[b', tau, sigma', a']
-        const int64_t rR = cr * Dr * Dr;
-        // U1[beta', b', b, sigma, s] = R[beta', b', b, beta] At[beta, (sigma, s)]
-        QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, rR, 2 * cl, cr, cur, rR, sc.At, cr, Y, rR));
-        // U2_s[(beta', b'), (tau, a)] = U1_s[(beta', b'), (b, sigma)] Wk[(b, sigma), (tau, a)]              batch = s
-        QIL_TRY(gemm_batched_all(ctx, dt, 0, 0, cr * Dr, 2 * Dl, 2 * Dr, Y, cr * Dr, sc.Wd, 2 * Dr, X, cr * Dr, cl, cr * Dr * 2 * Dr,
-                                 0, cr * Dr * 2 * Dl));
-        // U3_as[beta', (sigma', a')] = U2_as[beta', (b', tau)] conj(Wb[(b', tau), (sigma', a')])           batch = (a, s)
-        QIL_TRY(gemm_batched_all(ctx, dt, 0, 3, cr, 2 * Dl, 2 * Dr, X, cr, sc.Wr, 2 * Dr, Y, cr, Dl * cl, cr * 2 * Dr, 0,
-                                 cr * 2 * Dl));
-        // R_i[s', (a', a, s)] = At[(beta', sigma'), s']^H U3[(beta', sigma'), (a', a, s)]
+        QIL_TRY(qil_put_mps_site(ctx, dt, psi, i, QIL_SITE_REVERSED, sc.At));             // At[beta, sigma, s]
+        QIL_TRY(qil_put_mpo_site(ctx, dt, W, i, QIL_SITE_REVERSED, sc.Wd));               // Wk[b, sigma, tau, a]
+        QIL_TRY(qil_put_mpo_site(ctx, dt, W, i, QIL_SITE_REV_SWAPPED, sc.Wr));            // Wb[b', tau, sigma', a']
+        // the step of the middle with left and right exchanged: R_i[s', a', a, s] from R_{i+1}[beta', b', b, beta]
         T* dst = Rk[(size_t)i] ? Rk[(size_t)i] : X;
-        QIL_TRY(qil_dev_gemm(ctx, dt, 2, 0, cl, Dl * Dl * cl, 2 * cr, sc.At, 2 * cr, Y, 2 * cr, dst, cl));
+        QIL_TRY(qil_norm_env_step(ctx, dt, psi->dims[(size_t)i + 1], psi->dims[(size_t)i], W->dims[(size_t)i + 1], W->dims[(size_t)i], 1,
+                                  sc.At, sc.Wd, sc.Wr, cur, Y, X, dst));
         cur = dst;
     }
     return QIL_OK;
@@ -316,7 +212,6 @@ int weigh(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64_t nb, co
     // ---- device memory: everything belongs to `tmp`
     qil_scratch tmp(ctx);
     void *dspec = nullptr, *dout = nullptr;
-    QIL_TRY(tmp.alloc((size_t)std::max<int64_t>(nb * n, 1), &dspec));
     QIL_TRY(tmp.alloc((size_t)nb * sizeof(double), &dout));
     SiteScratch<T> sc;
     QIL_TRY(tmp.alloc((size_t)maxA * e, (void**)&sc.As));
@@ -338,15 +233,11 @@ int weigh(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64_t nb, co
     // the spec in sorted order (the lead's products pick the output bit of row j of a chunk at dspec[(r0 + j) n + i])
     std::vector<uint8_t> sorted((size_t)std::max<int64_t>(nb * n, 1));
     for (int64_t j = 0; j < nb; ++j) std::copy(spec + rows[(size_t)j].row * n, spec + (rows[(size_t)j].row + 1) * n, sorted.begin() + j * n);
-    if (n > 0) {
-        QIL_HIP(hipMemcpyAsync(dspec, sorted.data(), (size_t)(nb * n), hipMemcpyHostToDevice, qil_stream(ctx)));
-        QIL_HIP(qil_stream_sync(ctx));                 // `sorted` is this call's memory
-    }
+    QIL_TRY(qil_upload_bytes(tmp, sorted.data(), (size_t)(nb * n), &dspec));
     void* buf[5] = {};                                 // P, Q (the middle's ping-pong), M0, M1, X (the lead)
     const long long bufElems[5] = {maxMid, maxMid, maxM, maxM, maxX};
     for (int b = 0; b < 5; ++b) QIL_TRY(tmp.alloc((size_t)(chunk * bufElems[b] * e), &buf[b]));
     T *P = static_cast<T*>(buf[0]), *Q = static_cast<T*>(buf[1]);
-    const bool widenA = psi->dtype != dt;
     const double amp2 = psi->amplitude * psi->amplitude;
     const uint8_t* dsp = static_cast<const uint8_t*>(dspec);
     double* dres = static_cast<double*>(dout);
@@ -409,8 +300,7 @@ int weigh(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64_t nb, co
         // ---- the walk
         T *Mc = static_cast<T*>(buf[2]), *Mn = static_cast<T*>(buf[3]);
         T *E = P, *O = Q;                              // E holds the slots' environments, O is the other buffer
-        hipLaunchKernelGGL(apply_weight_fill_one<T>, dim3(grid_for(nr)), dim3(256), 0, qil_stream(ctx), Mc, (long long)nr);
-        QIL_HIP(hipGetLastError());
+        QIL_TRY(qil_dev_fill_ones(ctx, dt, Mc, nr));
         for (int64_t i = 0; i <= n; ++i) {
             const BondPlan& b = bp[(size_t)i];
             const int64_t cl = psi->dims[(size_t)i], Dl = W->dims[(size_t)i];
@@ -423,51 +313,36 @@ int weigh(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64_t nb, co
             const int64_t cr = psi->dims[(size_t)i + 1], Dr = W->dims[(size_t)i + 1];
             const int64_t sE = cl * Dl * Dl * cl;
             if (b.gather) {
-                hipLaunchKernelGGL(apply_weight_gather<T>, dim3(grid_for((long long)b.ngat * sE)), dim3(256), 0, qil_stream(ctx),
+                hipLaunchKernelGGL(apply_weight_gather<T>, dim3(qil_grid_for((long long)b.ngat * sE)), dim3(256), 0, qil_stream(ctx),
                                    dt_tab + b.gat, (long long)b.ngat, (const T*)E, O, (long long)sE);
                 QIL_HIP(hipGetLastError());
                 std::swap(E, O);
             }
             if (b.nact > b.nsurv) {
-                hipLaunchKernelGGL(apply_weight_seed<T>, dim3(grid_for((long long)(b.nact - b.nsurv) * sE)), dim3(256), 0,
+                hipLaunchKernelGGL(apply_weight_seed<T>, dim3(qil_grid_for((long long)(b.nact - b.nsurv) * sE)), dim3(256), 0,
                                    qil_stream(ctx), dt_tab + b.act, (int)b.nsurv, (long long)(b.nact - b.nsurv), (const T*)Mc, E,
                                    (int)cl, (int)Dl);
                 QIL_HIP(hipGetLastError());
             }
             if (b.nlead) {
-                QIL_TRY(qil_lazy_row_step(ctx, dt, W, psi, i, Mc, Mn, buf[4], sc.Wc, widenA ? sc.As : nullptr, b.nlead,
+                QIL_TRY(qil_lazy_row_step(ctx, dt, W, psi, i, Mc, Mn, buf[4], sc.Wc, psi->dtype != dt ? sc.As : nullptr, b.nlead,
                                           dsp + r0 * n + i, n));
                 std::swap(Mc, Mn);
             }
             if (b.nact) {
-                const int64_t na = (int64_t)b.nact, rE = cl * Dl * Dl;
-                const T* As = static_cast<const T*>(psi->site[(size_t)i]);
-                const T* Wd = static_cast<const T*>(W->site[(size_t)i]);
-                if (widenA) {
-                    QIL_TRY(put_mps_site<T>(ctx, psi, i, 0, sc.As));
-                    As = sc.As;
-                }
-                if (W->dtype != dt) {
-                    QIL_TRY(put_mpo_site<T>(ctx, W, i, 0, sc.Wd));
-                    Wd = sc.Wd;
-                }
-                QIL_TRY(put_mpo_site<T>(ctx, W, i, 1, sc.Wr));
-                // T1[s', a', a, s_in, beta] = E A                                                   batch = slot
-                QIL_TRY(gemm_batched_all(ctx, dt, 0, 0, rE, 2 * cr, cl, E, rE, As, cl, O, rE, na, rE * cl, 0, rE * 2 * cr));
-                // T2[s', a', s_out, b, beta] = T1_beta W                                            batch = (beta, slot)
-                QIL_TRY(gemm_batched_all(ctx, dt, 0, 0, cl * Dl, 2 * Dr, 2 * Dl, O, cl * Dl, Wd, 2 * Dl, E, cl * Dl, na * cr, rE * 2, 0,
-                                         cl * Dl * 2 * Dr));
+                const int64_t na = (int64_t)b.nact;
+                const void *As = nullptr, *Wd = nullptr;
+                QIL_TRY(qil_site_operand(ctx, dt, psi, i, sc.As, &As));
+                QIL_TRY(qil_site_operand(ctx, dt, W, i, sc.Wd, &Wd));
+                QIL_TRY(qil_put_mpo_site(ctx, dt, W, i, QIL_SITE_SWAPPED, sc.Wr));
+                QIL_TRY(qil_norm_env_ket(ctx, dt, cl, cr, Dl, Dr, na, As, Wd, E, O, E));   // T1 in O, T2 in E
                 if (b.any_fixed) {
-                    hipLaunchKernelGGL(apply_weight_mask<T>, dim3(grid_for(na * cl * Dl * Dr * cr)), dim3(256), 0, qil_stream(ctx), E,
+                    hipLaunchKernelGGL(apply_weight_mask<T>, dim3(qil_grid_for(na * cl * Dl * Dr * cr)), dim3(256), 0, qil_stream(ctx), E,
                                        dt_tab + b.act, (long long)na, (long long)(cl * Dl), (long long)(Dr * cr), dsp + r0 * n, (int)n,
                                        (int)i);
                     QIL_HIP(hipGetLastError());
                 }
-                // T3[s', s_in', b', b, beta] = T2_(b, beta) conj(Wr)                                batch = (b, beta, slot)
-                QIL_TRY(gemm_batched_all(ctx, dt, 0, 3, cl, 2 * Dr, 2 * Dl, E, cl, sc.Wr, 2 * Dl, O, cl, na * Dr * cr, cl * 2 * Dl, 0,
-                                         cl * 2 * Dr));
-                // E'[beta', b', b, beta] = A^H T3: the slots' blocks are the columns of ONE product
-                QIL_TRY(qil_dev_gemm(ctx, dt, 2, 0, cr, na * Dr * Dr * cr, 2 * cl, As, 2 * cl, O, 2 * cl, E, cr));
+                QIL_TRY(qil_norm_env_bra(ctx, dt, cl, cr, Dl, Dr, na, As, sc.Wr, E, O, E));    // T3 in O, E' in E
             }
         }
         QIL_TRY(dtab.release());

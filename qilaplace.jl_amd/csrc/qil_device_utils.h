@@ -1,8 +1,10 @@
 // Device-side helpers shared by the dense linear algebra (qil_linalg.hip), the MPO builders (qil_build*.hip), the
-// apply (qil_apply.hip), the read-outs (qil_readout.hip), the overlaps (qil_inner.hip), the sampler (qil_sample.hip) and
-// the truncation (qil_truncate.hip): the complex scalar type and its arithmetic, the splitmix64 hash, DPP cross-lane sums,
-// Jacobi rotations, the in-workgroup one-sided Jacobi sweep loop, and the site table, site lookup and stores of the grouped
-// launches.  gfx950 only.
+// apply (qil_apply.hip), the read-outs (qil_readout.hip), the overlaps (qil_inner.hip), the sampler (qil_sample.hip), the
+// Born weights (qil_weight.hip, qil_apply_weight.hip), the restriction (qil_restrict.hip), the sums (qil_sum.hip), the shared
+// contraction steps (qil_contract.hip) and the truncation (qil_truncate.hip): the complex scalar type, its arithmetic and its
+// parts (re_of / im_of / make_elem / shfl_xor_t), the one K step of a 16 x 16 tile on the f64 MFMA (mfma_step), the splitmix64
+// hash, DPP cross-lane sums, Jacobi rotations, the in-workgroup one-sided Jacobi sweep loop, and the site table, site lookup
+// and stores of the grouped launches.  gfx950 only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -59,6 +61,29 @@ template <>
 __device__ __forceinline__ c64 cast_elem<c64>(double v) { return c64{v, 0.0}; }
 template <class TD>
 __device__ __forceinline__ TD cast_elem(c64 v) { return v; }
+__device__ __forceinline__ double re_of(double v) { return v; }
+__device__ __forceinline__ double re_of(c64 v) { return v.re; }
+__device__ __forceinline__ double im_of(double) { return 0.0; }
+__device__ __forceinline__ double im_of(c64 v) { return v.im; }
+// (re, im) as an element of the type the null pointer names; the imaginary part of a real element is dropped
+__device__ __forceinline__ double make_elem(double re, double, double*) { return re; }
+__device__ __forceinline__ c64 make_elem(double re, double im, c64*) { return c64{re, im}; }
+__device__ __forceinline__ double shfl_xor_t(double v, int m) { return __shfl_xor(v, m, 64); }
+__device__ __forceinline__ c64 shfl_xor_t(c64 v, int m) { return c64{__shfl_xor(v.re, m, 64), __shfl_xor(v.im, m, 64)}; }
+
+// ------------------------------------------------------------------ the f64 MFMA tile step
+typedef double d4 __attribute__((ext_vector_type(4)));
+// one K step of a 16 x 16 tile on v_mfma_f64_16x16x4_f64: D[i][j] += sum_k X[i][k] Y[k][j], lane l supplies x = X[l & 15][l >> 4]
+// and y = Y[l >> 4][l & 15] and holds D[(l >> 4) + 4 reg][l & 15]; c64 through the real / imaginary split
+template <class T>
+__device__ __forceinline__ void mfma_step(T x, T y, d4& rr, d4& ii) {
+    rr = __builtin_amdgcn_mfma_f64_16x16x4f64(re_of(x), re_of(y), rr, 0, 0, 0);
+    if constexpr (sizeof(T) == 16) {
+        rr = __builtin_amdgcn_mfma_f64_16x16x4f64(-im_of(x), im_of(y), rr, 0, 0, 0);
+        ii = __builtin_amdgcn_mfma_f64_16x16x4f64(re_of(x), im_of(y), ii, 0, 0, 0);
+        ii = __builtin_amdgcn_mfma_f64_16x16x4f64(im_of(x), re_of(y), ii, 0, 0, 0);
+    }
+}
 
 // ------------------------------------------------------------------ counter-based random numbers
 // splitmix64 finaliser: the hash behind qil_dev_fill_normal's normals and qil_sample's uniforms

@@ -9,7 +9,8 @@
 //   qil_apply_inner  E[phi, a, psi]:         T1 = E A_psi, T2_beta = T1_beta W, E' = A_phi^H T2
 //   qil_apply_norm   E[psi', a', a, psi]:    ket A, ket W, bra conj(W), bra conj(A)
 //
-// Mixed dtypes contract in c64; a real operand is widened once per site into a scratch block.
+// Mixed dtypes contract in c64; a real operand is widened once per site into a scratch block (qil_site_operand).  The four
+// products of qil_apply_norm are qil_norm_env_step (qil_contract.hip).  Every temporary belongs to the call's qil_scratch.
 #include "qil_internal.h"
 #include "qil_device_utils.h"
 
@@ -20,70 +21,6 @@
 namespace {
 
 using namespace qil_dev;
-
-// ---- small helpers ---------------------------------------------------------------------------------------------
-// p[0] = 1 (the left boundary of every environment; a kernel, so the chain starts without an upload)
-template <class T>
-__global__ void set_one(T* __restrict__ p) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) p[0] = cast_elem<T>(1.0);
-}
-__global__ void widen_f64(const double* __restrict__ src, c64* __restrict__ dst, long long n) {
-    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x)
-        dst[t] = c64{src[t], 0.0};
-}
-// W[a, s_in, s_out, b] -> Wr[a, s_out, s_in, b] (optionally widened): the bra side of norm(W psi) contracts (a', s_out), which
-// are then adjacent, and (s_in, b') become the columns
-template <class TS, class TD>
-__global__ void mpo_swap_phys(const TS* __restrict__ W, TD* __restrict__ Wr, int Dl, int Dr) {
-    const long long total = 4LL * Dl * Dr;
-    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
-        const int a = (int)(t % Dl);
-        long long u = t / Dl;
-        const int so = (int)(u & 1);
-        u >>= 1;
-        const int si = (int)(u & 1);
-        const long long b = u >> 1;
-        Wr[t] = cast_elem<TD>(W[a + (long long)Dl * (si + 2 * (so + 2 * b))]);
-    }
-}
-
-static unsigned grid_for(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, 4096)); }
-
-// a real operand of a complex contraction: widened into `buf` (elems entries), else used as it lies
-static int operand(qil_context* ctx, int dt, int src_dt, const void* src, long long elems, void* buf, const void** use) {
-    if (dt == QIL_C64 && src_dt == QIL_F64) {
-        hipLaunchKernelGGL(widen_f64, dim3(grid_for(elems)), dim3(256), 0, qil_stream(ctx), (const double*)src, (c64*)buf, elems);
-        QIL_HIP(hipGetLastError());
-        *use = buf;
-    } else {
-        *use = src;
-    }
-    return QIL_OK;
-}
-
-static int launch_set_one(qil_context* ctx, int dt, void* p) {
-    if (dt == QIL_C64) hipLaunchKernelGGL(set_one<c64>, dim3(1), dim3(64), 0, qil_stream(ctx), (c64*)p);
-    else hipLaunchKernelGGL(set_one<double>, dim3(1), dim3(64), 0, qil_stream(ctx), (double*)p);
-    QIL_HIP(hipGetLastError());
-    return QIL_OK;
-}
-
-// the batched product in grid-sized pieces (the batch is the grid's y dimension)
-static int gemm_batched_all(qil_context* ctx, int dt, int opA, int opB, int64_t m, int64_t n, int64_t k, const void* A, int64_t lda,
-                            const void* B, int64_t ldb, void* C, int64_t ldc, int64_t count, int64_t a_bs, int64_t b_bs, int64_t c_bs) {
-    const size_t e = qil_elem_size(dt);
-    for (int64_t b0 = 0; b0 < count; b0 += 65535) {
-        qil_gemm_batch bt;
-        bt.count = std::min<int64_t>(65535, count - b0);
-        bt.a_bs = a_bs;
-        bt.b_bs = b_bs;
-        bt.c_bs = c_bs;
-        QIL_TRY(qil_dev_gemm_batched(ctx, dt, opA, opB, m, n, k, static_cast<const char*>(A) + (size_t)(b0 * a_bs) * e, lda,
-                                     static_cast<const char*>(B) + (size_t)(b0 * b_bs) * e, ldb,
-                                     static_cast<char*>(C) + (size_t)(b0 * c_bs) * e, ldc, &bt));
-    }
-    return QIL_OK;
-}
 
 // the environment's last 1 x 1 value to the host
 static int read_scalar(qil_context* ctx, int dt, const void* E, double h[2]) {
@@ -181,8 +118,9 @@ static int inner_chain_route(const qil_mps* phi, const qil_mps* psi, double h[2]
     for (int64_t i = 0; i < n; ++i)
         tab[(size_t)i] = InnerSite{phi->site[(size_t)i], psi->site[(size_t)i], (int)phi->dims[(size_t)i], (int)phi->dims[(size_t)i + 1],
                                    (int)psi->dims[(size_t)i], (int)psi->dims[(size_t)i + 1]};
+    qil_scratch tmp(ctx);
     void* dout = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, 16, &dout));
+    QIL_TRY(tmp.alloc(16, &dout));
     qil_dev_table dtab(ctx);
     QIL_TRY(dtab.upload(tab.data(), tab.size() * sizeof(InnerSite)));
     const double amp = phi->amplitude * psi->amplitude;
@@ -194,9 +132,7 @@ static int inner_chain_route(const qil_mps* phi, const qil_mps* psi, double h[2]
     else if (sc) QIL_TRY((launch_inner_chain<double, c64, c64>(ctx, t, (int)n, amp, o)));
     else QIL_TRY((launch_inner_chain<double, double, double>(ctx, t, (int)n, amp, o)));
     QIL_TRY(dtab.release());
-    QIL_TRY(qil_read_back(ctx, h, dout, 16));
-    qil_ctx_free(ctx, dout);
-    return QIL_OK;
+    return qil_read_back(ctx, h, dout, 16);
 }
 
 // ---- <phi|psi>: GEMM route --------------------------------------------------------------------------------------
@@ -215,32 +151,27 @@ static int inner_gemm_raw(const qil_mps* phi, const qil_mps* psi, double h[2]) {
         maxP = std::max(maxP, pl * 2 * pr);
         maxS = std::max(maxS, sl * 2 * sr);
     }
+    qil_scratch tmp(ctx);
     void *E = nullptr, *En = nullptr, *T = nullptr, *Pw = nullptr, *Sw = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxE * e, &E));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxE * e, &En));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxT * e, &T));
-    if (dt != phi->dtype) QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxP * e, &Pw));
-    if (dt != psi->dtype) QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxS * e, &Sw));
-    QIL_TRY(launch_set_one(ctx, dt, E));
+    QIL_TRY(tmp.alloc((size_t)maxE * e, &E));
+    QIL_TRY(tmp.alloc((size_t)maxE * e, &En));
+    QIL_TRY(tmp.alloc((size_t)maxT * e, &T));
+    if (dt != phi->dtype) QIL_TRY(tmp.alloc((size_t)maxP * e, &Pw));
+    if (dt != psi->dtype) QIL_TRY(tmp.alloc((size_t)maxS * e, &Sw));
+    QIL_TRY(qil_dev_fill_ones(ctx, dt, E, 1));
     for (int64_t i = 0; i < n; ++i) {
         const int64_t pl = phi->dims[(size_t)i], pr = phi->dims[(size_t)i + 1];
         const int64_t sl = psi->dims[(size_t)i], sr = psi->dims[(size_t)i + 1];
         const void *Ap = nullptr, *As = nullptr;
-        QIL_TRY(operand(ctx, dt, phi->dtype, phi->site[(size_t)i], pl * 2 * pr, Pw, &Ap));
-        QIL_TRY(operand(ctx, dt, psi->dtype, psi->site[(size_t)i], sl * 2 * sr, Sw, &As));
+        QIL_TRY(qil_site_operand(ctx, dt, phi, i, Pw, &Ap));
+        QIL_TRY(qil_site_operand(ctx, dt, psi, i, Sw, &As));
         // T (pl x 2sr) = E (pl x sl) * A_psi (sl x 2sr):  T[p, s, b]
         QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, pl, 2 * sr, sl, E, pl, As, sl, T, pl));
         // E' (pr x sr) = A_phi^H ((2pl) x pr)^H * T ((2pl) x sr)
         QIL_TRY(qil_dev_gemm(ctx, dt, 2, 0, pr, sr, 2 * pl, Ap, 2 * pl, T, 2 * pl, En, pr));
         std::swap(E, En);
     }
-    QIL_TRY(read_scalar(ctx, dt, E, h));
-    qil_ctx_free(ctx, E);
-    qil_ctx_free(ctx, En);
-    qil_ctx_free(ctx, T);
-    if (Pw) qil_ctx_free(ctx, Pw);
-    if (Sw) qil_ctx_free(ctx, Sw);
-    return QIL_OK;
+    return read_scalar(ctx, dt, E, h);
 }
 
 // phi against psi (or against the product W psi, which has psi's chain shape): same context, register kind, length, sites
@@ -326,25 +257,28 @@ extern "C" int qil_apply_inner(const qil_mps* phi, const qil_mpo* W, const qil_m
         maxS = std::max(maxS, sl * 2 * sr);
         maxW = std::max(maxW, Dl * 4 * Dr);
     }
+    qil_scratch tmp(ctx);
     void *E = nullptr, *En = nullptr, *T1 = nullptr, *T2 = nullptr, *Pw = nullptr, *Sw = nullptr, *Ww = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxE * e, &E));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxE * e, &En));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxT1 * e, &T1));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxT2 * e, &T2));
-    if (dt != phi->dtype) QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxP * e, &Pw));
-    if (dt != psi->dtype) QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxS * e, &Sw));
-    if (dt != W->dtype) QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxW * e, &Ww));
-    QIL_TRY(launch_set_one(ctx, dt, E));
+    QIL_TRY(tmp.alloc((size_t)maxE * e, &E));
+    QIL_TRY(tmp.alloc((size_t)maxE * e, &En));
+    QIL_TRY(tmp.alloc((size_t)maxT1 * e, &T1));
+    QIL_TRY(tmp.alloc((size_t)maxT2 * e, &T2));
+    if (dt != phi->dtype) QIL_TRY(tmp.alloc((size_t)maxP * e, &Pw));
+    if (dt != psi->dtype) QIL_TRY(tmp.alloc((size_t)maxS * e, &Sw));
+    if (dt != W->dtype) QIL_TRY(tmp.alloc((size_t)maxW * e, &Ww));
+    QIL_TRY(qil_dev_fill_ones(ctx, dt, E, 1));
     for (int64_t i = 0; i < n; ++i) {
         const int64_t pl = phi->dims[(size_t)i], pr = phi->dims[(size_t)i + 1];
         const int64_t sl = psi->dims[(size_t)i], sr = psi->dims[(size_t)i + 1];
         const int64_t Dl = W->dims[(size_t)i], Dr = W->dims[(size_t)i + 1];
         const void *Ap = nullptr, *As = nullptr, *Wd = nullptr;
-        QIL_TRY(operand(ctx, dt, phi->dtype, phi->site[(size_t)i], pl * 2 * pr, Pw, &Ap));
-        QIL_TRY(operand(ctx, dt, psi->dtype, psi->site[(size_t)i], sl * 2 * sr, Sw, &As));
-        QIL_TRY(operand(ctx, dt, W->dtype, W->site[(size_t)i], Dl * 4 * Dr, Ww, &Wd));
+        QIL_TRY(qil_site_operand(ctx, dt, phi, i, Pw, &Ap));
+        QIL_TRY(qil_site_operand(ctx, dt, psi, i, Sw, &As));
+        QIL_TRY(qil_site_operand(ctx, dt, W, i, Ww, &Wd));
         QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, pl * Dl, 2 * sr, sl, E, pl * Dl, As, sl, T1, pl * Dl));
-        QIL_TRY(gemm_batched_all(ctx, dt, 0, 0, pl, 2 * Dr, 2 * Dl, T1, pl, Wd, 2 * Dl, T2, pl, sr, pl * 2 * Dl, 0, pl * 2 * Dr));
+        qil_gemm_batch bt;                             // batch = beta
+        bt.count = sr, bt.a_bs = pl * 2 * Dl, bt.c_bs = pl * 2 * Dr;
+        QIL_TRY(qil_dev_gemm_batched(ctx, dt, 0, 0, pl, 2 * Dr, 2 * Dl, T1, pl, Wd, 2 * Dl, T2, pl, &bt));
         QIL_TRY(qil_dev_gemm(ctx, dt, 2, 0, pr, Dr * sr, 2 * pl, Ap, 2 * pl, T2, 2 * pl, En, pr));
         std::swap(E, En);
     }
@@ -353,12 +287,11 @@ extern "C" int qil_apply_inner(const qil_mps* phi, const qil_mpo* W, const qil_m
     const double amp = phi->amplitude * psi->amplitude;
     out[0] = h[0] * amp;
     out[1] = h[1] * amp;
-    for (void* p : {E, En, T1, T2, Pw, Sw, Ww})
-        if (p) qil_ctx_free(ctx, p);
     return QIL_OK;
 }
 
-// norm(W psi): E[s', a', a, s] (sl x Dl x Dl x sl) per site, two buffers in ping-pong (X: E, T2, E'; Y: T1, T3)
+// norm(W psi): E[s', a', a, s] (sl x Dl x Dl x sl) per site, two buffers in ping-pong (X: E, T2, E'; Y: T1, T3); the four products
+// are qil_norm_env_step (qil_contract.hip) on one environment:
 //   T1 ((sl Dl Dl) x 2sr)   = E * A_psi                                                T1[s', a', a, s_in, beta]
 //   T2_beta ((sl Dl) x 2Dr) = T1_beta ((sl Dl) x 2Dl) * W (2Dl x 2Dr)   (batch = beta) T2[s', a', s_out, b, beta]
 //   T3_bb (sl x 2Dr)        = T2_bb (sl x 2Dl) * conj(Wr) (2Dl x 2Dr)   (batch = (b, beta), Wr = W with s_in <-> s_out)
@@ -382,44 +315,24 @@ extern "C" int qil_apply_norm(const qil_mpo* W, const qil_mps* psi, double* out)
         maxS = std::max(maxS, sl * 2 * sr);
         maxW = std::max(maxW, Dl * 4 * Dr);
     }
+    qil_scratch tmp(ctx);
     void *X = nullptr, *Y = nullptr, *Sw = nullptr, *Ww = nullptr, *Wr = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxX * e, &X));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxY * e, &Y));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxW * e, &Wr));
-    if (dt != psi->dtype) QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxS * e, &Sw));
-    if (dt != W->dtype) QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxW * e, &Ww));
-    QIL_TRY(launch_set_one(ctx, dt, X));
+    QIL_TRY(tmp.alloc((size_t)maxX * e, &X));
+    QIL_TRY(tmp.alloc((size_t)maxY * e, &Y));
+    QIL_TRY(tmp.alloc((size_t)maxW * e, &Wr));
+    if (dt != psi->dtype) QIL_TRY(tmp.alloc((size_t)maxS * e, &Sw));
+    if (dt != W->dtype) QIL_TRY(tmp.alloc((size_t)maxW * e, &Ww));
+    QIL_TRY(qil_dev_fill_ones(ctx, dt, X, 1));
     for (int64_t i = 0; i < n; ++i) {
-        const int64_t sl = psi->dims[(size_t)i], sr = psi->dims[(size_t)i + 1];
-        const int64_t Dl = W->dims[(size_t)i], Dr = W->dims[(size_t)i + 1];
         const void *As = nullptr, *Wd = nullptr;
-        QIL_TRY(operand(ctx, dt, psi->dtype, psi->site[(size_t)i], sl * 2 * sr, Sw, &As));
-        QIL_TRY(operand(ctx, dt, W->dtype, W->site[(size_t)i], Dl * 4 * Dr, Ww, &Wd));
-        {
-            const unsigned g = grid_for(Dl * 4 * Dr);
-            const void* Ws = W->site[(size_t)i];
-            if (dt == QIL_F64)
-                hipLaunchKernelGGL((mpo_swap_phys<double, double>), dim3(g), dim3(256), 0, qil_stream(ctx), (const double*)Ws, (double*)Wr,
-                                   (int)Dl, (int)Dr);
-            else if (W->dtype == QIL_C64)
-                hipLaunchKernelGGL((mpo_swap_phys<c64, c64>), dim3(g), dim3(256), 0, qil_stream(ctx), (const c64*)Ws, (c64*)Wr, (int)Dl,
-                                   (int)Dr);
-            else
-                hipLaunchKernelGGL((mpo_swap_phys<double, c64>), dim3(g), dim3(256), 0, qil_stream(ctx), (const double*)Ws, (c64*)Wr,
-                                   (int)Dl, (int)Dr);
-            QIL_HIP(hipGetLastError());
-        }
-        const int64_t rE = sl * Dl * Dl;
-        QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, rE, 2 * sr, sl, X, rE, As, sl, Y, rE));
-        QIL_TRY(gemm_batched_all(ctx, dt, 0, 0, sl * Dl, 2 * Dr, 2 * Dl, Y, sl * Dl, Wd, 2 * Dl, X, sl * Dl, sr, rE * 2, 0,
-                                 sl * Dl * 2 * Dr));
-        QIL_TRY(gemm_batched_all(ctx, dt, 0, 3, sl, 2 * Dr, 2 * Dl, X, sl, Wr, 2 * Dl, Y, sl, Dr * sr, sl * 2 * Dl, 0, sl * 2 * Dr));
-        QIL_TRY(qil_dev_gemm(ctx, dt, 2, 0, sr, Dr * Dr * sr, 2 * sl, As, 2 * sl, Y, 2 * sl, X, sr));
+        QIL_TRY(qil_site_operand(ctx, dt, psi, i, Sw, &As));
+        QIL_TRY(qil_site_operand(ctx, dt, W, i, Ww, &Wd));
+        QIL_TRY(qil_put_mpo_site(ctx, dt, W, i, QIL_SITE_SWAPPED, Wr));
+        QIL_TRY(qil_norm_env_step(ctx, dt, psi->dims[(size_t)i], psi->dims[(size_t)i + 1], W->dims[(size_t)i], W->dims[(size_t)i + 1], 1,
+                                  As, Wd, Wr, X, Y, X, X));
     }
     double h[2];
     QIL_TRY(read_scalar(ctx, dt, X, h));
     *out = sqrt(sqrt(h[0] * h[0] + h[1] * h[1]));
-    for (void* p : {X, Y, Sw, Ww, Wr})
-        if (p) qil_ctx_free(ctx, p);
     return QIL_OK;
 }

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_complex.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -346,7 +347,8 @@ int qil_dev_gemm(qil_context* ctx, int dtype, int opA, int opB, int64_t m, int64
 int qil_dev_gemm_skinny(qil_context* ctx, int dtype, int opA, int opB, int64_t m, int64_t n, int64_t k,
                         const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc);
 // Strided batch of the same product (grid y = batch): operand/result b lives at base + b * stride elements;
-// optionally B of batch b is shifted by b_sel[b * b_sel_step] * b_sel_stride further elements.
+// optionally B of batch b is shifted by b_sel[b * b_sel_step] * b_sel_stride further elements.  A count above the grid's
+// y limit goes out in pieces of 65535.
 struct qil_gemm_batch {
     int64_t count = 1;
     int64_t a_bs = 0, b_bs = 0, c_bs = 0;
@@ -377,6 +379,36 @@ bool qil_dev_gemm_grouped_fits(size_t nproblems);
 // psi has the contraction dtype), X holds nq * chi_l 2 D_r elements.
 int qil_lazy_row_step(qil_context* ctx, int dt, const struct qil_mpo* W, const struct qil_mps* psi, int64_t i, const void* Mc,
                       void* Mn, void* X, void* Wc, void* Ac, int64_t nq, const uint8_t* sel, int64_t sel_step);
+// ---- (qil_contract.hip) the steps the overlap and Born-weight verbs share
+// blocks of 256 threads for `work` items of a grid-stride kernel
+inline unsigned qil_grid_for(long long work, long long cap = 4096) {
+    return (unsigned)std::max<long long>(1, std::min<long long>((work + 255) / 256, cap));
+}
+// p[t * stride] = 1 for t < count: the boundary [1] of an environment (count 1), the start of a batch of rows
+int qil_dev_fill_ones(qil_context* ctx, int dt, void* p, int64_t count, int64_t stride = 1);
+// Site i in the contraction dtype dt and the layout a product reads, into dst.  MPS A[s, sigma, beta]: PLAIN, REVERSED
+// (Ap[beta, sigma, s]).  MPO W[a, s_in, s_out, b]: PLAIN, SWAPPED (Wp[a, s_out, s_in, b]), REVERSED (Wp[b, s_in, s_out, a]),
+// REV_SWAPPED (Wp[b, s_out, s_in, a]), BIT_MAJOR (Wp[a, s_in, b, s_out]).
+enum qil_site_layout { QIL_SITE_PLAIN = 0, QIL_SITE_SWAPPED = 1, QIL_SITE_REVERSED = 2, QIL_SITE_REV_SWAPPED = 3, QIL_SITE_BIT_MAJOR = 4 };
+int qil_put_mps_site(qil_context* ctx, int dt, const struct qil_mps* psi, int64_t i, int layout, void* dst);
+int qil_put_mpo_site(qil_context* ctx, int dt, const struct qil_mpo* W, int64_t i, int layout, void* dst);
+// *use = site i of c as it lies when c has the dtype dt, else its PLAIN copy in buf
+int qil_site_operand(qil_context* ctx, int dt, const struct qil_chain* c, int64_t i, void* buf, const void** use);
+// The environment step of |W psi|^2 on nslots environments E[s', a', a, s] (cl Dl Dl cl each, packed), in two halves so that a
+// caller can project T2 between them:  ket  T1 = E A (in -> s1), T2 = T1 W (s1 -> s2);  bra  T3 = T2 conj(Wr) (s2 -> s1),
+// E' = A^H T3 (s1 -> out).  As, Wd: the sites in dt as they lie, Wr: the MPO site SWAPPED.  s2 may alias in and out.  The mirrored
+// (right-to-left) step is the same call with cl <-> cr, Dl <-> Dr and the REVERSED / REV_SWAPPED operands.
+int qil_norm_env_ket(qil_context* ctx, int dt, int64_t cl, int64_t cr, int64_t Dl, int64_t Dr, int64_t nslots, const void* As,
+                     const void* Wd, const void* in, void* s1, void* s2);
+int qil_norm_env_bra(qil_context* ctx, int dt, int64_t cl, int64_t cr, int64_t Dl, int64_t Dr, int64_t nslots, const void* As,
+                     const void* Wr, const void* s2, void* s1, void* out);
+inline int qil_norm_env_step(qil_context* ctx, int dt, int64_t cl, int64_t cr, int64_t Dl, int64_t Dr, int64_t nslots, const void* As,
+                             const void* Wd, const void* Wr, const void* in, void* s1, void* s2, void* out) {
+    QIL_TRY(qil_norm_env_ket(ctx, dt, cl, cr, Dl, Dr, nslots, As, Wd, in, s1, s2));
+    return qil_norm_env_bra(ctx, dt, cl, cr, Dl, Dr, nslots, As, Wr, s2, s1, out);
+}
+// `bytes` of caller memory into a new block of tmp (stream-synchronised: the source may go away when this returns)
+int qil_upload_bytes(qil_scratch& tmp, const void* host, size_t bytes, void** dev);
 // (qil_hadamard.hip) phi against psi under `verb`: context, paired flag (QIL_EINVAL_ARG), length (QIL_EINVAL_LENGTH), site ids
 // (QIL_EINVAL_SITES), in that order; touches no device
 int qil_check_pair(const char* verb, const struct qil_mps* phi, const struct qil_mps* psi);

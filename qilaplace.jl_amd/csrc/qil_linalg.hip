@@ -4738,20 +4738,24 @@ int qil_dev_gemm_batched(qil_context* ctx, int dtype, int opA, int opB, int64_t 
                          const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
                          const qil_gemm_batch* b) {
     gemm_batch bt;
-    bt.count = (int)b->count;
     bt.a_bs = b->a_bs;
     bt.b_bs = b->b_bs;
     bt.c_bs = b->c_bs;
-    bt.b_sel = b->b_sel;
     bt.b_sel_step = b->b_sel_step;
     bt.b_sel_stride = b->b_sel_stride;
-    if (b->count <= 0) return QIL_OK;
-    QIL_REQUIRE(b->count <= 65535, QIL_EINVAL_ARG, "gemm: batch count %lld exceeds the grid limit", (long long)b->count);
-    if (dtype == QIL_C64)
-        return gemm_dispatch<c64>(ctx, opA, opB, m, n, k, (const c64*)A, lda, (const c64*)B, ldb, (c64*)C, ldc, bt);
     static const int real_op[4] = {0, 1, 1, 0};
-    return gemm_dispatch<double>(ctx, real_op[opA & 3], real_op[opB & 3], m, n, k, (const double*)A, lda,
-                                 (const double*)B, ldb, (double*)C, ldc, bt);
+    // the batch is the grid's y dimension: in pieces of its limit
+    for (int64_t b0 = 0; b0 < b->count; b0 += 65535) {
+        bt.count = (int)std::min<int64_t>(65535, b->count - b0);
+        bt.b_sel = b->b_sel ? b->b_sel + b0 * b->b_sel_step : nullptr;
+        if (dtype == QIL_C64)
+            QIL_TRY(gemm_dispatch<c64>(ctx, opA, opB, m, n, k, (const c64*)A + b0 * b->a_bs, lda, (const c64*)B + b0 * b->b_bs, ldb,
+                                       (c64*)C + b0 * b->c_bs, ldc, bt));
+        else
+            QIL_TRY(gemm_dispatch<double>(ctx, real_op[opA & 3], real_op[opB & 3], m, n, k, (const double*)A + b0 * b->a_bs, lda,
+                                          (const double*)B + b0 * b->b_bs, ldb, (double*)C + b0 * b->c_bs, ldc, bt));
+    }
+    return QIL_OK;
 }
 
 int qil_dev_transpose(qil_context* ctx, int dtype, int conj, int64_t m, int64_t n, const void* A, int64_t lda,

@@ -19,13 +19,6 @@ namespace {
 
 using namespace qil_dev;
 
-__device__ __forceinline__ double shfl_xor_t(double v, int m) { return __shfl_xor(v, m, 64); }
-__device__ __forceinline__ c64 shfl_xor_t(c64 v, int m) {
-    return c64{__shfl_xor(v.re, m, 64), __shfl_xor(v.im, m, 64)};
-}
-__device__ __forceinline__ double one_t(double) { return 1.0; }
-__device__ __forceinline__ c64 one_t(c64) { return c64{1.0, 0.0}; }
-
 struct ChainSite {
     const void* A;  // MPS site
     const void* W;  // MPO site (lazy path) or null
@@ -45,7 +38,7 @@ __global__ __launch_bounds__(kThreads) void coefficient_chain(const ChainSite* _
     T* v_out = v_in + maxchi;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     constexpr int nwaves = kThreads / 64;
-    if (threadIdx.x == 0) v_in[0] = one_t(T{});
+    if (threadIdx.x == 0) v_in[0] = cast_elem<T>(1.0);
     __syncthreads();
     for (int i = 0; i < n; ++i) {
         const ChainSite S = sites[i];
@@ -137,23 +130,7 @@ __global__ __launch_bounds__(kThreads) void lazy_coefficient_chain(const ChainSi
     if (threadIdx.x == 0) out[q] = c64{M[0].re * amplitude, M[0].im * amplitude};
 }
 
-// One step of the dense contraction: T_k[beta + cr*idx'] = sum_alpha T_{k-1}[alpha + cl*idx] * A[alpha, s, beta]
-//   reverse = 0: idx' = 2*idx + s (site 1 = MSB);  reverse = 1: idx' = idx + s * 2^(k-1) (site 1 = LSB)
-template <class T>
-__global__ void select_slice(const T* __restrict__ Tm, long long nb, int cr, const uint8_t* __restrict__ bits,
-                             int n, int site, T* __restrict__ Vn) {
-    const long long total = nb * cr;
-    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < total;
-         t += (long long)gridDim.x * blockDim.x) {
-        const long long q = t % nb;
-        const long long beta = t / nb;
-        const int bit = bits[q * n + site];
-        Vn[t] = bit == 2 ? add_t(Tm[q + nb * (2 * beta)], Tm[q + nb * (1 + 2 * beta)])
-                         : Tm[q + nb * (bit + 2 * beta)];
-    }
-}
-
-// The same three steps in the table form of qil_launch.h: in a lock-step batch (the per-operator read-outs of a damping sweep)
+// The bit-sorted / slice-selecting read-out steps, in the table form of qil_launch.h: in a lock-step batch (the per-operator read-outs of a damping sweep)
 // the `select_slice` of up to 16 chains is ONE launch instead of one per chain and site (r04: 3 072 launches of 3.5 us per sweep
 // of 64 operators, each of which also drained its chain's ring to get onto the stream).
 template <class T>
@@ -196,7 +173,7 @@ struct gather_rows_k {
 };
 template <class T>
 __device__ __forceinline__ void fill_ones_body(const uint3 blockIdx, const uint3 gridDim, T* __restrict__ v, long long n) {
-    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x) v[t] = one_t(T{});
+    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x) v[t] = cast_elem<T>(1.0);
 }
 template <class T>
 struct fill_ones_k {
@@ -223,22 +200,11 @@ struct finish_coeff_k {
     }
 };
 
-template <class T>
-__global__ void fill_ones(T* __restrict__ v, long long n) {
-    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < n;
-         t += (long long)gridDim.x * blockDim.x)
-        v[t] = one_t(T{});
-}
-
+// the plain launch of finish_coeff_body (the lazy read-out's last step)
 template <class T>
 __global__ void finish_coeff(const T* __restrict__ v, long long nb, double amplitude, c64* __restrict__ out) {
-    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < nb;
-         t += (long long)gridDim.x * blockDim.x) {
-        const c64 r = to_c64(v[t]);
-        out[t] = c64{r.re * amplitude, r.im * amplitude};
-    }
+    finish_coeff_body<T>(make_uint3(blockIdx.x, 0, 0), make_uint3(gridDim.x, 1, 1), v, nb, amplitude, out);
 }
-
 
 // ---- dense read-out of a sub-lattice of configurations (grid scans) --------------------------------------
 template <class T>
@@ -265,38 +231,10 @@ __global__ void bit_reverse_scale(const T* __restrict__ in, T* __restrict__ out,
 }
 
 // ---- lazy read-out, GEMM form (many queries, large chi * D) ----------------------------------------------
-template <class TS>
-__global__ void widen_to_c64(const TS* __restrict__ src, c64* __restrict__ dst, long long n) {
-    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x)
-        dst[t] = to_c64(src[t]);
-}
-// W[a, s', s, b] -> Wp[a, s', b, s] (output bit slowest), optionally widened: each output-bit slice becomes one
-// contiguous (D_l x 2 D_r) operand
-template <class TS, class TD>
-__global__ void mpo_site_bit_major(const TS* __restrict__ W, TD* __restrict__ Wp, int Dl, int Dr) {
-    const long long total = 4LL * Dl * Dr;
-    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
-        const int a = (int)(t % Dl);
-        long long u = t / Dl;
-        const int sp = (int)(u & 1);
-        u >>= 1;
-        const int b = (int)(u % Dr);
-        const int bit = (int)(u / Dr);
-        Wp[t] = cast_elem<TD>(W[a + (long long)Dl * (sp + 2 * (bit + 2LL * b))]);
-    }
-}
-template <class T>
-__global__ void lazy_finish(const T* __restrict__ M, long long nb, double amplitude, c64* __restrict__ out) {
-    for (long long q = blockIdx.x * (long long)blockDim.x + threadIdx.x; q < nb; q += (long long)gridDim.x * blockDim.x) {
-        const c64 v = to_c64(M[q]);
-        out[q] = c64{v.re * amplitude, v.im * amplitude};
-    }
-}
-
 // All queries advance together; per site two strided-batch MFMA GEMMs (batch = query):
 //   X_q[alpha, (s', b)] = M_q[alpha, a] W[a, (s', b) | s = bit_q]               (chi_l x D_l) (D_l x 2 D_r)
 //   M'_q[beta, b]     = sum_{(alpha, s')} A[(alpha, s'), beta] X_q[(alpha, s'), b]  (chi_r x 2 chi_l) (2 chi_l x D_r)
-// The MPO site is re-laid once per site with the output bit slowest (a few hundred KB), so each query's
+// The MPO site is re-laid once per site with the output bit slowest (qil_put_mpo_site, QIL_SITE_BIT_MAJOR), so each query's
 // output-bit slice is one contiguous operand picked by the per-batch operand shift of the GEMM; A is used
 // exactly as it lies in HBM, and X_q comes out of the first product in the layout the second one reads.
 int lazy_gemm_path(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64_t nb, const uint8_t* dbits,
@@ -317,54 +255,39 @@ int lazy_gemm_path(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64
     // queries per pass: bounded scratch (X is the big one) and the grid's batch limit
     const long long per_query = (2 * maxM + maxX) * (long long)e;
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nb, 32768), (8LL << 30) / per_query));
+    qil_scratch tmp(ctx);
     void *M0 = nullptr, *M1 = nullptr, *X = nullptr, *Wc = nullptr, *Ac = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(chunk * maxM) * e, &M0));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(chunk * maxM) * e, &M1));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(chunk * maxX) * e, &X));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxW * e, &Wc));
-    if (dt == QIL_C64 && !ac) QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxA * 16, &Ac));
-    int st = QIL_OK;
-    for (int64_t q0 = 0; q0 < nb && st == QIL_OK; q0 += chunk) {
+    QIL_TRY(tmp.alloc((size_t)(chunk * maxM) * e, &M0));
+    QIL_TRY(tmp.alloc((size_t)(chunk * maxM) * e, &M1));
+    QIL_TRY(tmp.alloc((size_t)(chunk * maxX) * e, &X));
+    QIL_TRY(tmp.alloc((size_t)maxW * e, &Wc));
+    if (dt == QIL_C64 && !ac) QIL_TRY(tmp.alloc((size_t)maxA * 16, &Ac));
+    for (int64_t q0 = 0; q0 < nb; q0 += chunk) {
         const int64_t nq = std::min<int64_t>(chunk, nb - q0);
-        const unsigned g1 = (unsigned)std::min<long long>((nq + 255) / 256, 4096);
-        if (dt == QIL_C64) hipLaunchKernelGGL(fill_ones<c64>, dim3(g1), dim3(256), 0, qil_stream(ctx), (c64*)M0, (long long)nq);
-        else hipLaunchKernelGGL(fill_ones<double>, dim3(g1), dim3(256), 0, qil_stream(ctx), (double*)M0, (long long)nq);
+        QIL_TRY(qil_dev_fill_ones(ctx, dt, M0, nq));
         void *Mc = M0, *Mn = M1;
-        for (int64_t i = 0; i < n && st == QIL_OK; ++i) {
-            st = qil_lazy_row_step(ctx, dt, W, psi, i, Mc, Mn, X, Wc, Ac, nq, dbits + q0 * n + i, n);
+        for (int64_t i = 0; i < n; ++i) {
+            QIL_TRY(qil_lazy_row_step(ctx, dt, W, psi, i, Mc, Mn, X, Wc, Ac, nq, dbits + q0 * n + i, n));
             std::swap(Mc, Mn);
         }
-        if (st != QIL_OK) break;
+        const dim3 g1(qil_grid_for(nq));
         if (dt == QIL_C64)
-            hipLaunchKernelGGL(lazy_finish<c64>, dim3(g1), dim3(256), 0, qil_stream(ctx), (const c64*)Mc, (long long)nq,
-                               psi->amplitude, dout + q0);
+            hipLaunchKernelGGL(finish_coeff<c64>, g1, dim3(256), 0, qil_stream(ctx), (const c64*)Mc, (long long)nq, psi->amplitude,
+                               dout + q0);
         else
-            hipLaunchKernelGGL(lazy_finish<double>, dim3(g1), dim3(256), 0, qil_stream(ctx), (const double*)Mc, (long long)nq,
+            hipLaunchKernelGGL(finish_coeff<double>, g1, dim3(256), 0, qil_stream(ctx), (const double*)Mc, (long long)nq,
                                psi->amplitude, dout + q0);
-        if (hipGetLastError() != hipSuccess) st = qil_fail(QIL_EHIP, "lazy coefficient (GEMM form): launch failed");
+        if (hipGetLastError() != hipSuccess) return qil_fail(QIL_EHIP, "lazy coefficient (GEMM form): launch failed");
     }
-    qil_ctx_free(ctx, M0);
-    qil_ctx_free(ctx, M1);
-    qil_ctx_free(ctx, X);
-    qil_ctx_free(ctx, Wc);
-    if (Ac) qil_ctx_free(ctx, Ac);
-    return st;
+    return QIL_OK;
 }
 
-int upload_bits(qil_context* ctx, int64_t nb, int64_t n, const uint8_t* bits, uint8_t** dbits, int max_bit = 1) {
+// the caller's bits, checked, in a block of the call's scratch
+int upload_bits(qil_scratch& tmp, int64_t nb, int64_t n, const uint8_t* bits, uint8_t** dbits, int max_bit = 1) {
     for (int64_t t = 0; t < nb * n; ++t)
         QIL_REQUIRE(bits[t] <= max_bit, QIL_EINVAL_CONFIG, "coefficient: bit value %d outside [0,%d]", (int)bits[t],
                     max_bit);
-    void* p = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(nb * n), &p));
-    hipError_t e = hipMemcpyAsync(p, bits, (size_t)(nb * n), hipMemcpyHostToDevice, qil_stream(ctx));
-    if (e == hipSuccess) e = qil_stream_sync(ctx);  // `bits` is caller memory
-    if (e != hipSuccess) {
-        qil_ctx_free(ctx, p);
-        return qil_fail(QIL_EHIP, "bit upload failed: %s", hipGetErrorString(e));
-    }
-    *dbits = static_cast<uint8_t*>(p);
-    return QIL_OK;
+    return qil_upload_bytes(tmp, bits, (size_t)(nb * n), reinterpret_cast<void**>(dbits));
 }
 
 }  // namespace
@@ -375,28 +298,11 @@ int upload_bits(qil_context* ctx, int64_t nb, int64_t n, const uint8_t* bits, ui
 // needs no widening) the widened MPS site, X is nq * chi_l 2 D_r elements; Mc / Mn are packed per row (chi_l D_l and chi_r D_r).
 int qil_lazy_row_step(qil_context* ctx, int dt, const qil_mpo* W, const qil_mps* psi, int64_t i, const void* Mc, void* Mn, void* X,
                       void* Wc, void* Ac, int64_t nq, const uint8_t* sel, int64_t sel_step) {
-    const bool wc = W->dtype == QIL_C64;
     const long long cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1];
     const long long Dl = W->dims[(size_t)i], Dr = W->dims[(size_t)i + 1];
-    const void* Ap = psi->site[(size_t)i];
-    {
-        const unsigned g = (unsigned)std::min<long long>((Dl * 4 * Dr + 255) / 256, 4096);
-        const void* Ws = W->site[(size_t)i];
-        if (dt == QIL_F64)
-            hipLaunchKernelGGL((mpo_site_bit_major<double, double>), dim3(g), dim3(256), 0, qil_stream(ctx),
-                               (const double*)Ws, (double*)Wc, (int)Dl, (int)Dr);
-        else if (wc)
-            hipLaunchKernelGGL((mpo_site_bit_major<c64, c64>), dim3(g), dim3(256), 0, qil_stream(ctx), (const c64*)Ws,
-                               (c64*)Wc, (int)Dl, (int)Dr);
-        else
-            hipLaunchKernelGGL((mpo_site_bit_major<double, c64>), dim3(g), dim3(256), 0, qil_stream(ctx),
-                               (const double*)Ws, (c64*)Wc, (int)Dl, (int)Dr);
-    }
-    if (Ac) {
-        hipLaunchKernelGGL(widen_to_c64<double>, dim3((unsigned)std::min<long long>((cl * 2 * cr + 255) / 256, 4096)),
-                           dim3(256), 0, qil_stream(ctx), (const double*)Ap, (c64*)Ac, cl * 2 * cr);
-        Ap = Ac;
-    }
+    const void* Ap = nullptr;
+    QIL_TRY(qil_put_mpo_site(ctx, dt, W, i, QIL_SITE_BIT_MAJOR, Wc));
+    QIL_TRY(qil_site_operand(ctx, dt, psi, i, Ac, &Ap));
     qil_gemm_batch b1, b2;
     b1.count = nq;
     b1.a_bs = cl * Dl;
@@ -569,8 +475,9 @@ static int coefficient_impl(const qil_mps* psi, int64_t nb, const uint8_t* bits,
     qil_context* ctx = psi->ctx;
     QIL_TRY(qil_ctx_activate(ctx));
     qil_call_scope call_scope(ctx);
+    qil_scratch tmp(ctx);
     uint8_t* dbits = nullptr;
-    QIL_TRY(upload_bits(ctx, nb, psi->n(), bits, &dbits, max_bit));
+    QIL_TRY(upload_bits(tmp, nb, psi->n(), bits, &dbits, max_bit));
     SortPlan plan;
     if (wants_sort_plan(psi, nb, max_bit)) QIL_TRY(build_sort_plan(ctx, nb, psi->n(), bits, &plan));
     void* dout = nullptr;
@@ -580,7 +487,6 @@ static int coefficient_impl(const qil_mps* psi, int64_t nb, const uint8_t* bits,
     QIL_HIP(hipMemcpyAsync(out, dout, (size_t)nb * 16, hipMemcpyDeviceToHost, qil_stream(ctx)));
     QIL_HIP(qil_stream_sync(ctx));
     qil_ctx_free(ctx, dout);
-    qil_ctx_free(ctx, dbits);
     return QIL_OK;
 }
 
@@ -595,8 +501,9 @@ static int coefficient_impl(const qil_mps* psi, int64_t nb, const uint8_t* bits,
 int qil_apply_coefficient_sweep_dev(const qil_mpo* const* Ws, int64_t nw, const qil_mps* psi, int64_t nb, const uint8_t* bits,
                                     void* dout) {
     qil_context* ctx = psi->ctx;
+    qil_scratch tmp(ctx);
     uint8_t* dbits = nullptr;
-    QIL_TRY(upload_bits(ctx, nb, psi->n(), bits, &dbits, 1));
+    QIL_TRY(upload_bits(tmp, nb, psi->n(), bits, &dbits, 1));
     SortPlan plan;                                        // one plan for every operator's read-out (same configurations)
     if (nb >= 4) QIL_TRY(build_sort_plan(ctx, nb, psi->n(), bits, &plan));
     bool distinct = true;                                 // operators change context for the batch: each must be its own handle
@@ -626,7 +533,6 @@ int qil_apply_coefficient_sweep_dev(const qil_mpo* const* Ws, int64_t nw, const 
     } else {
         for (int64_t j = 0; j < nw; ++j) QIL_TRY(one(Ws[j], psi, j));
     }
-    qil_ctx_free(ctx, dbits);
     if (plan.dmap) qil_ctx_free(ctx, plan.dmap);
     return QIL_OK;
 }
@@ -671,23 +577,22 @@ extern "C" int qil_apply_coefficient_batch(const qil_mpo* W, const qil_mps* psi,
         msz = std::max<long long>(msz, W->dims[(size_t)i + 1] * psi->dims[(size_t)i + 1]);
         msz = std::max<long long>(msz, W->dims[(size_t)i + 1] * psi->dims[(size_t)i]);
     }
+    qil_scratch tmp(ctx);
     uint8_t* dbits = nullptr;
-    QIL_TRY(upload_bits(ctx, nb, n, bits, &dbits));
+    QIL_TRY(upload_bits(tmp, nb, n, bits, &dbits));
     void *scratch = nullptr, *dout = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)nb * 16, &dout));
+    QIL_TRY(tmp.alloc((size_t)nb * 16, &dout));
     // Many queries on a wide product bond: the per-query chains (one workgroup each, vector ALU) give way to
     // batched MFMA GEMMs.  Tuning aid: QIL_LAZY_GEMM_MIN = smallest chi * D that takes the GEMM form.
     static const long long lazy_min = 1024;   // measured crossover: 1.0 vs 2.0 ms at 1024, 0.85 vs 0.77 at 512
     if (nb >= 16 && msz >= lazy_min) {
-        int st = lazy_gemm_path(ctx, W, psi, nb, dbits, (c64*)dout);
-        if (st == QIL_OK && hipMemcpyAsync(out, dout, (size_t)nb * 16, hipMemcpyDeviceToHost, qil_stream(ctx)) != hipSuccess)
-            st = qil_fail(QIL_EHIP, "apply_coefficient: download failed");
-        if (st == QIL_OK && qil_stream_sync(ctx) != hipSuccess) st = qil_fail(QIL_EHIP, "sync failed");
-        qil_ctx_free(ctx, dout);
-        qil_ctx_free(ctx, dbits);
-        return st;
+        QIL_TRY(lazy_gemm_path(ctx, W, psi, nb, dbits, (c64*)dout));
+        if (hipMemcpyAsync(out, dout, (size_t)nb * 16, hipMemcpyDeviceToHost, qil_stream(ctx)) != hipSuccess)
+            return qil_fail(QIL_EHIP, "apply_coefficient: download failed");
+        if (qil_stream_sync(ctx) != hipSuccess) return qil_fail(QIL_EHIP, "sync failed");
+        return QIL_OK;
     }
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(4 * nb * msz) * 16, &scratch));
+    QIL_TRY(tmp.alloc((size_t)(4 * nb * msz) * 16, &scratch));
     qil_dev_table dtab(ctx);
     QIL_TRY(dtab.upload(tab.data(), tab.size() * sizeof(ChainSite)));
     const bool wc = W->dtype == QIL_C64, ac = psi->dtype == QIL_C64;
@@ -703,9 +608,6 @@ extern "C" int qil_apply_coefficient_batch(const qil_mpo* W, const qil_mps* psi,
     QIL_TRY(dtab.release());
     QIL_HIP(hipMemcpyAsync(out, dout, (size_t)nb * 16, hipMemcpyDeviceToHost, qil_stream(ctx)));
     QIL_HIP(qil_stream_sync(ctx));
-    qil_ctx_free(ctx, scratch);
-    qil_ctx_free(ctx, dout);
-    qil_ctx_free(ctx, dbits);
     return QIL_OK;
 }
 

@@ -40,14 +40,7 @@ constexpr int64_t kRunLdsMaxBond[2] = {QIL_RESTRICT_LDS_MAX_F64, QIL_RESTRICT_LD
 constexpr int kThreads = 256;                     // four waves: four output tiles of the absorb, one run of the run kernel
 constexpr int kCopyUnits = kThreads * 8;          // 16-byte units a workgroup copies (32 KiB)
 
-typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ double re_of(double v) { return v; }
-__device__ __forceinline__ double re_of(c64 v) { return v.re; }
-__device__ __forceinline__ double im_of(double) { return 0.0; }
-__device__ __forceinline__ double im_of(c64 v) { return v.im; }
-__device__ __forceinline__ double make_elem(double re, double, double*) { return re; }
-__device__ __forceinline__ c64 make_elem(double re, double im, c64*) { return c64{re, im}; }
 
 // the fused operand load: entry idx of a removed site's factor, slice 0 + slice 1 when the site is summed (off2 != 0)
 template <class T>
@@ -55,18 +48,6 @@ __device__ __forceinline__ T load_factor(const T* __restrict__ p, long long idx,
     T v = p[idx];
     if (off2) v = add_t(v, p[idx + off2]);
     return v;
-}
-
-// one K step of a 16 x 16 tile on v_mfma_f64_16x16x4_f64: D[i][j] += sum_k X[i][k] Y[k][j], lane l supplies x = X[l & 15][l >> 4]
-// and y = Y[l >> 4][l & 15] and holds D[(l >> 4) + 4 reg][l & 15]; c64 through the real / imaginary split
-template <class T>
-__device__ __forceinline__ void mfma_step(T x, T y, d4& rr, d4& ii) {
-    rr = __builtin_amdgcn_mfma_f64_16x16x4f64(re_of(x), re_of(y), rr, 0, 0, 0);
-    if constexpr (sizeof(T) == 16) {
-        rr = __builtin_amdgcn_mfma_f64_16x16x4f64(-im_of(x), im_of(y), rr, 0, 0, 0);
-        ii = __builtin_amdgcn_mfma_f64_16x16x4f64(re_of(x), im_of(y), ii, 0, 0, 0);
-        ii = __builtin_amdgcn_mfma_f64_16x16x4f64(im_of(x), re_of(y), ii, 0, 0, 0);
-    }
 }
 
 // ---- (a) grouped absorb

@@ -23,19 +23,6 @@ namespace {
 
 using namespace qil_dev;
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ double re_of(double v) { return v; }
-__device__ __forceinline__ double re_of(c64 v) { return v.re; }
-__device__ __forceinline__ double im_of(double) { return 0.0; }
-__device__ __forceinline__ double im_of(c64 v) { return v.im; }
-template <class T>
-__device__ __forceinline__ T make_t(double re, double im);
-template <>
-__device__ __forceinline__ double make_t<double>(double re, double) { return re; }
-template <>
-__device__ __forceinline__ c64 make_t<c64>(double re, double im) { return c64{re, im}; }
-
 // u_{r,i} = (splitmix64(seed ^ splitmix64(r n + i)) >> 11) 2^-53, in [0, 1)
 __device__ __forceinline__ double seeded_uniform(uint64_t seed, long long r, int n, int i) {
     const uint64_t h = splitmix64(seed ^ splitmix64((uint64_t)r * (uint64_t)n + (uint64_t)i));
@@ -60,10 +47,6 @@ __device__ __forceinline__ int choose(double q0, double q1, double u, double& fa
 }
 
 // ---- small kernels ---------------------------------------------------------------------------------------------
-template <class T>
-__global__ void set_one(T* __restrict__ p) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) p[0] = cast_elem<T>(1.0);
-}
 // v[r] = 1 (column 0 of the sample rows), p[r] = 1
 template <class T>
 __global__ void start_rows(T* __restrict__ V, double* __restrict__ prob, long long rows) {
@@ -102,8 +85,6 @@ __global__ void site_rows(const T* __restrict__ A, T* __restrict__ As, int cl, i
         As[t] = A[alpha + (long long)cl * (s + 2LL * beta)];
     }
 }
-
-static unsigned grid_for(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, 4096)); }
 
 // ---- fused sampling step ----------------------------------------------------------------------------------------
 constexpr int kRows = 32;               // sample rows per workgroup: two 16-row MFMA tiles
@@ -151,12 +132,7 @@ __global__ __launch_bounds__(kFusedThreads) void sample_fused(const T* __restric
             T a{}, b{};
             if (row < rows && k < cl) a = V[row + rows * k];
             if (col < cr && k < cl) b = Bs[col + (long long)cr * k];
-            rr = __builtin_amdgcn_mfma_f64_16x16x4f64(re_of(a), re_of(b), rr, 0, 0, 0);
-            if constexpr (CX) {
-                rr = __builtin_amdgcn_mfma_f64_16x16x4f64(-im_of(a), im_of(b), rr, 0, 0, 0);
-                ii = __builtin_amdgcn_mfma_f64_16x16x4f64(re_of(a), im_of(b), ii, 0, 0, 0);
-                ii = __builtin_amdgcn_mfma_f64_16x16x4f64(im_of(a), re_of(b), ii, 0, 0, 0);
-            }
+            mfma_step(a, b, rr, ii);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -228,7 +204,7 @@ __global__ __launch_bounds__(kFusedThreads) void sample_fused(const T* __restric
         if (row < rows) {
             const int idx = (ssel[r] * CP + beta) * kLdr + r;
             const double sc = sscl[r];
-            Vn[row + rows * beta] = make_t<T>(Tr[idx] * sc, CX ? Ti[idx] * sc : 0.0);
+            Vn[row + rows * beta] = make_elem(Tr[idx] * sc, CX ? Ti[idx] * sc : 0.0, (T*)nullptr);
         }
     }
 }
@@ -317,8 +293,7 @@ static int right_envs(const qil_mps* psi, const char* verb, void** Rall, std::ve
     T* Rb = static_cast<T*>(*Rall);
     double* logsum = log_norm2 ? static_cast<double*>(inv) + 1 : nullptr;
     if (logsum) QIL_HIP(hipMemsetAsync(logsum, 0, 8, qil_stream(ctx)));
-    hipLaunchKernelGGL(set_one<T>, dim3(1), dim3(64), 0, qil_stream(ctx), Rb + roff[(size_t)n]);
-    QIL_HIP(hipGetLastError());
+    QIL_TRY(qil_dev_fill_ones(ctx, dt, Rb + roff[(size_t)n], 1));
     for (int64_t i = n - 1; i >= 0; --i) {
         const int64_t cl = d[(size_t)i], cr = d[(size_t)i + 1];
         const void* A = psi->site[(size_t)i];
@@ -327,7 +302,7 @@ static int right_envs(const qil_mps* psi, const char* verb, void** Rall, std::ve
         QIL_TRY(qil_dev_gemm(ctx, dt, 0, 2, cl, cl, 2 * cr, Tenv, cl, A, cl, Rb + roff[(size_t)i], cl));
         hipLaunchKernelGGL(env_trace<T>, dim3(1), dim3(256), 0, qil_stream(ctx), (const T*)(Rb + roff[(size_t)i]), (int)cl, (double*)inv,
                            logsum);
-        hipLaunchKernelGGL(env_scale<T>, dim3(grid_for(cl * cl)), dim3(256), 0, qil_stream(ctx), Rb + roff[(size_t)i], (long long)(cl * cl),
+        hipLaunchKernelGGL(env_scale<T>, dim3(qil_grid_for(cl * cl)), dim3(256), 0, qil_stream(ctx), Rb + roff[(size_t)i], (long long)(cl * cl),
                            (const double*)inv);
         QIL_HIP(hipGetLastError());
     }
@@ -386,7 +361,7 @@ static int sample_impl(const qil_mps* psi, int64_t nb, uint64_t seed, const doub
         QIL_TRY(qil_ctx_alloc(ctx, (size_t)sitesum * e, &Ast));
         for (int64_t i = 0; i < n; ++i) {
             const int64_t cl = d[(size_t)i], cr = d[(size_t)i + 1];
-            hipLaunchKernelGGL(site_rows<T>, dim3(grid_for(2 * cl * cr)), dim3(256), 0, qil_stream(ctx), (const T*)psi->site[(size_t)i],
+            hipLaunchKernelGGL(site_rows<T>, dim3(qil_grid_for(2 * cl * cr)), dim3(256), 0, qil_stream(ctx), (const T*)psi->site[(size_t)i],
                                static_cast<T*>(Ast) + soff[(size_t)i], (int)cl, (int)cr);
         }
         QIL_HIP(hipGetLastError());
@@ -398,7 +373,7 @@ static int sample_impl(const qil_mps* psi, int64_t nb, uint64_t seed, const doub
         const long long rows = std::min<long long>(chunk, nb - r0);
         if (uniforms)
             QIL_HIP(hipMemcpyAsync(dU, uniforms + r0 * n, (size_t)(rows * n) * 8, hipMemcpyHostToDevice, qil_stream(ctx)));
-        hipLaunchKernelGGL(start_rows<T>, dim3(grid_for(rows)), dim3(256), 0, qil_stream(ctx), static_cast<T*>(V), (double*)dprob, rows);
+        hipLaunchKernelGGL(start_rows<T>, dim3(qil_grid_for(rows)), dim3(256), 0, qil_stream(ctx), static_cast<T*>(V), (double*)dprob, rows);
         QIL_HIP(hipGetLastError());
         const double* du = static_cast<const double*>(dU);
         for (int64_t i = 0; i < n; ++i) {

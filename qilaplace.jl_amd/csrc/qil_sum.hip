@@ -164,19 +164,9 @@ __global__ __launch_bounds__(kRows) void site_sum_grouped(const SumSite* __restr
 }
 
 // ---- grouped small GEMM: a table of independent products, one 16 x 16 output tile per wave, one launch
-typedef double d4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ double re_of(double v) { return v; }
-__device__ __forceinline__ double re_of(c64 v) { return v.re; }
-__device__ __forceinline__ double im_of(double) { return 0.0; }
-__device__ __forceinline__ double im_of(c64 v) { return v.im; }
-__device__ __forceinline__ double make_elem(double re, double, double*) { return re; }
-__device__ __forceinline__ c64 make_elem(double re, double im, c64*) { return c64{re, im}; }
-
-// v_mfma_f64_16x16x4_f64: lane l supplies A[l & 15][k = l >> 4] and B[k = l >> 4][l & 15] and holds
-// D[row = (l >> 4) + 4 reg][col = l & 15].  c64 through the real / imaginary split (four products per step).
+// the tile step and its lane layout: mfma_step (qil_device_utils.h)
 template <class T>
 __global__ __launch_bounds__(64) void gemm_grouped_small(const qil_gemm_problem* __restrict__ probs, int count) {
-    constexpr bool CX = sizeof(T) == 16;
     const int blk = (int)blockIdx.x;
     const qil_gemm_problem P = probs[last_entry_le<&qil_gemm_problem::tile_begin>(probs, count, blk)];   // tile -> problem
     const int t = blk - P.tile_begin, tm = (P.m + 15) >> 4;
@@ -191,12 +181,7 @@ __global__ __launch_bounds__(64) void gemm_grouped_small(const qil_gemm_problem*
         T a{}, b{};
         if (row < P.m && k < P.k) a = A[row + (long long)P.lda * k];
         if (col < P.n && k < P.k) b = B[k + (long long)P.ldb * col];
-        rr = __builtin_amdgcn_mfma_f64_16x16x4f64(re_of(a), re_of(b), rr, 0, 0, 0);
-        if constexpr (CX) {
-            rr = __builtin_amdgcn_mfma_f64_16x16x4f64(-im_of(a), im_of(b), rr, 0, 0, 0);
-            ii = __builtin_amdgcn_mfma_f64_16x16x4f64(re_of(a), im_of(b), ii, 0, 0, 0);
-            ii = __builtin_amdgcn_mfma_f64_16x16x4f64(im_of(a), re_of(b), ii, 0, 0, 0);
-        }
+        mfma_step(a, b, rr, ii);
     }
     T* __restrict__ Cm = static_cast<T*>(P.C);
 #pragma unroll

@@ -31,8 +31,6 @@ constexpr int kTile = 4 * kThreads;             // candidates per compaction wor
 constexpr int kScoreRows = 32, kScoreGroups = 8;
 constexpr long long kBeamHardCap = 1LL << 29;    // candidate indices 2r + s stay below 2^30 (int)
 
-static unsigned grid_for(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, 4096)); }
-
 __device__ __forceinline__ unsigned long long key_bits(double k) { return (unsigned long long)__double_as_longlong(k); }
 
 // ---- frontier start ----------------------------------------------------------------------------------------------------
@@ -402,13 +400,13 @@ static int top_k_impl(const qil_mps* psi, int64_t k, int64_t beam, uint8_t* bits
             dsel = static_cast<const int*>(sel);
         }
         if (!last) {
-            hipLaunchKernelGGL(gather_frontier<T>, dim3(grid_for(M * cr)), dim3(256), 0, qil_stream(ctx), (const T*)Tm, f, (int)cr,
+            hipLaunchKernelGGL(gather_frontier<T>, dim3(qil_grid_for(M * cr)), dim3(256), 0, qil_stream(ctx), (const T*)Tm, f, (int)cr,
                                (const double*)keys, (const double*)q, (const double*)g[cur], dsel, M, static_cast<T*>(V),
                                (double*)g[1 - cur], (double*)p[1 - cur], static_cast<int*>(anc) + i * fcap);
             cur = 1 - cur;
             f = M;
         } else {
-            hipLaunchKernelGGL(finish_rows<T>, dim3(grid_for(M)), dim3(256), 0, qil_stream(ctx), (const T*)Tm, f, (const double*)g[cur], dsel,
+            hipLaunchKernelGGL(finish_rows<T>, dim3(qil_grid_for(M)), dim3(256), 0, qil_stream(ctx), (const T*)Tm, f, (const double*)g[cur], dsel,
                                M, (const int*)anc, fcap, (int)n, lamp, sgn, (double*)dval, (uint8_t*)dbits);
         }
         QIL_HIP(hipGetLastError());

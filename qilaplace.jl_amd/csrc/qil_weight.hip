@@ -47,30 +47,6 @@ constexpr int kThreads = 1024;                    // sixteen waves: one LDS-boun
 static_assert((3 * kLdsMaxBond[0] * kLdsMaxBond[0] + 2 * kLdsMaxBond[0]) * 8 <= (int64_t)kLdsBytes, "f64 limit exceeds the LDS");
 static_assert((3 * kLdsMaxBond[1] * kLdsMaxBond[1] + 2 * kLdsMaxBond[1]) * 16 <= (int64_t)kLdsBytes, "c64 limit exceeds the LDS");
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ double re_of(double v) { return v; }
-__device__ __forceinline__ double re_of(c64 v) { return v.re; }
-__device__ __forceinline__ double im_of(double) { return 0.0; }
-__device__ __forceinline__ double im_of(c64 v) { return v.im; }
-__device__ __forceinline__ double make_elem(double re, double, double*) { return re; }
-__device__ __forceinline__ c64 make_elem(double re, double im, c64*) { return c64{re, im}; }
-__device__ __forceinline__ double one_t(double) { return 1.0; }
-__device__ __forceinline__ c64 one_t(c64) { return c64{1.0, 0.0}; }
-__device__ __forceinline__ double shfl_xor_t(double v, int m) { return __shfl_xor(v, m, 64); }
-__device__ __forceinline__ c64 shfl_xor_t(c64 v, int m) { return c64{__shfl_xor(v.re, m, 64), __shfl_xor(v.im, m, 64)}; }
-
-// one K step of a 16 x 16 tile on v_mfma_f64_16x16x4_f64: D[i][j] += sum_k X[i][k] Y[k][j], lane l supplies x = X[l & 15][l >> 4]
-// and y = Y[l >> 4][l & 15] and holds D[(l >> 4) + 4 reg][l & 15]; c64 through the real / imaginary split
-template <class T>
-__device__ __forceinline__ void mfma_step(T x, T y, d4& rr, d4& ii) {
-    rr = __builtin_amdgcn_mfma_f64_16x16x4f64(re_of(x), re_of(y), rr, 0, 0, 0);
-    if constexpr (sizeof(T) == 16) {
-        rr = __builtin_amdgcn_mfma_f64_16x16x4f64(-im_of(x), im_of(y), rr, 0, 0, 0);
-        ii = __builtin_amdgcn_mfma_f64_16x16x4f64(re_of(x), im_of(y), ii, 0, 0, 0);
-        ii = __builtin_amdgcn_mfma_f64_16x16x4f64(im_of(x), re_of(y), ii, 0, 0, 0);
-    }
-}
-
 struct WalkSite {
     const void* A;         // the site tensor [cl, 2, cr]
     int cl, cr;
@@ -121,7 +97,7 @@ __global__ __launch_bounds__(kThreads) void weight_walk_lds(const WalkSite* __re
     const uint8_t* __restrict__ bits = spec + (long long)blockIdx.x * n;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr int nwaves = kThreads / 64;
-    if (tid == 0) v_in[0] = one_t(T{});
+    if (tid == 0) v_in[0] = cast_elem<T>(1.0);
     __syncthreads();
     // the vector phase: v <- v A_b through the leading fixed sites, the dot products of coefficient_chain
     int i = 0;
@@ -180,11 +156,6 @@ __global__ __launch_bounds__(kThreads) void weight_walk_lds(const WalkSite* __re
 }
 
 // ---- the GEMM route
-template <class T>
-__global__ void weight_fill_one(T* __restrict__ rho, long long stride, long long rows) {
-    for (long long r = blockIdx.x * (long long)blockDim.x + threadIdx.x; r < rows; r += (long long)gridDim.x * blockDim.x)
-        rho[r * stride] = one_t(T{});
-}
 // rho_r <- P0_r, P1_r or P0_r + P1_r (slice 0 first) by the row's spec at this site
 template <class T>
 __global__ void weight_combine(const T* __restrict__ P0, const T* __restrict__ P1, T* __restrict__ rho, long long stride,
@@ -202,7 +173,7 @@ __global__ void weight_finish(const T* __restrict__ rho, long long stride, long 
         out[r] = amp2 * re_of(rho[r * stride]);
 }
 
-unsigned grid_for(long long work) { return (unsigned)std::min<long long>(std::max<long long>((work + 255) / 256, 1), 65536); }
+constexpr long long kGridCap = 65536;              // workgroups of the GEMM route's element-wise kernels
 
 template <class T>
 int walk_by_gemm(qil_context* ctx, const qil_mps* psi, int64_t nb, const uint8_t* dspec, double amp2, double* dout) {
@@ -218,8 +189,7 @@ int walk_by_gemm(qil_context* ctx, const qil_mps* psi, int64_t nb, const uint8_t
     T* P[2] = {static_cast<T*>(buf[2]), static_cast<T*>(buf[3])};
     for (int64_t r0 = 0; r0 < nb; r0 += chunk) {
         const int64_t rows = std::min<int64_t>(chunk, nb - r0);
-        hipLaunchKernelGGL(weight_fill_one<T>, dim3(grid_for(rows)), dim3(256), 0, qil_stream(ctx), rho, stride, (long long)rows);
-        QIL_HIP(hipGetLastError());
+        QIL_TRY(qil_dev_fill_ones(ctx, dt, rho, rows, stride));
         for (int64_t i = 0; i < n; ++i) {
             const int64_t cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1];
             for (int s = 0; s < 2; ++s) {
@@ -231,11 +201,11 @@ int walk_by_gemm(qil_context* ctx, const qil_mps* psi, int64_t nb, const uint8_t
                 QIL_TRY(qil_dev_gemm_batched(ctx, dt, 0, 0, cl, cr, cl, rho, cl, As, 2 * cl, U, cl, &b1));
                 QIL_TRY(qil_dev_gemm_batched(ctx, dt, 2, 0, cr, cr, cl, As, 2 * cl, U, cl, P[s], cr, &b2));
             }
-            hipLaunchKernelGGL(weight_combine<T>, dim3(grid_for(rows * cr * cr)), dim3(256), 0, qil_stream(ctx), (const T*)P[0],
+            hipLaunchKernelGGL(weight_combine<T>, dim3(qil_grid_for(rows * cr * cr, kGridCap)), dim3(256), 0, qil_stream(ctx), (const T*)P[0],
                                (const T*)P[1], rho, stride, (long long)(cr * cr), (long long)rows, dspec + r0 * n, (int)n, (int)i);
             QIL_HIP(hipGetLastError());
         }
-        hipLaunchKernelGGL(weight_finish<T>, dim3(grid_for(rows)), dim3(256), 0, qil_stream(ctx), (const T*)rho, stride,
+        hipLaunchKernelGGL(weight_finish<T>, dim3(qil_grid_for(rows, kGridCap)), dim3(256), 0, qil_stream(ctx), (const T*)rho, stride,
                            (long long)rows, amp2, dout + r0);
         QIL_HIP(hipGetLastError());
     }
@@ -291,12 +261,8 @@ extern "C" int qil_weight_batch(const qil_mps* psi, int64_t nb, const uint8_t* s
     qil_call_scope call_scope(ctx);
     qil_scratch tmp(ctx);
     void *dspec = nullptr, *dout = nullptr;
-    QIL_TRY(tmp.alloc((size_t)std::max<int64_t>(nb * n, 1), &dspec));
+    QIL_TRY(qil_upload_bytes(tmp, spec, (size_t)(nb * n), &dspec));
     QIL_TRY(tmp.alloc((size_t)nb * sizeof(double), &dout));
-    if (n > 0) {
-        QIL_HIP(hipMemcpyAsync(dspec, spec, (size_t)(nb * n), hipMemcpyHostToDevice, qil_stream(ctx)));
-        QIL_HIP(qil_stream_sync(ctx));                 // `spec` is caller memory
-    }
     const double amp2 = psi->amplitude * psi->amplitude;
     const bool lds = fits_lds(psi), cx = psi->dtype == QIL_C64;
     if (lds && cx) QIL_TRY(walk_in_lds<c64>(ctx, psi, nb, static_cast<const uint8_t*>(dspec), amp2, static_cast<double*>(dout)));

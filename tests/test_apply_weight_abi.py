@@ -81,10 +81,16 @@ def test_the_lazy_weights_have_kernels_of_their_own():
     for kernel in ("apply_weight_seed", "apply_weight_mask", "apply_weight_finish"):
         assert re.search(r"__global__ (__launch_bounds__\(\w+\) )?void " + kernel + r"\(", code), kernel
         assert "hipLaunchKernelGGL(" + kernel + "<" in code, kernel
-    assert "qil_dev_gemm_batched" in code and "qil_scratch" in code
+    assert "qil_scratch" in code
+    # the middle's four products are the shared environment step, strided-batch GEMMs, in two halves around the mask
+    assert code.index("qil_norm_env_ket(") < code.index("hipLaunchKernelGGL(apply_weight_mask<") < code.index("qil_norm_env_bra(")
+    contract = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "qilaplace.jl_amd", "csrc", "qil_contract.hip")).read())
+    for half in ("ket", "bra"):
+        m = re.search(r"\nint qil_norm_env_" + half + r"\(.*?\n}\n", contract, flags=re.S)
+        assert m and "qil_dev_gemm_batched(" in m.group(0), half
     assert "qil_lazy_row_step" in code                                             # the lead step is the read-out's, not a copy
     readout = open(os.path.join(ROOT, "qilaplace.jl_amd", "csrc", "qil_readout.hip")).read()
-    assert readout.count("int qil_lazy_row_step(") == 1 and "st = qil_lazy_row_step(" in readout
+    assert readout.count("int qil_lazy_row_step(") == 1 and "QIL_TRY(qil_lazy_row_step(" in readout
     assert "atomic" not in code and "asm" not in code
     assert 'getenv("QIL_APPLY_WEIGHT_RENV_BYTES")' in code and "kRightEnvBudget" in code and "kChunkBudget = 64LL << 20" in code
 

@@ -205,6 +205,28 @@ def test_rows_across_chunk_boundaries(qil, dts):
     assert np.all(err <= 1e-12), err.max()
 
 
+def test_strided_batches_past_the_grid_limit(qil):
+    """20000 rows that are all in the middle at once: f64, psi bonds (1, 2, 4, 4, 4, 2, 1) under W bonds (1, 2, 2, 2, 2, 2, 1), the
+    first site traced, the last fixed, the rest drawn from {0, 1, 2}.  Per-row temporaries are 2304 B, so one chunk holds every
+    row, and at the interior sites T2 is a strided batch of 20000 * 4 = 80000 products and T3 one of 20000 * 2 * 4 = 160000: both
+    go out in pieces of 65535, the grid's y limit.  Against weight_batch of the formed product, on the same rows."""
+    chi, D, nb = [2, 4, 4, 4, 2], [2, 2, 2, 2, 2], 20000
+    rng = np.random.default_rng(1717)
+    a, w = random_mps_data(chi, rng, F), random_mpo_data(D, rng, F)
+    rows = rng.integers(0, 3, size=(nb, len(a))).astype(np.uint8)
+    rows[:, 0] = TRACE
+    rows[:, -1] = rng.integers(0, 2, size=nb)
+    assert _chunk(chi, D, nb, 8) == nb and BUDGET // nb >= 2304 and nb * 4 > 65535
+    amp = _amp(F)
+    total = amp * amp * float((np.abs(apply_dense(w, a)) ** 2).sum())
+    W, psi = _operands(qil, a, w, False, amp)
+    got = qil.apply_weight_batch(W, psi, rows)
+    formed = qil.weight_batch(qil.apply(W, psi), rows)
+    err = np.abs(got - formed) / total
+    print(f"{nb} rows, batches of {nb * 4} and {nb * 8}: worst deviation {err.max():.2e} of the total weight")
+    assert got.shape == (nb,) and np.all(err <= 1e-12), (int(err.argmax()), err.max())
+
+
 # ---------------------------------------------------------------- 6. run to run
 @pytest.mark.parametrize("case", ["odd", "sat"])
 def test_two_runs_are_bit_equal(qil, case):

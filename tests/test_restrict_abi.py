@@ -73,7 +73,9 @@ def test_the_restriction_has_kernels_of_its_own():
     code = re.sub(r"//[^\n]*", "", _source())
     assert re.search(r"__global__ __launch_bounds__\(kThreads\) void restrict_absorb_grouped\(", code)
     assert re.search(r"__global__ __launch_bounds__\(kThreads\) void restrict_runs_lds\(", code)
-    assert "__builtin_amdgcn_mfma_f64_16x16x4f64" in code
+    assert "mfma_step(" in code                                         # the f64 MFMA tile step: one definition, in the shared header
+    utils = open(os.path.join(ROOT, "qilaplace.jl_amd", "csrc", "qil_device_utils.h")).read()
+    assert utils.count("void mfma_step(") == 1 and utils.count("__builtin_amdgcn_mfma_f64_16x16x4f64(") == 4
     assert code.count("hipLaunchKernelGGL(restrict_absorb_grouped<") == 2       # one launch site per dtype: all sites in one grid
     assert "asm" not in code
 

@@ -123,7 +123,9 @@ def test_the_sum_has_kernels_of_its_own():
     code = re.sub(r"//[^\n]*", "", src)
     assert re.search(r"__global__ __launch_bounds__\(kRows\) void site_sum_grouped\(", code)
     assert re.search(r"__global__ __launch_bounds__\(64\) void gemm_grouped_small\(", code)
-    assert "__builtin_amdgcn_mfma_f64_16x16x4f64" in code
+    assert "mfma_step(" in code                                         # the f64 MFMA tile step: one definition, in the shared header
+    utils = open(os.path.join(ROOT, "qilaplace.jl_amd", "csrc", "qil_device_utils.h")).read()
+    assert utils.count("void mfma_step(") == 1 and utils.count("__builtin_amdgcn_mfma_f64_16x16x4f64(") == 4
     assert "hipMemset" not in code and "qil_dev_zero" not in code      # zeros are stored by the one kernel, not by a memset
     assert code.count("site_sum_grouped<TA, TO, MIXED>") == 1           # one launch site: all sites in one grid
     assert "asm" not in code

@@ -77,7 +77,9 @@ def test_the_null_check_sits_first_in_the_body():
 def test_the_weights_have_a_kernel_of_their_own():
     code = re.sub(r"//[^\n]*", "", _source())
     assert re.search(r"__global__ __launch_bounds__\(kThreads\) void weight_walk_lds\(", code)
-    assert "__builtin_amdgcn_mfma_f64_16x16x4f64" in code
+    assert "mfma_step(" in code                                         # the f64 MFMA tile step: one definition, in the shared header
+    utils = open(os.path.join(ROOT, "qilaplace.jl_amd", "csrc", "qil_device_utils.h")).read()
+    assert utils.count("void mfma_step(") == 1 and utils.count("__builtin_amdgcn_mfma_f64_16x16x4f64(") == 4
     assert code.count("hipLaunchKernelGGL(weight_walk_lds<") == 1       # one launch site: the whole batch in one grid
     assert "qil_dev_table" in code and "qil_dev_gemm_batched" in code
     assert "asm" not in code
