@@ -397,6 +397,47 @@ QIL_API int qil_weight_batch(const qil_mps* psi, int64_t nb, const uint8_t* spec
  * value above 2.  nb = 0 is a no-op (out is not touched).
  * Left out: weights of operators, a device-resident out.                                                                   */
 QIL_API int qil_apply_weight_batch(const qil_mpo* W, const qil_mps* psi, int64_t nb, const uint8_t* spec, double* out);
+/* Perfect sampling of a transformed state, without forming it: nb configurations x drawn with probability
+ * |(W psi)_x|^2 / |W psi|^2, in exact arithmetic qil_sample(qil_apply(W, psi), nb, seed, uniforms, bits_out, prob_out).  bits_out
+ * (host, nb x n_tensors bytes, the layout of qil_coefficient_batch: the rows go straight into qil_apply_coefficient_batch),
+ * prob_out (nullable, host, nb doubles: |(W psi)_x|^2 / |W psi|^2), seed and uniforms are qil_sample's; the amplitude does not
+ * enter.  The operand checks are qil_apply's; the contraction runs in c64 if either operand is c64, a real operand being
+ * widened per site as in qil_apply_weight_batch.  W psi is never formed:
+ *   environments  R_n = [1];  R_k[alpha', a', a, alpha], the right environment of |W psi|^2 with the tensors k+1 .. n traced, by
+ *                 ONE right-to-left pass of the mirrored four-product step of qil_apply_norm (the pass of
+ *                 qil_apply_weight_batch's tail).  Each R_k is scaled on the device by 1 / t_k, t_k = Re sum_{alpha, a}
+ *                 R_k[alpha, a, a, alpha], and the pass goes on from the scaled R_k: only ratios matter afterwards, and a chain
+ *                 of 48 tensors neither overflows nor underflows.  All R_k, k = 1 .. n - 1, are kept for the call:
+ *                 e sum_k (chi_k D_k)^2 bytes, e = 8 (f64) or 16 (c64).  Above 16 GiB the call returns QIL_ENOMEM before it
+ *                 allocates anything, the message naming the bytes needed; QIL_APPLY_SAMPLE_RENV_BYTES overrides the figure
+ *                 (read on each call).  16 GiB is a stated condition, not a measurement: the natural zT operands at n = 24 need
+ *                 about 0.4 GiB, the padded headline shapes (chi 64, D 128) 48 GiB, which the caller has to ask for.
+ *   sweep         row r carries the lazy row vector M[alpha, a] of qil_apply_coefficient_batch, [1] at the start.  At tensor i
+ *                 both children M_s (s = 0, 1) are that read-out's step with the output bit s,
+ *                 M_s[beta, b] = sum W[a, s', s, b] M[alpha, a] A[alpha, s', beta], and q_s = Re(m_s R_{i+1} m_s^H) with
+ *                 m_s = vec(M_s) in the index pairing of qil_apply_weight_batch's prefix-fixed rows (at the last tensor
+ *                 q_s = |M_s|^2).  Then qil_sample's rule verbatim: s = 0 iff u_{r,i} (q_0 + q_1) < q_0, else s = 1;
+ *                 M <- M_s / sqrt(q_s); the probability is multiplied by q_s / (q_0 + q_1).  If q_0 + q_1 <= 0 on a reached
+ *                 prefix (rounding only), the larger q is taken, s = 0 when both are 0, and the probability factor is 0.
+ *   uniforms      the caller's (host, nb x n_tensors, sample-major, each in [0, 1)), or when uniforms is null
+ *                 u_{r,i} = (splitmix64(seed ^ splitmix64(r n + i)) >> 11) 2^-53, n = n_tensors.  Sample r depends only on
+ *                 (W, psi, seed, r): not on nb, on the chunking of the rows or on the route, up to rounding at a threshold.
+ * Rows are processed in chunks under 64 MiB of per-row temporaries (M, the next M, both children, their products with R_{i+1},
+ * the step's X, the partial sums):
+ *   chunk = max(1, min(nb, 32768, 64 MiB / ((5 maxM + maxX) e + 16 ceil(maxM / 64)))),  and over the tensors (chi_l, chi_r the
+ *   bonds of psi, D_l, D_r those of W)  maxM = max(chi_l D_l, chi_r D_r),  maxX = 2 chi_l D_r.
+ * Two routes form the q_s, each a fixed-order sum without atomics (QIL_APPLY_SAMPLE_ROUTE=fused / gemm forces one; unforced, the
+ * operands' bonds alone decide, so a given (W, psi) always takes one route): gemm, R^H [M_0 M_1] as one product and a reduce
+ * kernel; fused, an f64-MFMA kernel that keeps the products in registers and reads each tile of R once for both children.  The
+ * gemm route measured faster or equal at every bond tried (chi D = 24, 504, 2048), so it is the unforced route at every bond.
+ * A result is bit-identical from run to run.  Nothing but the outputs outlives the call, also when an allocation fails midway.
+ * Errors, all before the context is activated: QIL_EINVAL_ARG ("apply_sample: null argument") for a null W or psi or, when
+ * nb > 0, a null bits_out; QIL_EINVAL_ARG for nb < 0; the operand errors of qil_apply; QIL_EINVAL_CONFIG for a uniform outside
+ * [0, 1); QIL_ENOMEM for the environment cap.  After it: QIL_EDOMAIN ("apply_sample: the transformed state has zero norm") when
+ * a trace t_k is <= 0 or not finite.  nb = 0 is a no-op.
+ * Left out: apply_top_k (the beam search on the same scoring step), a device-resident output.                                */
+QIL_API int qil_apply_sample(const qil_mpo* W, const qil_mps* psi, int64_t nb, uint64_t seed, const double* uniforms,
+                             uint8_t* bits_out, double* prob_out);
 
 /* ------------------------------------------------------------------ truncation (K1, K2) */
 /* canonicalize!(psi, direction; center, cutoff=1e-12, maxdim) src/mps.jl:787-847.

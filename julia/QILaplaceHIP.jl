@@ -19,7 +19,7 @@ using ..ApplyMPO: _as_single_site_mpo
 export DeviceMPS, DeviceMPO, to_device, to_host, signal_mps_device, marginal, mps_block, apply_compress,
     compress_mpo!, build_dt_mpo_batch, build_qft_mpo_device, build_zt_qft_chain_device, apply_coefficient_sweep, apply!, rsvd_device, svd_device,
     Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm, sample, top_k,
-    hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress, restrict, weight_batch, apply_weight_batch
+    hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress, restrict, weight_batch, apply_weight_batch, apply_sample
 
 const LIB = get(ENV, "QILHIP_LIB", "libqilhip.so")
 
@@ -355,6 +355,24 @@ function apply_weight_batch(W::DeviceMPO, psi::DeviceMPS, specs::AbstractMatrix{
     GC.@preserve sp check(ccall((:qil_apply_weight_batch, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{Cdouble}),
                                 W.h, psi.h, nb, sp, out))
     return out
+end
+# perfect sampling of W * psi without the product (lazy row vector, shared right environments of |W psi|^2): nsamples x length(psi)
+# bit rows as apply_coefficient takes them and their probabilities |(W psi)_x|^2 / |W psi|^2; uniforms (nsamples x length(psi),
+# each in [0, 1)) replaces the seeded draws
+function apply_sample(W::DeviceMPO, psi::DeviceMPS, nsamples::Integer; seed::Integer=1234, uniforms=nothing)
+    n = length(psi)
+    b = Matrix{UInt8}(undef, n, nsamples)                                       # the ABI's row-major nsamples x n
+    p = Vector{Float64}(undef, nsamples)
+    u = C_NULL
+    if uniforms !== nothing
+        size(uniforms) == (nsamples, n) || throw(ArgumentError("sample: uniforms must have shape ($nsamples, $n)"))
+        all(x -> 0 <= x < 1, uniforms) || throw(ArgumentError("sample: uniforms must lie in [0, 1)"))
+        u = Matrix{Float64}(permutedims(uniforms))
+    end
+    GC.@preserve u check(ccall((:qil_apply_sample, LIB), Cint,
+                               (Ptr{Cvoid}, Ptr{Cvoid}, Int64, UInt64, Ptr{Cdouble}, Ptr{UInt8}, Ptr{Cdouble}),
+                               W.h, psi.h, nsamples, UInt64(seed), u, b, p))
+    return Matrix{UInt8}(permutedims(b)), p
 end
 function mps_to_vector(psi::DeviceMPS; reverse::Bool=false)                                        # mps.jl:716
     d = Ref{Cint}(0)

@@ -677,6 +677,40 @@ def sample(psi, nsamples, seed=1234, uniforms=None, bits=False):
     return _decode_rows(out, paired, bits), probs
 
 
+def apply_sample(W, psi, nsamples, seed=1234, uniforms=None, bits=False):
+    """Perfect sampling of W psi without the product (qil_apply_sample): `nsamples` configurations x drawn with probability
+    |(W psi)_x|^2 / |W psi|^2, with those probabilities -- in exact arithmetic `sample(apply(W, psi), ...)`.  The amplitude does
+    not enter.  `seed`, `uniforms` ((nsamples, n) in [0, 1), checked here before any native call) and the returned
+    configurations are `sample`'s: big-endian indices for a SignalMPS, (k, l) for a ZTMPS, the raw (nsamples, n) uint8 rows with
+    bits=True -- the rows `apply_coefficient_batch(W, psi, rows)` reads.
+
+    The call keeps the right environments of |W psi|^2, 8 or 16 bytes times the sum of (chi_k D_k)^2 over the inner bonds,
+    instead of the product; above 16 GiB it raises MemoryError with the bytes needed (QIL_APPLY_SAMPLE_RENV_BYTES raises the
+    cap).  Where the product fits and the bonds are small, `sample(apply(W, psi), ...)` is faster (4x at the natural zT bonds of
+    n = 20, MEASUREMENTS section 18); this call is for the operands whose product does not fit and breaks even near chi D = 2048."""
+    _require_operator(W, psi)
+    nb = int(nsamples)
+    if nb < 0:
+        raise ValueError("sample: nsamples must be non-negative")
+    n = _ntensors(psi)
+    paired = isinstance(psi, ZTMPS)
+    if not bits and (n if not paired else n // 2) > 62:
+        raise ValueError(f"sample: {n} sites do not fit an integer index; use bits=True")
+    u_ptr = None
+    if uniforms is not None:
+        u = np.ascontiguousarray(uniforms, dtype=np.float64)
+        if u.shape != (nb, n):
+            raise ValueError(f"sample: uniforms must have shape ({nb}, {n}), got {u.shape}")
+        if u.size and not bool(np.all((u >= 0.0) & (u < 1.0))):
+            raise ValueError("sample: uniform outside [0, 1)")
+        u_ptr = u.ctypes.data_as(C.POINTER(C.c_double))
+    out = np.zeros((nb, n), dtype=np.uint8)
+    probs = np.zeros(nb, dtype=np.float64)
+    L.check(L.lib.qil_apply_sample(W.handle, psi.handle, nb, int(seed) & 0xFFFFFFFFFFFFFFFF, u_ptr,
+                                   out.ctypes.data_as(C.POINTER(C.c_uint8)), probs.ctypes.data_as(C.POINTER(C.c_double))))
+    return _decode_rows(out, paired, bits), probs
+
+
 def _decode_rows(out, paired, bits):
     """(nb, n) bit rows -> the configurations `sample` and `top_k` return: the rows themselves (bits=True), (k, l) pairs for a
     ZTMPS (lsb(k) on the main sites, lsb(l) on the copy sites), big-endian indices (site 1 = MSB) otherwise."""
