@@ -435,9 +435,55 @@ QIL_API int qil_apply_weight_batch(const qil_mpo* W, const qil_mps* psi, int64_t
  * nb > 0, a null bits_out; QIL_EINVAL_ARG for nb < 0; the operand errors of qil_apply; QIL_EINVAL_CONFIG for a uniform outside
  * [0, 1); QIL_ENOMEM for the environment cap.  After it: QIL_EDOMAIN ("apply_sample: the transformed state has zero norm") when
  * a trace t_k is <= 0 or not finite.  nb = 0 is a no-op.
- * Left out: apply_top_k (the beam search on the same scoring step), a device-resident output.                                */
+ * The environment pass, its budget (QIL_APPLY_SAMPLE_RENV_BYTES) and the scoring routes (QIL_APPLY_SAMPLE_ROUTE) are shared with
+ * qil_apply_top_k below, the beam search on the same scoring step.
+ * Left out: a device-resident output.                                                                                        */
 QIL_API int qil_apply_sample(const qil_mpo* W, const qil_mps* psi, int64_t nb, uint64_t seed, const double* uniforms,
                              uint8_t* bits_out, double* prob_out);
+/* Top-k coefficient search of a transformed state, without forming it: the k configurations x with the largest |(W psi)_x|,
+ * their values and a bound on what the search may have dropped; in exact arithmetic
+ * qil_top_k(qil_apply(W, psi), k, beam, bits_out, val_out, bound_out).  bits_out: host, k x n_tensors bytes, the layout of
+ * qil_coefficient_batch (the rows go straight into qil_apply_coefficient_batch).  val_out: host, k complex (re, im), the numbers
+ * qil_apply_coefficient_batch gives on those rows (psi's amplitude included), in descending |value| (equal magnitudes: the order
+ * of the candidates).  bound_out: sqrt(largest key dropped before the last tensor) |W psi| |amp|, on the scale of the values;
+ * 0 if nothing was dropped.  The result is certified to be the exact top-k when bound < |value_k| (1 - 1e-10), qil_top_k's slack.
+ * The operand checks are qil_apply's; the contraction runs in c64 if either operand is c64.  W psi is never formed:
+ *   environments  qil_apply_sample's: R_n = [1], R_k[alpha', a', a, alpha] by the mirrored four-product step, each scaled on the
+ *                 device by 1 / t_k, t_k = Re sum R_k[alpha, a, a, alpha].  log |W psi|^2 = sum_{k=0}^{n-1} log t_k (t_0 = the trace
+ *                 of the last step's one number) is kept on the device, added up in the order k = n - 1 .. 0 by one workgroup,
+ *                 and read back with the outputs: a chain of 48 tensors with amplitude e^157 neither overflows nor underflows.
+ *                 The budget is qil_apply_sample's: e sum_k (chi_k D_k)^2 bytes against 16 GiB or QIL_APPLY_SAMPLE_RENV_BYTES
+ *                 (the same variable: the environments are the shared step), QIL_ENOMEM before anything is allocated.
+ *   search        the frontier starts as one row, M = [1], g = 0, p = 1 (row r carries the lazy row vector M[alpha, a] of
+ *                 qil_apply_coefficient_batch up to e^g, and p = its key).  At tensor i the children of every row are that
+ *                 read-out's step with the output bit s, M_s[beta, b] = sum W[a, s', s, b] M[alpha, a] A[alpha, s', beta], and
+ *                 q_s = Re(m_s R_{i+1} m_s^H), m_s = vec(M_s), in the index pairing of qil_apply_sample (at the last tensor
+ *                 R = [1]: q_s = |M_s|^2); a q_s that rounding made negative, or a NaN, counts as 0.  Candidate 2 r + s has
+ *                 key = p (q_s / (q_0 + q_1)), 0 when q_0 + q_1 <= 0.  The at most `beam` largest keys are kept (k at the last
+ *                 tensor), ties at the cut going to the lower candidate 2 r + s; the next frontier is in candidate order;
+ *                 the largest key dropped before the last tensor is recorded.  A kept row becomes M_s / sqrt(q_s) with
+ *                 g' = g + log(q_s) / 2 and p' = key.  At the last tensor value = amp M_s e^g.
+ * Memory.  Held for the whole frontier (at most min(2^(n-1), beam) rows): the rows, maxM e bytes each, both children, 2 maxM e,
+ * and the per-row bookkeeping (keys, q_s, g, p, the selection, 4 bytes per tensor for the back-walk); over the tensors
+ * maxM = max(chi_l D_l, chi_r D_r) and maxX = 2 chi_l D_r (chi the bonds of psi, D those of W), e = 8 (f64) or 16 (c64).  Hence
+ *   beam <= min(2^29, 2^30 / (3 maxM e + 4 n + 64)),  n = n_tensors: a function of the operands' shapes alone, checked before
+ *   the context is activated (1 GiB for the frontier; candidate indices stay below 2^30).
+ * The children's steps (strided batches of at most 32768 rows), their product with R_{i+1} and the step's X run over chunks of
+ * frontier rows under qil_apply_sample's 64 MiB of per-chunk temporaries:
+ *   chunk = max(1, min(largest frontier, 32768, 64 MiB / ((2 maxM + maxX) e + 16 ceil(maxM / 64)))).
+ * The keys of all 2 f candidates stay resident and the selection is over the whole candidate set.  Frontier sizes are
+ * min(2^i, beam), known on the host: no count is read back, and the result is bit-identical from run to run.
+ * Routes: the q_s through qil_apply_sample's two, chosen the same way (gemm unforced at every bond, QIL_APPLY_SAMPLE_ROUTE=fused /
+ * gemm forces one), each the other's check; the selection is qil_top_k's radix select and compaction.
+ * Nothing but the outputs outlives the call, also when an allocation fails midway.
+ * Errors, all before the context is activated, in this order: QIL_EINVAL_ARG ("apply_top_k: null argument") for a null W or
+ * psi; QIL_EINVAL_ARG for k < 0; for beam < k; the operand errors of qil_apply; QIL_EINVAL_ARG for beam above the cap; for
+ * k > 2^n_tensors (n_tensors <= 62); k = 0 is a no-op (the outputs are not touched); QIL_EINVAL_ARG ("apply_top_k: null
+ * argument") for a null output; QIL_ENOMEM for the environment budget.  After it: QIL_EDOMAIN ("apply_top_k: the transformed
+ * state has zero norm") when a trace t_k is <= 0 or not finite.
+ * Left out: a device-resident output, both children of the row step in one strided batch, a batch of (W, psi) pairs.         */
+QIL_API int qil_apply_top_k(const qil_mpo* W, const qil_mps* psi, int64_t k, int64_t beam, uint8_t* bits_out, double* val_out,
+                            double* bound_out);
 
 /* ------------------------------------------------------------------ truncation (K1, K2) */
 /* canonicalize!(psi, direction; center, cutoff=1e-12, maxdim) src/mps.jl:787-847.

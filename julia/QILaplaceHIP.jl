@@ -19,7 +19,7 @@ using ..ApplyMPO: _as_single_site_mpo
 export DeviceMPS, DeviceMPO, to_device, to_host, signal_mps_device, marginal, mps_block, apply_compress,
     compress_mpo!, build_dt_mpo_batch, build_qft_mpo_device, build_zt_qft_chain_device, apply_coefficient_sweep, apply!, rsvd_device, svd_device,
     Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm, sample, top_k,
-    hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress, restrict, weight_batch, apply_weight_batch, apply_sample
+    hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress, restrict, weight_batch, apply_weight_batch, apply_sample, apply_top_k
 
 const LIB = get(ENV, "QILHIP_LIB", "libqilhip.so")
 
@@ -373,6 +373,18 @@ function apply_sample(W::DeviceMPO, psi::DeviceMPS, nsamples::Integer; seed::Int
                                (Ptr{Cvoid}, Ptr{Cvoid}, Int64, UInt64, Ptr{Cdouble}, Ptr{UInt8}, Ptr{Cdouble}),
                                W.h, psi.h, nsamples, UInt64(seed), u, b, p))
     return Matrix{UInt8}(permutedims(b)), p
+end
+# top-k coefficient search of W * psi without the product (the beam search of top_k on the lazy row vector and the right
+# environments of apply_sample): the k bit rows with the largest |(W psi)_x| as apply_coefficient takes them, their values (psi's
+# amplitude included, descending |value|), the bound on what the search dropped, and whether the result is certified exact
+function apply_top_k(W::DeviceMPO, psi::DeviceMPS, k::Integer; beam::Integer=4096)
+    n = length(psi)
+    b = Matrix{UInt8}(undef, n, k)                                              # the ABI's row-major k x n
+    v = Vector{ComplexF64}(undef, k)
+    bound = Ref{Cdouble}(0.0)
+    check(ccall((:qil_apply_top_k, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{UInt8}, Ptr{Cvoid}, Ref{Cdouble}),
+                W.h, psi.h, k, beam, b, v, bound))
+    return Matrix{UInt8}(permutedims(b)), v, bound[], k == 0 || bound[] < abs(v[end]) * (1 - 1e-10)
 end
 function mps_to_vector(psi::DeviceMPS; reverse::Bool=false)                                        # mps.jl:716
     d = Ref{Cint}(0)

@@ -148,6 +148,7 @@ PROTOTYPES = {
     "qil_weight_batch": [_vp, _i64, _pu8, _pdbl],
     "qil_apply_weight_batch": [_vp, _vp, _i64, _pu8, _pdbl],
     "qil_apply_sample": [_vp, _vp, _i64, _u64, _pdbl, _pu8, _pdbl],
+    "qil_apply_top_k": [_vp, _vp, _i64, _i64, _pu8, _pdbl, _pdbl],
     "qil_canonicalize": [_vp, _int, _i64, _dbl, _i64],
     "qil_compress": [_vp, _i64, _dbl, _int],
     "qil_mpo_compress": [_vp, _int, _dbl, _i64],

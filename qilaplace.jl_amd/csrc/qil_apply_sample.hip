@@ -23,7 +23,9 @@
 //     chunk = max(1, min(nb, 32768, kChunkBudget / ((5 maxM + maxX) e + 16 ceil(maxM / 64))))     kChunkBudget = 64 MiB
 // rows: M, the next M, both children and U (5 maxM), the lead's X and the partials; maxM = max(chi_l D_l, chi_r D_r) and
 // maxX = 2 chi_l D_r over the tensors, e the element size of the contraction dtype.
-// Left out: apply_top_k (the beam search on the same scoring step), a device-resident output.
+// The environment pass and the scoring step are also qil_apply_top_k's (qil_apply_topk.hip): qil_apply_right_envs and
+// qil_apply_score_children below, declared in qil_internal.h with the budget and the route they go with.
+// Left out: a device-resident output.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -74,9 +76,10 @@ __device__ __forceinline__ long long paired_column(int k, int chi, int D) { retu
 
 // R (P x P, P = chi D) = X / t, t = Re sum_p X[p + P paired_column(p)].  Every workgroup sums the trace in the same fixed order
 // and scales its own share; X and R are different buffers.  flag[0] = 1 for a trace that is <= 0 or not finite (R = X then).
+// log_trace (nullable): workgroup 0 adds log t to it, so the launches of a pass add up in their stream order.
 template <class T>
 __global__ __launch_bounds__(256) void apply_sample_env_scale(const T* __restrict__ X, T* __restrict__ R, int chi, int D,
-                                                              int* __restrict__ flag) {
+                                                              int* __restrict__ flag, double* __restrict__ log_trace) {
     __shared__ double lds[4];
     const long long P = (long long)chi * D, total = P * P;
     double v[1] = {0.0};
@@ -84,6 +87,7 @@ __global__ __launch_bounds__(256) void apply_sample_env_scale(const T* __restric
     block_sum<1>(v, lds);
     const bool good = v[0] > 0.0 && v[0] <= 1.79769313486231570815e308;
     if (!good && blockIdx.x == 0 && threadIdx.x == 0) flag[0] = 1;
+    if (log_trace && good && blockIdx.x == 0 && threadIdx.x == 0) log_trace[0] += log(v[0]);
     const double s = good ? 1.0 / v[0] : 1.0;
     for (long long t = blockIdx.x * 256LL + threadIdx.x; t < total; t += (long long)gridDim.x * 256) R[t] = scale_t(X[t], s);
 }
@@ -242,8 +246,7 @@ int sample_lazy(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64_t 
     const int64_t n = psi->n();
     const int dt = sizeof(T) == 16 ? QIL_C64 : QIL_F64;
     const int64_t e = (int64_t)sizeof(T);
-    auto bond = [&](int64_t k) { return psi->dims[(size_t)k] * W->dims[(size_t)k]; };
-    long long maxM = 1, maxX = 1, maxW = 1, maxA = 1, maxPass = 1;
+    long long maxM = 1, maxX = 1, maxW = 1, maxA = 1;
     for (int64_t i = 0; i < n; ++i) {
         const long long cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1];
         const long long Dl = W->dims[(size_t)i], Dr = W->dims[(size_t)i + 1];
@@ -251,15 +254,10 @@ int sample_lazy(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64_t 
         maxX = std::max(maxX, 2 * cl * Dr);
         maxW = std::max(maxW, 4 * Dl * Dr);
         maxA = std::max(maxA, 2 * cl * cr);
-        maxPass = std::max({maxPass, cr * cr * Dr * Dr, 2 * cr * Dr * Dr * cl, 2 * cr * Dr * Dl * cl, 2 * cr * Dl * Dl * cl, cl * cl * Dl * Dl});
     }
-    bool fused = fused_by_default(maxM);
-    const char* route = getenv("QIL_APPLY_SAMPLE_ROUTE");
-    if (route && !strcmp(route, "fused")) fused = true;
-    else if (route && !strcmp(route, "gemm")) fused = false;
-    const long long maxPanels = (maxM + kPanel - 1) / kPanel;
-    const int64_t per_row = (5 * maxM + maxX) * e + 16 * maxPanels;
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nb, kMaxChunk), kChunkBudget / per_row));
+    const bool fused = qil_apply_score_fused(maxM);
+    const long long maxPanels = qil_apply_score_panels(maxM);
+    const int64_t chunk = qil_apply_chunk_rows(nb, (5 * maxM + maxX) * e + 16 * maxPanels);
 
     // ---- device memory: everything belongs to `tmp`
     qil_scratch tmp(ctx);
@@ -272,32 +270,14 @@ int sample_lazy(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64_t 
     QIL_TRY(tmp.alloc(sizeof(int), &dflag));
     const uint8_t both[2] = {0, 1};                    // the output bit of every row of a child's step (selector step 0)
     QIL_TRY(qil_upload_bytes(tmp, both, 2, &dsel));
-    std::vector<T*> Rk((size_t)n + 1, nullptr);
-    for (int64_t k = 1; k <= n; ++k) QIL_TRY(tmp.alloc((size_t)(bond(k) * bond(k) * e), (void**)&Rk[(size_t)k]));
+    std::vector<void*> Rk;
 
     // ---- environments, right to left; R_0 (one number, |W psi|^2 on the scale of R_1) is only checked
     {
-        void *X = nullptr, *Y = nullptr;
-        QIL_TRY(tmp.alloc((size_t)(maxPass * e), &X));
-        QIL_TRY(tmp.alloc((size_t)(maxPass * e), &Y));
-        QIL_HIP(hipMemsetAsync(dflag, 0, sizeof(int), qil_stream(ctx)));
-        QIL_TRY(qil_dev_fill_ones(ctx, dt, Rk[(size_t)n], 1));
-        for (int64_t i = n - 1; i >= 0; --i) {
-            const int64_t cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1], Dl = W->dims[(size_t)i], Dr = W->dims[(size_t)i + 1];
-            QIL_TRY(qil_put_mps_site(ctx, dt, psi, i, QIL_SITE_REVERSED, At));
-            QIL_TRY(qil_put_mpo_site(ctx, dt, W, i, QIL_SITE_REVERSED, Wd));
-            QIL_TRY(qil_put_mpo_site(ctx, dt, W, i, QIL_SITE_REV_SWAPPED, Wr));
-            QIL_TRY(qil_norm_env_step(ctx, dt, cr, cl, Dr, Dl, 1, At, Wd, Wr, Rk[(size_t)i + 1], Y, X, X));
-            T* dst = i > 0 ? Rk[(size_t)i] : static_cast<T*>(Y);
-            hipLaunchKernelGGL(apply_sample_env_scale<T>, dim3(qil_grid_for(cl * Dl * cl * Dl)), dim3(256), 0, qil_stream(ctx),
-                               (const T*)X, dst, (int)cl, (int)Dl, (int*)dflag);
-            QIL_HIP(hipGetLastError());
-        }
+        QIL_TRY(qil_apply_right_envs(ctx, tmp, dt, W, psi, At, Wd, Wr, Rk, (int*)dflag, nullptr));
         int bad = 0;
         QIL_TRY(qil_read_back(ctx, &bad, dflag, sizeof(int)));
         QIL_REQUIRE(bad == 0, QIL_EDOMAIN, "apply_sample: the transformed state has zero norm");
-        tmp.free(X);                                   // the pool recycles in stream order
-        tmp.free(Y);
     }
 
     // ---- the sweep, in chunks of rows
@@ -325,18 +305,7 @@ int sample_lazy(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64_t 
             for (int s = 0; s < 2; ++s)
                 QIL_TRY(qil_lazy_row_step(ctx, dt, W, psi, i, Mc, child + s * nr * P, Xb, Wc, As, nr, sel + s, 0));
             int panels = 1;
-            if (fused) {
-                panels = (int)((P + kPanel - 1) / kPanel);
-                hipLaunchKernelGGL(apply_sample_score<T>, dim3((unsigned)((nr + kTileRows - 1) / kTileRows), (unsigned)panels),
-                                   dim3(kScoreThreads), 0, qil_stream(ctx), (const T*)child, (long long)nr, (int)P, (int)cr, (int)Dr,
-                                   (const T*)Rk[(size_t)i + 1], (double*)part);
-            } else {
-                QIL_TRY(qil_dev_gemm(ctx, dt, 2, 0, P, 2 * nr, P, Rk[(size_t)i + 1], P, child, P, Uc, P));
-                hipLaunchKernelGGL(apply_sample_reduce<T>, dim3((unsigned)((2 * nr + kChooseRows - 1) / kChooseRows)),
-                                   dim3(64 * kChooseRows), 0, qil_stream(ctx), (const T*)Uc, (const T*)child, (long long)(2 * nr), (int)P,
-                                   (int)cr, (int)Dr, (double*)part);
-            }
-            QIL_HIP(hipGetLastError());
+            QIL_TRY(qil_apply_score_children(ctx, dt, fused, child, nr, cr, Dr, Rk[(size_t)i + 1], Uc, (double*)part, &panels));
             hipLaunchKernelGGL(apply_sample_choose<T>, dim3((unsigned)((nr + kChooseRows - 1) / kChooseRows)), dim3(64 * kChooseRows), 0,
                                qil_stream(ctx), (const double*)part, panels, (long long)nr, (int)P, (const T*)child, (const double*)dU,
                                seed, (long long)r0, (int)n, (int)i, (uint8_t*)dbits, (double*)dprob, Mn);
@@ -352,6 +321,110 @@ int sample_lazy(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64_t 
 
 }  // namespace
 
+// ---- the steps shared with qil_apply_top_k (qil_internal.h) ----------------------------------------------------------------
+int64_t qil_apply_env_budget() {
+    int64_t budget = kRightEnvBudget;                  // QIL_APPLY_SAMPLE_RENV_BYTES: read on each call
+    if (const char* v = getenv("QIL_APPLY_SAMPLE_RENV_BYTES")) {
+        char* end = nullptr;
+        const long long b = strtoll(v, &end, 10);
+        if (end != v && b >= 0) budget = b;
+    }
+    return budget;
+}
+
+double qil_apply_env_bytes(const qil_mpo* W, const qil_mps* psi) {   // e sum_k (chi_k D_k)^2, k = 1 .. n - 1
+    const bool cx = W->dtype == QIL_C64 || psi->dtype == QIL_C64;
+    double need = 0.0;
+    for (int64_t k = 1; k < psi->n(); ++k) {
+        const double P = (double)psi->dims[(size_t)k] * (double)W->dims[(size_t)k];
+        need += P * P * (cx ? 16.0 : 8.0);
+    }
+    return need;
+}
+
+int64_t qil_apply_score_panels(int64_t P) { return (P + kPanel - 1) / kPanel; }
+
+int64_t qil_apply_chunk_rows(int64_t rows, int64_t per_row_bytes) {
+    return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(rows, kMaxChunk), kChunkBudget / per_row_bytes));
+}
+
+bool qil_apply_score_fused(long long max_bond) {
+    const char* route = getenv("QIL_APPLY_SAMPLE_ROUTE");
+    if (route && !strcmp(route, "fused")) return true;
+    if (route && !strcmp(route, "gemm")) return false;
+    return fused_by_default(max_bond);
+}
+
+template <class T>
+static int right_envs(qil_context* ctx, qil_scratch& tmp, const qil_mpo* W, const qil_mps* psi, void* At, void* Wd, void* Wr,
+                      std::vector<void*>& Rk, int* flag, double* log_trace) {
+    const int64_t n = psi->n();
+    const int dt = sizeof(T) == 16 ? QIL_C64 : QIL_F64;
+    const int64_t e = (int64_t)sizeof(T);
+    auto bond = [&](int64_t k) { return psi->dims[(size_t)k] * W->dims[(size_t)k]; };
+    long long maxPass = 1;
+    for (int64_t i = 0; i < n; ++i) {
+        const long long cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1];
+        const long long Dl = W->dims[(size_t)i], Dr = W->dims[(size_t)i + 1];
+        maxPass = std::max({maxPass, cr * cr * Dr * Dr, 2 * cr * Dr * Dr * cl, 2 * cr * Dr * Dl * cl, 2 * cr * Dl * Dl * cl, cl * cl * Dl * Dl});
+    }
+    Rk.assign((size_t)n + 1, nullptr);
+    for (int64_t k = 1; k <= n; ++k) QIL_TRY(tmp.alloc((size_t)(bond(k) * bond(k) * e), &Rk[(size_t)k]));
+    // right to left; R_0 (one number, |W psi|^2 on the scale of R_1) only serves the flag and the log trace
+    void *X = nullptr, *Y = nullptr;
+    QIL_TRY(tmp.alloc((size_t)(maxPass * e), &X));
+    QIL_TRY(tmp.alloc((size_t)(maxPass * e), &Y));
+    QIL_HIP(hipMemsetAsync(flag, 0, sizeof(int), qil_stream(ctx)));
+    if (log_trace) QIL_HIP(hipMemsetAsync(log_trace, 0, sizeof(double), qil_stream(ctx)));
+    QIL_TRY(qil_dev_fill_ones(ctx, dt, Rk[(size_t)n], 1));
+    for (int64_t i = n - 1; i >= 0; --i) {
+        const int64_t cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1], Dl = W->dims[(size_t)i], Dr = W->dims[(size_t)i + 1];
+        QIL_TRY(qil_put_mps_site(ctx, dt, psi, i, QIL_SITE_REVERSED, At));
+        QIL_TRY(qil_put_mpo_site(ctx, dt, W, i, QIL_SITE_REVERSED, Wd));
+        QIL_TRY(qil_put_mpo_site(ctx, dt, W, i, QIL_SITE_REV_SWAPPED, Wr));
+        QIL_TRY(qil_norm_env_step(ctx, dt, cr, cl, Dr, Dl, 1, At, Wd, Wr, Rk[(size_t)i + 1], Y, X, X));
+        T* dst = static_cast<T*>(i > 0 ? Rk[(size_t)i] : Y);
+        hipLaunchKernelGGL(apply_sample_env_scale<T>, dim3(qil_grid_for(cl * Dl * cl * Dl)), dim3(256), 0, qil_stream(ctx),
+                           (const T*)X, dst, (int)cl, (int)Dl, flag, log_trace);
+        QIL_HIP(hipGetLastError());
+    }
+    tmp.free(X);                                       // the pool recycles in stream order
+    tmp.free(Y);
+    return QIL_OK;
+}
+
+int qil_apply_right_envs(qil_context* ctx, qil_scratch& tmp, int dt, const qil_mpo* W, const qil_mps* psi, void* At, void* Wd,
+                         void* Wr, std::vector<void*>& Rk, int* flag, double* log_trace) {
+    if (dt == QIL_C64) return right_envs<c64>(ctx, tmp, W, psi, At, Wd, Wr, Rk, flag, log_trace);
+    return right_envs<double>(ctx, tmp, W, psi, At, Wd, Wr, Rk, flag, log_trace);
+}
+
+template <class T>
+static int score_children(qil_context* ctx, bool fused, const T* child, int64_t nr, int64_t cr, int64_t Dr, const T* R, T* Uc,
+                          double* part, int* panels) {
+    const int dt = sizeof(T) == 16 ? QIL_C64 : QIL_F64;
+    const int64_t P = cr * Dr;
+    *panels = 1;
+    if (fused) {
+        *panels = (int)qil_apply_score_panels(P);
+        hipLaunchKernelGGL(apply_sample_score<T>, dim3((unsigned)((nr + kTileRows - 1) / kTileRows), (unsigned)*panels),
+                           dim3(kScoreThreads), 0, qil_stream(ctx), child, (long long)nr, (int)P, (int)cr, (int)Dr, R, part);
+    } else {
+        QIL_TRY(qil_dev_gemm(ctx, dt, 2, 0, P, 2 * nr, P, R, P, child, P, Uc, P));
+        hipLaunchKernelGGL(apply_sample_reduce<T>, dim3((unsigned)((2 * nr + kChooseRows - 1) / kChooseRows)),
+                           dim3(64 * kChooseRows), 0, qil_stream(ctx), (const T*)Uc, child, (long long)(2 * nr), (int)P, (int)cr,
+                           (int)Dr, part);
+    }
+    QIL_HIP(hipGetLastError());
+    return QIL_OK;
+}
+
+int qil_apply_score_children(qil_context* ctx, int dt, bool fused, const void* children, int64_t rows, int64_t chi, int64_t D,
+                             const void* R, void* U, double* part, int* panels) {
+    if (dt == QIL_C64) return score_children<c64>(ctx, fused, (const c64*)children, rows, chi, D, (const c64*)R, (c64*)U, part, panels);
+    return score_children<double>(ctx, fused, (const double*)children, rows, chi, D, (const double*)R, (double*)U, part, panels);
+}
+
 extern "C" int qil_apply_sample(const qil_mpo* W, const qil_mps* psi, int64_t nb, uint64_t seed, const double* uniforms,
                                 uint8_t* bits_out, double* prob_out) {
     QIL_REQUIRE(W && psi && (nb <= 0 || bits_out), QIL_EINVAL_ARG, "apply_sample: null argument");
@@ -364,17 +437,8 @@ extern "C" int qil_apply_sample(const qil_mpo* W, const qil_mps* psi, int64_t nb
                         (long long)t, uniforms[t]);
     if (nb == 0) return QIL_OK;
     const bool cx = W->dtype == QIL_C64 || psi->dtype == QIL_C64;
-    int64_t budget = kRightEnvBudget;                  // QIL_APPLY_SAMPLE_RENV_BYTES: read on each call
-    if (const char* v = getenv("QIL_APPLY_SAMPLE_RENV_BYTES")) {
-        char* end = nullptr;
-        const long long b = strtoll(v, &end, 10);
-        if (end != v && b >= 0) budget = b;
-    }
-    double need = 0.0;                                 // e sum_k (chi_k D_k)^2, k = 1 .. n - 1
-    for (int64_t k = 1; k < n; ++k) {
-        const double P = (double)psi->dims[(size_t)k] * (double)W->dims[(size_t)k];
-        need += P * P * (cx ? 16.0 : 8.0);
-    }
+    const int64_t budget = qil_apply_env_budget();
+    const double need = qil_apply_env_bytes(W, psi);
     QIL_REQUIRE(need <= (double)budget, QIL_ENOMEM,
                 "apply_sample: the right environments need %.0f bytes, above the %lld allowed (QIL_APPLY_SAMPLE_RENV_BYTES raises it)",
                 need, (long long)budget);

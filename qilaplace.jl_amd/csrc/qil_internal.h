@@ -409,6 +409,42 @@ inline int qil_norm_env_step(qil_context* ctx, int dt, int64_t cl, int64_t cr, i
 }
 // `bytes` of caller memory into a new block of tmp (stream-synchronised: the source may go away when this returns)
 int qil_upload_bytes(qil_scratch& tmp, const void* host, size_t bytes, void** dev);
+// ---- (qil_apply_sample.hip) the two steps qil_apply_sample and qil_apply_top_k share
+// bytes of right environments a call may keep (16 GiB, or QIL_APPLY_SAMPLE_RENV_BYTES, read on each call) and what (W, psi) needs
+int64_t qil_apply_env_budget();
+double qil_apply_env_bytes(const struct qil_mpo* W, const struct qil_mps* psi);
+// the scoring route of a call: QIL_APPLY_SAMPLE_ROUTE, else the default for the largest product bond
+bool qil_apply_score_fused(long long max_bond);
+// partials per child and row that the fused route writes for a bond P: ceil(P / 64), the panels of its scoring kernel
+int64_t qil_apply_score_panels(int64_t P);
+// rows per chunk: max(1, min(rows, 32768, 64 MiB / per_row_bytes)), the budget of per-row temporaries and the batch limit of
+// the row step's products
+int64_t qil_apply_chunk_rows(int64_t rows, int64_t per_row_bytes);
+// The trace-normalised right environments of |W psi|^2 in the contraction dtype dt: Rk[n] = [1], Rk[k] (k = 1 .. n - 1, bond_k^2
+// elements, bond_k = chi_k D_k) = the mirrored four-product step of the scaled Rk[k + 1] divided by its trace t_k.  Every Rk[k],
+// k = 1 .. n, is a block of tmp; At (2 max chi_l chi_r), Wd and Wr (4 max D_l D_r elements each) are the caller's site scratch.
+// flag (device int, zeroed here) is raised by a trace that is <= 0 or not finite: the caller reads it back and reports under its
+// own name.  log_trace (device double, zeroed here; nullable) receives sum_{k=0}^{n-1} log t_k = log |W psi|^2 without the
+// amplitude, added up in tensor order by one workgroup; with a null log_trace nothing else changes.  Only enqueues.
+int qil_apply_right_envs(qil_context* ctx, qil_scratch& tmp, int dt, const struct qil_mpo* W, const struct qil_mps* psi, void* At,
+                         void* Wd, void* Wr, std::vector<void*>& Rk, int* flag, double* log_trace);
+// Partial sums of q_s = Re(m_s R m_s^H) for both children of `rows` rows: child s of row r at children + (s rows + r) P,
+// P = chi D, R the environment of that bond.  gemm route (fused = false): U (2 rows P elements) receives R^H [M_0 M_1] and
+// *panels = 1; fused route: U is not used and *panels = ceil(P / 64).  part[(s *panels + panel) rows + r], to be summed in panel
+// order.  Only enqueues.
+int qil_apply_score_children(qil_context* ctx, int dt, bool fused, const void* children, int64_t rows, int64_t chi, int64_t D,
+                             const void* R, void* U, double* part, int* panels);
+// ---- (qil_topk.hip) the device-side selection qil_top_k and qil_apply_top_k share
+// sel[0 .. M) = the positions of the M largest of the C non-negative keys (0 < M < C < 2^31), in ascending position; ties at the
+// cut go to the lower position.  An MSD radix select on the keys' bit patterns, then a prefix-scan compaction.  state
+// (qil_dev_select_state_bytes()) and blk (qil_dev_select_block_bytes(C)) are the caller's; dropmax (device, nullable) is
+// raised to the bit pattern of the largest key that was not kept (an atomic max: the caller zeroes it once).  Only enqueues.
+size_t qil_dev_select_state_bytes();
+size_t qil_dev_select_block_bytes(long long C);
+int qil_dev_select_largest(qil_context* ctx, const double* keys, long long C, long long M, int* sel, unsigned long long* dropmax,
+                           void* state, void* blk);
+// the k found rows (device order) to the caller in descending |value|, equal magnitudes in the device's order
+void qil_top_k_deliver(int64_t k, int64_t n, const double* val, const uint8_t* bits, uint8_t* bits_out, double* val_out);
 // (qil_hadamard.hip) phi against psi under `verb`: context, paired flag (QIL_EINVAL_ARG), length (QIL_EINVAL_LENGTH), site ids
 // (QIL_EINVAL_SITES), in that order; touches no device
 int qil_check_pair(const char* verb, const struct qil_mps* phi, const struct qil_mps* psi);

@@ -89,7 +89,6 @@ struct select_state {
     long long need;
     unsigned hist[256];
     unsigned ticket;
-    unsigned long long dropmax;   // bit pattern of the largest key dropped before the last site (all levels)
 };
 
 __global__ void select_init(select_state* st, long long keep) {
@@ -321,6 +320,45 @@ __global__ void finish_rows(const T* __restrict__ Tm, long long f, const double*
     }
 }
 
+}  // namespace
+
+// ---- the selection, for qil_top_k and qil_apply_top_k (qil_internal.h) -----------------------------------------------------
+size_t qil_dev_select_state_bytes() { return sizeof(select_state); }
+size_t qil_dev_select_block_bytes(long long C) { return (size_t)(2 * ((C + kTile - 1) / kTile)) * 4; }
+
+int qil_dev_select_largest(qil_context* ctx, const double* keys, long long C, long long M, int* sel, unsigned long long* dropmax,
+                           void* state, void* blk) {
+    select_state* sst = static_cast<select_state*>(state);
+    const long long nblk = (C + kTile - 1) / kTile;
+    hipLaunchKernelGGL(select_init, dim3(1), dim3(256), 0, qil_stream(ctx), sst, M);
+    // few workgroups: a pass costs ~10 us at 64 of them and ~34 us at 512 (every workgroup's fence and ticket), not bandwidth
+    const unsigned pgrid = (unsigned)std::max<long long>(1, std::min<long long>((C + 2047) / 2048, 512));
+    for (int shift = 56; shift >= 0; shift -= 8)
+        hipLaunchKernelGGL(select_pass, dim3(pgrid), dim3(kThreads), 0, qil_stream(ctx), keys, C, shift, sst);
+    hipLaunchKernelGGL(compact_count, dim3((unsigned)nblk), dim3(kThreads), 0, qil_stream(ctx), keys, C, (const select_state*)sst,
+                       (unsigned*)blk);
+    hipLaunchKernelGGL(compact_scan, dim3(1), dim3(kThreads), 0, qil_stream(ctx), (unsigned*)blk, nblk);
+    hipLaunchKernelGGL(compact_write, dim3((unsigned)nblk), dim3(kThreads), 0, qil_stream(ctx), keys, C, (const select_state*)sst,
+                       (const unsigned*)blk, sel, dropmax);
+    QIL_HIP(hipGetLastError());
+    return QIL_OK;
+}
+
+void qil_top_k_deliver(int64_t k, int64_t n, const double* val, const uint8_t* bits, uint8_t* bits_out, double* val_out) {
+    std::vector<int64_t> ord((size_t)k);
+    std::iota(ord.begin(), ord.end(), 0);
+    auto mag = [&](int64_t j) { return std::hypot(val[2 * j], val[2 * j + 1]); };
+    std::stable_sort(ord.begin(), ord.end(), [&](int64_t a, int64_t b) { return mag(a) > mag(b); });
+    for (int64_t j = 0; j < k; ++j) {
+        const int64_t o = ord[(size_t)j];
+        val_out[2 * j] = val[2 * o];
+        val_out[2 * j + 1] = val[2 * o + 1];
+        std::copy_n(bits + o * n, n, bits_out + j * n);
+    }
+}
+
+namespace {
+
 // ---- the call -----------------------------------------------------------------------------------------------------------
 template <class T>
 static int top_k_impl(const qil_mps* psi, int64_t k, int64_t beam, uint8_t* bits_out, double* val_out, double* bound_out) {
@@ -343,9 +381,8 @@ static int top_k_impl(const qil_mps* psi, int64_t k, int64_t beam, uint8_t* bits
     const T* Rb = static_cast<const T*>(Rall);
 
     // ---- buffers: frontier, both children, T_s R, the per-candidate and per-row bookkeeping, the backtrack
-    const long long nblk_max = (2 * fcap + kTile - 1) / kTile;
     void *V = nullptr, *Tm = nullptr, *Us = nullptr, *keys = nullptr, *q = nullptr, *g[2] = {nullptr, nullptr}, *p[2] = {nullptr, nullptr};
-    void *sel = nullptr, *anc = nullptr, *blk = nullptr, *st = nullptr, *dval = nullptr, *dbits = nullptr;
+    void *sel = nullptr, *anc = nullptr, *blk = nullptr, *st = nullptr, *drop = nullptr, *dval = nullptr, *dbits = nullptr;
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)(fcap * maxchi) * e, &V));
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)(fcap * 2 * maxchi) * e, &Tm));
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)(fcap * 2 * maxchi) * e, &Us));
@@ -357,12 +394,12 @@ static int top_k_impl(const qil_mps* psi, int64_t k, int64_t beam, uint8_t* bits
     }
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)(2 * fcap) * 4, &sel));
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)(std::max<int64_t>(n - 1, 1) * fcap) * 4, &anc));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(2 * nblk_max) * 4, &blk));
-    QIL_TRY(qil_ctx_alloc(ctx, sizeof(select_state), &st));
+    QIL_TRY(qil_ctx_alloc(ctx, qil_dev_select_block_bytes(2 * fcap), &blk));
+    QIL_TRY(qil_ctx_alloc(ctx, qil_dev_select_state_bytes(), &st));
+    QIL_TRY(qil_ctx_alloc(ctx, 8, &drop));   // bit pattern of the largest key dropped before the last site (all levels)
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)k * 16, &dval));
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)(k * n), &dbits));
-    select_state* sst = static_cast<select_state*>(st);
-    QIL_HIP(hipMemsetAsync(&sst->dropmax, 0, 8, qil_stream(ctx)));
+    QIL_HIP(hipMemsetAsync(drop, 0, 8, qil_stream(ctx)));
     hipLaunchKernelGGL(start_frontier<T>, dim3(1), dim3(64), 0, qil_stream(ctx), static_cast<T*>(V), (double*)g[0], (double*)p[0]);
     QIL_HIP(hipGetLastError());
 
@@ -385,18 +422,7 @@ static int top_k_impl(const qil_mps* psi, int64_t k, int64_t beam, uint8_t* bits
         const long long C = 2 * f, M = std::min<long long>(C, last ? k : beam);
         const int* dsel = nullptr;
         if (M < C) {
-            const long long nblk = (C + kTile - 1) / kTile;
-            hipLaunchKernelGGL(select_init, dim3(1), dim3(256), 0, qil_stream(ctx), sst, M);
-            // few workgroups: a pass costs ~10 us at 64 of them and ~34 us at 512 (every workgroup's fence and ticket), not bandwidth
-            const unsigned pgrid = (unsigned)std::max<long long>(1, std::min<long long>((C + 2047) / 2048, 512));
-            for (int shift = 56; shift >= 0; shift -= 8)
-                hipLaunchKernelGGL(select_pass, dim3(pgrid), dim3(kThreads), 0, qil_stream(ctx), (const double*)keys, C, shift, sst);
-            hipLaunchKernelGGL(compact_count, dim3((unsigned)nblk), dim3(kThreads), 0, qil_stream(ctx), (const double*)keys, C,
-                               (const select_state*)sst, (unsigned*)blk);
-            hipLaunchKernelGGL(compact_scan, dim3(1), dim3(kThreads), 0, qil_stream(ctx), (unsigned*)blk, nblk);
-            hipLaunchKernelGGL(compact_write, dim3((unsigned)nblk), dim3(kThreads), 0, qil_stream(ctx), (const double*)keys, C,
-                               (const select_state*)sst, (const unsigned*)blk, (int*)sel, last ? nullptr : &sst->dropmax);
-            QIL_HIP(hipGetLastError());
+            QIL_TRY(qil_dev_select_largest(ctx, (const double*)keys, C, M, (int*)sel, last ? nullptr : (unsigned long long*)drop, st, blk));
             dsel = static_cast<const int*>(sel);
         }
         if (!last) {
@@ -416,21 +442,11 @@ static int top_k_impl(const qil_mps* psi, int64_t k, int64_t beam, uint8_t* bits
     unsigned long long hdrop = 0;
     QIL_HIP(hipMemcpyAsync(hval.data(), dval, (size_t)k * 16, hipMemcpyDeviceToHost, qil_stream(ctx)));
     QIL_HIP(hipMemcpyAsync(hbits.data(), dbits, (size_t)(k * n), hipMemcpyDeviceToHost, qil_stream(ctx)));
-    QIL_HIP(hipMemcpyAsync(&hdrop, &sst->dropmax, 8, hipMemcpyDeviceToHost, qil_stream(ctx)));
+    QIL_HIP(hipMemcpyAsync(&hdrop, drop, 8, hipMemcpyDeviceToHost, qil_stream(ctx)));
     QIL_HIP(qil_stream_sync(ctx));
-    for (void* b : {Rall, V, Tm, Us, keys, q, g[0], g[1], p[0], p[1], sel, anc, blk, st, dval, dbits}) qil_ctx_free(ctx, b);
+    for (void* b : {Rall, V, Tm, Us, keys, q, g[0], g[1], p[0], p[1], sel, anc, blk, st, drop, dval, dbits}) qil_ctx_free(ctx, b);
 
-    // descending |value|; equal magnitudes keep the device's candidate order
-    std::vector<int64_t> ord((size_t)k);
-    std::iota(ord.begin(), ord.end(), 0);
-    auto mag = [&](int64_t j) { return std::hypot(hval[(size_t)(2 * j)], hval[(size_t)(2 * j + 1)]); };
-    std::stable_sort(ord.begin(), ord.end(), [&](int64_t a, int64_t b) { return mag(a) > mag(b); });
-    for (int64_t j = 0; j < k; ++j) {
-        const int64_t o = ord[(size_t)j];
-        val_out[2 * j] = hval[(size_t)(2 * o)];
-        val_out[2 * j + 1] = hval[(size_t)(2 * o + 1)];
-        std::copy_n(hbits.begin() + o * n, n, bits_out + j * n);
-    }
+    qil_top_k_deliver(k, n, hval.data(), hbits.data(), bits_out, val_out);
     double dropped = 0.0;
     std::memcpy(&dropped, &hdrop, 8);
     *bound_out = dropped > 0.0 ? std::exp(0.5 * (std::log(dropped) + log_norm2) + lamp) : 0.0;
