@@ -60,6 +60,24 @@ typedef struct qil_gemm_plan_info {
 QIL_API int qil_gemm_plan(int dtype, int opA, int opB, int64_t m, int64_t n, int64_t k, int64_t lda, int64_t ldb, int64_t ldc,
                           int64_t count, int64_t c_bs, int has_cmap, int skinny_m, qil_gemm_plan_info* plan);
 
+/* Which code path a read-out call takes: THE decision, not a copy of it -- qil_coefficient_batch, qil_coefficient_marginal_batch,
+ * qil_apply_coefficient_sweep and qil_apply_coefficient_batch switch on the value this function returns.  Host only: no context,
+ * no GPU.  verb: which entry is asked; dtype: of the chain that is contracted (QIL_C64 when W or psi is complex); nb queries;
+ * chain_dims: the n + 1 bond dimensions of the chain that is read out -- psi for the plain, marginal and lazy verbs; for the sweep
+ * the product W psi, or psi together with op_dims; op_dims: the operator's n + 1 bond dimensions (required for QIL_READOUT_LAZY,
+ * optional for QIL_READOUT_SWEEP, null otherwise).  *pass_queries (may be null): queries per pass on QIL_ROUTE_LAZY_GEMM -- its
+ * scratch is bounded by 8 GiB and its batch by the grid limit -- and nb on every other route. */
+enum { QIL_READOUT_PLAIN = 0, QIL_READOUT_MARGINAL = 1, QIL_READOUT_SWEEP = 2, QIL_READOUT_LAZY = 3 };
+enum {
+    QIL_ROUTE_CHAIN = 0,        /* one workgroup per query walks the chain (coefficient_chain) */
+    QIL_ROUTE_GEMM_SELECT = 1,  /* all queries together: one GEMM with the whole site, each query keeps its slice (or their sum) */
+    QIL_ROUTE_GEMM_SORTED = 2,  /* all queries together, sorted by their bit at every site: one GEMM per slice, rows gathered */
+    QIL_ROUTE_LAZY_CHAIN = 3,   /* <bits|W psi>, one workgroup per query (lazy_coefficient_chain) */
+    QIL_ROUTE_LAZY_GEMM = 4     /* <bits|W psi>, two strided-batch GEMMs per site, pass_queries queries at a time */
+};
+QIL_API int qil_readout_route(int verb, int dtype, int64_t nb, int64_t n, const int64_t* chain_dims, const int64_t* op_dims,
+                              int* route, int64_t* pass_queries);
+
 /* One operand of qil_gemm_batched_host: a whole host buffer of `elems` elements; the product uses base + off with leading dimension
  * ld, batch b a further b * bs elements on. */
 typedef struct qil_gemm_host_operand {

@@ -167,6 +167,7 @@ PROTOTYPES = {
     "qil_build_zt_qft_chain": [_vp, _i64, _dbl, _i64, _pi64, _pvp, _pint],
     "qil_gemm": [_vp, _int, _int, _int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64],
     "qil_gemm_plan": [_int, _int, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, C.POINTER(GemmPlanInfo)],
+    "qil_readout_route": [_int, _int, _i64, _i64, _pi64, _pi64, _pint, _pi64],
     "qil_gemm_batched_host": [_vp, _int, _int, _int, _i64, _i64, _i64, _pop, _pop, _pop, _i64, _int, _int, _pu8, _i64, _i64,
                               C.POINTER(C.c_int32), _i64],
     "qil_qr_positive": [_vp, _int, _i64, _i64, _vp, _vp, _vp],

@@ -11,9 +11,60 @@
 #include "qil_internal.h"
 #include "qil_launch.h"
 #include "qil_device_utils.h"
+#include "qilaplace_hip_testing.h"
 #include <set>
 #include <mutex>
 #include <map>
+
+// The route of a read-out call: THE decision, not a copy of it -- wants_sort_plan, coefficient_enqueue, the sweep and the lazy verb
+// switch on the value returned here, and qil_readout_route hands the same function to the tests.  dims: the n + 1 bond dimensions
+// of the chain that is read (for QIL_READOUT_SWEEP with wdims: of psi, the product W psi having bonds dims[i] * wdims[i]);
+// wdims: the operator's n + 1 bond dimensions (QIL_READOUT_LAZY, optional for the sweep).  *pass_queries: queries per pass of
+// QIL_ROUTE_LAZY_GEMM (bounded scratch -- X is the big one -- and the grid's batch limit), nb on every other route.
+static int readout_route(int verb, bool cx, int64_t nb, int64_t n, const int64_t* dims, const int64_t* wdims, int64_t* pass_queries) {
+    if (pass_queries) *pass_queries = nb;
+    if (verb == QIL_READOUT_LAZY) {
+        long long msz = 1, maxM = 1, maxX = 1;               // M: Dr*cr, X[s']: Dr*cl
+        for (int64_t i = 0; i < n; ++i) {
+            const long long cl = dims[i], cr = dims[i + 1], Dl = wdims[i], Dr = wdims[i + 1];
+            msz = std::max(msz, std::max(Dr * cr, Dr * cl));
+            maxM = std::max(maxM, std::max(cl * Dl, cr * Dr));
+            maxX = std::max(maxX, cl * 2 * Dr);
+        }
+        // Many queries on a wide product bond: the per-query chains (one workgroup each, vector ALU) give way to batched MFMA
+        // GEMMs.  Measured crossover of chi * D: 1.0 vs 2.0 ms at 1024, 0.85 vs 0.77 at 512.
+        if (!(nb >= 16 && msz >= 1024)) return QIL_ROUTE_LAZY_CHAIN;
+        const long long per_query = (2 * maxM + maxX) * (cx ? 16LL : 8LL);
+        if (pass_queries)
+            *pass_queries = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nb, 32768), (8LL << 30) / per_query));
+        return QIL_ROUTE_LAZY_GEMM;
+    }
+    long long maxchi = 1;
+    for (int64_t i = 1; i <= n; ++i) maxchi = std::max<long long>(maxchi, dims[i] * (wdims ? wdims[i] : 1));
+    // Crossover between one-workgroup-per-query chains and the all-queries-together GEMM forms.  Measured on a 256 x 256 grid
+    // scan (65,536 queries): bond 504 chains 0.40 s vs GEMM 0.09 s; bond 23 chains 4.9 ms vs GEMM 3.2 ms -- many queries favour
+    // the GEMM form at any bond dimension.  Few queries, 40 complex sites: bond 64 chains 0.37 ms vs GEMM 0.55 ms, bond 128 1.07
+    // vs 0.81 ms, bond 512 9.2 vs 2.1 ms.
+    if (!(nb >= 4 && (maxchi >= 128 || (nb >= 1024 && maxchi >= 16)))) return QIL_ROUTE_CHAIN;
+    // a marginal (bit 2) needs both slices of its site: one product with the whole site, then each query keeps its own columns;
+    // plain bits are sorted by site so that every query multiplies with ONE slice
+    return verb == QIL_READOUT_MARGINAL ? QIL_ROUTE_GEMM_SELECT : QIL_ROUTE_GEMM_SORTED;
+}
+
+extern "C" int qil_readout_route(int verb, int dtype, int64_t nb, int64_t n, const int64_t* chain_dims, const int64_t* op_dims,
+                                 int* route, int64_t* pass_queries) {
+    QIL_REQUIRE(route && chain_dims, QIL_EINVAL_ARG, "readout_route: null argument");
+    QIL_REQUIRE(verb >= QIL_READOUT_PLAIN && verb <= QIL_READOUT_LAZY, QIL_EINVAL_ARG, "readout_route: unknown verb %d", verb);
+    QIL_REQUIRE(dtype == QIL_F64 || dtype == QIL_C64, QIL_EINVAL_ARG, "readout_route: unknown dtype %d", dtype);
+    QIL_REQUIRE(nb >= 0 && n >= 1, QIL_EINVAL_ARG, "readout_route: needs nb >= 0 and at least one site");
+    QIL_REQUIRE(verb != QIL_READOUT_LAZY || op_dims, QIL_EINVAL_ARG, "readout_route: the lazy verb needs the operator's bond dimensions");
+    QIL_REQUIRE(!op_dims || verb >= QIL_READOUT_SWEEP, QIL_EINVAL_ARG, "readout_route: only the sweep and the lazy verb take an operator");
+    for (int64_t i = 0; i <= n; ++i)
+        QIL_REQUIRE(chain_dims[i] >= 1 && (!op_dims || op_dims[i] >= 1), QIL_EINVAL_ARG, "readout_route: bond dimension %lld is not positive",
+                    (long long)i);
+    *route = readout_route(verb, dtype == QIL_C64, nb, n, chain_dims, op_dims, pass_queries);
+    return QIL_OK;
+}
 
 namespace {
 
@@ -237,7 +288,7 @@ __global__ void bit_reverse_scale(const T* __restrict__ in, T* __restrict__ out,
 // The MPO site is re-laid once per site with the output bit slowest (qil_put_mpo_site, QIL_SITE_BIT_MAJOR), so each query's
 // output-bit slice is one contiguous operand picked by the per-batch operand shift of the GEMM; A is used
 // exactly as it lies in HBM, and X_q comes out of the first product in the layout the second one reads.
-int lazy_gemm_path(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64_t nb, const uint8_t* dbits,
+int lazy_gemm_path(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64_t nb, int64_t chunk, const uint8_t* dbits,
                    c64* dout) {
     const int64_t n = psi->n();
     const bool wc = W->dtype == QIL_C64, ac = psi->dtype == QIL_C64;
@@ -252,9 +303,7 @@ int lazy_gemm_path(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64
         maxW = std::max(maxW, Dl * 4 * Dr);
         maxA = std::max(maxA, cl * 2 * cr);
     }
-    // queries per pass: bounded scratch (X is the big one) and the grid's batch limit
-    const long long per_query = (2 * maxM + maxX) * (long long)e;
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nb, 32768), (8LL << 30) / per_query));
+    // chunk = queries per pass (readout_route)
     qil_scratch tmp(ctx);
     void *M0 = nullptr, *M1 = nullptr, *X = nullptr, *Wc = nullptr, *Ac = nullptr;
     QIL_TRY(tmp.alloc((size_t)(chunk * maxM) * e, &M0));
@@ -376,15 +425,12 @@ static int build_sort_plan(qil_context* ctx, int64_t nb, int64_t n, const uint8_
     plan->dmap = static_cast<int*>(p);
     return QIL_OK;
 }
-// queries x bonds from which the sorted GEMM form is taken (same crossover as the GEMM form itself)
-static bool wants_sort_plan(const qil_mps* psi, int64_t nb, int max_bit) {
-    if (max_bit > 1 || nb < 4) return false;                 // a marginal (bit 2) needs both slices of its site
-    long long maxchi = 1;
-    for (int64_t i = 0; i < psi->n(); ++i) maxchi = std::max<long long>(maxchi, psi->dims[(size_t)i + 1]);
-    return maxchi >= 128 || (nb >= 1024 && maxchi >= 16);
+// the read-out of psi under `verb` takes the sorted GEMM form: it needs a plan
+static bool wants_sort_plan(const qil_mps* psi, int64_t nb, int verb) {
+    return readout_route(verb, psi->dtype == QIL_C64, nb, psi->n(), psi->dims.data(), nullptr, nullptr) == QIL_ROUTE_GEMM_SORTED;
 }
 
-static int coefficient_enqueue(const qil_mps* psi, int64_t nb, const uint8_t* dbits, void* dout, const SortPlan* plan = nullptr) {
+static int coefficient_enqueue(const qil_mps* psi, int64_t nb, const uint8_t* dbits, void* dout, int verb, const SortPlan* plan) {
     qil_context* ctx = psi->ctx;
     const int64_t n = psi->n();
     std::vector<ChainSite> tab((size_t)n);
@@ -395,13 +441,10 @@ static int coefficient_enqueue(const qil_mps* psi, int64_t nb, const uint8_t* db
         maxchi = std::max<long long>(maxchi, psi->dims[(size_t)i + 1]);
     }
     const size_t esz = qil_elem_size(psi->dtype);
-    // crossover between one-workgroup-per-query chains and the all-queries-together GEMM path (tuning aid:
-    // QIL_COEFF_GEMM_MINCHI)
-    // Measured on a 256 x 256 grid scan (65,536 queries): bond 504 chains 0.40 s vs GEMM 0.09 s; bond 23
-    // chains 4.9 ms vs GEMM 3.2 ms -- many queries favour the GEMM path at any bond dimension.  Few queries, 40
-    // complex sites: bond 64 chains 0.37 ms vs GEMM 0.55 ms, bond 128 1.07 vs 0.81 ms, bond 512 9.2 vs 2.1 ms.
-    static const long long min_chi = 128;
-    if (nb >= 4 && (maxchi >= min_chi || (nb >= 1024 && maxchi >= 16))) {
+    const int route = readout_route(verb, psi->dtype == QIL_C64, nb, n, psi->dims.data(), nullptr, nullptr);
+    if (route != QIL_ROUTE_CHAIN) {
+        const bool sorted = route == QIL_ROUTE_GEMM_SORTED;
+        QIL_REQUIRE(!sorted || (plan && plan->dmap), QIL_EINVAL_ARG, "coefficient: the sorted read-out was not given its plan");
         // Large bonds: all queries advance together, one f64-MFMA GEMM per site.  The site tensor is
         // read ONCE for the whole batch: T (nb x 2 chi_r) = V (nb x chi_l) * A_i (chi_l x 2 chi_r),
         // then each query keeps the column block of its own bit.
@@ -416,7 +459,7 @@ static int coefficient_enqueue(const qil_mps* psi, int64_t nb, const uint8_t* db
         for (int64_t i = 0; i < n; ++i) {
             const int64_t cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1];
             const unsigned g = (unsigned)std::min<long long>((nb * cr + 255) / 256, 65536);
-            if (plan && plan->dmap) {
+            if (sorted) {
                 // bit-sorted: rows [0, n0) take slice 0, rows [n0, nb) slice 1 (slice s of A[alpha, s, beta]: offset s chi_l, ld 2 chi_l)
                 const int64_t z = plan->n0[(size_t)i];
                 const char* site = static_cast<const char*>(psi->site[(size_t)i]);
@@ -478,11 +521,12 @@ static int coefficient_impl(const qil_mps* psi, int64_t nb, const uint8_t* bits,
     qil_scratch tmp(ctx);
     uint8_t* dbits = nullptr;
     QIL_TRY(upload_bits(tmp, nb, psi->n(), bits, &dbits, max_bit));
+    const int verb = max_bit > 1 ? QIL_READOUT_MARGINAL : QIL_READOUT_PLAIN;
     SortPlan plan;
-    if (wants_sort_plan(psi, nb, max_bit)) QIL_TRY(build_sort_plan(ctx, nb, psi->n(), bits, &plan));
+    if (wants_sort_plan(psi, nb, verb)) QIL_TRY(build_sort_plan(ctx, nb, psi->n(), bits, &plan));
     void* dout = nullptr;
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)nb * 16, &dout));
-    QIL_TRY(coefficient_enqueue(psi, nb, dbits, dout, &plan));
+    QIL_TRY(coefficient_enqueue(psi, nb, dbits, dout, verb, &plan));
     if (plan.dmap) qil_ctx_free(ctx, plan.dmap);
     QIL_HIP(hipMemcpyAsync(out, dout, (size_t)nb * 16, hipMemcpyDeviceToHost, qil_stream(ctx)));
     QIL_HIP(qil_stream_sync(ctx));
@@ -504,21 +548,26 @@ int qil_apply_coefficient_sweep_dev(const qil_mpo* const* Ws, int64_t nw, const 
     qil_scratch tmp(ctx);
     uint8_t* dbits = nullptr;
     QIL_TRY(upload_bits(tmp, nb, psi->n(), bits, &dbits, 1));
-    SortPlan plan;                                        // one plan for every operator's read-out (same configurations)
-    if (nb >= 4) QIL_TRY(build_sort_plan(ctx, nb, psi->n(), bits, &plan));
     bool distinct = true;                                 // operators change context for the batch: each must be its own handle
+    bool sorted = false;                                  // some product W_j psi is read out in the sorted GEMM form
     {
         std::set<const qil_mpo*> seen;
         for (int64_t j = 0; j < nw; ++j) {
             QIL_REQUIRE(Ws[j], QIL_EINVAL_ARG, "apply_coefficient_sweep: null operator %lld", (long long)j);
             QIL_REQUIRE(Ws[j]->ctx == ctx, QIL_EINVAL_ARG, "apply: MPO and MPS belong to different contexts");
             distinct = distinct && seen.insert(Ws[j]).second;
+            // (an operator of another length is refused by the apply below)
+            sorted = sorted || (Ws[j]->n() == psi->n() &&
+                                readout_route(QIL_READOUT_SWEEP, true, nb, psi->n(), psi->dims.data(), Ws[j]->dims.data(), nullptr) ==
+                                    QIL_ROUTE_GEMM_SORTED);
         }
     }
+    SortPlan plan;                                        // one plan for every operator's read-out (same configurations)
+    if (sorted) QIL_TRY(build_sort_plan(ctx, nb, psi->n(), bits, &plan));
     auto one = [&](const qil_mpo* W, const qil_mps* state, int64_t j) {
         qil_mps* prod = nullptr;
         QIL_TRY(qil_apply_shared_state(W, state, &prod));
-        const int st = coefficient_enqueue(prod, nb, dbits, static_cast<char*>(dout) + (size_t)(j * nb) * 16, &plan);
+        const int st = coefficient_enqueue(prod, nb, dbits, static_cast<char*>(dout) + (size_t)(j * nb) * 16, QIL_READOUT_SWEEP, &plan);
         qil_mps_destroy(prod);
         return st;
     };
@@ -582,11 +631,10 @@ extern "C" int qil_apply_coefficient_batch(const qil_mpo* W, const qil_mps* psi,
     QIL_TRY(upload_bits(tmp, nb, n, bits, &dbits));
     void *scratch = nullptr, *dout = nullptr;
     QIL_TRY(tmp.alloc((size_t)nb * 16, &dout));
-    // Many queries on a wide product bond: the per-query chains (one workgroup each, vector ALU) give way to
-    // batched MFMA GEMMs.  Tuning aid: QIL_LAZY_GEMM_MIN = smallest chi * D that takes the GEMM form.
-    static const long long lazy_min = 1024;   // measured crossover: 1.0 vs 2.0 ms at 1024, 0.85 vs 0.77 at 512
-    if (nb >= 16 && msz >= lazy_min) {
-        QIL_TRY(lazy_gemm_path(ctx, W, psi, nb, dbits, (c64*)dout));
+    int64_t pass = nb;
+    const bool cx = W->dtype == QIL_C64 || psi->dtype == QIL_C64;
+    if (readout_route(QIL_READOUT_LAZY, cx, nb, n, psi->dims.data(), W->dims.data(), &pass) == QIL_ROUTE_LAZY_GEMM) {
+        QIL_TRY(lazy_gemm_path(ctx, W, psi, nb, pass, dbits, (c64*)dout));
         if (hipMemcpyAsync(out, dout, (size_t)nb * 16, hipMemcpyDeviceToHost, qil_stream(ctx)) != hipSuccess)
             return qil_fail(QIL_EHIP, "apply_coefficient: download failed");
         if (qil_stream_sync(ctx) != hipSuccess) return qil_fail(QIL_EHIP, "sync failed");

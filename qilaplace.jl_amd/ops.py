@@ -1274,6 +1274,28 @@ def gemm_plan(dtype, m, n, k, opA="N", opB="N", lda=None, ldb=None, ldc=None, co
     return {name: int(getattr(info, name)) for name, _ in info._fields_}
 
 
+READOUT_VERBS = {"plain": 0, "marginal": 1, "sweep": 2, "lazy": 3}
+READOUT_ROUTES = ("CHAIN", "GEMM_SELECT", "GEMM_SORTED", "LAZY_CHAIN", "LAZY_GEMM")
+
+
+def readout_route(verb, nb, chain_dims, op_dims=None, dtype=np.float64):
+    """Which code path a read-out call takes (testing hook; needs no GPU): qil_readout_route, the one host function
+    coefficient_batch ("plain"), marginal_batch ("marginal"), apply_coefficient_sweep ("sweep") and apply_coefficient_batch
+    ("lazy") switch on.  chain_dims: the n + 1 bond dimensions, edges included, of the chain that is read -- psi; for the sweep the
+    product W psi, or psi together with op_dims; op_dims: the operator's (lazy: required).  dtype: complex128 when W or psi is
+    complex.  Returns (route name, queries per pass): the second is smaller than nb only on LAZY_GEMM."""
+    code = L.QIL_C64 if np.dtype(dtype) == np.complex128 else L.QIL_F64
+    cd = np.ascontiguousarray(chain_dims, dtype=np.int64)
+    od = None if op_dims is None else np.ascontiguousarray(op_dims, dtype=np.int64)
+    if cd.ndim != 1 or cd.size < 2 or (od is not None and od.shape != cd.shape):
+        raise ValueError("readout_route: bond dimensions are n + 1 entries per chain")
+    route, per_pass = C.c_int(), C.c_int64()
+    L.check(L.lib.qil_readout_route(READOUT_VERBS[verb], code, int(nb), cd.size - 1, cd.ctypes.data_as(C.POINTER(C.c_int64)),
+                                    od.ctypes.data_as(C.POINTER(C.c_int64)) if od is not None else None,
+                                    C.byref(route), C.byref(per_pass)))
+    return READOUT_ROUTES[route.value], per_pass.value
+
+
 def gemm_batched(A, B, Cbuf, m, n, k, opA="N", opB="N", a=(0, None, 0), b=(0, None, 0), c=(0, None, 0), count=1,
                  subtract=False, skinny_m=False, b_sel=None, b_sel_step=0, b_sel_stride=0, cmap=None, cmap_blk=1, ctx=None):
     """The batched / epilogue forms of the MFMA GEMM on host buffers (testing hook).  A, B, Cbuf are flat parent buffers of one

@@ -965,7 +965,8 @@ def test_config3_n24_chi64_D128_full_size_vs_cpu_oracle(qil):
 
 @pytest.mark.parametrize("dt", [np.float64, np.complex128])
 def test_coefficient_batched_gemm_path(qil, dt):
-    """Bonds >= 512 route coefficient_batch through the per-site MFMA GEMM (all queries together)."""
+    """From four queries and a bond of 128 on, coefficient_batch takes the per-site MFMA GEMM (all queries together); which route a
+    shape reaches is asserted in tests/test_readout_cases_oracle.py."""
     rng = np.random.default_rng(41)
     a = random_mps_data([2, 4, 8, 600, 513, 8, 4, 2], rng, dt)
     psi = qil.SignalMPS(a, amplitude=0.9)
