@@ -242,6 +242,30 @@ QIL_API int qil_apply_inner(const qil_mps* phi, const qil_mpo* W, const qil_mps*
 /* norm(W psi) without materialising W psi: the same number as qil_norm(qil_apply(W, psi))
  * (without amplitude, as qil_norm / mps.jl:754-771).  (W, psi) pass the checks of qil_apply.              */
 QIL_API int qil_apply_norm(const qil_mpo* W, const qil_mps* psi, double* out);
+/* Schmidt spectra of every bond (ITensors' svd(...).spec at every cut; no entry of the reference returns them).  S_out: host,
+ * sum_k bond_k doubles; bond k (k = 1 .. N - 1 in tensor order, interleaved for paired chains) owns the bond_k slots that start
+ * at the sum of the earlier bond dimensions, as qil_mps_bond_dims reports them at the time of the call.  Each block holds the
+ * Schmidt values of the NORMALISED state at that cut in descending order (their squares sum to 1); slots beyond what the cut
+ * can carry (non-minimal or rank-deficient bonds) are exact zeros.  The accuracy is absolute, a modest multiple of
+ * N chi eps on the unit scale; relative accuracy of tiny values is not promised (the QR sweeps do not preserve it).
+ * norm_out (nullable): |psi| without the amplitude, the number qil_norm returns, from the logarithms of what the sweep divides
+ * out -- finite also where |psi|^2 is outside the double range.  psi is not modified: the work happens on a clone in pool
+ * memory.  N = 1: no bonds, S_out is not written (may be NULL), norm_out is.
+ *   route     exact right-orthonormal gauge of the clone, then a left-to-right sweep of thin QRs that keeps the triangular carry
+ *             of every bond; the singular values of all carries in ONE launch (one workgroup per bond, values-only one-sided
+ *             Jacobi in LDS) while the bond is <= 138 (f64) / 97 (c64); larger bonds, and any whose iteration reaches its
+ *             sweep cap, through the one-matrix SVD.  QIL_SPECTRA_ROUTE=svd (read on each call) sends every bond there.
+ *   syncs     the packed values, the logarithms and the per-bond flags come back in one read-back at the end; before it the call
+ *             reads one flag back (a zero or non-finite site, ahead of the gauge sweep), and every QR step of the two sweeps
+ *             reads its orthonormality measure.
+ * Errors: QIL_EINVAL_ARG "bond_spectra: null argument" (psi, or S_out with N > 1); QIL_EDOMAIN "bond_spectra: zero or
+ * non-finite state" for a site or a carry that is exactly zero or holds a non-finite entry -- a state that vanishes only by
+ * cancellation between non-zero sites is reported so when its carry comes out exactly zero; otherwise the call returns the
+ * spectrum of the rounding residue with a norm_out at rounding level of the sites' scale.  QIL_ENOMEM leaves nothing allocated. */
+QIL_API int qil_bond_spectra(const qil_mps* psi, double* S_out, double* norm_out);
+/* The same for an operator: the operator-Schmidt values of W / |W|_F at every bond (physical block 4 wide), layout by
+ * qil_mpo_bond_dims; norm_out (nullable) receives |W|_F.                                                              */
+QIL_API int qil_mpo_bond_spectra(const qil_mpo* W, double* S_out, double* norm_out);
 
 /* ------------------------------------------------------------------ element-wise products, adjoints (no reference counterpart) */
 /* The element-wise (Hadamard) product out_x = (conj?)(phi_x) psi_x, materialised: amplitude amp_phi * amp_psi, dtype

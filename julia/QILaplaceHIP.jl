@@ -19,7 +19,7 @@ using ..ApplyMPO: _as_single_site_mpo
 export DeviceMPS, DeviceMPO, to_device, to_host, signal_mps_device, marginal, mps_block, apply_compress,
     compress_mpo!, build_dt_mpo_batch, build_qft_mpo_device, build_zt_qft_chain_device, apply_coefficient_sweep, apply!, rsvd_device, svd_device,
     Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm, sample, top_k,
-    hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress, restrict, weight_batch, apply_weight_batch, apply_sample, apply_top_k
+    hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress, restrict, weight_batch, apply_weight_batch, apply_sample, apply_top_k, bond_spectra
 
 const LIB = get(ENV, "QILHIP_LIB", "libqilhip.so")
 
@@ -238,6 +238,38 @@ function apply_norm(W::DeviceMPO, psi::DeviceMPS)                              #
     v = Ref{Cdouble}(0)
     check(ccall((:qil_apply_norm, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Cdouble}), W.h, psi.h, v))
     return v[]
+end
+# Schmidt values of the normalised state (operator-Schmidt values of W / |W|_F) at every bond: one descending vector per bond
+# in tensor order, exact zeros beyond what the cut can carry; the operand is not modified.  return_norm adds the norm (without
+# the amplitude, as `norm`; |W|_F for an operator)
+function _split_spectra(vals::Vector{Float64}, dims::Vector{Int64})
+    out = Vector{Vector{Float64}}()
+    at = 0
+    for d in dims
+        push!(out, vals[at + 1:at + Int(d)])
+        at += Int(d)
+    end
+    return out
+end
+function bond_spectra(psi::DeviceMPS; return_norm::Bool=false)
+    n = length(psi.sites)
+    dims = Vector{Int64}(undef, max(n - 1, 0))
+    check(ccall((:qil_mps_bond_dims, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}), psi.h, dims))
+    vals = zeros(Float64, max(1, sum(dims)))
+    nrm = Ref{Cdouble}(0)
+    check(ccall((:qil_bond_spectra, LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ref{Cdouble}), psi.h, vals, nrm))
+    spec = _split_spectra(vals, dims)
+    return return_norm ? (spec, nrm[]) : spec
+end
+function bond_spectra(W::DeviceMPO; return_norm::Bool=false)
+    n = length(W.sites)
+    dims = Vector{Int64}(undef, max(n - 1, 0))
+    check(ccall((:qil_mpo_bond_dims, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}), W.h, dims))
+    vals = zeros(Float64, max(1, sum(dims)))
+    nrm = Ref{Cdouble}(0)
+    check(ccall((:qil_mpo_bond_spectra, LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ref{Cdouble}), W.h, vals, nrm))
+    spec = _split_spectra(vals, dims)
+    return return_norm ? (spec, nrm[]) : spec
 end
 # perfect sampling (ITensors' sample on device chains): nsamples x length(psi) bit rows, sample-major as
 # coefficient takes them, and their probabilities |psi_x|^2 / |psi|^2 (the amplitude does not enter)

@@ -16,7 +16,8 @@ from .containers import (Context, default_context, set_default_context, device_c
                          SignalMPS, ZTMPS, SingleSiteMPO, PairedSiteMPO)
 from .ops import (apply, apply_compress, apply_compress_batch, mpo_compress, compress_batch, mpo_compress_batch, mps_block, coefficient, coefficient_batch, apply_coefficient_batch, apply_coefficient_sweep,  # noqa: F401
                   marginal_batch, coefficient_grid, laplace_values,
-                  mps_to_vector, norm, inner, apply_norm, distance, apply_distance, sample, apply_sample, top_k, apply_top_k, hadamard, hadamard_compress, diagonal_mpo, adjoint, convolve, correlate,
+                  mps_to_vector, norm, inner, apply_norm, distance, apply_distance, bond_spectra, mpo_bond_spectra, entanglement_entropy,
+                  truncation_error_bounds, required_maxdim, sample, apply_sample, top_k, apply_top_k, hadamard, hadamard_compress, diagonal_mpo, adjoint, convolve, correlate,
                   power_spectrum, linear_combination, linear_combination_compress, add, sub, scale, exponential_tensors,
                   exponential_mps, exponential_sum, restrict, zt_row, zt_column, copy_marginal, weight_batch, weight, bit_probabilities,
                   range_weight, weight_quantiles, zt_row_weights, zt_column_weights, apply_weight_batch, apply_weight,
@@ -33,7 +34,8 @@ __all__ = [
     "Context", "default_context", "set_default_context", "device_count", "host_cpu_budget",
     "SignalMPS", "ZTMPS", "SingleSiteMPO", "PairedSiteMPO",
     "apply", "apply_compress", "apply_compress_batch", "coefficient", "coefficient_batch", "apply_coefficient_batch", "apply_coefficient_sweep", "marginal_batch", "coefficient_grid", "laplace_values", "mps_to_vector", "norm",
-    "inner", "apply_norm", "distance", "apply_distance", "sample", "apply_sample", "top_k", "apply_top_k",
+    "inner", "apply_norm", "distance", "apply_distance", "bond_spectra", "mpo_bond_spectra", "entanglement_entropy",
+    "truncation_error_bounds", "required_maxdim", "sample", "apply_sample", "top_k", "apply_top_k",
     "hadamard", "hadamard_compress", "diagonal_mpo", "adjoint", "convolve", "correlate", "power_spectrum",
     "linear_combination", "linear_combination_compress", "add", "sub", "scale", "exponential_tensors", "exponential_mps",
     "exponential_sum", "restrict", "zt_row", "zt_column", "copy_marginal",

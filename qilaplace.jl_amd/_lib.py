@@ -136,6 +136,8 @@ PROTOTYPES = {
     "qil_inner": [_vp, _vp, _pdbl],
     "qil_apply_inner": [_vp, _vp, _vp, _pdbl],
     "qil_apply_norm": [_vp, _vp, _pdbl],
+    "qil_bond_spectra": [_vp, _pdbl, _pdbl],
+    "qil_mpo_bond_spectra": [_vp, _pdbl, _pdbl],
     "qil_sample": [_vp, _i64, _u64, _pdbl, _pu8, _pdbl],
     "qil_top_k": [_vp, _i64, _i64, _pu8, _pdbl, _pdbl],
     "qil_hadamard": [_vp, _int, _vp, _pvp],

@@ -460,6 +460,9 @@ long long qil_product_sites(const qil_chain* left, const qil_chain* right, const
 // w = nb (re, im) weights with the amplitudes folded in, odt = result dtype
 int qil_sum_compress_impl(qil_context* ctx, const struct qil_mps* const* terms, int64_t nb, const double* w, int odt,
                           int64_t maxdim, double tol, int sweeps, int64_t zip_maxdim, struct qil_mps** out);
+// (qil_truncate.hip) the exact gauge sweep of any chain (MPS or MPO) towards `center` (0 = the end of the direction): thin QR
+// where the site is tall enough, the SVD at cut-off 0 otherwise; nothing is truncated.  Context active, call scope open.
+int qil_gauge_exact(struct qil_chain* c, int direction, int64_t center);
 // |r_jj|^2 (j < n <= 1024) of a triangular factor on the device, to the host
 int qil_dev_diag_abs2(qil_context* ctx, int dtype, const void* R, int64_t ldr, int64_t n, double* host_out);
 // At (n x m, ldt) = A^T (conj = 0) or A^H (conj = 1)

@@ -998,6 +998,12 @@ struct widen_f64_k {
 
 }  // namespace
 
+// the exact QR gauge sweep for the other translation units (qil_spectra.hip): canonicalize_impl(c, direction, center, 0, none,
+// gauge_qr = true).  Context active, call scope open.
+int qil_gauge_exact(qil_chain* c, int direction, int64_t center) {
+    return canonicalize_impl(c, direction, center, 0.0, kNoCap, true);
+}
+
 // ---------------------------------------------------------------- exported
 extern "C" int qil_canonicalize(qil_mps* psi, int direction, int64_t center, double cutoff, int64_t maxdim) {
     QIL_REQUIRE(psi, QIL_EINVAL_ARG, "canonicalize!: null handle");

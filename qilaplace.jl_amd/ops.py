@@ -644,6 +644,105 @@ def apply_distance(phi, W, psi) -> float:
     return _distance(nphi * nphi, nwpsi * nwpsi, inner(phi, W, psi))
 
 
+# ---------------------------------------------------------------- Schmidt spectra
+def _spectra(entry, x, return_norm):
+    dims = x.bond_dims
+    out = np.zeros(max(1, sum(dims)), dtype=np.float64)
+    nrm = C.c_double()
+    L.check(entry(x.handle, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(nrm)))
+    spectra, at = [], 0
+    for d in dims:
+        spectra.append(out[at:at + d].copy())
+        at += d
+    return (spectra, nrm.value) if return_norm else spectra
+
+
+def bond_spectra(psi, return_norm=False):
+    """The Schmidt values of the normalised state at every bond: a list of N - 1 float64 arrays (tensor order, 2n - 1 for a
+    ZTMPS), array k of length bond_dims[k], descending, squares summing to 1, exact zeros beyond what the cut can carry.
+    Absolute accuracy, a modest multiple of N chi eps; tiny values carry no relative accuracy.  psi is not modified.
+    return_norm=True adds ||psi|| without the amplitude, the number `norm` returns."""
+    _require_mps(psi, "bond_spectra")
+    return _spectra(L.lib.qil_bond_spectra, psi, return_norm)
+
+
+def mpo_bond_spectra(W, return_norm=False):
+    """The operator-Schmidt values of W / ||W||_F at every bond, as `bond_spectra`; return_norm=True adds ||W||_F."""
+    if not isinstance(W, SingleSiteMPO):
+        raise TypeError("mpo_bond_spectra: unsupported operand types")
+    return _spectra(L.lib.qil_mpo_bond_spectra, W, return_norm)
+
+
+def _as_spectra(x, what):
+    """A handle's spectra, or a list of spectra as it is (the helpers below are pure numpy on top)."""
+    if isinstance(x, SignalMPS):
+        return bond_spectra(x)
+    if isinstance(x, SingleSiteMPO):
+        return mpo_bond_spectra(x)
+    if isinstance(x, (list, tuple)):
+        return [np.asarray(s, dtype=np.float64).reshape(-1) for s in x]
+    raise TypeError(f"{what}: expected an MPS, an MPO or a list of spectra")
+
+
+def entanglement_entropy(x, alpha=1.0, base=2.0):
+    """One entropy per bond of the probabilities p = s^2 / sum(s^2): von Neumann -sum p log p at alpha = 1, Renyi
+    log(sum p^alpha) / (1 - alpha) otherwise, in units of log(base).  Zero values contribute nothing."""
+    alpha, base = float(alpha), float(base)
+    if not (alpha > 0.0 and base > 0.0 and base != 1.0):
+        raise ValueError("entanglement_entropy: needs alpha > 0 and a base > 0 other than 1")
+    out = []
+    for s in _as_spectra(x, "entanglement_entropy"):
+        p = s * s
+        tot = p.sum()
+        p = p[p > 0.0] / tot if tot > 0.0 else p[:0]
+        if p.size == 0:
+            out.append(0.0)
+        elif alpha == 1.0:
+            out.append(float(-(p * np.log(p)).sum() / np.log(base)) + 0.0)
+        else:
+            out.append(float(np.log((p ** alpha).sum()) / (1.0 - alpha) / np.log(base)) + 0.0)
+    return np.array(out, dtype=np.float64)
+
+
+def _tail_weights(spectra, maxdim):
+    """t_k = the squares beyond the first `maxdim` values of bond k, relative to the bond's total."""
+    t = []
+    for s in spectra:
+        p = np.sort(s * s)[::-1]
+        tot = p.sum()
+        t.append(float(p[maxdim:].sum() / tot) if tot > 0.0 else 0.0)
+    return np.array(t, dtype=np.float64)
+
+
+def truncation_error_bounds(x, maxdim):
+    """(lower, upper) for the distance of the state from its best bond-`maxdim` approximations, relative to ||psi||, with
+    t_k the sum of squares beyond the first `maxdim` values of bond k: lower = sqrt(max_k t_k), the Eckart-Young bound at the
+    worst cut, which no state of that bond dimension beats; upper = sqrt(sum_k t_k), what one truncating sweep stays below."""
+    maxdim = int(maxdim)
+    if maxdim < 1:
+        raise ValueError("truncation_error_bounds: maxdim must be at least 1")
+    t = _tail_weights(_as_spectra(x, "truncation_error_bounds"), maxdim)
+    if t.size == 0:
+        return 0.0, 0.0
+    return float(np.sqrt(t.max())), float(np.sqrt(t.sum()))
+
+
+def required_maxdim(x, tol):
+    """The smallest maxdim whose `truncation_error_bounds` upper bound is <= tol."""
+    spectra = _as_spectra(x, "required_maxdim")
+    tol = float(tol)
+    if not tol >= 0.0:
+        raise ValueError("required_maxdim: tol must be non-negative")
+    lo, hi = 1, max([1] + [len(s) for s in spectra])
+    while lo < hi:                      # the upper bound does not increase with maxdim
+        mid = (lo + hi) // 2
+        if np.sqrt(_tail_weights(spectra, mid).sum()) <= tol:
+            hi = mid
+        else:
+            lo = mid + 1
+    return lo
+
+
 # ---------------------------------------------------------------- sampling
 def sample(psi, nsamples, seed=1234, uniforms=None, bits=False):
     """Perfect sampling: `nsamples` configurations x drawn with probability |psi_x|^2 / |psi|^2 (ITensors' sample), with
