@@ -23,8 +23,10 @@
 //     chunk = max(1, min(nb, 32768, kChunkBudget / ((5 maxM + maxX) e + 16 ceil(maxM / 64))))     kChunkBudget = 64 MiB
 // rows: M, the next M, both children and U (5 maxM), the lead's X and the partials; maxM = max(chi_l D_l, chi_r D_r) and
 // maxX = 2 chi_l D_r over the tensors, e the element size of the contraction dtype.
-// The environment pass and the scoring step are also qil_apply_top_k's (qil_apply_topk.hip): qil_apply_right_envs and
-// qil_apply_score_children below, declared in qil_internal.h with the budget and the route they go with.
+// The start of a call and the scoring step are also qil_apply_top_k's (qil_apply_topk.hip): qil_apply_right_envs (the bond
+// sizes of qil_apply_sizes_of, the site scratch, the selector, the environment pass and the read-back of its flag) and
+// qil_apply_score_children below, declared in qil_internal.h with the budget and the route they go with.  The uniforms and
+// the choice (seeded_uniform, choose) are qil_sample's, in qil_device_utils.h.
 // Left out: a device-resident output.
 #include <algorithm>
 #include <cmath>
@@ -47,29 +49,6 @@ constexpr int kKTile = 32;                          // K elements of the rows' t
 constexpr int kScoreThreads = 256;
 constexpr int kLdA = kTileRows + 1;                 // LDS pitch of a K line: odd, so the transposing stores spread over the banks
 constexpr int kChooseRows = 4;                      // rows per workgroup of the reduce and choose kernels: one wave each
-
-// u_{r,i} = (splitmix64(seed ^ splitmix64(r n + i)) >> 11) 2^-53, in [0, 1): qil_sample's
-__device__ __forceinline__ double seeded_uniform(uint64_t seed, long long r, int n, int i) {
-    const uint64_t h = splitmix64(seed ^ splitmix64((uint64_t)r * (uint64_t)n + (uint64_t)i));
-    return (double)(h >> 11) * (1.0 / 9007199254740992.0);
-}
-
-// qil_sample's choice of one sample at one site.  q_0 + q_1 <= 0 (a prefix of weight zero reached through rounding): the larger
-// q, s = 0 when both are 0, and the probability factor is 0.  The row is rescaled by 1 / sqrt(q_s), or zeroed when q_s <= 0.
-__device__ __forceinline__ int choose(double q0, double q1, double u, double& factor, double& scl) {
-    const double sum = q0 + q1;
-    int s;
-    if (sum > 0.0) {
-        s = u * sum < q0 ? 0 : 1;
-        factor = (s ? q1 : q0) / sum;
-    } else {
-        s = q1 > q0 ? 1 : 0;
-        factor = 0.0;
-    }
-    const double qs = s ? q1 : q0;
-    scl = qs > 0.0 ? 1.0 / sqrt(qs) : 0.0;
-    return s;
-}
 
 // the column of R that pairs with the vector index k = alpha + chi a: a + D alpha
 __device__ __forceinline__ long long paired_column(int k, int chi, int D) { return k / chi + (long long)D * (k % chi); }
@@ -246,39 +225,17 @@ int sample_lazy(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64_t 
     const int64_t n = psi->n();
     const int dt = sizeof(T) == 16 ? QIL_C64 : QIL_F64;
     const int64_t e = (int64_t)sizeof(T);
-    long long maxM = 1, maxX = 1, maxW = 1, maxA = 1;
-    for (int64_t i = 0; i < n; ++i) {
-        const long long cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1];
-        const long long Dl = W->dims[(size_t)i], Dr = W->dims[(size_t)i + 1];
-        maxM = std::max({maxM, cl * Dl, cr * Dr});
-        maxX = std::max(maxX, 2 * cl * Dr);
-        maxW = std::max(maxW, 4 * Dl * Dr);
-        maxA = std::max(maxA, 2 * cl * cr);
-    }
+    // ---- device memory: everything belongs to `tmp`.  Environments, right to left; R_0 (one number, |W psi|^2 on the scale of
+    // R_1) is only checked
+    qil_scratch tmp(ctx);
+    qil_apply_lazy lz;
+    int bad = 0;
+    QIL_TRY(qil_apply_right_envs(ctx, tmp, dt, W, psi, lz, &bad, nullptr));
+    QIL_REQUIRE(bad == 0, QIL_EDOMAIN, "apply_sample: the transformed state has zero norm");
+    const long long maxM = lz.b.maxM, maxX = lz.b.maxX;
     const bool fused = qil_apply_score_fused(maxM);
     const long long maxPanels = qil_apply_score_panels(maxM);
     const int64_t chunk = qil_apply_chunk_rows(nb, (5 * maxM + maxX) * e + 16 * maxPanels);
-
-    // ---- device memory: everything belongs to `tmp`
-    qil_scratch tmp(ctx);
-    void *As = nullptr, *At = nullptr, *Wd = nullptr, *Wr = nullptr, *Wc = nullptr, *dsel = nullptr, *dflag = nullptr;
-    if (psi->dtype != dt) QIL_TRY(tmp.alloc((size_t)maxA * e, &As));
-    QIL_TRY(tmp.alloc((size_t)maxA * e, &At));
-    QIL_TRY(tmp.alloc((size_t)maxW * e, &Wd));
-    QIL_TRY(tmp.alloc((size_t)maxW * e, &Wr));
-    QIL_TRY(tmp.alloc((size_t)maxW * e, &Wc));
-    QIL_TRY(tmp.alloc(sizeof(int), &dflag));
-    const uint8_t both[2] = {0, 1};                    // the output bit of every row of a child's step (selector step 0)
-    QIL_TRY(qil_upload_bytes(tmp, both, 2, &dsel));
-    std::vector<void*> Rk;
-
-    // ---- environments, right to left; R_0 (one number, |W psi|^2 on the scale of R_1) is only checked
-    {
-        QIL_TRY(qil_apply_right_envs(ctx, tmp, dt, W, psi, At, Wd, Wr, Rk, (int*)dflag, nullptr));
-        int bad = 0;
-        QIL_TRY(qil_read_back(ctx, &bad, dflag, sizeof(int)));
-        QIL_REQUIRE(bad == 0, QIL_EDOMAIN, "apply_sample: the transformed state has zero norm");
-    }
 
     // ---- the sweep, in chunks of rows
     void *M0 = nullptr, *M1 = nullptr, *Mch = nullptr, *Xb = nullptr, *Uc = nullptr, *part = nullptr, *dbits = nullptr, *dprob = nullptr,
@@ -292,7 +249,6 @@ int sample_lazy(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64_t 
     QIL_TRY(tmp.alloc((size_t)(chunk * n), &dbits));
     QIL_TRY(tmp.alloc((size_t)chunk * 8, &dprob));
     if (uniforms) QIL_TRY(tmp.alloc((size_t)(chunk * n) * 8, &dU));
-    const uint8_t* sel = static_cast<const uint8_t*>(dsel);
     for (int64_t r0 = 0; r0 < nb; r0 += chunk) {
         const int64_t nr = std::min<int64_t>(chunk, nb - r0);
         if (uniforms) QIL_HIP(hipMemcpyAsync(dU, uniforms + r0 * n, (size_t)(nr * n) * 8, hipMemcpyHostToDevice, qil_stream(ctx)));
@@ -303,9 +259,9 @@ int sample_lazy(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64_t 
             const int64_t cr = psi->dims[(size_t)i + 1], Dr = W->dims[(size_t)i + 1], P = cr * Dr;
             T* child = static_cast<T*>(Mch);
             for (int s = 0; s < 2; ++s)
-                QIL_TRY(qil_lazy_row_step(ctx, dt, W, psi, i, Mc, child + s * nr * P, Xb, Wc, As, nr, sel + s, 0));
+                QIL_TRY(qil_lazy_row_step(ctx, dt, W, psi, i, Mc, child + s * nr * P, Xb, lz.Wc, lz.As, nr, lz.both + s, 0));
             int panels = 1;
-            QIL_TRY(qil_apply_score_children(ctx, dt, fused, child, nr, cr, Dr, Rk[(size_t)i + 1], Uc, (double*)part, &panels));
+            QIL_TRY(qil_apply_score_children(ctx, dt, fused, child, nr, cr, Dr, lz.Rk[(size_t)i + 1], Uc, (double*)part, &panels));
             hipLaunchKernelGGL(apply_sample_choose<T>, dim3((unsigned)((nr + kChooseRows - 1) / kChooseRows)), dim3(64 * kChooseRows), 0,
                                qil_stream(ctx), (const double*)part, panels, (long long)nr, (int)P, (const T*)child, (const double*)dU,
                                seed, (long long)r0, (int)n, (int)i, (uint8_t*)dbits, (double*)dprob, Mn);
@@ -340,6 +296,19 @@ double qil_apply_env_bytes(const qil_mpo* W, const qil_mps* psi) {   // e sum_k 
         need += P * P * (cx ? 16.0 : 8.0);
     }
     return need;
+}
+
+qil_apply_bond_sizes qil_apply_sizes_of(const qil_mpo* W, const qil_mps* psi) {
+    qil_apply_bond_sizes b;
+    for (int64_t i = 0; i < psi->n(); ++i) {
+        const long long cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1];
+        const long long Dl = W->dims[(size_t)i], Dr = W->dims[(size_t)i + 1];
+        b.maxM = std::max({b.maxM, cl * Dl, cr * Dr});
+        b.maxX = std::max(b.maxX, 2 * cl * Dr);
+        b.maxW = std::max(b.maxW, 4 * Dl * Dr);
+        b.maxA = std::max(b.maxA, 2 * cl * cr);
+    }
+    return b;
 }
 
 int64_t qil_apply_score_panels(int64_t P) { return (P + kPanel - 1) / kPanel; }
@@ -393,10 +362,25 @@ static int right_envs(qil_context* ctx, qil_scratch& tmp, const qil_mpo* W, cons
     return QIL_OK;
 }
 
-int qil_apply_right_envs(qil_context* ctx, qil_scratch& tmp, int dt, const qil_mpo* W, const qil_mps* psi, void* At, void* Wd,
-                         void* Wr, std::vector<void*>& Rk, int* flag, double* log_trace) {
-    if (dt == QIL_C64) return right_envs<c64>(ctx, tmp, W, psi, At, Wd, Wr, Rk, flag, log_trace);
-    return right_envs<double>(ctx, tmp, W, psi, At, Wd, Wr, Rk, flag, log_trace);
+int qil_apply_right_envs(qil_context* ctx, qil_scratch& tmp, int dt, const qil_mpo* W, const qil_mps* psi, qil_apply_lazy& lz,
+                         int* bad, double** log_trace) {
+    const size_t e = qil_elem_size(dt);
+    void *dflag = nullptr, *dlog = nullptr, *dsel = nullptr;
+    lz.b = qil_apply_sizes_of(W, psi);
+    if (psi->dtype != dt) QIL_TRY(tmp.alloc((size_t)lz.b.maxA * e, &lz.As));
+    QIL_TRY(tmp.alloc((size_t)lz.b.maxA * e, &lz.At));
+    QIL_TRY(tmp.alloc((size_t)lz.b.maxW * e, &lz.Wd));
+    QIL_TRY(tmp.alloc((size_t)lz.b.maxW * e, &lz.Wr));
+    QIL_TRY(tmp.alloc((size_t)lz.b.maxW * e, &lz.Wc));
+    QIL_TRY(tmp.alloc(sizeof(int), &dflag));
+    if (log_trace) QIL_TRY(tmp.alloc(sizeof(double), &dlog));
+    const uint8_t both[2] = {0, 1};                    // the output bit of every row of a child's step (selector step 0)
+    QIL_TRY(qil_upload_bytes(tmp, both, 2, &dsel));
+    lz.both = static_cast<const uint8_t*>(dsel);
+    if (log_trace) *log_trace = static_cast<double*>(dlog);
+    if (dt == QIL_C64) QIL_TRY(right_envs<c64>(ctx, tmp, W, psi, lz.At, lz.Wd, lz.Wr, lz.Rk, (int*)dflag, (double*)dlog));
+    else QIL_TRY(right_envs<double>(ctx, tmp, W, psi, lz.At, lz.Wd, lz.Wr, lz.Rk, (int*)dflag, (double*)dlog));
+    return qil_read_back(ctx, bad, dflag, sizeof(int));
 }
 
 template <class T>

@@ -1,13 +1,16 @@
 // Lazy top-k search for gfx950: qil_apply_top_k returns the k configurations x with the largest |(W psi)_x|, their values and a
 // bound on what the search may have dropped, without forming W psi.  The arithmetic is fixed in include/qilaplace_hip.h.  It is
-// qil_top_k's beam search (qil_topk.hip) with the lazy row vector of qil_apply_coefficient_batch in place of the prefix vector,
-// and it joins three things that exist:
-//   environments   qil_apply_right_envs (qil_apply_sample.hip): the trace-normalised right environments R_k of |W psi|^2, here
-//                  with the log trace: log |W psi|^2 = sum_k log t_k stays on the device until the outputs are read back
+// qil_top_k's beam search (qil_beam_search, qil_topk.hip: bookkeeping, selection, back-walk levels, read-back, delivery, bound)
+// over the lazy row vector of qil_apply_coefficient_batch in place of the prefix vector: lazy_rows below is its qil_beam_rows.
+// It joins three things that exist:
+//   start          qil_apply_right_envs (qil_apply_sample.hip): site scratch, selector and the trace-normalised right environments
+//                  R_k of |W psi|^2, here with the log trace: log |W psi|^2 = sum_k log t_k stays on the device until the
+//                  search reads it back with the outputs
 //   scoring        qil_apply_score_children (qil_apply_sample.hip), either route: partial sums of q_s = Re(m_s R_{i+1} m_s^H)
 //                  for both children M_s = qil_lazy_row_step (qil_readout.hip) of every frontier row
-//   selection      qil_dev_select_largest (qil_topk.hip): radix select + compaction over all 2 f candidates
-// and adds the per-tensor kernels of the lazy row layout (a row is P = chi D contiguous elements):
+//   search         qil_beam_search (qil_topk.hip), with its radix select + compaction over all 2 f candidates
+// and adds the per-tensor kernels of the lazy row layout (a row is P = chi D contiguous elements), whose per-row arithmetic
+// (beam_keys, beam_child_scale, beam_gather_row, beam_finish_row; qil_device_utils.h) is the one of qil_top_k's kernels:
 //   apply_top_k_keys     one wave per row: the partials of both children summed in panel order (apply_sample_choose's order),
 //                        q_s and key(2 r + s) = p_r q_s / (q_0 + q_1)
 //   apply_top_k_gather   the kept children, scaled by 1 / sqrt(q_s), become the next frontier; g' = g + log(q_s) / 2, p' = key
@@ -67,15 +70,7 @@ __global__ __launch_bounds__(64 * kKeyRows) void apply_top_k_keys(const double* 
         q0 += part[(long long)t * rows + row];
         q1 += part[((long long)panels + t) * rows + row];
     }
-    q0 = fmax(q0, 0.0);
-    q1 = fmax(q1, 0.0);
-    const double sum = q0 + q1, pr = p[row];
-    if (lane == 0) {
-        keys[2 * row] = sum > 0.0 ? pr * (q0 / sum) : 0.0;
-        keys[2 * row + 1] = sum > 0.0 ? pr * (q1 / sum) : 0.0;
-        q[2 * row] = q0;
-        q[2 * row + 1] = q1;
-    }
+    if (lane == 0) beam_keys(q0, q1, row, p, keys, q);
 }
 
 // Next frontier row j = the kept candidate c = sel[j] (c = j when everything is kept): child c & 1 of row c >> 1, scaled by
@@ -95,12 +90,8 @@ __global__ __launch_bounds__(256) void apply_top_k_gather(const T* __restrict__ 
         const long long row = c >> 1;
         const double qq = q[c];
         const T v = load_elem(Mch + child_row(row, c & 1, f, chunk) * P + k);
-        store_elem(Mn + t, scale_t(v, qq > 0.0 ? 1.0 / sqrt(qq) : 0.0));
-        if (k == 0) {
-            gn[j] = g[row] + (qq > 0.0 ? 0.5 * log(qq) : 0.0);
-            pn[j] = keys[c];
-            anc[j] = c;
-        }
+        store_elem(Mn + t, scale_t(v, beam_child_scale(qq)));
+        if (k == 0) beam_gather_row(j, c, qq, keys, g, gn, pn, anc);
     }
 }
 
@@ -113,161 +104,87 @@ __global__ __launch_bounds__(256) void apply_top_k_finish(const T* __restrict__ 
                                                           double sgn, double* __restrict__ val, uint8_t* __restrict__ bits) {
     for (long long j = blockIdx.x * 256LL + threadIdx.x; j < M; j += (long long)gridDim.x * 256) {
         const int c = sel ? sel[j] : (int)j;
-        long long row = c >> 1;
-        const c64 v = to_c64(scale_t(Mch[child_row(row, c & 1, f, chunk)], sgn * exp(g[row] + lamp)));
-        val[2 * j] = v.re;
-        val[2 * j + 1] = v.im;
-        bits[j * n + n - 1] = (uint8_t)(c & 1);
-        for (int lvl = n - 2; lvl >= 0; --lvl) {
-            const int a = anc[lvl * stride + row];
-            bits[j * n + lvl] = (uint8_t)(a & 1);
-            row = a >> 1;
-        }
+        beam_finish_row(j, c, Mch[child_row(c >> 1, c & 1, f, chunk)], g, anc, stride, n, lamp, sgn, val, bits);
     }
-}
-
-struct bond_sizes {
-    long long maxM = 1, maxX = 1, maxW = 1, maxA = 1;
-};
-bond_sizes sizes_of(const qil_mpo* W, const qil_mps* psi) {
-    bond_sizes b;
-    for (int64_t i = 0; i < psi->n(); ++i) {
-        const long long cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1];
-        const long long Dl = W->dims[(size_t)i], Dr = W->dims[(size_t)i + 1];
-        b.maxM = std::max({b.maxM, cl * Dl, cr * Dr});
-        b.maxX = std::max(b.maxX, 2 * cl * Dr);
-        b.maxW = std::max(b.maxW, 4 * Dl * Dr);
-        b.maxA = std::max(b.maxA, 2 * cl * cr);
-    }
-    return b;
 }
 
 // beam <= min(2^29, 2^30 / (3 maxM e + 4 n + 64)): the rows (maxM e per row), both children (2 maxM e) and the per-row
 // bookkeeping fit in 1 GiB.  A function of the operands' shapes alone.
 int64_t beam_cap(const qil_mpo* W, const qil_mps* psi) {
     const long long e = W->dtype == QIL_C64 || psi->dtype == QIL_C64 ? 16 : 8;
-    const long long per_row = 3 * sizes_of(W, psi).maxM * e + 4 * psi->n() + 64;
+    const long long per_row = 3 * qil_apply_sizes_of(W, psi).maxM * e + 4 * psi->n() + 64;
     return std::min<long long>(kBeamHardCap, (1LL << 30) / per_row);
 }
 
+// the rows of qil_apply_top_k: the lazy row vectors (Mf, packed, P elements each) and their children (Mch, the head comment's
+// packing), scored chunk by chunk through Xb, Uc and part
 template <class T>
-int top_k_lazy(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64_t k, int64_t beam, uint8_t* bits_out, double* val_out,
-               double* bound_out) {
-    const int64_t n = psi->n();
-    const int dt = sizeof(T) == 16 ? QIL_C64 : QIL_F64;
-    const int64_t e = (int64_t)sizeof(T);
-    const bond_sizes b = sizes_of(W, psi);
-    const bool fused = qil_apply_score_fused(b.maxM);
-    const long long maxPanels = qil_apply_score_panels(b.maxM);
-    // frontier sizes f_0 = 1, f_{i+1} = min(2 f_i, beam): the largest one sizes the buffers
-    long long fcap = 1;
-    for (long long f = 1, i = 0; i < n; ++i, f = std::min<long long>(2 * f, beam)) fcap = std::max(fcap, f);
-    const int64_t chunk = qil_apply_chunk_rows(fcap, (2 * b.maxM + b.maxX) * e + 16 * maxPanels);
+struct lazy_rows final : qil_beam_rows {
+    static constexpr int dt = sizeof(T) == 16 ? QIL_C64 : QIL_F64;
+    qil_context* ctx;
+    const qil_mpo* W;
+    const qil_mps* psi;
+    const qil_apply_lazy& lz;
+    bool fused;
+    int64_t chunk;
+    void *Mf = nullptr, *Mch = nullptr, *Xb = nullptr, *Uc = nullptr, *part = nullptr;
+    lazy_rows(qil_context* c, const qil_mpo* w, const qil_mps* x, const qil_apply_lazy& l, bool fu, int64_t ch)
+        : ctx(c), W(w), psi(x), lz(l), fused(fu), chunk(ch) {}
+    int64_t bond(int64_t k) const { return psi->dims[(size_t)k] * W->dims[(size_t)k]; }
 
-    // ---- device memory: everything belongs to `tmp`
-    qil_scratch tmp(ctx);
-    void *As = nullptr, *At = nullptr, *Wd = nullptr, *Wr = nullptr, *Wc = nullptr, *dsel = nullptr, *dflag = nullptr, *dlog = nullptr;
-    if (psi->dtype != dt) QIL_TRY(tmp.alloc((size_t)b.maxA * e, &As));
-    QIL_TRY(tmp.alloc((size_t)b.maxA * e, &At));
-    QIL_TRY(tmp.alloc((size_t)b.maxW * e, &Wd));
-    QIL_TRY(tmp.alloc((size_t)b.maxW * e, &Wr));
-    QIL_TRY(tmp.alloc((size_t)b.maxW * e, &Wc));
-    QIL_TRY(tmp.alloc(sizeof(int), &dflag));
-    QIL_TRY(tmp.alloc(sizeof(double), &dlog));
-    const uint8_t both[2] = {0, 1};                    // the output bit of every row of a child's step (selector step 0)
-    QIL_TRY(qil_upload_bytes(tmp, both, 2, &dsel));
-
-    // ---- environments, right to left, with log |W psi|^2
-    std::vector<void*> Rk;
-    QIL_TRY(qil_apply_right_envs(ctx, tmp, dt, W, psi, At, Wd, Wr, Rk, (int*)dflag, (double*)dlog));
-    int bad = 0;
-    QIL_TRY(qil_read_back(ctx, &bad, dflag, sizeof(int)));
-    QIL_REQUIRE(bad == 0, QIL_EDOMAIN, "apply_top_k: the transformed state has zero norm");
-
-    // ---- the frontier's buffers, then the chunk's
-    void *Mf = nullptr, *Mch = nullptr, *keys = nullptr, *q = nullptr, *g[2] = {nullptr, nullptr}, *p[2] = {nullptr, nullptr};
-    void *sel = nullptr, *anc = nullptr, *blk = nullptr, *st = nullptr, *drop = nullptr, *dval = nullptr, *dbits = nullptr;
-    void *Xb = nullptr, *Uc = nullptr, *part = nullptr;
-    QIL_TRY(tmp.alloc((size_t)(fcap * b.maxM * e), &Mf));
-    QIL_TRY(tmp.alloc((size_t)(fcap * 2 * b.maxM * e), &Mch));
-    QIL_TRY(tmp.alloc((size_t)(2 * fcap) * 8, &keys));
-    QIL_TRY(tmp.alloc((size_t)(2 * fcap) * 8, &q));
-    for (int t = 0; t < 2; ++t) {
-        QIL_TRY(tmp.alloc((size_t)fcap * 8, &g[t]));
-        QIL_TRY(tmp.alloc((size_t)fcap * 8, &p[t]));
-    }
-    QIL_TRY(tmp.alloc((size_t)(2 * fcap) * 4, &sel));
-    QIL_TRY(tmp.alloc((size_t)(std::max<int64_t>(n - 1, 1) * fcap) * 4, &anc));
-    QIL_TRY(tmp.alloc(qil_dev_select_block_bytes(2 * fcap), &blk));
-    QIL_TRY(tmp.alloc(qil_dev_select_state_bytes(), &st));
-    QIL_TRY(tmp.alloc(8, &drop));                      // bit pattern of the largest key dropped before the last tensor
-    QIL_TRY(tmp.alloc((size_t)k * 16, &dval));
-    QIL_TRY(tmp.alloc((size_t)(k * n), &dbits));
-    QIL_TRY(tmp.alloc((size_t)(chunk * b.maxX * e), &Xb));
-    if (!fused) QIL_TRY(tmp.alloc((size_t)(chunk * 2 * b.maxM * e), &Uc));
-    QIL_TRY(tmp.alloc((size_t)(chunk * 2 * (fused ? maxPanels : 1) * 8), &part));
-    QIL_HIP(hipMemsetAsync(drop, 0, 8, qil_stream(ctx)));
-    QIL_HIP(hipMemsetAsync(g[0], 0, 8, qil_stream(ctx)));
-    QIL_TRY(qil_dev_fill_ones(ctx, dt, Mf, 1));
-    QIL_TRY(qil_dev_fill_ones(ctx, QIL_F64, p[0], 1));
-
-    // ---- the search, tensor by tensor
-    const double amp = psi->amplitude;
-    const double lamp = std::log(std::fabs(amp)), sgn = amp < 0.0 ? -1.0 : 1.0;
-    const uint8_t* bit = static_cast<const uint8_t*>(dsel);
-    long long f = 1;
-    int cur = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t cl = psi->dims[(size_t)i], Dl = W->dims[(size_t)i], cr = psi->dims[(size_t)i + 1], Dr = W->dims[(size_t)i + 1];
-        const int64_t Pl = cl * Dl, P = cr * Dr;
-        const bool last = i == n - 1;
+    int expand(int64_t i, long long f, const double* p, double* keys, double* q) override {
+        const int64_t cr = psi->dims[(size_t)i + 1], Dr = W->dims[(size_t)i + 1], Pl = bond(i), P = cr * Dr;
         for (int64_t r0 = 0; r0 < f; r0 += chunk) {
             const int64_t nr = std::min<int64_t>(chunk, f - r0);
             T* child = static_cast<T*>(Mch) + 2 * r0 * P;
             for (int s = 0; s < 2; ++s)
-                QIL_TRY(qil_lazy_row_step(ctx, dt, W, psi, i, static_cast<const T*>(Mf) + r0 * Pl, child + s * nr * P, Xb, Wc, As, nr,
-                                          bit + s, 0));
+                QIL_TRY(qil_lazy_row_step(ctx, dt, W, psi, i, static_cast<const T*>(Mf) + r0 * Pl, child + s * nr * P, Xb, lz.Wc, lz.As, nr,
+                                          lz.both + s, 0));
             int panels = 1;
-            QIL_TRY(qil_apply_score_children(ctx, dt, fused, child, nr, cr, Dr, Rk[(size_t)i + 1], Uc, (double*)part, &panels));
+            QIL_TRY(qil_apply_score_children(ctx, dt, fused, child, nr, cr, Dr, lz.Rk[(size_t)i + 1], Uc, (double*)part, &panels));
             hipLaunchKernelGGL(apply_top_k_keys, dim3((unsigned)((nr + kKeyRows - 1) / kKeyRows)), dim3(64 * kKeyRows), 0, qil_stream(ctx),
-                               (const double*)part, panels, (long long)nr, (const double*)p[cur] + r0, (double*)keys + 2 * r0,
-                               (double*)q + 2 * r0);
-            QIL_HIP(hipGetLastError());
+                               (const double*)part, panels, (long long)nr, p + r0, keys + 2 * r0, q + 2 * r0);
         }
-        const long long C = 2 * f, M = std::min<long long>(C, last ? k : beam);
-        const int* kept = nullptr;
-        if (M < C) {
-            QIL_TRY(qil_dev_select_largest(ctx, (const double*)keys, C, M, (int*)sel, last ? nullptr : (unsigned long long*)drop, st, blk));
-            kept = static_cast<const int*>(sel);
-        }
-        if (!last) {
-            hipLaunchKernelGGL(apply_top_k_gather<T>, dim3(qil_grid_for(M * P)), dim3(256), 0, qil_stream(ctx), (const T*)Mch, f,
-                               (long long)chunk, (int)P, (const double*)keys, (const double*)q, (const double*)g[cur], kept, M,
-                               static_cast<T*>(Mf), (double*)g[1 - cur], (double*)p[1 - cur], static_cast<int*>(anc) + i * fcap);
-            cur = 1 - cur;
-            f = M;
-        } else {
-            hipLaunchKernelGGL(apply_top_k_finish<T>, dim3(qil_grid_for(M)), dim3(256), 0, qil_stream(ctx), (const T*)Mch, f,
-                               (long long)chunk, (const double*)g[cur], kept, M, (const int*)anc, fcap, (int)n, lamp, sgn, (double*)dval,
-                               (uint8_t*)dbits);
-        }
-        QIL_HIP(hipGetLastError());
+        return QIL_OK;
     }
-    std::vector<double> hval((size_t)(2 * k));
-    std::vector<uint8_t> hbits((size_t)(k * n));
-    unsigned long long hdrop = 0;
-    double log_norm2 = 0.0;
-    QIL_HIP(hipMemcpyAsync(hval.data(), dval, (size_t)k * 16, hipMemcpyDeviceToHost, qil_stream(ctx)));
-    QIL_HIP(hipMemcpyAsync(hbits.data(), dbits, (size_t)(k * n), hipMemcpyDeviceToHost, qil_stream(ctx)));
-    QIL_HIP(hipMemcpyAsync(&hdrop, drop, 8, hipMemcpyDeviceToHost, qil_stream(ctx)));
-    QIL_HIP(hipMemcpyAsync(&log_norm2, dlog, 8, hipMemcpyDeviceToHost, qil_stream(ctx)));
-    QIL_HIP(qil_stream_sync(ctx));
+    void gather(int64_t i, long long f, const double* keys, const double* q, const double* g, const int* sel, long long M, double* gn,
+                double* pn, int* anc) override {
+        const int64_t P = bond(i + 1);
+        hipLaunchKernelGGL(apply_top_k_gather<T>, dim3(qil_grid_for(M * P)), dim3(256), 0, qil_stream(ctx), (const T*)Mch, f,
+                           (long long)chunk, (int)P, keys, q, g, sel, M, static_cast<T*>(Mf), gn, pn, anc);
+    }
+    void finish(long long f, const double* g, const int* sel, long long M, const int* anc, long long stride, double lamp, double sgn,
+                double* val, uint8_t* bits) override {
+        hipLaunchKernelGGL(apply_top_k_finish<T>, dim3(qil_grid_for(M)), dim3(256), 0, qil_stream(ctx), (const T*)Mch, f,
+                           (long long)chunk, g, sel, M, anc, stride, (int)psi->n(), lamp, sgn, val, bits);
+    }
+};
 
-    qil_top_k_deliver(k, n, hval.data(), hbits.data(), bits_out, val_out);
-    double dropped = 0.0;
-    std::memcpy(&dropped, &hdrop, 8);
-    *bound_out = dropped > 0.0 ? std::exp(0.5 * (std::log(dropped) + log_norm2) + lamp) : 0.0;
-    return QIL_OK;
+template <class T>
+int top_k_lazy(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64_t k, int64_t beam, uint8_t* bits_out, double* val_out,
+               double* bound_out) {
+    const int64_t e = (int64_t)sizeof(T);
+    // ---- device memory: everything belongs to `tmp`.  Environments, right to left, with log |W psi|^2 (it stays on the device)
+    qil_scratch tmp(ctx);
+    qil_apply_lazy lz;
+    int bad = 0;
+    double* dlog = nullptr;
+    QIL_TRY(qil_apply_right_envs(ctx, tmp, lazy_rows<T>::dt, W, psi, lz, &bad, &dlog));
+    QIL_REQUIRE(bad == 0, QIL_EDOMAIN, "apply_top_k: the transformed state has zero norm");
+
+    // ---- the frontier's rows and children, then the chunk's buffers
+    const bool fused = qil_apply_score_fused(lz.b.maxM);
+    const long long maxPanels = qil_apply_score_panels(lz.b.maxM);
+    const long long fcap = qil_beam_frontier_cap(psi->n(), beam);
+    const int64_t chunk = qil_apply_chunk_rows(fcap, (2 * lz.b.maxM + lz.b.maxX) * e + 16 * maxPanels);
+    lazy_rows<T> rows(ctx, W, psi, lz, fused, chunk);
+    QIL_TRY(tmp.alloc((size_t)(fcap * lz.b.maxM * e), &rows.Mf));
+    QIL_TRY(tmp.alloc((size_t)(fcap * 2 * lz.b.maxM * e), &rows.Mch));
+    QIL_TRY(tmp.alloc((size_t)(chunk * lz.b.maxX * e), &rows.Xb));
+    if (!fused) QIL_TRY(tmp.alloc((size_t)(chunk * 2 * lz.b.maxM * e), &rows.Uc));
+    QIL_TRY(tmp.alloc((size_t)(chunk * 2 * (fused ? maxPanels : 1) * 8), &rows.part));
+    QIL_TRY(qil_dev_fill_ones(ctx, lazy_rows<T>::dt, rows.Mf, 1));
+    return qil_beam_search(ctx, tmp, rows, psi->n(), k, beam, psi->amplitude, 0.0, dlog, bits_out, val_out, bound_out);
 }
 
 }  // namespace

@@ -3,7 +3,8 @@
 // Born weights (qil_weight.hip, qil_apply_weight.hip), the restriction (qil_restrict.hip), the sums (qil_sum.hip), the shared
 // contraction steps (qil_contract.hip) and the truncation (qil_truncate.hip): the complex scalar type, its arithmetic and its
 // parts (re_of / im_of / make_elem / shfl_xor_t), the one K step of a 16 x 16 tile on the f64 MFMA (mfma_step), the splitmix64
-// hash, DPP cross-lane sums, Jacobi rotations, the in-workgroup one-sided Jacobi sweep loop, and the site table, site lookup
+// hash, the sampling rule (seeded_uniform, choose), the row sums of both children (children_row_sums), the per-row steps of
+// the beam search (beam_keys, beam_child_scale, beam_gather_row, beam_finish_row), DPP cross-lane sums, Jacobi rotations, the in-workgroup one-sided Jacobi sweep loop, and the site table, site lookup
 // and stores of the grouped launches.  gfx950 only.
 #pragma once
 
@@ -92,6 +93,97 @@ __host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
     x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
     x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
     return x ^ (x >> 31);
+}
+
+// ------------------------------------------------------------------ the sampling rule of qil_sample and qil_apply_sample
+// u_{r,i} = (splitmix64(seed ^ splitmix64(r n + i)) >> 11) 2^-53, in [0, 1)
+__device__ __forceinline__ double seeded_uniform(uint64_t seed, long long r, int n, int i) {
+    const uint64_t h = splitmix64(seed ^ splitmix64((uint64_t)r * (uint64_t)n + (uint64_t)i));
+    return (double)(h >> 11) * (1.0 / 9007199254740992.0);
+}
+
+// The choice of one sample at one site.  q_0 + q_1 <= 0 (a prefix of weight zero reached through rounding): the larger q,
+// s = 0 when both are 0, and the probability factor is 0.  The row is rescaled by 1 / sqrt(q_s), or zeroed when q_s <= 0.
+__device__ __forceinline__ int choose(double q0, double q1, double u, double& factor, double& scl) {
+    const double sum = q0 + q1;
+    int s;
+    if (sum > 0.0) {
+        s = u * sum < q0 ? 0 : 1;
+        factor = (s ? q1 : q0) / sum;
+    } else {
+        s = q1 > q0 ? 1 : 0;
+        factor = 0.0;
+    }
+    const double qs = s ? q1 : q0;
+    scl = qs > 0.0 ? 1.0 / sqrt(qs) : 0.0;
+    return s;
+}
+
+// q_s = Re sum_beta U_s[row, beta] conj(T_s[row, beta]) for both children of a workgroup's Rows rows (qil_sample's GEMM route,
+// qil_top_k).  T (rows x 2 chi_r, column s + 2 beta) and U_s = T_s R (rows x chi_r at Us + s rows chi_r), both ld = rows.  Thread
+// (r, g) = (threadIdx.x % Rows, threadIdx.x / Rows) sums the columns g, g + Groups, .. of its row; LDS sums the groups in a fixed
+// order.  The whole workgroup calls it (one barrier); true with (a, b) = (q_0, q_1) for the group-0 thread of a row below `rows`.
+template <int Rows, int Groups, class T>
+__device__ __forceinline__ bool children_row_sums(const T* __restrict__ Tm, const T* __restrict__ Us, long long rows, int cr,
+                                                  double (&qs)[2][Groups][Rows], double& a, double& b) {
+    const int r = threadIdx.x % Rows, g = threadIdx.x / Rows;
+    const long long row = (long long)blockIdx.x * Rows + r;
+    double q0 = 0.0, q1 = 0.0;
+    if (row < rows)
+        for (int beta = g; beta < cr; beta += Groups) {
+            const T t0 = Tm[row + rows * (2LL * beta)], t1 = Tm[row + rows * (1 + 2LL * beta)];
+            const T u0 = Us[row + rows * (long long)beta], u1 = Us[row + rows * ((long long)cr + beta)];
+            q0 += re_of(u0) * re_of(t0) + im_of(u0) * im_of(t0);
+            q1 += re_of(u1) * re_of(t1) + im_of(u1) * im_of(t1);
+        }
+    qs[0][g][r] = q0;
+    qs[1][g][r] = q1;
+    __syncthreads();
+    if (g != 0 || row >= rows) return false;
+    a = 0.0, b = 0.0;
+    for (int j = 0; j < Groups; ++j) a += qs[0][j][r], b += qs[1][j][r];
+    return true;
+}
+
+// ------------------------------------------------------------------ the per-row steps of the beam search (qil_top_k, qil_apply_top_k)
+// Both children of frontier row `row`: q_s < 0 (rounding of a PSD form) or NaN counts as 0; key(2 row + s) = p q_s / (q_0 + q_1),
+// the child's weight / the norm, 0 when the sum is not positive.
+__device__ __forceinline__ void beam_keys(double q0, double q1, long long row, const double* __restrict__ p,
+                                          double* __restrict__ keys, double* __restrict__ q) {
+    q0 = fmax(q0, 0.0);
+    q1 = fmax(q1, 0.0);
+    const double sum = q0 + q1, pr = p[row];
+    keys[2 * row] = sum > 0.0 ? pr * (q0 / sum) : 0.0;
+    keys[2 * row + 1] = sum > 0.0 ? pr * (q1 / sum) : 0.0;
+    q[2 * row] = q0;
+    q[2 * row + 1] = q1;
+}
+// a kept child is scaled by 1 / sqrt(q), zeroed when q <= 0
+__device__ __forceinline__ double beam_child_scale(double qq) { return qq > 0.0 ? 1.0 / sqrt(qq) : 0.0; }
+// next frontier row j = candidate c (child c & 1 of row c >> 1): g' = g + log(q) / 2, p' = key, the index for the back-walk
+__device__ __forceinline__ void beam_gather_row(long long j, int c, double qq, const double* __restrict__ keys,
+                                                const double* __restrict__ g, double* __restrict__ gn, double* __restrict__ pn,
+                                                int* __restrict__ anc) {
+    gn[j] = g[c >> 1] + (qq > 0.0 ? 0.5 * log(qq) : 0.0);
+    pn[j] = keys[c];
+    anc[j] = c;
+}
+// Result row j = candidate c at the last site, where a child is one number, the complete product up to e^g: value =
+// sgn e^{g + lamp} child (lamp = log |amp|); the bits are the candidate indices walked back (anc: level lvl at lvl * stride).
+template <class T>
+__device__ __forceinline__ void beam_finish_row(long long j, int c, T child, const double* __restrict__ g,
+                                                const int* __restrict__ anc, long long stride, int n, double lamp, double sgn,
+                                                double* __restrict__ val, uint8_t* __restrict__ bits) {
+    long long row = c >> 1;
+    const c64 v = to_c64(scale_t(child, sgn * exp(g[row] + lamp)));
+    val[2 * j] = v.re;
+    val[2 * j + 1] = v.im;
+    bits[j * n + n - 1] = (uint8_t)(c & 1);
+    for (int lvl = n - 2; lvl >= 0; --lvl) {
+        const int a = anc[lvl * stride + row];
+        bits[j * n + lvl] = (uint8_t)(a & 1);
+        row = a >> 1;
+    }
 }
 
 // ------------------------------------------------------------------ block reductions

@@ -331,10 +331,11 @@ struct qil_call_scope {
 };
 
 // (qil_sample.hip) the trace-normalised right environments of qil_sample: R_n = [1], R_{i-1} = sum_s A_i[:, s, :] R_i A_i[:, s, :]^H
-// scaled by 1 / Re tr, in one pool block (*Rall, bond b's chi_b x chi_b matrix at element roff[b]).  log_norm2 (nullable,
-// host) receives the sum of the log traces, log |psi|^2 without the amplitude.  QIL_EDOMAIN ("<verb>: the state has zero norm")
-// for a state of norm 0.
-int qil_dev_right_envs(const struct qil_mps* psi, const char* verb, void** Rall, std::vector<long long>& roff, double* log_norm2);
+// scaled by 1 / Re tr, in one block of tmp (*Rall, bond b's chi_b x chi_b matrix at element roff[b]); the pass's own two
+// temporaries come from tmp and go back before it returns.  log_norm2 (nullable, host) receives the sum of the log traces,
+// log |psi|^2 without the amplitude.  QIL_EDOMAIN ("<verb>: the state has zero norm") for a state of norm 0.
+int qil_dev_right_envs(const struct qil_mps* psi, qil_scratch& tmp, const char* verb, void** Rall, std::vector<long long>& roff,
+                       double* log_norm2);
 
 // ---------------------------------------------------------------- device linear algebra (qil_linalg.hip)
 // All matrices column-major on the device, dtype QIL_F64/QIL_C64.
@@ -420,14 +421,27 @@ int64_t qil_apply_score_panels(int64_t P);
 // rows per chunk: max(1, min(rows, 32768, 64 MiB / per_row_bytes)), the budget of per-row temporaries and the batch limit of
 // the row step's products
 int64_t qil_apply_chunk_rows(int64_t rows, int64_t per_row_bytes);
-// The trace-normalised right environments of |W psi|^2 in the contraction dtype dt: Rk[n] = [1], Rk[k] (k = 1 .. n - 1, bond_k^2
-// elements, bond_k = chi_k D_k) = the mirrored four-product step of the scaled Rk[k + 1] divided by its trace t_k.  Every Rk[k],
-// k = 1 .. n, is a block of tmp; At (2 max chi_l chi_r), Wd and Wr (4 max D_l D_r elements each) are the caller's site scratch.
-// flag (device int, zeroed here) is raised by a trace that is <= 0 or not finite: the caller reads it back and reports under its
-// own name.  log_trace (device double, zeroed here; nullable) receives sum_{k=0}^{n-1} log t_k = log |W psi|^2 without the
-// amplitude, added up in tensor order by one workgroup; with a null log_trace nothing else changes.  Only enqueues.
-int qil_apply_right_envs(qil_context* ctx, qil_scratch& tmp, int dt, const struct qil_mpo* W, const struct qil_mps* psi, void* At,
-                         void* Wd, void* Wr, std::vector<void*>& Rk, int* flag, double* log_trace);
+// over the tensors: maxM = max(chi_l D_l, chi_r D_r) (a row vector), maxX = 2 chi_l D_r, maxW = 4 D_l D_r, maxA = 2 chi_l chi_r
+struct qil_apply_bond_sizes {
+    long long maxM = 1, maxX = 1, maxW = 1, maxA = 1;
+};
+qil_apply_bond_sizes qil_apply_sizes_of(const struct qil_mpo* W, const struct qil_mps* psi);
+// What a lazy sweep works with, all of it blocks of tmp: the site scratch of qil_lazy_row_step (Wc, and As where psi's dtype is
+// not dt) and of the environment pass (At, Wd, Wr), the selector bytes {0, 1} (both + s: output bit s for every row of a step)
+// and the environments Rk[1 .. n] (bond_k^2 elements, bond_k = chi_k D_k)
+struct qil_apply_lazy {
+    qil_apply_bond_sizes b;
+    void *As = nullptr, *At = nullptr, *Wd = nullptr, *Wr = nullptr, *Wc = nullptr;
+    const uint8_t* both = nullptr;
+    std::vector<void*> Rk;
+};
+// The start of qil_apply_sample and qil_apply_top_k: fills lz, with the trace-normalised right environments of |W psi|^2 in the
+// contraction dtype dt: Rk[n] = [1], Rk[k] = the mirrored four-product step of the scaled Rk[k + 1] divided by its trace t_k.
+// *bad = 1 after a trace that is <= 0 or not finite (read back here); the caller reports it under its own name.  log_trace
+// (nullable): *log_trace is a device double of tmp that receives sum_{k=0}^{n-1} log t_k = log |W psi|^2 without the amplitude,
+// added up in tensor order by one workgroup; with a null log_trace nothing else changes.
+int qil_apply_right_envs(qil_context* ctx, qil_scratch& tmp, int dt, const struct qil_mpo* W, const struct qil_mps* psi,
+                         qil_apply_lazy& lz, int* bad, double** log_trace);
 // Partial sums of q_s = Re(m_s R m_s^H) for both children of `rows` rows: child s of row r at children + (s rows + r) P,
 // P = chi D, R the environment of that bond.  gemm route (fused = false): U (2 rows P elements) receives R^H [M_0 M_1] and
 // *panels = 1; fused route: U is not used and *panels = ceil(P / 64).  part[(s *panels + panel) rows + r], to be summed in panel
@@ -445,6 +459,29 @@ int qil_dev_select_largest(qil_context* ctx, const double* keys, long long C, lo
                            void* state, void* blk);
 // the k found rows (device order) to the caller in descending |value|, equal magnitudes in the device's order
 void qil_top_k_deliver(int64_t k, int64_t n, const double* val, const uint8_t* bits, uint8_t* bits_out, double* val_out);
+// ---- (qil_topk.hip) the beam search of qil_top_k and qil_apply_top_k
+// The rows of a frontier, as the search sees them: row r of the f current rows has the children c = 2 r + s.  All pointers are
+// device memory of the search; the calls only enqueue, and the search checks the launches.
+struct qil_beam_rows {
+    // both children of every row at site i: keys[c] and q[c] from p[r] (beam_keys, qil_device_utils.h)
+    virtual int expand(int64_t i, long long f, const double* p, double* keys, double* q) = 0;
+    // the M kept candidates sel[j] (j itself when sel is null) become the rows of site i + 1: gn, pn, anc by beam_gather_row
+    virtual void gather(int64_t i, long long f, const double* keys, const double* q, const double* g, const int* sel, long long M,
+                        double* gn, double* pn, int* anc) = 0;
+    // the last site: val and bits of the M kept candidates by beam_finish_row
+    virtual void finish(long long f, const double* g, const int* sel, long long M, const int* anc, long long stride, double lamp,
+                        double sgn, double* val, uint8_t* bits) = 0;
+
+protected:
+    ~qil_beam_rows() = default;
+};
+long long qil_beam_frontier_cap(int64_t n, int64_t beam);   // the largest frontier: f_0 = 1, f_{i+1} = min(2 f_i, beam)
+// The search over n sites from one row [1] (the caller's): per site expand, keep the min(2 f, beam) largest keys (min(2 f, k) at
+// the last site), gather or finish; then the read-back, qil_top_k_deliver and the bound exp((log dropped + log_norm2) / 2) |amp|
+// on the largest key dropped before the last site.  log_norm2: the host value, or with dev_log_norm2 the device double read back
+// with the outputs.  The bookkeeping belongs to tmp.  One stream synchronisation, at the end.
+int qil_beam_search(qil_context* ctx, qil_scratch& tmp, qil_beam_rows& rows, int64_t n, int64_t k, int64_t beam, double amp,
+                    double log_norm2, const double* dev_log_norm2, uint8_t* bits_out, double* val_out, double* bound_out);
 // (qil_hadamard.hip) phi against psi under `verb`: context, paired flag (QIL_EINVAL_ARG), length (QIL_EINVAL_LENGTH), site ids
 // (QIL_EINVAL_SITES), in that order; touches no device
 int qil_check_pair(const char* verb, const struct qil_mps* phi, const struct qil_mps* psi);

@@ -12,6 +12,9 @@
 //          T in LDS (transposed, so the second product can take it as its row operand), neither T nor T R_i goes to HBM
 //   gemm   any bonds: T = V A_i and U_s = T_s R_i through qil_dev_gemm, then a reduce-and-choose kernel
 // Sample rows live column-major (row fastest, ld = rows of the chunk) on both routes.
+// Shared: the uniforms and the choice (seeded_uniform, choose) and the GEMM route's row sums (children_row_sums, qil_top_k's
+// too) are in qil_device_utils.h, where qil_apply_sample finds the same rule.  Every pool block of a call belongs to the
+// qil_scratch of sample_impl; qil_dev_right_envs takes its caller's.
 #include "qil_internal.h"
 #include "qil_device_utils.h"
 
@@ -22,29 +25,6 @@
 namespace {
 
 using namespace qil_dev;
-
-// u_{r,i} = (splitmix64(seed ^ splitmix64(r n + i)) >> 11) 2^-53, in [0, 1)
-__device__ __forceinline__ double seeded_uniform(uint64_t seed, long long r, int n, int i) {
-    const uint64_t h = splitmix64(seed ^ splitmix64((uint64_t)r * (uint64_t)n + (uint64_t)i));
-    return (double)(h >> 11) * (1.0 / 9007199254740992.0);
-}
-
-// The choice of one sample at one site.  q_0 + q_1 <= 0 (a prefix of weight zero reached through rounding): the larger q,
-// s = 0 when both are 0, and the probability factor is 0.  The row is rescaled by 1 / sqrt(q_s), or zeroed when q_s <= 0.
-__device__ __forceinline__ int choose(double q0, double q1, double u, double& factor, double& scl) {
-    const double sum = q0 + q1;
-    int s;
-    if (sum > 0.0) {
-        s = u * sum < q0 ? 0 : 1;
-        factor = (s ? q1 : q0) / sum;
-    } else {
-        s = q1 > q0 ? 1 : 0;
-        factor = 0.0;
-    }
-    const double qs = s ? q1 : q0;
-    scl = qs > 0.0 ? 1.0 / sqrt(qs) : 0.0;
-    return s;
-}
 
 // ---- small kernels ---------------------------------------------------------------------------------------------
 // v[r] = 1 (column 0 of the sample rows), p[r] = 1
@@ -222,8 +202,8 @@ static int launch_fused(qil_context* ctx, const void* V, long long rows, int cl,
 }
 
 // ---- GEMM route: reduce and choose -------------------------------------------------------------------------------
-// T (rows x 2 chi_r, column s + 2 beta) and U_s = T_s R (rows x chi_r at U + s rows chi_r), both ld = rows.  A workgroup
-// owns 32 rows; its 8 groups of 32 threads split the columns (coalesced over the rows), LDS sums the groups.
+// T (rows x 2 chi_r) and U_s = T_s R in the layout of children_row_sums (qil_device_utils.h, qil_top_k's reduction too): a
+// workgroup owns 32 rows, its 8 groups of 32 threads split the columns; then the choice, and the chosen child rescaled.
 constexpr int kChooseRows = 32, kChooseGroups = 8;
 template <class T>
 __global__ __launch_bounds__(kChooseRows* kChooseGroups) void gemm_choose(const T* __restrict__ Tm, const T* __restrict__ Us,
@@ -236,26 +216,12 @@ __global__ __launch_bounds__(kChooseRows* kChooseGroups) void gemm_choose(const 
     __shared__ int ssel[kChooseRows];
     const int r = threadIdx.x % kChooseRows, g = threadIdx.x / kChooseRows;
     const long long row = (long long)blockIdx.x * kChooseRows + r;
-    double q0 = 0.0, q1 = 0.0;
-    if (row < rows)
-        for (int beta = g; beta < cr; beta += kChooseGroups) {
-            const T t0 = Tm[row + rows * (2LL * beta)], t1 = Tm[row + rows * (1 + 2LL * beta)];
-            const T u0 = Us[row + rows * (long long)beta], u1 = Us[row + rows * ((long long)cr + beta)];
-            q0 += re_of(u0) * re_of(t0) + im_of(u0) * im_of(t0);
-            q1 += re_of(u1) * re_of(t1) + im_of(u1) * im_of(t1);
-        }
-    qs[0][g][r] = q0;
-    qs[1][g][r] = q1;
-    __syncthreads();
+    double a = 0.0, b = 0.0;
+    const bool mine = children_row_sums<kChooseRows, kChooseGroups>(Tm, Us, rows, cr, qs, a, b);
     if (g == 0) {
         int s = 0;
         double scl = 0.0;
-        if (row < rows) {
-            double a = 0.0, b = 0.0;
-            for (int j = 0; j < kChooseGroups; ++j) {
-                a += qs[0][j][r];
-                b += qs[1][j][r];
-            }
+        if (mine) {
             const double u = U ? U[row * n + site] : seeded_uniform(seed, gbase + row, n, site);
             double f;
             s = choose(a, b, u, f, scl);
@@ -273,7 +239,8 @@ __global__ __launch_bounds__(kChooseRows* kChooseGroups) void gemm_choose(const 
 
 // ---- right environments (shared with qil_top_k) -------------------------------------------------------------------
 template <class T>
-static int right_envs(const qil_mps* psi, const char* verb, void** Rall, std::vector<long long>& roff, double* log_norm2) {
+static int right_envs(const qil_mps* psi, qil_scratch& tmp, const char* verb, void** Rall, std::vector<long long>& roff,
+                      double* log_norm2) {
     qil_context* ctx = psi->ctx;
     const int dt = psi->dtype;
     const size_t e = sizeof(T);
@@ -287,9 +254,9 @@ static int right_envs(const qil_mps* psi, const char* verb, void** Rall, std::ve
     }
     for (int64_t i = 0; i < n; ++i) maxT = std::max<long long>(maxT, 2 * d[(size_t)i] * d[(size_t)i + 1]);
     void *Tenv = nullptr, *inv = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)envsum * e, Rall));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxT * e, &Tenv));
-    QIL_TRY(qil_ctx_alloc(ctx, log_norm2 ? 16 : 8, &inv));
+    QIL_TRY(tmp.alloc((size_t)envsum * e, Rall));
+    QIL_TRY(tmp.alloc((size_t)maxT * e, &Tenv));
+    QIL_TRY(tmp.alloc(log_norm2 ? 16 : 8, &inv));
     T* Rb = static_cast<T*>(*Rall);
     double* logsum = log_norm2 ? static_cast<double*>(inv) + 1 : nullptr;
     if (logsum) QIL_HIP(hipMemsetAsync(logsum, 0, 8, qil_stream(ctx)));
@@ -312,8 +279,8 @@ static int right_envs(const qil_mps* psi, const char* verb, void** Rall, std::ve
         QIL_REQUIRE(h[0] > 0.0, QIL_EDOMAIN, "%s: the state has zero norm", verb);
         if (logsum) QIL_TRY(qil_read_back(ctx, log_norm2, logsum, 8));
     }
-    qil_ctx_free(ctx, Tenv);
-    qil_ctx_free(ctx, inv);
+    tmp.free(Tenv);                                    // the pool recycles in stream order
+    tmp.free(inv);
     return QIL_OK;
 }
 
@@ -343,8 +310,9 @@ static int sample_impl(const qil_mps* psi, int64_t nb, uint64_t seed, const doub
     else if (route && !strcmp(route, "gemm")) fused = false;
 
     // ---- environments, right to left
+    qil_scratch tmp(ctx);
     void* Rall = nullptr;
-    QIL_TRY(right_envs<T>(psi, "sample", &Rall, roff, nullptr));
+    QIL_TRY(right_envs<T>(psi, tmp, "sample", &Rall, roff, nullptr));
     T* Rb = static_cast<T*>(Rall);
 
     // ---- the sweep, in chunks of rows (row buffers ~1 GB)
@@ -352,13 +320,13 @@ static int sample_impl(const qil_mps* psi, int64_t nb, uint64_t seed, const doub
     long long chunk = std::max<long long>(kRows, ((1LL << 30) / per_row) / kRows * kRows);
     chunk = std::min<long long>(chunk, nb);
     void *V = nullptr, *Vn = nullptr, *dbits = nullptr, *dprob = nullptr, *dU = nullptr, *Tm = nullptr, *Us = nullptr, *Ast = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(chunk * maxchi) * e, &V));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(chunk * maxchi) * e, &Vn));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(chunk * n), &dbits));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)chunk * 8, &dprob));
-    if (uniforms) QIL_TRY(qil_ctx_alloc(ctx, (size_t)(chunk * n) * 8, &dU));
+    QIL_TRY(tmp.alloc((size_t)(chunk * maxchi) * e, &V));
+    QIL_TRY(tmp.alloc((size_t)(chunk * maxchi) * e, &Vn));
+    QIL_TRY(tmp.alloc((size_t)(chunk * n), &dbits));
+    QIL_TRY(tmp.alloc((size_t)chunk * 8, &dprob));
+    if (uniforms) QIL_TRY(tmp.alloc((size_t)(chunk * n) * 8, &dU));
     if (fused) {
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)sitesum * e, &Ast));
+        QIL_TRY(tmp.alloc((size_t)sitesum * e, &Ast));
         for (int64_t i = 0; i < n; ++i) {
             const int64_t cl = d[(size_t)i], cr = d[(size_t)i + 1];
             hipLaunchKernelGGL(site_rows<T>, dim3(qil_grid_for(2 * cl * cr)), dim3(256), 0, qil_stream(ctx), (const T*)psi->site[(size_t)i],
@@ -366,8 +334,8 @@ static int sample_impl(const qil_mps* psi, int64_t nb, uint64_t seed, const doub
         }
         QIL_HIP(hipGetLastError());
     } else {
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(chunk * 2 * maxchi) * e, &Tm));
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(chunk * 2 * maxchi) * e, &Us));
+        QIL_TRY(tmp.alloc((size_t)(chunk * 2 * maxchi) * e, &Tm));
+        QIL_TRY(tmp.alloc((size_t)(chunk * 2 * maxchi) * e, &Us));
     }
     for (long long r0 = 0; r0 < nb; r0 += chunk) {
         const long long rows = std::min<long long>(chunk, nb - r0);
@@ -399,16 +367,15 @@ static int sample_impl(const qil_mps* psi, int64_t nb, uint64_t seed, const doub
         if (prob_out) QIL_HIP(hipMemcpyAsync(prob_out + r0, dprob, (size_t)rows * 8, hipMemcpyDeviceToHost, qil_stream(ctx)));
         QIL_HIP(qil_stream_sync(ctx));
     }
-    for (void* p : {Rall, V, Vn, dbits, dprob, dU, Tm, Us, Ast})
-        if (p) qil_ctx_free(ctx, p);
     return QIL_OK;
 }
 
 }  // namespace
 
-int qil_dev_right_envs(const qil_mps* psi, const char* verb, void** Rall, std::vector<long long>& roff, double* log_norm2) {
-    if (psi->dtype == QIL_C64) return right_envs<c64>(psi, verb, Rall, roff, log_norm2);
-    return right_envs<double>(psi, verb, Rall, roff, log_norm2);
+int qil_dev_right_envs(const qil_mps* psi, qil_scratch& tmp, const char* verb, void** Rall, std::vector<long long>& roff,
+                       double* log_norm2) {
+    if (psi->dtype == QIL_C64) return right_envs<c64>(psi, tmp, verb, Rall, roff, log_norm2);
+    return right_envs<double>(psi, tmp, verb, Rall, roff, log_norm2);
 }
 
 extern "C" int qil_sample(const qil_mps* psi, int64_t nb, uint64_t seed, const double* uniforms, uint8_t* bits_out, double* prob_out) {

@@ -15,6 +15,11 @@
 //   last site      value = amp T_s e^g (R_n = [1]), bits by walking the candidate indices back; the host orders the k rows
 // Frontier sizes are min(2^i, beam): known on the host, so no count is read back.  All reductions have a fixed order and the
 // counts are integer atomics: the output is bit-identical from run to run.
+// One search for two verbs.  qil_beam_search below owns the bookkeeping (keys, q, g, p, the selection, the back-walk levels),
+// the frontier sizes, the read-back, the delivery and the bound; it sees the rows through qil_beam_rows (qil_internal.h):
+// expand, gather, finish.  prefix_rows is qil_top_k's (V, T, U_s and the three kernels here), lazy_rows qil_apply_top_k's
+// (qil_apply_topk.hip).  The per-row arithmetic of those kernels -- beam_keys, beam_child_scale, beam_gather_row,
+// beam_finish_row -- and the row sums of score_children (children_row_sums, qil_sample's too) are in qil_device_utils.h.
 #include "qil_internal.h"
 #include "qil_device_utils.h"
 
@@ -34,51 +39,26 @@ constexpr long long kBeamHardCap = 1LL << 29;    // candidate indices 2r + s sta
 __device__ __forceinline__ unsigned long long key_bits(double k) { return (unsigned long long)__double_as_longlong(k); }
 
 // ---- frontier start ----------------------------------------------------------------------------------------------------
-template <class T>
-__global__ void start_frontier(T* __restrict__ V, double* __restrict__ g, double* __restrict__ p) {
+// g_0 = 0, p_0 = 1 and nothing dropped yet; the one row itself ([1]) is the verb's
+__global__ void start_frontier(double* __restrict__ g, double* __restrict__ p, unsigned long long* __restrict__ drop) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
-        V[0] = cast_elem<T>(1.0);
         g[0] = 0.0;
         p[0] = 1.0;
+        drop[0] = 0;
     }
 }
 
 // ---- scoring: both children's weights ------------------------------------------------------------------------------------
-// T (rows x 2 chi_r, column s + 2 beta) and U_s = T_s R (rows x chi_r at U + s rows chi_r), both ld = rows.  A workgroup owns 32
-// rows; its 8 groups of 32 threads split the columns (coalesced over the rows), LDS sums the groups in a fixed order.
-// q_s < 0 (rounding of a PSD form) or NaN counts as 0.
+// T (rows x 2 chi_r) and U_s = T_s R in the layout of children_row_sums (qil_device_utils.h): a workgroup owns 32 rows, its 8
+// groups of 32 threads split the columns; then the keys (beam_keys).
 template <class T>
 __global__ __launch_bounds__(kScoreRows* kScoreGroups) void score_children(const T* __restrict__ Tm, const T* __restrict__ Us,
                                                                            long long rows, int cr, const double* __restrict__ p,
                                                                            double* __restrict__ keys, double* __restrict__ q) {
     __shared__ double qs[2][kScoreGroups][kScoreRows];
-    const int r = threadIdx.x % kScoreRows, g = threadIdx.x / kScoreRows;
-    const long long row = (long long)blockIdx.x * kScoreRows + r;
-    double q0 = 0.0, q1 = 0.0;
-    if (row < rows)
-        for (int beta = g; beta < cr; beta += kScoreGroups) {
-            const c64 t0 = to_c64(Tm[row + rows * (2LL * beta)]), t1 = to_c64(Tm[row + rows * (1 + 2LL * beta)]);
-            const c64 u0 = to_c64(Us[row + rows * (long long)beta]), u1 = to_c64(Us[row + rows * ((long long)cr + beta)]);
-            q0 += u0.re * t0.re + u0.im * t0.im;
-            q1 += u1.re * t1.re + u1.im * t1.im;
-        }
-    qs[0][g][r] = q0;
-    qs[1][g][r] = q1;
-    __syncthreads();
-    if (g == 0 && row < rows) {
-        double a = 0.0, b = 0.0;
-        for (int j = 0; j < kScoreGroups; ++j) {
-            a += qs[0][j][r];
-            b += qs[1][j][r];
-        }
-        a = fmax(a, 0.0);
-        b = fmax(b, 0.0);
-        const double sum = a + b, pr = p[row];
-        keys[2 * row] = sum > 0.0 ? pr * (a / sum) : 0.0;
-        keys[2 * row + 1] = sum > 0.0 ? pr * (b / sum) : 0.0;
-        q[2 * row] = a;
-        q[2 * row + 1] = b;
-    }
+    double a = 0.0, b = 0.0;
+    if (children_row_sums<kScoreRows, kScoreGroups>(Tm, Us, rows, cr, qs, a, b))
+        beam_keys(a, b, (long long)blockIdx.x * kScoreRows + threadIdx.x % kScoreRows, p, keys, q);
 }
 
 // ---- radix select -------------------------------------------------------------------------------------------------------
@@ -290,33 +270,20 @@ __global__ void gather_frontier(const T* __restrict__ Tm, long long f, int cr, c
         const long long row = c >> 1;
         const int s = c & 1;
         const double qq = q[c];
-        V[j + M * beta] = scale_t(Tm[row + f * (s + 2LL * beta)], qq > 0.0 ? 1.0 / sqrt(qq) : 0.0);
-        if (beta == 0) {
-            gn[j] = g[row] + (qq > 0.0 ? 0.5 * log(qq) : 0.0);
-            pn[j] = keys[c];
-            anc[j] = c;
-        }
+        V[j + M * beta] = scale_t(Tm[row + f * (s + 2LL * beta)], beam_child_scale(qq));
+        if (beta == 0) beam_gather_row(j, c, qq, keys, g, gn, pn, anc);
     }
 }
 
 // ---- the last site: values and bit rows ----------------------------------------------------------------------------------
-// T (f x 2, chi_r = 1) holds the complete products up to e^g; the bits are the candidate indices walked back, level by level.
+// T (f x 2, chi_r = 1) holds the complete products up to e^g: beam_finish_row on child c & 1 of row c >> 1
 template <class T>
 __global__ void finish_rows(const T* __restrict__ Tm, long long f, const double* __restrict__ g, const int* __restrict__ sel,
                             long long M, const int* __restrict__ anc, long long stride, int n, double lamp, double sgn,
                             double* __restrict__ val, uint8_t* __restrict__ bits) {
     for (long long j = blockIdx.x * (long long)blockDim.x + threadIdx.x; j < M; j += (long long)gridDim.x * blockDim.x) {
         const int c = sel ? sel[j] : (int)j;
-        long long row = c >> 1;
-        const c64 v = to_c64(scale_t(Tm[row + f * (c & 1)], sgn * exp(g[row] + lamp)));
-        val[2 * j] = v.re;
-        val[2 * j + 1] = v.im;
-        bits[j * n + n - 1] = (uint8_t)(c & 1);
-        for (int lvl = n - 2; lvl >= 0; --lvl) {
-            const int a = anc[lvl * stride + row];
-            bits[j * n + lvl] = (uint8_t)(a & 1);
-            row = a >> 1;
-        }
+        beam_finish_row(j, c, Tm[(c >> 1) + f * (c & 1)], g, anc, stride, n, lamp, sgn, val, bits);
     }
 }
 
@@ -357,83 +324,56 @@ void qil_top_k_deliver(int64_t k, int64_t n, const double* val, const uint8_t* b
     }
 }
 
-namespace {
-
-// ---- the call -----------------------------------------------------------------------------------------------------------
-template <class T>
-static int top_k_impl(const qil_mps* psi, int64_t k, int64_t beam, uint8_t* bits_out, double* val_out, double* bound_out) {
-    qil_context* ctx = psi->ctx;
-    const int dt = psi->dtype;
-    const size_t e = sizeof(T);
-    const int64_t n = psi->n();
-    const std::vector<int64_t>& d = psi->dims;
-    long long maxchi = 1;
-    for (int64_t b = 0; b <= n; ++b) maxchi = std::max<long long>(maxchi, d[(size_t)b]);
-    // frontier sizes f_0 = 1, f_{i+1} = min(2 f_i, beam): the largest one sizes the buffers
+// ---- the search, for qil_top_k and qil_apply_top_k (qil_internal.h) ---------------------------------------------------------
+long long qil_beam_frontier_cap(int64_t n, int64_t beam) {
     long long fcap = 1;
     for (long long f = 1, i = 0; i < n; ++i, f = std::min<long long>(2 * f, beam)) fcap = std::max(fcap, f);
+    return fcap;
+}
 
-    // ---- environments, right to left
-    void* Rall = nullptr;
-    std::vector<long long> roff;
-    double log_norm2 = 0.0;
-    QIL_TRY(qil_dev_right_envs(psi, "top_k", &Rall, roff, &log_norm2));
-    const T* Rb = static_cast<const T*>(Rall);
-
-    // ---- buffers: frontier, both children, T_s R, the per-candidate and per-row bookkeeping, the backtrack
-    void *V = nullptr, *Tm = nullptr, *Us = nullptr, *keys = nullptr, *q = nullptr, *g[2] = {nullptr, nullptr}, *p[2] = {nullptr, nullptr};
+int qil_beam_search(qil_context* ctx, qil_scratch& tmp, qil_beam_rows& rows, int64_t n, int64_t k, int64_t beam, double amp,
+                    double log_norm2, const double* dev_log_norm2, uint8_t* bits_out, double* val_out, double* bound_out) {
+    const long long fcap = qil_beam_frontier_cap(n, beam);
+    // ---- the per-candidate and per-row bookkeeping, the selection's state, the back-walk, the result
+    void *keys = nullptr, *q = nullptr, *g[2] = {nullptr, nullptr}, *p[2] = {nullptr, nullptr};
     void *sel = nullptr, *anc = nullptr, *blk = nullptr, *st = nullptr, *drop = nullptr, *dval = nullptr, *dbits = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(fcap * maxchi) * e, &V));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(fcap * 2 * maxchi) * e, &Tm));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(fcap * 2 * maxchi) * e, &Us));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(2 * fcap) * 8, &keys));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(2 * fcap) * 8, &q));
+    QIL_TRY(tmp.alloc((size_t)(2 * fcap) * 8, &keys));
+    QIL_TRY(tmp.alloc((size_t)(2 * fcap) * 8, &q));
     for (int b = 0; b < 2; ++b) {
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)fcap * 8, &g[b]));
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)fcap * 8, &p[b]));
+        QIL_TRY(tmp.alloc((size_t)fcap * 8, &g[b]));
+        QIL_TRY(tmp.alloc((size_t)fcap * 8, &p[b]));
     }
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(2 * fcap) * 4, &sel));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(std::max<int64_t>(n - 1, 1) * fcap) * 4, &anc));
-    QIL_TRY(qil_ctx_alloc(ctx, qil_dev_select_block_bytes(2 * fcap), &blk));
-    QIL_TRY(qil_ctx_alloc(ctx, qil_dev_select_state_bytes(), &st));
-    QIL_TRY(qil_ctx_alloc(ctx, 8, &drop));   // bit pattern of the largest key dropped before the last site (all levels)
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)k * 16, &dval));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(k * n), &dbits));
-    QIL_HIP(hipMemsetAsync(drop, 0, 8, qil_stream(ctx)));
-    hipLaunchKernelGGL(start_frontier<T>, dim3(1), dim3(64), 0, qil_stream(ctx), static_cast<T*>(V), (double*)g[0], (double*)p[0]);
+    QIL_TRY(tmp.alloc((size_t)(2 * fcap) * 4, &sel));
+    QIL_TRY(tmp.alloc((size_t)(std::max<int64_t>(n - 1, 1) * fcap) * 4, &anc));
+    QIL_TRY(tmp.alloc(qil_dev_select_block_bytes(2 * fcap), &blk));
+    QIL_TRY(tmp.alloc(qil_dev_select_state_bytes(), &st));
+    QIL_TRY(tmp.alloc(8, &drop));   // bit pattern of the largest key dropped before the last site (all levels)
+    QIL_TRY(tmp.alloc((size_t)k * 16, &dval));
+    QIL_TRY(tmp.alloc((size_t)(k * n), &dbits));
+    hipLaunchKernelGGL(start_frontier, dim3(1), dim3(64), 0, qil_stream(ctx), (double*)g[0], (double*)p[0], (unsigned long long*)drop);
     QIL_HIP(hipGetLastError());
 
-    // ---- the search, site by site
-    const double amp = psi->amplitude;
+    // ---- site by site: frontier sizes f_0 = 1, f_{i+1} = min(2 f_i, beam)
     const double lamp = std::log(std::fabs(amp)), sgn = amp < 0.0 ? -1.0 : 1.0;
     long long f = 1;
     int cur = 0;
     for (int64_t i = 0; i < n; ++i) {
-        const int64_t cl = d[(size_t)i], cr = d[(size_t)i + 1];
-        const T* R = Rb + roff[(size_t)i + 1];
         const bool last = i == n - 1;
-        // T (f x 2 chi_r) = V A;  U_s (f x chi_r) = T_s R  (slice s: offset s rows, ld 2 rows)
-        QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, f, 2 * cr, cl, V, f, psi->site[(size_t)i], cl, Tm, f));
-        for (int s = 0; s < 2; ++s)
-            QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, f, cr, cr, static_cast<const T*>(Tm) + s * f, 2 * f, R, cr, static_cast<T*>(Us) + s * f * cr, f));
-        hipLaunchKernelGGL(score_children<T>, dim3((unsigned)((f + kScoreRows - 1) / kScoreRows)), dim3(kScoreRows * kScoreGroups), 0,
-                           qil_stream(ctx), (const T*)Tm, (const T*)Us, f, (int)cr, (const double*)p[cur], (double*)keys, (double*)q);
+        QIL_TRY(rows.expand(i, f, (const double*)p[cur], (double*)keys, (double*)q));
         QIL_HIP(hipGetLastError());
         const long long C = 2 * f, M = std::min<long long>(C, last ? k : beam);
-        const int* dsel = nullptr;
+        const int* kept = nullptr;
         if (M < C) {
             QIL_TRY(qil_dev_select_largest(ctx, (const double*)keys, C, M, (int*)sel, last ? nullptr : (unsigned long long*)drop, st, blk));
-            dsel = static_cast<const int*>(sel);
+            kept = static_cast<const int*>(sel);
         }
-        if (!last) {
-            hipLaunchKernelGGL(gather_frontier<T>, dim3(qil_grid_for(M * cr)), dim3(256), 0, qil_stream(ctx), (const T*)Tm, f, (int)cr,
-                               (const double*)keys, (const double*)q, (const double*)g[cur], dsel, M, static_cast<T*>(V),
-                               (double*)g[1 - cur], (double*)p[1 - cur], static_cast<int*>(anc) + i * fcap);
+        if (last) {
+            rows.finish(f, (const double*)g[cur], kept, M, (const int*)anc, fcap, lamp, sgn, (double*)dval, (uint8_t*)dbits);
+        } else {
+            rows.gather(i, f, (const double*)keys, (const double*)q, (const double*)g[cur], kept, M, (double*)g[1 - cur],
+                        (double*)p[1 - cur], static_cast<int*>(anc) + i * fcap);
             cur = 1 - cur;
             f = M;
-        } else {
-            hipLaunchKernelGGL(finish_rows<T>, dim3(qil_grid_for(M)), dim3(256), 0, qil_stream(ctx), (const T*)Tm, f, (const double*)g[cur], dsel,
-                               M, (const int*)anc, fcap, (int)n, lamp, sgn, (double*)dval, (uint8_t*)dbits);
         }
         QIL_HIP(hipGetLastError());
     }
@@ -443,14 +383,78 @@ static int top_k_impl(const qil_mps* psi, int64_t k, int64_t beam, uint8_t* bits
     QIL_HIP(hipMemcpyAsync(hval.data(), dval, (size_t)k * 16, hipMemcpyDeviceToHost, qil_stream(ctx)));
     QIL_HIP(hipMemcpyAsync(hbits.data(), dbits, (size_t)(k * n), hipMemcpyDeviceToHost, qil_stream(ctx)));
     QIL_HIP(hipMemcpyAsync(&hdrop, drop, 8, hipMemcpyDeviceToHost, qil_stream(ctx)));
+    if (dev_log_norm2) QIL_HIP(hipMemcpyAsync(&log_norm2, dev_log_norm2, 8, hipMemcpyDeviceToHost, qil_stream(ctx)));
     QIL_HIP(qil_stream_sync(ctx));
-    for (void* b : {Rall, V, Tm, Us, keys, q, g[0], g[1], p[0], p[1], sel, anc, blk, st, drop, dval, dbits}) qil_ctx_free(ctx, b);
 
     qil_top_k_deliver(k, n, hval.data(), hbits.data(), bits_out, val_out);
     double dropped = 0.0;
     std::memcpy(&dropped, &hdrop, 8);
     *bound_out = dropped > 0.0 ? std::exp(0.5 * (std::log(dropped) + log_norm2) + lamp) : 0.0;
     return QIL_OK;
+}
+
+namespace {
+
+// ---- the call -----------------------------------------------------------------------------------------------------------
+// the rows of qil_top_k: the prefix vectors v_r (f x chi, ld f, row fastest), both children T = V A_i and U_s = T_s R_{i+1}
+template <class T>
+struct prefix_rows final : qil_beam_rows {
+    qil_context* ctx;
+    const qil_mps* psi;
+    const T* Rb;
+    const std::vector<long long>& roff;
+    void *V, *Tm, *Us;
+    prefix_rows(const qil_mps* x, const void* R, const std::vector<long long>& off, void* v, void* t, void* u)
+        : ctx(x->ctx), psi(x), Rb(static_cast<const T*>(R)), roff(off), V(v), Tm(t), Us(u) {}
+
+    int expand(int64_t i, long long f, const double* p, double* keys, double* q) override {
+        const int dt = psi->dtype;
+        const int64_t cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1];
+        const T* R = Rb + roff[(size_t)i + 1];
+        // T (f x 2 chi_r) = V A;  U_s (f x chi_r) = T_s R  (slice s: offset s rows, ld 2 rows)
+        QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, f, 2 * cr, cl, V, f, psi->site[(size_t)i], cl, Tm, f));
+        for (int s = 0; s < 2; ++s)
+            QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, f, cr, cr, static_cast<const T*>(Tm) + s * f, 2 * f, R, cr, static_cast<T*>(Us) + s * f * cr, f));
+        hipLaunchKernelGGL(score_children<T>, dim3((unsigned)((f + kScoreRows - 1) / kScoreRows)), dim3(kScoreRows * kScoreGroups), 0,
+                           qil_stream(ctx), (const T*)Tm, (const T*)Us, f, (int)cr, p, keys, q);
+        return QIL_OK;
+    }
+    void gather(int64_t i, long long f, const double* keys, const double* q, const double* g, const int* sel, long long M, double* gn,
+                double* pn, int* anc) override {
+        const int64_t cr = psi->dims[(size_t)i + 1];
+        hipLaunchKernelGGL(gather_frontier<T>, dim3(qil_grid_for(M * cr)), dim3(256), 0, qil_stream(ctx), (const T*)Tm, f, (int)cr, keys, q,
+                           g, sel, M, static_cast<T*>(V), gn, pn, anc);
+    }
+    void finish(long long f, const double* g, const int* sel, long long M, const int* anc, long long stride, double lamp, double sgn,
+                double* val, uint8_t* bits) override {
+        hipLaunchKernelGGL(finish_rows<T>, dim3(qil_grid_for(M)), dim3(256), 0, qil_stream(ctx), (const T*)Tm, f, g, sel, M, anc, stride,
+                           (int)psi->n(), lamp, sgn, val, bits);
+    }
+};
+
+template <class T>
+static int top_k_impl(const qil_mps* psi, int64_t k, int64_t beam, uint8_t* bits_out, double* val_out, double* bound_out) {
+    qil_context* ctx = psi->ctx;
+    const size_t e = sizeof(T);
+    long long maxchi = 1;
+    for (int64_t b : psi->dims) maxchi = std::max<long long>(maxchi, b);
+    const long long fcap = qil_beam_frontier_cap(psi->n(), beam);
+    qil_scratch tmp(ctx);
+
+    // ---- environments, right to left
+    void* Rall = nullptr;
+    std::vector<long long> roff;
+    double log_norm2 = 0.0;
+    QIL_TRY(qil_dev_right_envs(psi, tmp, "top_k", &Rall, roff, &log_norm2));
+
+    // ---- the rows: frontier, both children, T_s R
+    void *V = nullptr, *Tm = nullptr, *Us = nullptr;
+    QIL_TRY(tmp.alloc((size_t)(fcap * maxchi) * e, &V));
+    QIL_TRY(tmp.alloc((size_t)(fcap * 2 * maxchi) * e, &Tm));
+    QIL_TRY(tmp.alloc((size_t)(fcap * 2 * maxchi) * e, &Us));
+    QIL_TRY(qil_dev_fill_ones(ctx, psi->dtype, V, 1));
+    prefix_rows<T> rows(psi, Rall, roff, V, Tm, Us);
+    return qil_beam_search(ctx, tmp, rows, psi->n(), k, beam, psi->amplitude, log_norm2, nullptr, bits_out, val_out, bound_out);
 }
 
 // beam <= min(2^29, 2^30 / (3 chi s + 4 n + 64)): chi = the largest bond, s = 8 (f64) / 16 (c64), n = the number of site

@@ -756,24 +756,7 @@ def sample(psi, nsamples, seed=1234, uniforms=None, bits=False):
     bits=True: the raw (nsamples, n) uint8 rows, the layout of `coefficient_batch` (required when n > 62)."""
     if not isinstance(psi, SignalMPS):
         raise TypeError("sample: unsupported operand types")
-    nb = int(nsamples)
-    if nb < 0:
-        raise ValueError("sample: nsamples must be non-negative")
-    n = _ntensors(psi)
-    paired = isinstance(psi, ZTMPS)
-    if not bits and (n if not paired else n // 2) > 62:
-        raise ValueError(f"sample: {n} sites do not fit an integer index; use bits=True")
-    u_ptr = None
-    if uniforms is not None:
-        u = np.ascontiguousarray(uniforms, dtype=np.float64)
-        if u.shape != (nb, n):
-            raise ValueError(f"sample: uniforms must have shape ({nb}, {n}), got {u.shape}")
-        u_ptr = u.ctypes.data_as(C.POINTER(C.c_double))
-    out = np.zeros((nb, n), dtype=np.uint8)
-    probs = np.zeros(nb, dtype=np.float64)
-    L.check(L.lib.qil_sample(psi.handle, nb, int(seed) & 0xFFFFFFFFFFFFFFFF, u_ptr, out.ctypes.data_as(C.POINTER(C.c_uint8)),
-                             probs.ctypes.data_as(C.POINTER(C.c_double))))
-    return _decode_rows(out, paired, bits), probs
+    return _sample(L.lib.qil_sample, (psi,), nsamples, seed, uniforms, bits, check_uniforms=False)
 
 
 def apply_sample(W, psi, nsamples, seed=1234, uniforms=None, bits=False):
@@ -788,6 +771,13 @@ def apply_sample(W, psi, nsamples, seed=1234, uniforms=None, bits=False):
     cap).  Where the product fits and the bonds are small, `sample(apply(W, psi), ...)` is faster (4x at the natural zT bonds of
     n = 20, MEASUREMENTS section 18); this call is for the operands whose product does not fit and breaks even near chi D = 2048."""
     _require_operator(W, psi)
+    return _sample(L.lib.qil_apply_sample, (W, psi), nsamples, seed, uniforms, bits, check_uniforms=True)
+
+
+def _sample(entry, operands, nsamples, seed, uniforms, bits, check_uniforms):
+    """The argument checks, the native call and the decoding of `sample` and `apply_sample`; operands = (psi,) or (W, psi).  Only
+    `apply_sample` checks the uniforms' range here; `sample` leaves that to the library, whose message names the offender."""
+    psi = operands[-1]
     nb = int(nsamples)
     if nb < 0:
         raise ValueError("sample: nsamples must be non-negative")
@@ -800,13 +790,13 @@ def apply_sample(W, psi, nsamples, seed=1234, uniforms=None, bits=False):
         u = np.ascontiguousarray(uniforms, dtype=np.float64)
         if u.shape != (nb, n):
             raise ValueError(f"sample: uniforms must have shape ({nb}, {n}), got {u.shape}")
-        if u.size and not bool(np.all((u >= 0.0) & (u < 1.0))):
+        if check_uniforms and u.size and not bool(np.all((u >= 0.0) & (u < 1.0))):
             raise ValueError("sample: uniform outside [0, 1)")
         u_ptr = u.ctypes.data_as(C.POINTER(C.c_double))
     out = np.zeros((nb, n), dtype=np.uint8)
     probs = np.zeros(nb, dtype=np.float64)
-    L.check(L.lib.qil_apply_sample(W.handle, psi.handle, nb, int(seed) & 0xFFFFFFFFFFFFFFFF, u_ptr,
-                                   out.ctypes.data_as(C.POINTER(C.c_uint8)), probs.ctypes.data_as(C.POINTER(C.c_double))))
+    L.check(entry(*(x.handle for x in operands), nb, int(seed) & 0xFFFFFFFFFFFFFFFF, u_ptr, out.ctypes.data_as(C.POINTER(C.c_uint8)),
+                  probs.ctypes.data_as(C.POINTER(C.c_double))))
     return _decode_rows(out, paired, bits), probs
 
 

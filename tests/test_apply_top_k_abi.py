@@ -95,9 +95,17 @@ def test_the_verb_has_kernels_of_its_own_and_shares_the_rest():
         assert re.search(r"hipLaunchKernelGGL\(" + kernel + r"[<,]", code), kernel
     assert "qil_scratch" in code and "qil_call_scope" in code and "asm" not in code
     for shared in ("qil_apply_right_envs(", "qil_apply_score_children(", "qil_apply_score_fused(", "qil_apply_env_budget(",
-                   "qil_lazy_row_step(", "qil_dev_select_largest(", "qil_top_k_deliver("):
+                   "qil_lazy_row_step(", "qil_beam_search("):
         assert shared in code, shared
     assert "getenv" not in code                                                    # budget and route are read in one place
+    # the search itself, with the selection and the delivery, is the driver's: declared once, defined once, and each of the two
+    # calls occurs once in the tree outside its definition
+    sources = {f: _code(f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))}
+    assert sources["qil_internal.h"].count("int qil_beam_search(") == 1 and sources["qil_topk.hip"].count("int qil_beam_search(") == 1
+    assert sorted(f for f, text in sources.items() if "int qil_beam_search(" in text) == ["qil_internal.h", "qil_topk.hip"]
+    for call, definition in (("qil_dev_select_largest(", "int qil_dev_select_largest("), ("qil_top_k_deliver(", "void qil_top_k_deliver(")):
+        uses = {f: text.count(call) - text.count(definition) for f, text in sources.items()}
+        assert {f: u for f, u in uses.items() if u} == {"qil_topk.hip": 1}, (call, uses)
     internal = open(os.path.join(CSRC, "qil_internal.h")).read()
     for decl in ("int qil_apply_right_envs(", "int qil_apply_score_children(", "int qil_dev_select_largest("):
         assert internal.count(decl) == 1, decl

@@ -100,6 +100,22 @@ def test_uniform_formula_lies_in_the_unit_interval():
     assert hits == ["qil_device_utils.h"]
 
 
+def test_the_sampling_rule_has_one_home_and_the_temporaries_one_owner():
+    """`sample` and `apply_sample` promise the same arithmetic: the uniforms and the choice are defined once, in the shared device
+    header.  The direct verbs hold every pool block through a qil_scratch: no hand-kept free list is left in their files, and
+    the environment pass they share takes the caller's scratch."""
+    csrc = os.path.join(ROOT, "qilaplace.jl_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f), errors="replace").read() for f in os.listdir(csrc)}
+    for definition in ("seeded_uniform(uint64_t", "int choose("):
+        assert [f for f in sorted(text) if definition in text[f]] == ["qil_device_utils.h"], definition
+        assert text["qil_device_utils.h"].count(definition) == 1, definition
+    for f in ("qil_sample.hip", "qil_topk.hip"):
+        assert "qil_ctx_free(" not in text[f] and "qil_scratch tmp(ctx);" in text[f], f
+    for f in ("qil_internal.h", "qil_sample.hip"):
+        assert re.search(r"int qil_dev_right_envs\(const (struct )?qil_mps\* psi, qil_scratch& tmp,", text[f]), f
+        assert text[f].count("int qil_dev_right_envs(") == 1, f
+
+
 def test_julia_shim_binds_sample():
     src = open(os.path.join(ROOT, "julia", "QILaplaceHIP.jl")).read()
     assert re.search(r"import ITensors:.*\bsample\b", src)

@@ -1,4 +1,4 @@
-"""Bit-for-bit record of the overlap, read-out, weight, sampling, restriction and sum verbs on a fixed, seeded list of small cases,
+"""Bit-for-bit record of the overlap, read-out, weight, sampling, top-k, restriction and sum verbs on a fixed, seeded list of small cases,
 for comparing two builds of libqilhip.so (a refactor against its parent).  Public Python API only, so it runs unchanged against
 either library through QILHIP_LIB:
 
@@ -11,7 +11,11 @@ Cases: chains of 6 to 8 tensors, bonds at most 8, MPO bonds at most 4, in f64, c
 read once per process: that stage is a child process of its own), apply_weight_batch with QIL_APPLY_WEIGHT_RENV_BYTES unset and 0
 (rows with no traced site, only traced sites, a fixed last site, and tails of different lengths, which leave the slot list from
 the inside), sample on both routes (QIL_SAMPLE_ROUTE), restrict with a summed and a fixed site, linear_combination_compress with
-three terms (the grouped small GEMM).  Beyond those: 20000 rows of apply_weight_batch whose strided batches exceed 65535 entries
+three terms (the grouped small GEMM); top_k with k = 5 at a beam that drops prefixes (6) and at the full beam 2^n; apply_sample (70
+rows, seeded and with given uniforms) and apply_top_k (the same two beams) on both QIL_APPLY_SAMPLE_ROUTE settings, each a child
+process of its own.  The top-k verbs record (rows, values, bound, certified).  Beyond those: top_k and apply_top_k of 12 tensors at
+beam 1500, a frontier of 3000 candidates (more than one selection tile of 1024), for the lazy verb at chi D = 1024 in c64, where
+the row step's chunk (1020 rows) is below the frontier; 20000 rows of apply_weight_batch whose strided batches exceed 65535 entries
 (the piece boundary inside qil_dev_gemm_batched), and apply_coefficient_batch at chi D = 1024 (its GEMM form).
 
 The process that is started never opens the GPU: every stage is a fresh child."""
@@ -30,7 +34,9 @@ DT_IDS = ["f64-f64", "f64-c64", "c64-f64", "c64-c64"]
 CHI = [[2, 3, 5, 7, 5, 3, 2], [2, 4, 8, 8, 8, 4, 2]]            # interior bonds of psi (cut to n - 1): odd, saturated
 PHI = [2, 4, 6, 8, 6, 4, 2]
 DW = [3, 4, 2, 4, 3, 4, 2]
-STAGES = {"default": {}, "weight_gemm": {"QIL_WEIGHT_NO_LDS": "1"}}
+STAGES = {"default": {}, "weight_gemm": {"QIL_WEIGHT_NO_LDS": "1"}, "apply_fused": {"QIL_APPLY_SAMPLE_ROUTE": "fused"},
+          "apply_gemm": {"QIL_APPLY_SAMPLE_ROUTE": "gemm"}}
+WIDE_N, WIDE_BEAM = 12, 1500                                       # frontiers 1, 2, .., 1024, 1500, 1500: 3000 candidates at the cuts
 
 
 def _mps(bonds, rng, dt):
@@ -85,6 +91,14 @@ def boundary_case(qil):
     return qil.SingleSiteMPO(w), qil.SignalMPS(a, amplitude=1.7), rows
 
 
+def wide_lazy_case(qil):
+    """c64, 12 tensors, chi D = 1024 in the middle: (2 maxM + maxX) e + 16 ceil(maxM / 64) = 65792 B per row, 1020 rows per chunk"""
+    rng = np.random.default_rng(2323)
+    a = _mps([2, 4, 8, 16, 32, 32, 32, 16, 8, 4, 2], rng, Z)
+    w = _mpo([4, 16, 32, 32, 32, 32, 32, 32, 32, 16, 4], rng, Z)
+    return qil.SingleSiteMPO(w), qil.SignalMPS(a, amplitude=1.7)
+
+
 def run_stage(stage):
     sys.path.insert(0, ROOT)
     import qilaplace_jl_amd as qil
@@ -93,6 +107,26 @@ def run_stage(stage):
     def put(key, v):
         assert key not in res, key
         res[key] = np.ascontiguousarray(v)
+
+    def put_top_k(key, found):
+        for name, v in zip(("rows", "values", "bound", "certified"), found):
+            put(f"{key}/{name}", v)
+
+    if stage.startswith("apply_"):
+        for k, (dta, dtw) in enumerate(DT_PAIRS):
+            n = 6 + k % 3
+            rng = np.random.default_rng(500 + k)
+            tag = DT_IDS[k]
+            psi = qil.SignalMPS(_mps(CHI[k % 2][:n - 1], rng, dta), amplitude=1.7)
+            W = qil.SingleSiteMPO(_mpo(DW[:n - 1], rng, dtw))
+            for name, kw in (("seed", dict(seed=99 + k)), ("uniforms", dict(uniforms=rng.random((70, n))))):
+                bits, probs = qil.apply_sample(W, psi, 70, bits=True, **kw)
+                put(f"apply_sample[{stage}, {name}]/bits/{tag}", bits)
+                put(f"apply_sample[{stage}, {name}]/probs/{tag}", probs)
+            for beam in (6, 2 ** n):
+                put_top_k(f"apply_top_k[{stage}, beam={beam}]/{tag}", qil.apply_top_k(W, psi, 5, beam=beam, bits=True))
+        put_top_k(f"apply_top_k[{stage}, wide]", qil.apply_top_k(*wide_lazy_case(qil), 5, beam=WIDE_BEAM, bits=True))
+        return res
 
     def put_sites(key, mps):
         put(key + "/bonds", np.array(mps.bond_dims, dtype=np.int64))
@@ -129,12 +163,19 @@ def run_stage(stage):
             put(f"sample[{route}]/bits/{tag}", bits)
             put(f"sample[{route}]/probs/{tag}", probs)
         _env("QIL_SAMPLE_ROUTE", None)
+        for beam in (6, 2 ** n):
+            put_top_k(f"top_k[beam={beam}]/{tag}", qil.top_k(psi, 5, beam=beam, bits=True))
+            put_top_k(f"top_k[beam={beam}]/phi/{tag}", qil.top_k(phi, 5, beam=beam, bits=True))
         spec = np.full(n, 3, dtype=np.uint8)
         spec[1], spec[n - 2] = 2, 1                                                   # a summed and a fixed site
         put_sites(f"restrict/{tag}", qil.restrict(psi, spec))
         terms = [psi, qil.SignalMPS(_mps(PHI[:n - 1], rng, dta), amplitude=0.8), qil.SignalMPS(_mps(CHI[1][:n - 1], rng, dta))]
         put_sites(f"linear_combination_compress/{tag}", qil.linear_combination_compress(terms, [1.0, -0.5, 0.25], maxdim=6, tol=1e-10))
     if stage == "default":
+        for k, dt in enumerate((F, Z)):                                               # more than one selection tile
+            rng = np.random.default_rng(2300 + k)
+            psi = qil.SignalMPS(_mps([2, 4, 8, 8, 8, 8, 8, 8, 8, 4, 2], rng, dt), amplitude=1.7)
+            put_top_k(f"top_k[wide]/{DT_IDS[3 * k]}", qil.top_k(psi, 5, beam=WIDE_BEAM, bits=True))
         W, psi, rows = boundary_case(qil)
         put("apply_weight_batch/piece_boundary", qil.apply_weight_batch(W, psi, rows))
         for k, (dta, dtw) in enumerate(DT_PAIRS):                                     # chi D = 1024: the GEMM form of the lazy read-out
