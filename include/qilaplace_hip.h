@@ -583,6 +583,40 @@ QIL_API int qil_signal_mps_batch(qil_context* ctx, const void* const* xs, int64_
 QIL_API int qil_signal_ztmps_batch(qil_context* ctx, const void* const* xs, int64_t nb, int64_t len, int dtype, int method,
                            double cutoff, int64_t maxdim, int64_t k, int64_t p, int q, uint64_t seed, int64_t mindim,
                            qil_mps** outs);
+/* Cross-interpolation encoder: the MPS of a signal of 2^n samples from O(n maxdim^2) of them, chosen adaptively by
+ * full-pivot LU factorisations of two-site blocks (two-site sweeps l = 1 .. n-1 and back; a final forward sweep writes the
+ * sites).  Sample j has the bits b_1 .. b_n, site 1 the most significant, as in qil_signal_mps.  The result obeys the
+ * invariants of qil_signal_mps: a unit-norm chain whose amplitude is the norm of the represented signal.
+ *   n 1 .. 62; maxdim finite, 1 .. 256 (QIL_MAXDIM_NONE is an error); tol >= 0, relative to the largest |x| sampled;
+ *   max_sweeps >= 1; seeds: 1 .. 1024 host indices in [0, 2^n), the suffixes the first sweep starts from.
+ *   *est: the largest remaining |entry| over the last back-and-forth sweep, relative to the largest |x| sampled;
+ *   *nevals: samples asked for (the seeds not counted); *converged: every bond's estimate of that sweep was <= tol.
+ * A feature that no pivot's row or column touches is invisible to the interpolation AND to its estimate (an isolated
+ * spike is the standard case): pass its index among the seeds.  QIL_EDOMAIN when every sampled value is 0.
+ *
+ * The evaluator of a session is the caller (pull style, no callbacks): while qil_cross_pending reports count > 0, fetch the
+ * count int64 sample indices into a device buffer (qil_cross_indices), evaluate them, and hand count values of `dtype`
+ * back in a device buffer (qil_cross_supply: factors the block and advances; the buffer may be reused on return).  When
+ * count is 0, qil_cross_finish delivers the chain once.  qil_cross_destroy frees the session at any point; destroy it
+ * before its context.  qil_cross_indices / _supply with nothing pending and qil_cross_finish with samples pending are
+ * QIL_EINVAL_ARG.  The first request is the seeds themselves.                                                        */
+typedef struct qil_cross qil_cross;
+QIL_API int qil_cross_begin(qil_context* ctx, int64_t n, int dtype, int64_t maxdim, double tol, int max_sweeps,
+                    const int64_t* seeds, int64_t nseeds, qil_cross** out);
+QIL_API int qil_cross_pending(qil_cross* s, int64_t* count);
+QIL_API int qil_cross_indices(qil_cross* s, int64_t* idx_dev);
+QIL_API int qil_cross_supply(qil_cross* s, const void* values_dev);
+QIL_API int qil_cross_finish(qil_cross* s, qil_mps** out, double* est, int64_t* nevals, int* sweeps, int* converged);
+QIL_API int qil_cross_destroy(qil_cross* s);
+/* The same session driven by a gather from a dense signal: x is len values of `dtype` in host memory or in HBM, as in
+ * qil_signal_mps; n = round(log2 len), a shorter signal reads as zero-filled, len > 2^n is QIL_EINVAL_LENGTH.       */
+QIL_API int qil_signal_mps_cross(qil_context* ctx, const void* x, int64_t len, int dtype, int64_t maxdim, double tol,
+                         int max_sweeps, const int64_t* seeds, int64_t nseeds, qil_mps** out, double* est,
+                         int64_t* nevals, int* sweeps, int* converged);
+/* The paired chain of a SignalMPS: the per-site delta-fuse and split of qil_signal_ztmps (SignalConverters.jl:261-276) on
+ * a state that exists already, so that qil_ztmps_from_mps(qil_signal_mps(x, cutoff), cutoff) is qil_signal_ztmps(x, cutoff).
+ * psi is left intact; a paired psi is QIL_EINVAL_ARG.  maxdim <= 0: no cap.                                          */
+QIL_API int qil_ztmps_from_mps(const qil_mps* psi, double cutoff, int64_t maxdim, qil_mps** out);
 /* rsvd(A, Linds...; k, p, q, random_seed, cutoff, maxdim, mindim) src/linalg/rsvd.jl:38-121
  * on the matricised operand A (m x n, host, column-major).  Outputs (host, caller
  * allocated for rank min(k+p, m, n)): U m x r, S r, Vh r x n; *rank = r kept.        */

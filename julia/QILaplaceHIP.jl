@@ -10,6 +10,7 @@ using ITensors
 import ITensors: apply, inner, sample
 import Base: *, getindex, length
 import LinearAlgebra: norm, adjoint
+import Random
 import ..Mps
 import ..Mps: coefficient, compress!, canonicalize!, mps_to_vector      # extended below with device methods
 using ..Mps: SignalMPS, ZTMPS, _as_signal_2n, _writeback_signal_2n
@@ -19,7 +20,8 @@ using ..ApplyMPO: _as_single_site_mpo
 export DeviceMPS, DeviceMPO, to_device, to_host, signal_mps_device, marginal, mps_block, apply_compress,
     compress_mpo!, build_dt_mpo_batch, build_qft_mpo_device, build_zt_qft_chain_device, apply_coefficient_sweep, apply!, rsvd_device, svd_device,
     Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm, sample, top_k,
-    hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress, restrict, weight_batch, apply_weight_batch, apply_sample, apply_top_k, bond_spectra
+    hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress, restrict, weight_batch, apply_weight_batch, apply_sample, apply_top_k, bond_spectra,
+    signal_mps_cross, ztmps_from_mps
 
 const LIB = get(ENV, "QILHIP_LIB", "libqilhip.so")
 
@@ -473,6 +475,69 @@ function signal_mps_device(xs::AbstractVector{<:AbstractVector{<:Number}}; metho
     end
     n = max(1, round(Int, log2(length(host[1]))))
     return [finalizer(_free!, DeviceMPS(h, [Index(2; tags="site-$i") for i in 1:(paired ? 2n : n)], paired)) for h in outs]
+end
+
+# Cross-interpolation encoder: O(n maxdim^2) samples chosen by full-pivot LU of two-site blocks instead of all 2^n.
+# A feature no pivot's row or column touches (an isolated spike) is invisible to it and to its estimate: pass its index in `seeds`.
+_cross_seeds(n::Int, seeds, random_seed::Int) =
+    seeds === nothing ? vcat(Int64[0, (Int64(1) << n) - 1], rand(Random.MersenneTwister(random_seed), Int64(0):((Int64(1) << n) - 1), 62)) : Vector{Int64}(seeds)
+_cross_info(est, nevals, sweeps, converged) = (est=est[], nevals=nevals[], sweeps=Int(sweeps[]), converged=converged[] != 0)
+
+# ... of a dense signal (host vector): (psi, info)
+function signal_mps_cross(x::AbstractVector{<:Number}; maxdim::Int=64, tol::Real=1e-10, max_sweeps::Int=8, seeds=nothing,
+                          random_seed::Int=1234)
+    T = eltype(x) <: Complex ? ComplexF64 : Float64
+    xs = Vector{T}(x)
+    n = max(1, round(Int, log2(length(xs))))
+    sd = _cross_seeds(n, seeds, random_seed)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    est, nevals, sweeps, converged = Ref{Cdouble}(0), Ref{Int64}(0), Ref{Cint}(0), Ref{Cint}(0)
+    check(ccall((:qil_signal_mps_cross, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cint, Int64, Cdouble, Cint, Ptr{Int64}, Int64, Ref{Ptr{Cvoid}}, Ref{Cdouble}, Ref{Int64}, Ref{Cint}, Ref{Cint}),
+        ctx().h, xs, length(xs), _code(T), maxdim, tol, max_sweeps, sd, length(sd), r, est, nevals, sweeps, converged))
+    sites = [Index(2; tags="site-$i") for i in 1:n]
+    return finalizer(_free!, DeviceMPS(r[], sites, false)), _cross_info(est, nevals, sweeps, converged)
+end
+
+# ... of a function: eval!(values, indices, count) fills the device buffer `values` (count elements of T) with the samples at
+# the count Int64 indices of the device buffer `indices`; alloc(bytes) returns a device buffer the caller owns
+function signal_mps_cross(eval!::Function, alloc::Function, n::Int, ::Type{T}; maxdim::Int=64, tol::Real=1e-10,
+                          max_sweeps::Int=8, seeds=nothing, random_seed::Int=1234) where {T<:Union{Float64,ComplexF64}}
+    sd = _cross_seeds(n, seeds, random_seed)
+    s = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:qil_cross_begin, LIB), Cint, (Ptr{Cvoid}, Int64, Cint, Int64, Cdouble, Cint, Ptr{Int64}, Int64, Ref{Ptr{Cvoid}}),
+        ctx().h, n, _code(T), maxdim, tol, max_sweeps, sd, length(sd), s))
+    try
+        count = Ref{Int64}(0)
+        while true
+            check(ccall((:qil_cross_pending, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}), s[], count))
+            count[] == 0 && break
+            idx = alloc(8 * count[])
+            vals = alloc(sizeof(T) * count[])
+            check(ccall((:qil_cross_indices, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}), s[], idx))
+            eval!(vals, idx, count[])
+            check(ccall((:qil_cross_supply, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), s[], vals))
+        end
+        r = Ref{Ptr{Cvoid}}(C_NULL)
+        est, nevals, sweeps, converged = Ref{Cdouble}(0), Ref{Int64}(0), Ref{Cint}(0), Ref{Cint}(0)
+        check(ccall((:qil_cross_finish, LIB), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ref{Cdouble}, Ref{Int64}, Ref{Cint}, Ref{Cint}),
+            s[], r, est, nevals, sweeps, converged))
+        sites = [Index(2; tags="site-$i") for i in 1:n]
+        return finalizer(_free!, DeviceMPS(r[], sites, false)), _cross_info(est, nevals, sweeps, converged)
+    finally
+        ccall((:qil_cross_destroy, LIB), Cint, (Ptr{Cvoid},), s[])
+    end
+end
+
+# the ZTMPS of a SignalMPS that exists already (the delta-fuse and split loop of signal_ztmps): how a cross-encoded state enters
+# the z-transform pipeline
+function ztmps_from_mps(psi::DeviceMPS; cutoff::Real=1e-10, maxdim::Int=typemax(Int))
+    psi.paired && throw(ArgumentError("ztmps_from_mps: the operand is a paired state already"))
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:qil_ztmps_from_mps, LIB), Cint, (Ptr{Cvoid}, Cdouble, Int64, Ref{Ptr{Cvoid}}), psi.h, cutoff, maxdim, r))
+    n = length(psi.sites)
+    sites = [Index(2; tags="site-$i") for i in 1:2n]
+    return finalizer(_free!, DeviceMPS(r[], sites, true))
 end
 
 # ---------------------------------------------------------------- back to the reference's host types

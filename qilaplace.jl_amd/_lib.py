@@ -162,6 +162,14 @@ PROTOTYPES = {
     "qil_signal_ztmps": [_vp, _vp, _i64, _int, _int, _dbl, _i64, _i64, _i64, _int, _u64, _i64, _pvp],
     "qil_signal_mps_batch": [_vp, _pvp, _i64, _i64, _int, _int, _dbl, _i64, _i64, _i64, _int, _u64, _i64, _pvp],
     "qil_signal_ztmps_batch": [_vp, _pvp, _i64, _i64, _int, _int, _dbl, _i64, _i64, _i64, _int, _u64, _i64, _pvp],
+    "qil_cross_begin": [_vp, _i64, _int, _i64, _dbl, _int, _pi64, _i64, _pvp],
+    "qil_cross_pending": [_vp, _pi64],
+    "qil_cross_indices": [_vp, _vp],
+    "qil_cross_supply": [_vp, _vp],
+    "qil_cross_finish": [_vp, _pvp, _pdbl, _pi64, _pint, _pint],
+    "qil_cross_destroy": [_vp],
+    "qil_signal_mps_cross": [_vp, _vp, _i64, _int, _i64, _dbl, _int, _pi64, _i64, _pvp, _pdbl, _pi64, _pint, _pint],
+    "qil_ztmps_from_mps": [_vp, _dbl, _i64, _pvp],
     "qil_rsvd": [_vp, _vp, _i64, _i64, _int, _i64, _i64, _int, _u64, _dbl, _i64, _i64, _pi64, _vp, _pdbl, _vp],
     "qil_build_dt_mpo_batch": [_vp, _i64, _i64, _pdbl, _dbl, _i64, _pi64, _pvp],
     "qil_build_zt_mpo_batch": [_vp, _i64, _i64, _pdbl, _dbl, _i64, _pi64, _pvp],

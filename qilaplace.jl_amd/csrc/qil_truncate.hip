@@ -1600,6 +1600,8 @@ extern "C" int qil_signal_mps(qil_context* ctx, const void* x, int64_t len, int 
     return signal_mps_impl(ctx, x, len, dtype, P, out);
 }
 
+static int ztmps_from_sites(qil_context* ctx, const qil_mps* sig, double cutoff, int64_t maxdim, qil_mps** out);
+
 extern "C" int qil_signal_ztmps(qil_context* ctx, const void* x, int64_t len, int dtype, int method,
                                 double cutoff, int64_t maxdim, int64_t k, int64_t p, int q, uint64_t seed,
                                 int64_t mindim, qil_mps** out) {
@@ -1608,7 +1610,22 @@ extern "C" int qil_signal_ztmps(qil_context* ctx, const void* x, int64_t len, in
     EncodeParams P{method, cutoff, maxdim <= 0 ? kNoCap : maxdim, k, p, q, seed, mindim < 1 ? 1 : mindim};
     qil_result_guard<qil_mps> sig_own(nullptr);       // gone on every return: only zt leaves the call
     QIL_TRY(signal_mps_impl(ctx, x, len, dtype, P, &sig_own.p));                  // SignalConverters.jl:251
-    const qil_mps* const sig = sig_own.p;
+    return ztmps_from_sites(ctx, sig_own.p, P.cutoff, P.maxdim, out);
+}
+
+extern "C" int qil_ztmps_from_mps(const qil_mps* psi, double cutoff, int64_t maxdim, qil_mps** out) {
+    QIL_REQUIRE(psi && out, QIL_EINVAL_ARG, "ztmps_from_mps: null argument");
+    QIL_REQUIRE(!psi->paired && psi->phys_rank == 1, QIL_EINVAL_ARG, "ztmps_from_mps: the operand is a paired state already");
+    qil_context* ctx = psi->ctx;
+    QIL_TRY(qil_ctx_activate(ctx));
+    qil_call_scope call_scope(ctx);
+    return ztmps_from_sites(ctx, psi, cutoff, maxdim <= 0 ? kNoCap : maxdim, out);
+}
+
+// The per-site delta-fuse and split of SignalConverters.jl:261-276: site i of sig becomes core_main [b_{i-1}, s_main, c] and
+// core_copy [c, s_copy, b_i] of a paired chain with sig's amplitude.  Context active, call scope open; sig is left intact.
+static int ztmps_from_sites(qil_context* ctx, const qil_mps* sig, double cutoff, int64_t maxdim, qil_mps** out) {
+    const int dtype = sig->dtype;
     const int64_t n = sig->n();
     const size_t e = qil_elem_size(dtype);
     qil_result_guard<qil_mps> zt_own(qil_mps_empty(ctx, 2 * n, dtype, 1, nullptr, sig->amplitude));
@@ -1623,7 +1640,7 @@ extern "C" int qil_signal_ztmps(qil_context* ctx, const void* x, int64_t len, in
             QIL_TRY((qil_klaunch<fuse_delta_k<double>>(ctx, dim3(nblk(4 * cl * cr)), dim3(256), 0, (const double*)sig->site[(size_t)i], (int)cl, (int)cr, (double*)T)));
         int64_t r = 0;
         void *U = nullptr, *SV = nullptr;
-        QIL_TRY(svd_trunc_dev(ctx, dtype, 2 * cl, 2 * cr, T, 2 * cl, P.cutoff, true, P.maxdim, 1, 2, &r, &U, &SV, nullptr));
+        QIL_TRY(svd_trunc_dev(ctx, dtype, 2 * cl, 2 * cr, T, 2 * cl, cutoff, true, maxdim, 1, 2, &r, &U, &SV, nullptr));
         qil_ctx_free(ctx, T);
         qil_chain_adopt(zt, 2 * i, U);        // core_main [b_{i-1}, s_main, c]
         qil_chain_adopt(zt, 2 * i + 1, SV);   // core_copy [c, s_copy, b_i]

@@ -1199,19 +1199,18 @@ def exponential_sum(amps, zs, n, maxdim=None, tol=1e-12):
 
 
 # ---------------------------------------------------------------- encode
-def _encode(fn, cls, x, method, cutoff, maxdim, k, p, q, random_seed, mindim, ctx):
-    if method not in ("svd", "rsvd"):
-        raise ValueError(f"tensor_to_mps: unknown method {method}. Use :svd or :rsvd.")
-    ctx = ctx or default_context()
+def _signal_operand(x, what):
+    """What an encoder hands to the library for the signal x: (the object that keeps the samples alive, pointer, length, dtype
+    code, n = round(log2 length)); warns when the length is not 2^n (the library zero-fills)."""
     cai = getattr(x, "__cuda_array_interface__", None)
     if cai is not None:
         # samples already in HBM (a torch / cupy-style device array): hand the device pointer over, no PCIe
         # trip.  Must be 1-D, contiguous, float64 or complex128; the producer's stream is drained first.
         if len(cai["shape"]) != 1 or cai.get("strides") not in (None, (np.dtype(cai["typestr"]).itemsize,)):
-            raise ValueError("signal_mps: device signal must be a contiguous 1-D array")
+            raise ValueError(f"{what}: device signal must be a contiguous 1-D array")
         dt = np.dtype(cai["typestr"])
         if dt not in (np.dtype(np.float64), np.dtype(np.complex128)):
-            raise ValueError(f"signal_mps: device signal must be float64 or complex128, got {dt}")
+            raise ValueError(f"{what}: device signal must be float64 or complex128, got {dt}")
         code = L.QIL_C64 if dt == np.dtype(np.complex128) else L.QIL_F64
         N = int(cai["shape"][0])
         ptr = C.c_void_p(int(cai["data"][0]))
@@ -1229,6 +1228,14 @@ def _encode(fn, cls, x, method, cutoff, maxdim, k, p, q, random_seed, mindim, ct
     n = max(1, int(round(np.log2(max(N, 1)))))
     if N < 2 ** n:
         warnings.warn(f"_array_to_tensor: input length {N} is not a power of 2; zero-filling to {2**n}")
+    return keep, ptr, N, code, n
+
+
+def _encode(fn, cls, x, method, cutoff, maxdim, k, p, q, random_seed, mindim, ctx):
+    if method not in ("svd", "rsvd"):
+        raise ValueError(f"tensor_to_mps: unknown method {method}. Use :svd or :rsvd.")
+    ctx = ctx or default_context()
+    keep, ptr, N, code, _ = _signal_operand(x, "signal_mps")
     h = C.c_void_p()
     L.check(fn(ctx.handle, ptr, N, code,
                L.QIL_METHOD_SVD if method == "svd" else L.QIL_METHOD_RSVD, float(cutoff), _maxdim(maxdim),
@@ -1280,6 +1287,117 @@ def signal_ztmps(x, cutoff=1e-10, maxdim=None, method="svd", k=20, p=10, q=0, ra
                  ctx=None):
     """signal_ztmps(x; cutoff=1e-10, maxdim, kwargs...)."""
     return _encode(L.lib.qil_signal_ztmps, ZTMPS, x, method, cutoff, maxdim, k, p, q, random_seed, mindim, ctx)
+
+
+def _cross_seeds(n, seeds, random_seed):
+    if seeds is None:
+        drawn = np.random.default_rng(random_seed).integers(0, 2 ** n, size=62, dtype=np.int64)
+        seeds = np.concatenate([np.array([0, 2 ** n - 1], dtype=np.int64), drawn])
+    seeds = np.ascontiguousarray(np.asarray(seeds).reshape(-1), dtype=np.int64)
+    return seeds, seeds.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def _cross_info(est, nevals, sweeps, converged):
+    return {"est": est.value, "nevals": nevals.value, "sweeps": sweeps.value, "converged": converged.value}
+
+
+def _cross_from_callable(f, n, maxdim, tol, max_sweeps, seeds, random_seed, ctx):
+    import torch
+    if n is None:
+        raise ValueError("signal_mps_cross: a callable needs n, the number of sites")
+    n = int(n)
+    if not 1 <= n <= 62:
+        raise ValueError(f"signal_mps_cross: n = {n} outside 1 .. 62")
+    dev = torch.device("cuda", ctx.device)
+
+    def evaluate(idx, code=None):
+        v = f(idx)
+        if not isinstance(v, torch.Tensor) or v.device != idx.device or v.shape != idx.shape:
+            raise ValueError("signal_mps_cross: the callable must return a device tensor of its argument's length")
+        if v.dtype not in (torch.float64, torch.complex128):
+            raise ValueError(f"signal_mps_cross: the callable must return float64 or complex128, got {v.dtype}")
+        got = L.QIL_C64 if v.dtype == torch.complex128 else L.QIL_F64
+        if code is not None and got != code:
+            if code == L.QIL_F64:
+                raise ValueError("signal_mps_cross: the callable returned complex values after real ones")
+            v = v.to(torch.complex128)
+            got = code
+        return v.contiguous(), got
+
+    seeds_np, seeds_p = _cross_seeds(n, seeds, random_seed)
+    if len(seeds_np) < 1 or seeds_np.min() < 0 or seeds_np.max() >= 2 ** n:
+        raise ValueError(f"signal_mps_cross: seeds must be indices in [0, 2^{n})")
+    # the dtype comes from the first evaluation
+    _, code = evaluate(torch.from_numpy(seeds_np).to(dev))
+    s = C.c_void_p()
+    L.check(L.lib.qil_cross_begin(ctx.handle, n, code, int(maxdim), float(tol), int(max_sweeps), seeds_p, len(seeds_np),
+                                  C.byref(s)))
+    try:
+        count = C.c_int64()
+        while True:
+            L.check(L.lib.qil_cross_pending(s, C.byref(count)))
+            if count.value == 0:
+                break
+            idx = torch.empty(count.value, dtype=torch.int64, device=dev)
+            L.check(L.lib.qil_cross_indices(s, C.c_void_p(idx.data_ptr())))
+            vals, _ = evaluate(idx, code)
+            torch.cuda.current_stream(dev).synchronize()
+            L.check(L.lib.qil_cross_supply(s, C.c_void_p(vals.data_ptr())))
+        h = C.c_void_p()
+        est, nevals, sweeps, converged = C.c_double(), C.c_int64(), C.c_int(), C.c_int()
+        L.check(L.lib.qil_cross_finish(s, C.byref(h), C.byref(est), C.byref(nevals), C.byref(sweeps), C.byref(converged)))
+    finally:
+        L.lib.qil_cross_destroy(s)
+    return SignalMPS(ctx=ctx, _handle=h), _cross_info(est, nevals, sweeps, converged)
+
+
+def signal_mps_cross(x_or_f, n=None, maxdim=64, tol=1e-10, max_sweeps=8, seeds=None, random_seed=1234, return_info=False,
+                     ctx=None):
+    """The SignalMPS of a signal by tensor cross interpolation: O(n maxdim^2) samples, chosen adaptively by full-pivot LU
+    factorisations of two-site blocks, instead of all 2^n of them.
+
+    x_or_f: an array or a `__cuda_array_interface__` object, as signal_mps accepts (n = round(log2 len); a length that is not a
+    power of two reads as zero-filled, with a warning), or a callable f(idx): a 1-D int64 torch tensor on the device ->
+    float64 or complex128 values of the same length (requires n, up to 62; the dtype comes from the first evaluation).
+    maxdim: the rank cap, 1 .. 256.  tol: pivots stop when the largest remaining |entry| of a block is <= tol times the largest
+    |x| sampled; the encode has converged when that holds at every bond over a whole back-and-forth sweep.  seeds: the sample
+    indices whose suffixes the first sweep starts from; by default 0, 2^n - 1 and 62 indices drawn from random_seed.
+    return_info adds a dict: est (the largest remaining |entry| of the last sweep, relative to the largest |x| sampled),
+    nevals (samples read), sweeps, converged.
+
+    Known blind spot of cross interpolation: a feature that no pivot's row or column touches is invisible, and the estimate
+    does not see it either -- an isolated spike is the standard case (converged, est small, spike missing).  The remedy is
+    to pass its index in `seeds`."""
+    ctx = ctx or default_context()
+    if not isinstance(maxdim, (int, np.integer)) or isinstance(maxdim, bool):
+        raise ValueError("signal_mps_cross: maxdim must be an integer, 1 .. 256")
+    if callable(x_or_f):
+        psi, info = _cross_from_callable(x_or_f, n, maxdim, tol, max_sweeps, seeds, random_seed, ctx)
+        return (psi, info) if return_info else psi
+    keep, ptr, N, code, nn = _signal_operand(x_or_f, "signal_mps_cross")
+    if n is not None and int(n) != nn:
+        raise ValueError(f"signal_mps_cross: n = {n} does not match a signal of {N} samples")
+    seeds_np, seeds_p = _cross_seeds(min(nn, 62), seeds, random_seed)
+    h = C.c_void_p()
+    est, nevals, sweeps, converged = C.c_double(), C.c_int64(), C.c_int(), C.c_int()
+    L.check(L.lib.qil_signal_mps_cross(ctx.handle, ptr, N, code, int(maxdim), float(tol), int(max_sweeps), seeds_p, len(seeds_np),
+                                       C.byref(h), C.byref(est), C.byref(nevals), C.byref(sweeps), C.byref(converged)))
+    del keep
+    psi = SignalMPS(ctx=ctx, _handle=h)
+    return (psi, _cross_info(est, nevals, sweeps, converged)) if return_info else psi
+
+
+def ztmps_from_mps(psi, cutoff=1e-10, maxdim=None):
+    """The ZTMPS of a SignalMPS that exists already: the per-site delta-fuse and split of signal_ztmps, so that
+    ztmps_from_mps(signal_mps(x, cutoff=c), cutoff=c) is signal_ztmps(x, cutoff=c).  The way of a cross-encoded state
+    (signal_mps_cross) into the z-transform pipeline.  psi is left intact; a paired psi raises ValueError."""
+    if not isinstance(psi, SignalMPS):
+        raise TypeError(f"ztmps_from_mps: unsupported operand types ({type(psi).__name__})")
+    if isinstance(psi, ZTMPS) or psi.paired:
+        raise ValueError("ztmps_from_mps: the operand is a paired state already")
+    h = C.c_void_p()
+    L.check(L.lib.qil_ztmps_from_mps(psi.handle, float(cutoff), _maxdim(maxdim), C.byref(h)))
+    return ZTMPS(ctx=psi.ctx, _handle=h)
 
 
 def _factor_out(m, n, r0, code):
