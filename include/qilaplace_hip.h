@@ -167,6 +167,21 @@ QIL_API int qil_coefficient_batch(const qil_mps* psi, int64_t nb, const uint8_t*
  * (docs/src/tutorials/dt.jl:187-197 sums N coefficient calls per value; zt.jl:283-309 scans 256 x 256
  * grids) with one chain per value instead of N. */
 QIL_API int qil_coefficient_marginal_batch(const qil_mps* psi, int64_t nb, const uint8_t* bits, double* out);
+/* Product-vector read-out, the contraction of coefficient (src/mps.jl:669-678) with a weighted sum of the two physical
+ * slices in place of one of them:
+ *   out[r] = amplitude * prod_i ( v[r,i,0] A_i[:,0,:] + v[r,i,1] A_i[:,1,:] ),  r < nb, i < n tensors (2n for a paired state).
+ * v: host, nb * n * 2 complex values (re, im interleaved; row-major in r, i, s).  out: host, nb complex values.
+ * With v = e_bit it is qil_coefficient_batch; with v = (1, 1) on a site, that site's marginal.  With v[r,i,:] = (1, w^(2^(n-i)))
+ * it is sum_j x_j w^j of the encoded signal, at any complex w: O(n chi^2) per row, no operator and no grid.
+ * The carry is complex for either site dtype; real weights on a real state give an imaginary part of exactly zero.
+ * Errors, before the context is activated: QIL_EINVAL_ARG for a null psi, nb < 0, a null v or out with nb > 0, or a weight that
+ * is not finite (the message names the row and the tensor).  nb = 0 is a no-op.
+ * Route: the marginal read-out's decision for (nb, bonds), except that bonds below 128 stay on the first route while
+ * nb * bond^2 < 2^21.  One workgroup per row with the carry in LDS (bonds up to QIL_PRODUCT_CHAIN_MAX_BOND), or one f64-MFMA GEMM
+ * per tensor for all rows and a kernel that combines each row's two slices; QIL_PRODUCT_ROUTE=chain / gemm (read per call)
+ * forces one where it fits. */
+#define QIL_PRODUCT_CHAIN_MAX_BOND 1024
+QIL_API int qil_product_batch(const qil_mps* psi, int64_t nb, const double* v, double* out);
 /* <bits| W psi> without materialising W*psi (same numbers as
  * qil_coefficient_batch(qil_apply(W, psi))).                                      */
 QIL_API int qil_apply_coefficient_batch(const qil_mpo* W, const qil_mps* psi, int64_t nb,

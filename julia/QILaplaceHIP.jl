@@ -21,7 +21,7 @@ export DeviceMPS, DeviceMPO, to_device, to_host, signal_mps_device, marginal, mp
     compress_mpo!, build_dt_mpo_batch, build_qft_mpo_device, build_zt_qft_chain_device, apply_coefficient_sweep, apply!, rsvd_device, svd_device,
     Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm, sample, top_k,
     hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress, restrict, weight_batch, apply_weight_batch, apply_sample, apply_top_k, bond_spectra,
-    signal_mps_cross, ztmps_from_mps
+    signal_mps_cross, ztmps_from_mps, product_batch
 
 const LIB = get(ENV, "QILHIP_LIB", "libqilhip.so")
 
@@ -167,6 +167,17 @@ function marginal(psi::DeviceMPS, bits::AbstractMatrix{<:Integer})
     out = Vector{ComplexF64}(undef, nb)
     check(ccall((:qil_coefficient_marginal_batch, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{Cvoid}),
                 psi.h, nb, b, out))
+    return out
+end
+# product vectors: v[r, i, :] weighs the two physical slices of tensor i in row r; with v[r, i, :] = (1, w^(2^(n-i))) the value is
+# sum_j x_j w^j, the transform of the encoded signal at any complex w (no operator, no grid)
+function product_batch(psi::DeviceMPS, v::AbstractArray{<:Number,3})          # nb x n x 2
+    nb, n, two = size(v)
+    (n == length(psi) && two == 2) || throw(ArgumentError("product_batch: expected weights of shape (nb, $(length(psi)), 2), got $(size(v))"))
+    all(isfinite, v) || throw(ArgumentError("product_batch: the weights must be finite"))
+    w = Array{ComplexF64,3}(permutedims(v, (3, 2, 1)))                          # (s, i, r): row-major in r, i, s for the ABI
+    out = Vector{ComplexF64}(undef, nb)
+    GC.@preserve w out check(ccall((:qil_product_batch, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}), psi.h, nb, w, out))
     return out
 end
 coefficient(psi::DeviceMPS, cfg::AbstractVector{<:Integer}) = coefficient(psi, reshape(collect(cfg), 1, :))[1]

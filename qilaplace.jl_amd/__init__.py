@@ -15,7 +15,8 @@ from ._lib import QilError, QilDomainError, LIB_PATH, last_error  # noqa: F401
 from .containers import (Context, default_context, set_default_context, device_count, host_cpu_budget,  # noqa: F401
                          SignalMPS, ZTMPS, SingleSiteMPO, PairedSiteMPO)
 from .ops import (apply, apply_compress, apply_compress_batch, mpo_compress, compress_batch, mpo_compress_batch, mps_block, coefficient, coefficient_batch, apply_coefficient_batch, apply_coefficient_sweep,  # noqa: F401
-                  marginal_batch, coefficient_grid, laplace_values,
+                  marginal_batch, coefficient_grid, laplace_values, product_batch, laplace_weights, laplace_sum, power_sum, dft_eval, dt_eval,
+                  zt_eval, refine_frequencies,
                   mps_to_vector, norm, inner, apply_norm, distance, apply_distance, bond_spectra, mpo_bond_spectra, entanglement_entropy,
                   truncation_error_bounds, required_maxdim, sample, apply_sample, top_k, apply_top_k, hadamard, hadamard_compress, diagonal_mpo, adjoint, convolve, correlate,
                   power_spectrum, linear_combination, linear_combination_compress, add, sub, scale, exponential_tensors,
@@ -34,6 +35,7 @@ __all__ = [
     "Context", "default_context", "set_default_context", "device_count", "host_cpu_budget",
     "SignalMPS", "ZTMPS", "SingleSiteMPO", "PairedSiteMPO",
     "apply", "apply_compress", "apply_compress_batch", "coefficient", "coefficient_batch", "apply_coefficient_batch", "apply_coefficient_sweep", "marginal_batch", "coefficient_grid", "laplace_values", "mps_to_vector", "norm",
+    "product_batch", "laplace_weights", "laplace_sum", "power_sum", "dft_eval", "dt_eval", "zt_eval", "refine_frequencies",
     "inner", "apply_norm", "distance", "apply_distance", "bond_spectra", "mpo_bond_spectra", "entanglement_entropy",
     "truncation_error_bounds", "required_maxdim", "sample", "apply_sample", "top_k", "apply_top_k",
     "hadamard", "hadamard_compress", "diagonal_mpo", "adjoint", "convolve", "correlate", "power_spectrum",

@@ -380,6 +380,8 @@ bool qil_dev_gemm_grouped_fits(size_t nproblems);
 // psi has the contraction dtype), X holds nq * chi_l 2 D_r elements.
 int qil_lazy_row_step(qil_context* ctx, int dt, const struct qil_mpo* W, const struct qil_mps* psi, int64_t i, const void* Mc,
                       void* Mn, void* X, void* Wc, void* Ac, int64_t nq, const uint8_t* sel, int64_t sel_step);
+// (qil_readout.hip) dout[t] = amplitude * v[t] (complex out, v of dtype dt), t < nb: the last step of a GEMM-form read-out
+int qil_dev_finish_coeff(qil_context* ctx, int dt, const void* v, int64_t nb, double amplitude, void* dout);
 // ---- (qil_contract.hip) the steps the overlap and Born-weight verbs share
 // blocks of 256 threads for `work` items of a grid-stride kernel
 inline unsigned qil_grid_for(long long work, long long cap = 4096) {

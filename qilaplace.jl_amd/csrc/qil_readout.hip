@@ -366,6 +366,13 @@ int qil_lazy_row_step(qil_context* ctx, int dt, const qil_mpo* W, const qil_mps*
     return qil_dev_gemm_batched(ctx, dt, 1, 0, cr, Dr, 2 * cl, Ap, 2 * cl, X, 2 * cl, Mn, cr, &b2);
 }
 
+// out[t] = amplitude * v[t], t < nb: the last step of the GEMM read-outs, for qil_product_batch (qil_product.hip) as well
+int qil_dev_finish_coeff(qil_context* ctx, int dt, const void* v, int64_t nb, double amplitude, void* dout) {
+    const dim3 g1(qil_grid_for(nb));
+    if (dt == QIL_C64) return qil_klaunch<finish_coeff_k<c64>>(ctx, g1, dim3(256), 0, (const c64*)v, (long long)nb, amplitude, (c64*)dout);
+    return qil_klaunch<finish_coeff_k<double>>(ctx, g1, dim3(256), 0, (const double*)v, (long long)nb, amplitude, (c64*)dout);
+}
+
 static int coefficient_impl(const qil_mps* psi, int64_t nb, const uint8_t* bits, double* out, int max_bit);
 
 extern "C" int qil_coefficient_batch(const qil_mps* psi, int64_t nb, const uint8_t* bits, double* out) {

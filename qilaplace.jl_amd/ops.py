@@ -7,6 +7,8 @@
   inner              ITensors' inner(phi, psi) / inner(phi, W, psi) on device chains (no reference counterpart)
   sample             ITensors' sample(::MPS) on device chains (no reference counterpart)
   top_k              the k largest |psi_x| by a certified beam search (no reference counterpart: replaces argmax over grid scans)
+  product_batch      the contraction of coefficient with a weighted sum of the two physical slices per site: sum_j x_j w^j at any
+                     complex w (laplace_sum, dft_eval, dt_eval, zt_eval, refine_frequencies; no reference counterpart)
   hadamard, adjoint  element-wise products of states and W^dagger; convolve / correlate / power_spectrum on top of them (no
                      reference counterpart)
   canonicalize       src/mps.jl:787-847, 866-901   (Julia: canonicalize!)
@@ -1196,6 +1198,178 @@ def exponential_sum(amps, zs, n, maxdim=None, tol=1e-12):
     if maxdim is None and tol is None:
         return linear_combination(terms, amps)
     return linear_combination_compress(terms, amps, maxdim=maxdim, tol=1e-12 if tol is None else tol)
+
+
+# ---------------------------------------------------------------- product-vector read-outs: off-grid transform values
+PRODUCT_CHAIN_MAX_BOND = 1024           # QIL_PRODUCT_CHAIN_MAX_BOND (include/qilaplace_hip.h): the chain route's LDS carry
+PRODUCT_MANY_ROWS_CHAIN_WORK = 1 << 21  # kManyRowsChainWork (csrc/qil_product.hip): bonds < 128 stay on the chain below this rows * bond^2
+
+
+def _product_weights(psi, v, what):
+    """The checks of `product_batch`, before any native call: (nb, n_tensors, 2) numbers."""
+    if not isinstance(psi, SignalMPS):
+        raise TypeError(f"{what}: unsupported operand types")
+    w = np.asarray(v)
+    if w.dtype.kind not in "iufc":
+        raise TypeError(f"{what}: the weights must be real or complex numbers, got dtype {w.dtype}")
+    n = _ntensors(psi)
+    if w.ndim != 3 or w.shape[1:] != (n, 2):
+        raise ValueError(f"{what}: expected weights of shape (nb, {n}, 2), got {w.shape}")
+    return w
+
+
+def product_batch(psi, v, conj=False):
+    """out[r] = amplitude * prod_i (v[r,i,0] A_i[:,0,:] + v[r,i,1] A_i[:,1,:])  (qil_product_batch): the overlap of psi with nb
+    product vectors given as numbers, v of shape (nb, n_tensors, 2), real or complex.  conj=True conjugates the weights:
+    <v|psi>.  v = e_bit is `coefficient_batch`, v = (1, 1) on a tensor sums it as `marginal_batch`'s 2 does.  Returns complex
+    values, or real ones when the state and the weights are both real."""
+    w = _product_weights(psi, v, "product_batch")
+    real = not np.iscomplexobj(w) and psi.dtype != np.complex128
+    w = np.ascontiguousarray(w.conj() if conj else w, dtype=np.complex128)
+    nb = w.shape[0]
+    out = np.zeros(nb, dtype=np.complex128)
+    if nb:
+        L.check(L.lib.qil_product_batch(psi.handle, nb, w.ctypes.data_as(L._pdbl), out.ctypes.data_as(L._pdbl)))
+    return out.real.copy() if real else out
+
+
+def laplace_weights(sigma, cycles, n):
+    """(Public for the reason `exponential_tensors` is: it needs no device.)  The (nb, n, 2) weights [1, w^(2^(n-i))] of
+    w = exp(-(sigma + 2 pi i c)), tensor i = 1 .. n with tensor 1 the most significant bit, for `product_batch` on an n-site
+    SignalMPS; sigma and cycles (c, in cycles per sample) are broadcast against each other.
+
+    w^(2^m) = exp(-sigma 2^m) exp(-2 pi i frac(c 2^m)): the scaling by 2^m and the reduction mod 1 are exact in double, so
+    every weight is one exp, one cos and one sin away from its argument -- never a square of a rounded w, which loses a bit per
+    level (2^39 u at n = 40).  sigma < 0 may overflow at a high bit: ValueError naming the bit.  Underflow to 0 is the value."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("laplace_weights: n must be >= 1")
+    s, c = np.broadcast_arrays(np.asarray(sigma, dtype=np.float64), np.asarray(cycles, dtype=np.float64))
+    s, c = s.reshape(-1), c.reshape(-1)
+    if not (np.isfinite(s).all() and np.isfinite(c).all()):
+        raise ValueError("laplace_weights: sigma and cycles must be finite")
+    scale = np.ldexp(1.0, n - 1 - np.arange(n))[None, :]          # tensor i (0-based) carries bit m = n - 1 - i
+    ld = np.longdouble                                            # wider than double where the platform has it: one rounding at the end
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        # a grid of points repeats its sigmas and its cycles: one exp per distinct sigma, one cos / sin per distinct c
+        (us, js), (uc, jc) = np.unique(s, return_inverse=True), np.unique(c, return_inverse=True)
+        t = uc[:, None] * scale                                   # exact: a scaling by a power of two
+        frac = t - np.rint(t)                                     # exact: t mod 1, in [-1/2, 1/2]
+        mod = np.exp(-(us[:, None] * scale).astype(ld))[js.reshape(-1)]
+        ang = (-8 * np.arctan(ld(1))) * frac.astype(ld)
+        t, re, im = t[jc.reshape(-1)], np.cos(ang)[jc.reshape(-1)], np.sin(ang)[jc.reshape(-1)]
+        hi = (mod * re).astype(np.float64) + 1j * (mod * im).astype(np.float64)
+    bad = ~(np.isfinite(hi) & np.isfinite(t))
+    if bad.any():
+        r, i = np.argwhere(bad)[0]
+        raise ValueError(f"laplace_weights: exp(-sigma 2^m) overflows at bit m = {n - 1 - int(i)} (sigma = {float(s[r])!r})")
+    out = np.ones((s.size, n, 2), dtype=np.complex128)
+    out[:, :, 1] = hi
+    return out
+
+
+def _signal_weights(psi, hi, what):
+    """(nb, n) upper weights, bit of tensor i of the signal register -> the (nb, n_tensors, 2) weights of psi: a ZTMPS of a signal
+    carries main and copy tensors interleaved with the copy register delta-fused, so its copy tensors get (1, 1)."""
+    if not isinstance(psi, SignalMPS):
+        raise TypeError(f"{what}: unsupported operand types")
+    nb, n = hi.shape
+    if isinstance(psi, ZTMPS):
+        w = np.ones((nb, 2 * n, 2), dtype=hi.dtype)
+        w[:, 0::2, 1] = hi
+    else:
+        w = np.ones((nb, n, 2), dtype=hi.dtype)
+        w[:, :, 1] = hi
+    return w
+
+
+def laplace_sum(psi, sigma, cycles):
+    """sum_j x_j exp(-(sigma + 2 pi i c) j) of the signal psi encodes (a SignalMPS, or the ZTMPS of a signal), amplitude
+    included, at any real sigma and c (cycles per sample; broadcast against each other; the result has the broadcast shape).
+    One `product_batch` call: O(n chi^2) per point, no operator, no grid."""
+    if not isinstance(psi, SignalMPS):
+        raise TypeError("laplace_sum: unsupported operand types")
+    shape = np.broadcast(np.asarray(sigma), np.asarray(cycles)).shape
+    w = laplace_weights(sigma, cycles, len(psi))
+    out = product_batch(psi, _signal_weights(psi, w[:, :, 1], "laplace_sum"))
+    return np.asarray(out, dtype=np.complex128).reshape(shape)
+
+
+def power_sum(psi, w):
+    """sum_j x_j w^j for callers who hold w itself (any complex numbers, any shape): the dyadic powers w^(2^m) come correctly
+    rounded from `_dyadic_powers`.  A power that overflows raises ValueError."""
+    if not isinstance(psi, SignalMPS):
+        raise TypeError("power_sum: unsupported operand types")
+    ws = np.asarray(w, dtype=np.complex128)
+    n = len(psi)
+    hi = np.empty((ws.size, n), dtype=np.complex128)
+    for r, z in enumerate(ws.reshape(-1)):
+        hi[r] = _dyadic_powers(z, n)[::-1]
+    if not np.isfinite(hi).all():
+        r, i = np.argwhere(~np.isfinite(hi))[0]
+        raise ValueError(f"power_sum: w^(2^{n - 1 - int(i)}) overflows for w = {ws.reshape(-1)[r]!r}")
+    if not np.iscomplexobj(np.asarray(w)):
+        hi = hi.real.copy()
+    out = product_batch(psi, _signal_weights(psi, hi, "power_sum"))
+    return np.asarray(out).reshape(ws.shape)
+
+
+def dft_eval(psi, f):
+    """The unitary DFT of the encoded signal at ANY real frequency f (in bins): (1 / sqrt N) sum_j x_j exp(-2 pi i f j / N)."""
+    if not isinstance(psi, SignalMPS):
+        raise TypeError("dft_eval: unsupported operand types")
+    N = 2.0 ** len(psi)
+    return laplace_sum(psi, 0.0, np.asarray(f, dtype=np.float64) / N) / np.sqrt(N)
+
+
+def dt_eval(psi, wr, k):
+    """The damping transform at any real k: (1 / sqrt N) sum_j x_j exp(-wr k j / N)."""
+    if not isinstance(psi, SignalMPS):
+        raise TypeError("dt_eval: unsupported operand types")
+    N = 2.0 ** len(psi)
+    return laplace_sum(psi, float(wr) * np.asarray(k, dtype=np.float64) / N, 0.0) / np.sqrt(N)
+
+
+def zt_eval(psi, wr, k, l):
+    """The z-transform at any real (k, l), broadcast against each other: (1 / N) sum_j x_j exp(-((wr k + 2 pi i l) / N) j)
+    (the reference's grid values with wi = 2 pi, dt = 1)."""
+    if not isinstance(psi, SignalMPS):
+        raise TypeError("zt_eval: unsupported operand types")
+    N = 2.0 ** len(psi)
+    return laplace_sum(psi, float(wr) * np.asarray(k, dtype=np.float64) / N, np.asarray(l, dtype=np.float64) / N) / N
+
+
+_GOLDEN = (np.sqrt(5.0) - 1.0) / 2.0
+
+
+def _golden_maximise(evaluate, lo, hi, tol):
+    """Golden-section search for the maximiser of evaluate(x) (vectorised: one call evaluates every interval's two probes)
+    inside each [lo, hi]; stops when every interval is shorter than tol.  Returns the midpoints."""
+    lo, hi = np.array(lo, dtype=np.float64), np.array(hi, dtype=np.float64)
+    a, b = hi - _GOLDEN * (hi - lo), lo + _GOLDEN * (hi - lo)
+    fa, fb = np.split(np.asarray(evaluate(np.concatenate([a, b]))), 2)
+    while (hi - lo).max(initial=0.0) > tol:
+        left = fa >= fb                                   # the maximum lies in [lo, b], else in [a, hi]
+        hi, lo = np.where(left, b, hi), np.where(left, lo, a)
+        na, nb_ = hi - _GOLDEN * (hi - lo), lo + _GOLDEN * (hi - lo)
+        probe = np.asarray(evaluate(np.where(left, na, nb_)))     # one new point per interval, all in one call
+        a, b, fa, fb = (np.where(left, na, b), np.where(left, a, nb_), np.where(left, probe, fb), np.where(left, fa, probe))
+    return 0.5 * (lo + hi)
+
+
+def refine_frequencies(psi, f0, half_width=0.5, sigma=0.0, tol=1e-6):
+    """Sub-bin refinement of the bins `top_k` finds: for each starting bin f0 the maximiser of |laplace_sum(psi, sigma, f / N)|
+    along the circle of fixed sigma within f0 +- half_width, by a golden-section search down to `tol` bins; every iteration
+    evaluates all candidates' points in one `product_batch` call.  Returns (f, value at f).
+
+    One-dimensional on purpose: the transform of a finite record is a polynomial in w, and the modulus of a polynomial has no
+    interior maximum (maximum modulus principle) -- a search over (sigma, f) would run to the boundary of any window."""
+    if not isinstance(psi, SignalMPS):
+        raise TypeError("refine_frequencies: unsupported operand types")
+    f0 = np.atleast_1d(np.asarray(f0, dtype=np.float64))
+    N = 2.0 ** len(psi)
+    f = _golden_maximise(lambda x: np.abs(laplace_sum(psi, float(sigma), x / N)), f0 - half_width, f0 + half_width, float(tol))
+    return f, laplace_sum(psi, float(sigma), f / N)
 
 
 # ---------------------------------------------------------------- encode
