@@ -299,10 +299,13 @@ double qil_apply_env_bytes(const qil_mpo* W, const qil_mps* psi) {   // e sum_k 
 }
 
 qil_apply_bond_sizes qil_apply_sizes_of(const qil_mpo* W, const qil_mps* psi) {
+    return qil_apply_sizes_of(psi->n(), psi->dims.data(), W->dims.data());
+}
+qil_apply_bond_sizes qil_apply_sizes_of(int64_t n, const int64_t* chain_dims, const int64_t* op_dims) {
     qil_apply_bond_sizes b;
-    for (int64_t i = 0; i < psi->n(); ++i) {
-        const long long cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1];
-        const long long Dl = W->dims[(size_t)i], Dr = W->dims[(size_t)i + 1];
+    for (int64_t i = 0; i < n; ++i) {
+        const long long cl = chain_dims[i], cr = chain_dims[i + 1];
+        const long long Dl = op_dims[i], Dr = op_dims[i + 1];
         b.maxM = std::max({b.maxM, cl * Dl, cr * Dr});
         b.maxX = std::max(b.maxX, 2 * cl * Dr);
         b.maxW = std::max(b.maxW, 4 * Dl * Dr);

@@ -5,19 +5,30 @@
 //   qil_norm_env_ket /   the four-product environment step of |W psi|^2, E' = A^H ((E A) W) conj(Wr), on nslots packed environments
 //   qil_norm_env_bra
 //   qil_upload_bytes     caller memory into a block of the call's qil_scratch
+//   qil_download         device memory to the caller, complete when it returns
 // Declared in qil_internal.h.  The f64 MFMA tile step and the small type helpers of the kernels are in qil_device_utils.h.
 #include "qil_internal.h"
+#include "qil_launch.h"
 #include "qil_device_utils.h"
 
 namespace {
 
 using namespace qil_dev;
 
+// in the table form of qil_launch.h: the starts of the read-outs of a lock-step batch are ONE launch
 template <class T>
-__global__ void fill_ones(T* __restrict__ p, long long count, long long stride) {
+__device__ __forceinline__ void fill_ones_body(const uint3 blockIdx, const uint3 gridDim, T* __restrict__ p, long long count, long long stride) {
     for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < count; t += (long long)gridDim.x * blockDim.x)
         p[t * stride] = cast_elem<T>(1.0);
 }
+template <class T>
+struct fill_ones_k {
+    static constexpr int NT = 256, MINW = 1;
+    template <class... QA>
+    static __device__ __forceinline__ void run(const uint3 b, const uint3 g, QA... a) {
+        fill_ones_body<T>(b, g, a...);
+    }
+};
 
 // A[s, sigma, beta] -> Ap (cast to TD): QIL_SITE_PLAIN as it lies (a widened copy), QIL_SITE_REVERSED Ap[beta, sigma, s]
 template <class TS, class TD>
@@ -70,11 +81,10 @@ void for_site_dtypes(int dt, int src_dt, F go) {
 }  // namespace
 
 int qil_dev_fill_ones(qil_context* ctx, int dt, void* p, int64_t count, int64_t stride) {
-    const dim3 g(qil_grid_for(count, 65536));
-    if (dt == QIL_C64) hipLaunchKernelGGL(fill_ones<c64>, g, dim3(256), 0, qil_stream(ctx), (c64*)p, (long long)count, (long long)stride);
-    else hipLaunchKernelGGL(fill_ones<double>, g, dim3(256), 0, qil_stream(ctx), (double*)p, (long long)count, (long long)stride);
-    QIL_HIP(hipGetLastError());
-    return QIL_OK;
+    return for_elem_type(dt == QIL_C64, [&](auto t) {
+        using T = decltype(t);
+        return qil_klaunch<fill_ones_k<T>>(ctx, dim3(qil_grid_for(count, 65536)), dim3(256), 0, (T*)p, (long long)count, (long long)stride);
+    });
 }
 
 int qil_put_mps_site(qil_context* ctx, int dt, const qil_mps* psi, int64_t i, int layout, void* dst) {
@@ -133,5 +143,11 @@ int qil_upload_bytes(qil_scratch& tmp, const void* host, size_t bytes, void** de
         QIL_HIP(hipMemcpyAsync(*dev, host, bytes, hipMemcpyHostToDevice, qil_stream(tmp.ctx)));
         QIL_HIP(qil_stream_sync(tmp.ctx));             // `host` is the caller's memory
     }
+    return QIL_OK;
+}
+
+int qil_download(qil_context* ctx, void* host_dst, const void* dev_src, size_t bytes) {
+    QIL_HIP(hipMemcpyAsync(host_dst, dev_src, bytes, hipMemcpyDeviceToHost, qil_stream(ctx)));
+    QIL_HIP(qil_stream_sync(ctx));
     return QIL_OK;
 }

@@ -5,7 +5,7 @@
 // parts (re_of / im_of / make_elem / shfl_xor_t), the one K step of a 16 x 16 tile on the f64 MFMA (mfma_step), the splitmix64
 // hash, the sampling rule (seeded_uniform, choose), the row sums of both children (children_row_sums), the per-row steps of
 // the beam search (beam_keys, beam_child_scale, beam_gather_row, beam_finish_row), DPP cross-lane sums, Jacobi rotations, the in-workgroup one-sided Jacobi sweep loop, and the site table, site lookup
-// and stores of the grouped launches.  gfx950 only.
+// and stores of the grouped launches; on the host, the dtype switch of a launch (for_elem_type, for_elem_types).  gfx950 only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -15,6 +15,18 @@ namespace qil_dev {
 struct c64 {
     double re, im;
 };
+
+// The dtype switch of a launch (host): go(element) with a value of the element type, c64 where `complex`; for_elem_types is
+// the two-operand form, go(first element, second element).  Returns what go returns.
+template <class F>
+auto for_elem_type(bool complex, F go) {
+    if (complex) return go(c64{});
+    return go(double{});
+}
+template <class F>
+auto for_elem_types(bool complex_a, bool complex_b, F go) {
+    return for_elem_type(complex_a, [&](auto a) { return for_elem_type(complex_b, [&](auto b) { return go(a, b); }); });
+}
 
 __device__ __forceinline__ double conj_t(double v) { return v; }
 __device__ __forceinline__ c64 conj_t(c64 v) { return c64{v.re, -v.im}; }

@@ -412,6 +412,8 @@ inline int qil_norm_env_step(qil_context* ctx, int dt, int64_t cl, int64_t cr, i
 }
 // `bytes` of caller memory into a new block of tmp (stream-synchronised: the source may go away when this returns)
 int qil_upload_bytes(qil_scratch& tmp, const void* host, size_t bytes, void** dev);
+// `bytes` of device memory to the caller, ordered after everything ctx has enqueued and complete on return (stream-synchronised)
+int qil_download(qil_context* ctx, void* host_dst, const void* dev_src, size_t bytes);
 // ---- (qil_apply_sample.hip) the two steps qil_apply_sample and qil_apply_top_k share
 // bytes of right environments a call may keep (16 GiB, or QIL_APPLY_SAMPLE_RENV_BYTES, read on each call) and what (W, psi) needs
 int64_t qil_apply_env_budget();
@@ -428,6 +430,8 @@ struct qil_apply_bond_sizes {
     long long maxM = 1, maxX = 1, maxW = 1, maxA = 1;
 };
 qil_apply_bond_sizes qil_apply_sizes_of(const struct qil_mpo* W, const struct qil_mps* psi);
+// ... from the n + 1 bond dimensions of the state and of the operator (readout_route has no handles)
+qil_apply_bond_sizes qil_apply_sizes_of(int64_t n, const int64_t* chain_dims, const int64_t* op_dims);
 // What a lazy sweep works with, all of it blocks of tmp: the site scratch of qil_lazy_row_step (Wc, and As where psi's dtype is
 // not dt) and of the environment pass (At, Wd, Wr), the selector bytes {0, 1} (both + s: output bit s for every row of a step)
 // and the environments Rk[1 .. n] (bond_k^2 elements, bond_k = chi_k D_k)

@@ -13,8 +13,13 @@
 #include "qil_device_utils.h"
 #include "qilaplace_hip_testing.h"
 #include <set>
-#include <mutex>
-#include <map>
+
+// elements per query of the lazy chain's row vector M and of each half of its X: max over the sites of D_r chi_r and D_r chi_l
+static long long lazy_chain_elems(int64_t n, const int64_t* dims, const int64_t* wdims) {
+    long long msz = 1;
+    for (int64_t i = 0; i < n; ++i) msz = std::max<long long>({msz, wdims[i + 1] * dims[i + 1], wdims[i + 1] * dims[i]});
+    return msz;
+}
 
 // The route of a read-out call: THE decision, not a copy of it -- wants_sort_plan, coefficient_enqueue, the sweep and the lazy verb
 // switch on the value returned here, and qil_readout_route hands the same function to the tests.  dims: the n + 1 bond dimensions
@@ -24,17 +29,11 @@
 static int readout_route(int verb, bool cx, int64_t nb, int64_t n, const int64_t* dims, const int64_t* wdims, int64_t* pass_queries) {
     if (pass_queries) *pass_queries = nb;
     if (verb == QIL_READOUT_LAZY) {
-        long long msz = 1, maxM = 1, maxX = 1;               // M: Dr*cr, X[s']: Dr*cl
-        for (int64_t i = 0; i < n; ++i) {
-            const long long cl = dims[i], cr = dims[i + 1], Dl = wdims[i], Dr = wdims[i + 1];
-            msz = std::max(msz, std::max(Dr * cr, Dr * cl));
-            maxM = std::max(maxM, std::max(cl * Dl, cr * Dr));
-            maxX = std::max(maxX, cl * 2 * Dr);
-        }
         // Many queries on a wide product bond: the per-query chains (one workgroup each, vector ALU) give way to batched MFMA
         // GEMMs.  Measured crossover of chi * D: 1.0 vs 2.0 ms at 1024, 0.85 vs 0.77 at 512.
-        if (!(nb >= 16 && msz >= 1024)) return QIL_ROUTE_LAZY_CHAIN;
-        const long long per_query = (2 * maxM + maxX) * (cx ? 16LL : 8LL);
+        if (!(nb >= 16 && lazy_chain_elems(n, dims, wdims) >= 1024)) return QIL_ROUTE_LAZY_CHAIN;
+        const qil_apply_bond_sizes b = qil_apply_sizes_of(n, dims, wdims);
+        const long long per_query = (2 * b.maxM + b.maxX) * (cx ? 16LL : 8LL);
         if (pass_queries)
             *pass_queries = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nb, 32768), (8LL << 30) / per_query));
         return QIL_ROUTE_LAZY_GEMM;
@@ -75,6 +74,14 @@ struct ChainSite {
     const void* W;  // MPO site (lazy path) or null
     int cl, cr, Dl, Dr;
 };
+// the site table of the per-query chains; W null: the direct verbs
+std::vector<ChainSite> chain_sites(const qil_mps* psi, const qil_mpo* W) {
+    std::vector<ChainSite> tab((size_t)psi->n());
+    for (size_t i = 0; i < tab.size(); ++i)
+        tab[i] = ChainSite{psi->site[i], W ? W->site[i] : nullptr, (int)psi->dims[i], (int)psi->dims[i + 1],
+                           W ? (int)W->dims[i] : 1, W ? (int)W->dims[i + 1] : 1};
+    return tab;
+}
 
 constexpr int kThreads = 256;
 
@@ -223,18 +230,6 @@ struct gather_rows_k {
     }
 };
 template <class T>
-__device__ __forceinline__ void fill_ones_body(const uint3 blockIdx, const uint3 gridDim, T* __restrict__ v, long long n) {
-    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x) v[t] = cast_elem<T>(1.0);
-}
-template <class T>
-struct fill_ones_k {
-    static constexpr int NT = 256, MINW = 1;
-    template <class... QA>
-    static __device__ __forceinline__ void run(const uint3 b, const uint3 g, QA... a) {
-        fill_ones_body<T>(b, g, a...);
-    }
-};
-template <class T>
 __device__ __forceinline__ void finish_coeff_body(const uint3 blockIdx, const uint3 gridDim, const T* __restrict__ v, long long nb,
                                                   double amplitude, c64* __restrict__ out) {
     for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < nb; t += (long long)gridDim.x * blockDim.x) {
@@ -250,12 +245,6 @@ struct finish_coeff_k {
         finish_coeff_body<T>(b, g, a...);
     }
 };
-
-// the plain launch of finish_coeff_body (the lazy read-out's last step)
-template <class T>
-__global__ void finish_coeff(const T* __restrict__ v, long long nb, double amplitude, c64* __restrict__ out) {
-    finish_coeff_body<T>(make_uint3(blockIdx.x, 0, 0), make_uint3(gridDim.x, 1, 1), v, nb, amplitude, out);
-}
 
 // ---- dense read-out of a sub-lattice of configurations (grid scans) --------------------------------------
 template <class T>
@@ -294,23 +283,15 @@ int lazy_gemm_path(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64
     const bool wc = W->dtype == QIL_C64, ac = psi->dtype == QIL_C64;
     const int dt = (wc || ac) ? QIL_C64 : QIL_F64;
     const size_t e = qil_elem_size(dt);
-    long long maxM = 1, maxX = 1, maxW = 1, maxA = 1;
-    for (int64_t i = 0; i < n; ++i) {
-        const long long cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1];
-        const long long Dl = W->dims[(size_t)i], Dr = W->dims[(size_t)i + 1];
-        maxM = std::max(maxM, std::max(cl * Dl, cr * Dr));
-        maxX = std::max(maxX, cl * 2 * Dr);
-        maxW = std::max(maxW, Dl * 4 * Dr);
-        maxA = std::max(maxA, cl * 2 * cr);
-    }
+    const qil_apply_bond_sizes b = qil_apply_sizes_of(W, psi);
     // chunk = queries per pass (readout_route)
     qil_scratch tmp(ctx);
     void *M0 = nullptr, *M1 = nullptr, *X = nullptr, *Wc = nullptr, *Ac = nullptr;
-    QIL_TRY(tmp.alloc((size_t)(chunk * maxM) * e, &M0));
-    QIL_TRY(tmp.alloc((size_t)(chunk * maxM) * e, &M1));
-    QIL_TRY(tmp.alloc((size_t)(chunk * maxX) * e, &X));
-    QIL_TRY(tmp.alloc((size_t)maxW * e, &Wc));
-    if (dt == QIL_C64 && !ac) QIL_TRY(tmp.alloc((size_t)maxA * 16, &Ac));
+    QIL_TRY(tmp.alloc((size_t)(chunk * b.maxM) * e, &M0));
+    QIL_TRY(tmp.alloc((size_t)(chunk * b.maxM) * e, &M1));
+    QIL_TRY(tmp.alloc((size_t)(chunk * b.maxX) * e, &X));
+    QIL_TRY(tmp.alloc((size_t)b.maxW * e, &Wc));
+    if (dt == QIL_C64 && !ac) QIL_TRY(tmp.alloc((size_t)b.maxA * 16, &Ac));
     for (int64_t q0 = 0; q0 < nb; q0 += chunk) {
         const int64_t nq = std::min<int64_t>(chunk, nb - q0);
         QIL_TRY(qil_dev_fill_ones(ctx, dt, M0, nq));
@@ -319,16 +300,27 @@ int lazy_gemm_path(qil_context* ctx, const qil_mpo* W, const qil_mps* psi, int64
             QIL_TRY(qil_lazy_row_step(ctx, dt, W, psi, i, Mc, Mn, X, Wc, Ac, nq, dbits + q0 * n + i, n));
             std::swap(Mc, Mn);
         }
-        const dim3 g1(qil_grid_for(nq));
-        if (dt == QIL_C64)
-            hipLaunchKernelGGL(finish_coeff<c64>, g1, dim3(256), 0, qil_stream(ctx), (const c64*)Mc, (long long)nq, psi->amplitude,
-                               dout + q0);
-        else
-            hipLaunchKernelGGL(finish_coeff<double>, g1, dim3(256), 0, qil_stream(ctx), (const double*)Mc, (long long)nq,
-                               psi->amplitude, dout + q0);
-        if (hipGetLastError() != hipSuccess) return qil_fail(QIL_EHIP, "lazy coefficient (GEMM form): launch failed");
+        QIL_TRY(qil_dev_finish_coeff(ctx, dt, Mc, nq, psi->amplitude, dout + q0));
     }
     return QIL_OK;
+}
+
+// Lazy read-out, chain form: one workgroup per query walks all sites in ONE launch
+int lazy_chain_path(qil_context* ctx, qil_scratch& tmp, const qil_mpo* W, const qil_mps* psi, int64_t nb, const uint8_t* dbits,
+                    c64* dout) {
+    const int64_t n = psi->n();
+    const long long msz = lazy_chain_elems(n, psi->dims.data(), W->dims.data());
+    void* scratch = nullptr;
+    QIL_TRY(tmp.alloc((size_t)(4 * nb * msz) * 16, &scratch));
+    const std::vector<ChainSite> tab = chain_sites(psi, W);
+    qil_dev_table dtab(ctx);
+    QIL_TRY(dtab.upload(tab.data(), tab.size() * sizeof(ChainSite)));
+    for_elem_types(W->dtype == QIL_C64, psi->dtype == QIL_C64, [&](auto w, auto a) {
+        hipLaunchKernelGGL((lazy_coefficient_chain<decltype(w), decltype(a)>), dim3((unsigned)nb), dim3(kThreads), 0, qil_stream(ctx),
+                           dtab.as<ChainSite>(), (int)n, dbits, (c64*)scratch, msz, dout, psi->amplitude);
+    });
+    QIL_HIP(hipGetLastError());
+    return dtab.release();
 }
 
 // the caller's bits, checked, in a block of the call's scratch
@@ -368,9 +360,10 @@ int qil_lazy_row_step(qil_context* ctx, int dt, const qil_mpo* W, const qil_mps*
 
 // out[t] = amplitude * v[t], t < nb: the last step of the GEMM read-outs, for qil_product_batch (qil_product.hip) as well
 int qil_dev_finish_coeff(qil_context* ctx, int dt, const void* v, int64_t nb, double amplitude, void* dout) {
-    const dim3 g1(qil_grid_for(nb));
-    if (dt == QIL_C64) return qil_klaunch<finish_coeff_k<c64>>(ctx, g1, dim3(256), 0, (const c64*)v, (long long)nb, amplitude, (c64*)dout);
-    return qil_klaunch<finish_coeff_k<double>>(ctx, g1, dim3(256), 0, (const double*)v, (long long)nb, amplitude, (c64*)dout);
+    return for_elem_type(dt == QIL_C64, [&](auto t) {
+        using T = decltype(t);
+        return qil_klaunch<finish_coeff_k<T>>(ctx, dim3(qil_grid_for(nb)), dim3(256), 0, (const T*)v, (long long)nb, amplitude, (c64*)dout);
+    });
 }
 
 static int coefficient_impl(const qil_mps* psi, int64_t nb, const uint8_t* bits, double* out, int max_bit);
@@ -386,18 +379,17 @@ extern "C" int qil_coefficient_marginal_batch(const qil_mps* psi, int64_t nb, co
     return coefficient_impl(psi, nb, bits, out, 2);
 }
 
-// Enqueue the read-out of nb configurations (device bits) of psi into dout (nb complex, device); no
-// synchronisation, every temporary goes back to the pool in stream order.
 // Plan of the bit-sorted GEMM read-out (built on the host from the caller's bits, shared by every chain read at the same
 // configurations): before site i the query vectors are stored in order_i = queries with bit_i = 0 first (stable), so the site
 // costs two products with ONE slice each -- n0[i] x chi_l by chi_l x chi_r and (nb - n0[i]) x chi_l by chi_l x chi_r -- instead
 // of one nb x chi_l by chi_l x 2 chi_r product that computes both slices for every query and throws half away.  map[i][r] = row
-// of site i's result that becomes row r of site i + 1's operand (the last map restores the caller's order).
+// of site i's result that becomes row r of site i + 1's operand (the last map restores the caller's order).  The map is a block
+// of the scratch of the call that built the plan: the plan does not own it.
 struct SortPlan {
-    int* dmap = nullptr;                 // [n][nb], device
+    const int* dmap = nullptr;           // [n][nb], device
     std::vector<int64_t> n0;             // per site: queries with bit 0
 };
-static int build_sort_plan(qil_context* ctx, int64_t nb, int64_t n, const uint8_t* bits, SortPlan* plan) {
+static int build_sort_plan(qil_scratch& tmp, int64_t nb, int64_t n, const uint8_t* bits, SortPlan* plan) {
     std::vector<int> map((size_t)(n * nb)), order((size_t)nb), next((size_t)nb), pos((size_t)nb);
     plan->n0.assign((size_t)n, 0);
     auto order_of = [&](int64_t site, std::vector<int>& o) -> int64_t {
@@ -422,14 +414,8 @@ static int build_sort_plan(qil_context* ctx, int64_t nb, int64_t n, const uint8_
         order.swap(next);
     }
     void* p = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, map.size() * sizeof(int), &p));
-    hipError_t e = hipMemcpyAsync(p, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice, qil_stream(ctx));
-    if (e == hipSuccess) e = qil_stream_sync(ctx);         // `map` is a local
-    if (e != hipSuccess) {
-        qil_ctx_free(ctx, p);
-        return qil_fail(QIL_EHIP, "read-out plan upload failed: %s", hipGetErrorString(e));
-    }
-    plan->dmap = static_cast<int*>(p);
+    QIL_TRY(qil_upload_bytes(tmp, map.data(), map.size() * sizeof(int), &p));
+    plan->dmap = static_cast<const int*>(p);
     return QIL_OK;
 }
 // the read-out of psi under `verb` takes the sorted GEMM form: it needs a plan
@@ -437,86 +423,102 @@ static bool wants_sort_plan(const qil_mps* psi, int64_t nb, int verb) {
     return readout_route(verb, psi->dtype == QIL_C64, nb, psi->n(), psi->dims.data(), nullptr, nullptr) == QIL_ROUTE_GEMM_SORTED;
 }
 
-static int coefficient_enqueue(const qil_mps* psi, int64_t nb, const uint8_t* dbits, void* dout, int verb, const SortPlan* plan) {
+// QIL_ROUTE_CHAIN: one workgroup per query walks all sites in ONE launch
+static int readout_chain(qil_scratch& tmp, const qil_mps* psi, int64_t nb, const uint8_t* dbits, void* dout) {
     qil_context* ctx = psi->ctx;
     const int64_t n = psi->n();
-    std::vector<ChainSite> tab((size_t)n);
-    long long maxchi = 1;
-    for (int64_t i = 0; i < n; ++i) {
-        tab[(size_t)i] = ChainSite{psi->site[(size_t)i], nullptr, (int)psi->dims[(size_t)i],
-                                   (int)psi->dims[(size_t)i + 1], 1, 1};
-        maxchi = std::max<long long>(maxchi, psi->dims[(size_t)i + 1]);
-    }
-    const size_t esz = qil_elem_size(psi->dtype);
-    const int route = readout_route(verb, psi->dtype == QIL_C64, nb, n, psi->dims.data(), nullptr, nullptr);
-    if (route != QIL_ROUTE_CHAIN) {
-        const bool sorted = route == QIL_ROUTE_GEMM_SORTED;
-        QIL_REQUIRE(!sorted || (plan && plan->dmap), QIL_EINVAL_ARG, "coefficient: the sorted read-out was not given its plan");
-        // Large bonds: all queries advance together, one f64-MFMA GEMM per site.  The site tensor is
-        // read ONCE for the whole batch: T (nb x 2 chi_r) = V (nb x chi_l) * A_i (chi_l x 2 chi_r),
-        // then each query keeps the column block of its own bit.
-        void *V = nullptr, *Vn = nullptr, *Tm = nullptr;
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(nb * maxchi) * esz, &V));
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(nb * maxchi) * esz, &Vn));
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(2 * nb * maxchi) * esz, &Tm));
-        const bool cx = psi->dtype == QIL_C64;
-        const unsigned g1 = (unsigned)std::min<long long>((nb + 255) / 256, 4096);
-        if (cx) QIL_TRY((qil_klaunch<fill_ones_k<c64>>(ctx, dim3(g1), dim3(256), 0, (c64*)V, (long long)nb)));
-        else QIL_TRY((qil_klaunch<fill_ones_k<double>>(ctx, dim3(g1), dim3(256), 0, (double*)V, (long long)nb)));
-        for (int64_t i = 0; i < n; ++i) {
-            const int64_t cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1];
-            const unsigned g = (unsigned)std::min<long long>((nb * cr + 255) / 256, 65536);
-            if (sorted) {
-                // bit-sorted: rows [0, n0) take slice 0, rows [n0, nb) slice 1 (slice s of A[alpha, s, beta]: offset s chi_l, ld 2 chi_l)
-                const int64_t z = plan->n0[(size_t)i];
-                const char* site = static_cast<const char*>(psi->site[(size_t)i]);
-                for (int sl = 0; sl < 2; ++sl) {
-                    const int64_t r0 = sl ? z : 0, rows = sl ? nb - z : z;
-                    if (rows == 0) continue;
-                    const void* Vs = static_cast<const char*>(V) + (size_t)r0 * esz;
-                    void* Ts = static_cast<char*>(Tm) + (size_t)r0 * esz;
-                    const void* As = site + (size_t)(sl * cl) * esz;
-                    if (rows <= 48) QIL_TRY(qil_dev_gemm_skinny(ctx, psi->dtype, 0, 0, rows, cr, cl, Vs, nb, As, 2 * cl, Ts, nb));
-                    else QIL_TRY(qil_dev_gemm(ctx, psi->dtype, 0, 0, rows, cr, cl, Vs, nb, As, 2 * cl, Ts, nb));
-                }
-                const int* map = plan->dmap + (size_t)(i * nb);
-                if (cx) QIL_TRY((qil_klaunch<gather_rows_k<c64>>(ctx, dim3(g), dim3(256), 0, (const c64*)Tm, (long long)nb, (int)cr, map, (c64*)Vn)));
-                else QIL_TRY((qil_klaunch<gather_rows_k<double>>(ctx, dim3(g), dim3(256), 0, (const double*)Tm, (long long)nb, (int)cr, map, (double*)Vn)));
-                std::swap(V, Vn);
-                continue;
-            }
-            QIL_TRY(qil_dev_gemm(ctx, psi->dtype, 0, 0, nb, 2 * cr, cl, V, nb, psi->site[(size_t)i], cl, Tm, nb));
-            if (cx)
-                QIL_TRY((qil_klaunch<select_slice_k<c64>>(ctx, dim3(g), dim3(256), 0, (const c64*)Tm, (long long)nb, (int)cr,
-                                                          (const uint8_t*)dbits, (int)n, (int)i, (c64*)Vn)));
-            else
-                QIL_TRY((qil_klaunch<select_slice_k<double>>(ctx, dim3(g), dim3(256), 0, (const double*)Tm, (long long)nb, (int)cr,
-                                                             (const uint8_t*)dbits, (int)n, (int)i, (double*)Vn)));
-            std::swap(V, Vn);
-        }
-        if (cx) QIL_TRY((qil_klaunch<finish_coeff_k<c64>>(ctx, dim3(g1), dim3(256), 0, (const c64*)V, (long long)nb, psi->amplitude, (c64*)dout)));
-        else QIL_TRY((qil_klaunch<finish_coeff_k<double>>(ctx, dim3(g1), dim3(256), 0, (const double*)V, (long long)nb, psi->amplitude, (c64*)dout)));
-        qil_ctx_free(ctx, V);
-        qil_ctx_free(ctx, Vn);
-        qil_ctx_free(ctx, Tm);
-        return QIL_OK;
-    }
+    const long long maxchi = *std::max_element(psi->dims.begin() + 1, psi->dims.end());
     void* scratch = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(2 * nb * maxchi) * esz, &scratch));
+    QIL_TRY(tmp.alloc((size_t)(2 * nb * maxchi) * qil_elem_size(psi->dtype), &scratch));
+    const std::vector<ChainSite> tab = chain_sites(psi, nullptr);
     qil_dev_table dtab(ctx);
     QIL_TRY(dtab.upload(tab.data(), tab.size() * sizeof(ChainSite)));
-    if (psi->dtype == QIL_C64)
-        hipLaunchKernelGGL(coefficient_chain<c64>, dim3((unsigned)nb), dim3(kThreads), 0, qil_stream(ctx),
-                           dtab.as<ChainSite>(), (int)n, dbits, (c64*)scratch, maxchi, (c64*)dout,
-                           psi->amplitude);
-    else
-        hipLaunchKernelGGL(coefficient_chain<double>, dim3((unsigned)nb), dim3(kThreads), 0, qil_stream(ctx),
-                           dtab.as<ChainSite>(), (int)n, dbits, (double*)scratch, maxchi, (c64*)dout,
-                           psi->amplitude);
+    for_elem_type(psi->dtype == QIL_C64, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(coefficient_chain<T>, dim3((unsigned)nb), dim3(kThreads), 0, qil_stream(ctx), dtab.as<ChainSite>(), (int)n,
+                           dbits, (T*)scratch, maxchi, (c64*)dout, psi->amplitude);
+    });
     QIL_HIP(hipGetLastError());
-    QIL_TRY(dtab.release());
-    qil_ctx_free(ctx, scratch);
-    return QIL_OK;
+    return dtab.release();
+}
+
+// The GEMM routes (large bonds): all queries advance together, V (nb x chi_l) -> Vn (nb x chi_r) through Tm per site, on f64-MFMA
+// GEMMs.  What both share: the three blocks, the start V = ones, and qil_dev_finish_coeff at the end.
+struct GemmRows {
+    void *V = nullptr, *Vn = nullptr, *Tm = nullptr;
+};
+static int gemm_rows_begin(qil_scratch& tmp, const qil_mps* psi, int64_t nb, GemmRows* r) {
+    const long long maxchi = *std::max_element(psi->dims.begin() + 1, psi->dims.end());
+    const size_t esz = qil_elem_size(psi->dtype);
+    QIL_TRY(tmp.alloc((size_t)(nb * maxchi) * esz, &r->V));
+    QIL_TRY(tmp.alloc((size_t)(nb * maxchi) * esz, &r->Vn));
+    QIL_TRY(tmp.alloc((size_t)(2 * nb * maxchi) * esz, &r->Tm));
+    return qil_dev_fill_ones(tmp.ctx, psi->dtype, r->V, nb);
+}
+
+// QIL_ROUTE_GEMM_SELECT: the site tensor is read ONCE for the whole batch, T (nb x 2 chi_r) = V (nb x chi_l) * A_i (chi_l x 2 chi_r),
+// then each query keeps the column block of its own bit (a marginal: the sum of both)
+static int readout_gemm_select(qil_scratch& tmp, const qil_mps* psi, int64_t nb, const uint8_t* dbits, void* dout) {
+    qil_context* ctx = psi->ctx;
+    const int64_t n = psi->n();
+    GemmRows r;
+    QIL_TRY(gemm_rows_begin(tmp, psi, nb, &r));
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1];
+        QIL_TRY(qil_dev_gemm(ctx, psi->dtype, 0, 0, nb, 2 * cr, cl, r.V, nb, psi->site[(size_t)i], cl, r.Tm, nb));
+        QIL_TRY(for_elem_type(psi->dtype == QIL_C64, [&](auto t) {
+            using T = decltype(t);
+            return qil_klaunch<select_slice_k<T>>(ctx, dim3(qil_grid_for(nb * cr, 65536)), dim3(256), 0, (const T*)r.Tm, (long long)nb,
+                                                  (int)cr, dbits, (int)n, (int)i, (T*)r.Vn);
+        }));
+        std::swap(r.V, r.Vn);
+    }
+    return qil_dev_finish_coeff(ctx, psi->dtype, r.V, nb, psi->amplitude, dout);
+}
+
+// QIL_ROUTE_GEMM_SORTED: rows [0, n0) take slice 0, rows [n0, nb) slice 1 (slice s of A[alpha, s, beta]: offset s chi_l, ld 2 chi_l),
+// then the rows move into the next site's order
+static int readout_gemm_sorted(qil_scratch& tmp, const qil_mps* psi, int64_t nb, const SortPlan& plan, void* dout) {
+    qil_context* ctx = psi->ctx;
+    const size_t esz = qil_elem_size(psi->dtype);
+    GemmRows r;
+    QIL_TRY(gemm_rows_begin(tmp, psi, nb, &r));
+    for (int64_t i = 0; i < psi->n(); ++i) {
+        const int64_t cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1];
+        const int64_t z = plan.n0[(size_t)i];
+        const char* site = static_cast<const char*>(psi->site[(size_t)i]);
+        for (int sl = 0; sl < 2; ++sl) {
+            const int64_t r0 = sl ? z : 0, rows = sl ? nb - z : z;
+            if (rows == 0) continue;
+            const void* Vs = static_cast<const char*>(r.V) + (size_t)r0 * esz;
+            void* Ts = static_cast<char*>(r.Tm) + (size_t)r0 * esz;
+            const void* As = site + (size_t)(sl * cl) * esz;
+            if (rows <= 48) QIL_TRY(qil_dev_gemm_skinny(ctx, psi->dtype, 0, 0, rows, cr, cl, Vs, nb, As, 2 * cl, Ts, nb));
+            else QIL_TRY(qil_dev_gemm(ctx, psi->dtype, 0, 0, rows, cr, cl, Vs, nb, As, 2 * cl, Ts, nb));
+        }
+        const int* map = plan.dmap + (size_t)(i * nb);
+        QIL_TRY(for_elem_type(psi->dtype == QIL_C64, [&](auto t) {
+            using T = decltype(t);
+            return qil_klaunch<gather_rows_k<T>>(ctx, dim3(qil_grid_for(nb * cr, 65536)), dim3(256), 0, (const T*)r.Tm, (long long)nb,
+                                                 (int)cr, map, (T*)r.Vn);
+        }));
+        std::swap(r.V, r.Vn);
+    }
+    return qil_dev_finish_coeff(ctx, psi->dtype, r.V, nb, psi->amplitude, dout);
+}
+
+// Enqueue the read-out of nb configurations (device bits) of psi into dout (nb complex, device); no synchronisation, every
+// temporary is a block of a scratch of psi's context (in a sweep batch: the product's slot) and goes back to the pool in stream
+// order.
+static int coefficient_enqueue(const qil_mps* psi, int64_t nb, const uint8_t* dbits, void* dout, int verb, const SortPlan* plan) {
+    qil_scratch tmp(psi->ctx);
+    switch (readout_route(verb, psi->dtype == QIL_C64, nb, psi->n(), psi->dims.data(), nullptr, nullptr)) {
+        case QIL_ROUTE_CHAIN: return readout_chain(tmp, psi, nb, dbits, dout);
+        case QIL_ROUTE_GEMM_SELECT: return readout_gemm_select(tmp, psi, nb, dbits, dout);
+        default:
+            QIL_REQUIRE(plan && plan->dmap, QIL_EINVAL_ARG, "coefficient: the sorted read-out was not given its plan");
+            return readout_gemm_sorted(tmp, psi, nb, *plan, dout);
+    }
 }
 
 static int coefficient_impl(const qil_mps* psi, int64_t nb, const uint8_t* bits, double* out, int max_bit) {
@@ -530,15 +532,11 @@ static int coefficient_impl(const qil_mps* psi, int64_t nb, const uint8_t* bits,
     QIL_TRY(upload_bits(tmp, nb, psi->n(), bits, &dbits, max_bit));
     const int verb = max_bit > 1 ? QIL_READOUT_MARGINAL : QIL_READOUT_PLAIN;
     SortPlan plan;
-    if (wants_sort_plan(psi, nb, verb)) QIL_TRY(build_sort_plan(ctx, nb, psi->n(), bits, &plan));
+    if (wants_sort_plan(psi, nb, verb)) QIL_TRY(build_sort_plan(tmp, nb, psi->n(), bits, &plan));
     void* dout = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)nb * 16, &dout));
+    QIL_TRY(tmp.alloc((size_t)nb * 16, &dout));
     QIL_TRY(coefficient_enqueue(psi, nb, dbits, dout, verb, &plan));
-    if (plan.dmap) qil_ctx_free(ctx, plan.dmap);
-    QIL_HIP(hipMemcpyAsync(out, dout, (size_t)nb * 16, hipMemcpyDeviceToHost, qil_stream(ctx)));
-    QIL_HIP(qil_stream_sync(ctx));
-    qil_ctx_free(ctx, dout);
-    return QIL_OK;
+    return qil_download(ctx, out, dout, (size_t)nb * 16);
 }
 
 // The body of a damping sweep (BASELINE.json configs[3]; the reference loops `W = build_dt_mpo(psi, wr); out = W * psi;
@@ -570,7 +568,7 @@ int qil_apply_coefficient_sweep_dev(const qil_mpo* const* Ws, int64_t nw, const 
         }
     }
     SortPlan plan;                                        // one plan for every operator's read-out (same configurations)
-    if (sorted) QIL_TRY(build_sort_plan(ctx, nb, psi->n(), bits, &plan));
+    if (sorted) QIL_TRY(build_sort_plan(tmp, nb, psi->n(), bits, &plan));
     auto one = [&](const qil_mpo* W, const qil_mps* state, int64_t j) {
         qil_mps* prod = nullptr;
         QIL_TRY(qil_apply_shared_state(W, state, &prod));
@@ -589,7 +587,6 @@ int qil_apply_coefficient_sweep_dev(const qil_mpo* const* Ws, int64_t nw, const 
     } else {
         for (int64_t j = 0; j < nw; ++j) QIL_TRY(one(Ws[j], psi, j));
     }
-    if (plan.dmap) qil_ctx_free(ctx, plan.dmap);
     return QIL_OK;
 }
 
@@ -600,13 +597,11 @@ extern "C" int qil_apply_coefficient_sweep(const qil_mpo* const* Ws, int64_t nw,
     qil_context* ctx = psi->ctx;
     QIL_TRY(qil_ctx_activate(ctx));
     qil_call_scope call_scope(ctx);
+    qil_scratch tmp(ctx);
     void* dout = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(nw * nb) * 16, &dout));
+    QIL_TRY(tmp.alloc((size_t)(nw * nb) * 16, &dout));
     QIL_TRY(qil_apply_coefficient_sweep_dev(Ws, nw, psi, nb, bits, dout));
-    QIL_HIP(hipMemcpyAsync(out, dout, (size_t)(nw * nb) * 16, hipMemcpyDeviceToHost, qil_stream(ctx)));
-    QIL_HIP(qil_stream_sync(ctx));
-    qil_ctx_free(ctx, dout);
-    return QIL_OK;
+    return qil_download(ctx, out, dout, (size_t)(nw * nb) * 16);
 }
 
 extern "C" int qil_apply_coefficient_batch(const qil_mpo* W, const qil_mps* psi, int64_t nb,
@@ -622,48 +617,19 @@ extern "C" int qil_apply_coefficient_batch(const qil_mpo* W, const qil_mps* psi,
     qil_context* ctx = psi->ctx;
     QIL_TRY(qil_ctx_activate(ctx));
     qil_call_scope call_scope(ctx);
-    const int64_t n = psi->n();
-    std::vector<ChainSite> tab((size_t)n);
-    long long msz = 1;
-    for (int64_t i = 0; i < n; ++i) {
-        tab[(size_t)i] = ChainSite{psi->site[(size_t)i], W->site[(size_t)i], (int)psi->dims[(size_t)i],
-                                   (int)psi->dims[(size_t)i + 1], (int)W->dims[(size_t)i],
-                                   (int)W->dims[(size_t)i + 1]};
-        // M: Dr*cr, X[s']: Dr*cl
-        msz = std::max<long long>(msz, W->dims[(size_t)i + 1] * psi->dims[(size_t)i + 1]);
-        msz = std::max<long long>(msz, W->dims[(size_t)i + 1] * psi->dims[(size_t)i]);
-    }
     qil_scratch tmp(ctx);
+    const int64_t n = psi->n();
     uint8_t* dbits = nullptr;
     QIL_TRY(upload_bits(tmp, nb, n, bits, &dbits));
-    void *scratch = nullptr, *dout = nullptr;
+    void* dout = nullptr;
     QIL_TRY(tmp.alloc((size_t)nb * 16, &dout));
     int64_t pass = nb;
     const bool cx = W->dtype == QIL_C64 || psi->dtype == QIL_C64;
-    if (readout_route(QIL_READOUT_LAZY, cx, nb, n, psi->dims.data(), W->dims.data(), &pass) == QIL_ROUTE_LAZY_GEMM) {
+    if (readout_route(QIL_READOUT_LAZY, cx, nb, n, psi->dims.data(), W->dims.data(), &pass) == QIL_ROUTE_LAZY_GEMM)
         QIL_TRY(lazy_gemm_path(ctx, W, psi, nb, pass, dbits, (c64*)dout));
-        if (hipMemcpyAsync(out, dout, (size_t)nb * 16, hipMemcpyDeviceToHost, qil_stream(ctx)) != hipSuccess)
-            return qil_fail(QIL_EHIP, "apply_coefficient: download failed");
-        if (qil_stream_sync(ctx) != hipSuccess) return qil_fail(QIL_EHIP, "sync failed");
-        return QIL_OK;
-    }
-    QIL_TRY(tmp.alloc((size_t)(4 * nb * msz) * 16, &scratch));
-    qil_dev_table dtab(ctx);
-    QIL_TRY(dtab.upload(tab.data(), tab.size() * sizeof(ChainSite)));
-    const bool wc = W->dtype == QIL_C64, ac = psi->dtype == QIL_C64;
-#define LAUNCH_LAZY(TW, TA)                                                                             \
-    hipLaunchKernelGGL((lazy_coefficient_chain<TW, TA>), dim3((unsigned)nb), dim3(kThreads), 0, qil_stream(ctx), \
-                       dtab.as<ChainSite>(), (int)n, dbits, (c64*)scratch, msz, (c64*)dout, psi->amplitude)
-    if (wc && ac) LAUNCH_LAZY(c64, c64);
-    else if (wc) LAUNCH_LAZY(c64, double);
-    else if (ac) LAUNCH_LAZY(double, c64);
-    else LAUNCH_LAZY(double, double);
-#undef LAUNCH_LAZY
-    QIL_HIP(hipGetLastError());
-    QIL_TRY(dtab.release());
-    QIL_HIP(hipMemcpyAsync(out, dout, (size_t)nb * 16, hipMemcpyDeviceToHost, qil_stream(ctx)));
-    QIL_HIP(qil_stream_sync(ctx));
-    return QIL_OK;
+    else
+        QIL_TRY(lazy_chain_path(ctx, tmp, W, psi, nb, dbits, (c64*)dout));
+    return qil_download(ctx, out, dout, (size_t)nb * 16);
 }
 
 // All 2^F coefficients of the configurations that agree with `spec` on the fixed sites -- the (k, l) grid scans
@@ -679,6 +645,7 @@ extern "C" int qil_mps_block(const qil_mps* psi, const uint8_t* spec, int revers
     qil_context* ctx = psi->ctx;
     QIL_TRY(qil_ctx_activate(ctx));
     qil_call_scope call_scope(ctx);
+    qil_scratch tmp(ctx);
     const int64_t n = psi->n();
     int nfree = 0;
     for (int64_t i = 0; i < n; ++i) {
@@ -695,12 +662,10 @@ extern "C" int qil_mps_block(const qil_mps* psi, const uint8_t* spec, int revers
         maxslice = std::max<long long>(maxslice, psi->dims[(size_t)i] * psi->dims[(size_t)i + 1]);
     }
     void *bufA = nullptr, *bufB = nullptr, *sl = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxel * e, &bufA));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxel * e, &bufB));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxslice * e, &sl));
-    const double one[2] = {1.0, 0.0};
-    QIL_HIP(hipMemcpyAsync(bufA, one, e, hipMemcpyHostToDevice, qil_stream(ctx)));
-    QIL_HIP(qil_stream_sync(ctx));
+    QIL_TRY(tmp.alloc((size_t)maxel * e, &bufA));
+    QIL_TRY(tmp.alloc((size_t)maxel * e, &bufB));
+    QIL_TRY(tmp.alloc((size_t)maxslice * e, &sl));
+    QIL_TRY(qil_dev_fill_ones(ctx, dt, bufA, 1));
     // the fixed / summed sites BEHIND the last free one fold into a right boundary vector first (O(chi^2) each,
     // instead of dragging the 2^F rows of T through them)
     int64_t last_free = -1;
@@ -709,20 +674,18 @@ extern "C" int qil_mps_block(const qil_mps* psi, const uint8_t* spec, int revers
     long long maxchi = 1;
     for (int64_t i = 0; i <= n; ++i) maxchi = std::max<long long>(maxchi, psi->dims[(size_t)i]);
     void *rv = nullptr, *rv2 = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxchi * e, &rv));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)maxchi * e, &rv2));
-    QIL_HIP(hipMemcpyAsync(rv, one, e, hipMemcpyHostToDevice, qil_stream(ctx)));
-    QIL_HIP(qil_stream_sync(ctx));
+    QIL_TRY(tmp.alloc((size_t)maxchi * e, &rv));
+    QIL_TRY(tmp.alloc((size_t)maxchi * e, &rv2));
+    QIL_TRY(qil_dev_fill_ones(ctx, dt, rv, 1));
     auto site_slice = [&](int64_t i, const void** B, long long* ldb) -> int {   // the (chi_l x chi_r) factor of site i
         const long long cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1];
         const char* A = static_cast<const char*>(psi->site[(size_t)i]);
         if (spec[i] == 2) {
-            const unsigned g = (unsigned)std::min<long long>((cl * cr + 255) / 256, 4096);
-            if (dt == QIL_C64)
-                hipLaunchKernelGGL(slice_sum<c64>, dim3(g), dim3(256), 0, qil_stream(ctx), (const c64*)A, (int)cl, (int)cr, (c64*)sl);
-            else
-                hipLaunchKernelGGL(slice_sum<double>, dim3(g), dim3(256), 0, qil_stream(ctx), (const double*)A, (int)cl, (int)cr,
-                                   (double*)sl);
+            for_elem_type(dt == QIL_C64, [&](auto t) {
+                using T = decltype(t);
+                hipLaunchKernelGGL(slice_sum<T>, dim3(qil_grid_for(cl * cr)), dim3(256), 0, qil_stream(ctx), (const T*)A, (int)cl, (int)cr,
+                                   (T*)sl);
+            });
             *B = sl;
             *ldb = cl;
         } else {
@@ -760,22 +723,13 @@ extern "C" int qil_mps_block(const qil_mps* psi, const uint8_t* spec, int revers
         std::swap(cur, nxt);
     }
     // natural order: the first free site is the LOWEST bit of idx
-    const unsigned g = (unsigned)std::min<long long>((rows + 255) / 256, 65536);
-    if (dt == QIL_C64)
-        hipLaunchKernelGGL(bit_reverse_scale<c64>, dim3(g), dim3(256), 0, qil_stream(ctx), (const c64*)cur, (c64*)nxt, nfree,
-                           psi->amplitude, reverse ? 0 : 1);
-    else
-        hipLaunchKernelGGL(bit_reverse_scale<double>, dim3(g), dim3(256), 0, qil_stream(ctx), (const double*)cur, (double*)nxt,
+    for_elem_type(dt == QIL_C64, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(bit_reverse_scale<T>, dim3(qil_grid_for(rows, 65536)), dim3(256), 0, qil_stream(ctx), (const T*)cur, (T*)nxt,
                            nfree, psi->amplitude, reverse ? 0 : 1);
+    });
     QIL_HIP(hipGetLastError());
-    QIL_HIP(hipMemcpyAsync(host_out, nxt, (size_t)rows * e, hipMemcpyDeviceToHost, qil_stream(ctx)));
-    QIL_HIP(qil_stream_sync(ctx));
-    qil_ctx_free(ctx, bufA);
-    qil_ctx_free(ctx, bufB);
-    qil_ctx_free(ctx, sl);
-    qil_ctx_free(ctx, rv);
-    qil_ctx_free(ctx, rv2);
-    return QIL_OK;
+    return qil_download(ctx, host_out, nxt, (size_t)rows * e);
 }
 
 extern "C" int qil_mps_to_vector(const qil_mps* psi, int reverse, void* host_out) {

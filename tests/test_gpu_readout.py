@@ -296,6 +296,21 @@ def test_failed_readouts_leave_no_device_memory_behind(qil):
     before = (W * phi).to_host()
     same = lambda: all(np.array_equal(x, y) for x, y in zip((W * phi).to_host(), before))
     _failing_then_working(qil, lambda: qil.apply_coefficient_batch(W, phi, bits), lambda: same() or pytest.fail("operands changed"))
+    # the smallest c64 case of each route whose temporaries belong to the read-out's own scratch: the per-query chain, the sorted
+    # GEMM form (which builds a plan) and the lazy chain
+    for name, route in (("one_site_plain-c64-cone", "CHAIN"), ("threshold_nb4_bond128_plain-c64-cone", "GEMM_SORTED")):
+        c = R.BY_NAME[name]
+        assert c.route == route
+        data, cbits = R.operands(c)
+        chi = _psi(qil, data)
+        cnorm = qil.norm(chi)
+        _failing_then_working(qil, lambda: qil.coefficient_batch(chi, cbits), lambda: np.testing.assert_equal(qil.norm(chi), cnorm))
+    c = R.BY_NAME["lazy_small_nb1-Wc64-psic64-cone"]
+    assert c.route == "LAZY_CHAIN"
+    w, a, bits = R.operands(c)
+    W, phi = qil.SingleSiteMPO(w), _psi(qil, a)
+    before = (W * phi).to_host()
+    _failing_then_working(qil, lambda: qil.apply_coefficient_batch(W, phi, bits), lambda: same() or pytest.fail("operands changed"))
 
 
 def test_failed_sweep_returns_its_operators_home(qil):

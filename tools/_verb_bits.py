@@ -16,7 +16,8 @@ rows, seeded and with given uniforms) and apply_top_k (the same two beams) on bo
 process of its own.  The top-k verbs record (rows, values, bound, certified).  Beyond those: top_k and apply_top_k of 12 tensors at
 beam 1500, a frontier of 3000 candidates (more than one selection tile of 1024), for the lazy verb at chi D = 1024 in c64, where
 the row step's chunk (1020 rows) is below the frontier; 20000 rows of apply_weight_batch whose strided batches exceed 65535 entries
-(the piece boundary inside qil_dev_gemm_batched), and apply_coefficient_batch at chi D = 1024 (its GEMM form).
+(the piece boundary inside qil_dev_gemm_batched), and apply_coefficient_batch at chi D = 1024 (its GEMM form).  The read-out verbs on
+every route of theirs: readout_cases below.
 
 The process that is started never opens the GPU: every stage is a fresh child."""
 import argparse
@@ -97,6 +98,63 @@ def wide_lazy_case(qil):
     a = _mps([2, 4, 8, 16, 32, 32, 32, 16, 8, 4, 2], rng, Z)
     w = _mpo([4, 16, 32, 32, 32, 32, 32, 32, 32, 16, 4], rng, Z)
     return qil.SingleSiteMPO(w), qil.SignalMPS(a, amplitude=1.7)
+
+
+def readout_cases(qil, put):
+    """Every route of the read-out verbs (the route names are asserted through qil.readout_route, which needs no device):
+    coefficient_batch / marginal_batch on CHAIN (bonds <= 8), GEMM_SELECT and GEMM_SORTED (1 x 128 x 1 interior profile of four tensors,
+    12 queries of which the first site's are all 0: a slice of no rows, and slices of <= 48 rows: the skinny GEMM; 200 queries: the
+    wide GEMM), the many-rows arm (1024 queries at bond 16); apply_coefficient_sweep of 3 operators (one after the other) and of 5
+    distinct ones (the lock-step batch), with product bonds 8 (CHAIN) and 128 (one sorted plan for all); a two-pass
+    apply_coefficient_batch (32808 queries at chi D = 1024 in f64: 32768 per pass, 1 GiB of temporaries); mps_block with fixed,
+    summed and free sites, the last free site last and not last, both bit orders; mps_to_vector; coefficient_grid through the dense
+    block and through batches."""
+    for k, dt in enumerate((F, Z)):
+        tag = DT_IDS[3 * k]
+        rng = np.random.default_rng(2500 + k)
+        for name, bonds, nb, routes in (("chain", [2, 4, 8, 8, 4, 2], 40, ("CHAIN", "CHAIN")),
+                                        ("wide", [2, 128, 2], 12, ("GEMM_SORTED", "GEMM_SELECT")),
+                                        ("wide", [2, 128, 2], 200, ("GEMM_SORTED", "GEMM_SELECT")),
+                                        ("many_rows", [2, 4, 16, 16, 4, 2], 1024, ("GEMM_SORTED", "GEMM_SELECT"))):
+            n = len(bonds) + 1
+            dims = [1] + bonds + [1]
+            psi = qil.SignalMPS(_mps(bonds, rng, dt), amplitude=1.7)
+            bits = rng.integers(0, 2, size=(nb, n)).astype(np.uint8)
+            if name == "wide":
+                bits[:, 0] = 0                                                      # no query takes slice 1 of the first site
+            assert (qil.readout_route("plain", nb, dims)[0], qil.readout_route("marginal", nb, dims)[0]) == routes, (name, nb)
+            put(f"coefficient_batch[{name}, nb={nb}]/{tag}", qil.coefficient_batch(psi, bits))
+            summed = bits.copy()
+            summed[rng.random(bits.shape) < 0.3] = 2
+            put(f"marginal_batch[{name}, nb={nb}]/{tag}", qil.marginal_batch(psi, summed))
+        for name, pb, wb in (("chain", [2, 4, 4, 4, 2], [2, 2, 2, 2, 2]), ("sorted", [2, 16, 16, 16, 2], [4, 8, 8, 8, 4])):
+            n = len(pb) + 1
+            psi = qil.SignalMPS(_mps(pb, rng, dt), amplitude=1.7)
+            ops = [qil.SingleSiteMPO(_mpo(wb, rng, (F, Z)[(j + k) % 2])) for j in range(5)]
+            bits = rng.integers(0, 2, size=(24, n)).astype(np.uint8)
+            want = "CHAIN" if name == "chain" else "GEMM_SORTED"
+            assert qil.readout_route("sweep", 24, [1] + pb + [1], [1] + wb + [1])[0] == want
+            for nw in (3, 5):
+                put(f"apply_coefficient_sweep[{name}, nw={nw}]/{tag}", qil.apply_coefficient_sweep(ops[:nw], psi, bits))
+        n = 9
+        data = _mps(CHI[1] + [2], rng, dt)
+        psi = qil.SignalMPS(data, amplitude=1.7)
+        for label, spec in (("free_last", [3, 0, 2, 3, 3, 1, 2, 3, 3]), ("right_fold", [1, 3, 2, 3, 0, 3, 3, 2, 1]),
+                            ("none_free", [0, 1, 2, 2, 1, 0, 2, 1, 0])):
+            for rev in (False, True):
+                put(f"mps_block[{label}, reverse={rev}]/{tag}", qil.mps_block(psi, np.array(spec, dtype=np.uint8), reverse=rev))
+        for rev in (False, True):
+            put(f"mps_to_vector[reverse={rev}]/{tag}", qil.mps_to_vector(psi, reverse=rev))
+        zt = qil.ZTMPS(_mps(CHI[1][:7], rng, dt), amplitude=1.7)                      # 8 tensors: 4 bits per register
+        put(f"coefficient_grid[block]/{tag}", qil.coefficient_grid(zt, np.arange(8), np.arange(16)))
+        perm = rng.permutation(16)
+        put(f"coefficient_grid[batches]/{tag}", qil.coefficient_grid(zt, perm[:11], perm))
+    rng = np.random.default_rng(2600)
+    nb, dims = 32768 + 40, [1, 32, 32, 1]
+    assert qil.readout_route("lazy", nb, dims, dims) == ("LAZY_GEMM", 32768)
+    psi, W = qil.SignalMPS(_mps([32, 32], rng, F), amplitude=1.7), qil.SingleSiteMPO(_mpo([32, 32], rng, F))
+    bits = rng.integers(0, 2, size=(nb, 3)).astype(np.uint8)
+    put("apply_coefficient_batch[gemm form, two passes]/f64-f64", qil.apply_coefficient_batch(W, psi, bits))
 
 
 def run_stage(stage):
@@ -183,6 +241,7 @@ def run_stage(stage):
             psi = qil.SignalMPS(_mps([2, 32, 32, 32, 2], rng, dta), amplitude=1.7)
             W = qil.SingleSiteMPO(_mpo([4, 32, 32, 32, 4], rng, dtw))
             put(f"apply_coefficient_batch[gemm form]/{DT_IDS[k]}", qil.apply_coefficient_batch(W, psi, rng.integers(0, 2, size=(40, 6)).astype(np.uint8)))
+        readout_cases(qil, put)
     return res
 
 
