@@ -348,6 +348,34 @@ QIL_API int qil_mps_sum(const qil_mps* const* terms, int64_t nb, const double* c
 QIL_API int qil_mps_sum_compress(const qil_mps* const* terms, int64_t nb, const double* coeffs, int64_t maxdim, double tol,
                                  int sweeps, int64_t zip_maxdim, qil_mps** out);
 
+/* ------------------------------------------------------------------ operator algebra (no reference counterpart) */
+/* out = sum_j c_j terms[j] for operators, materialised as the direct sum of the chains: the operator twin of qil_mps_sum, with
+ * its promises.  coeffs, repeated and zero-weight terms, dtype (promote(terms), c64 when a coefficient has a non-zero imaginary
+ * part), site ids and paired flag (of terms[0]) and bonds (sum_j D_j) as there; MPOs carry no amplitude, so w_j = c_j.
+ *   layout    an MPO site [Dl, 2, 2, Dr] (column-major) is the MPS-shaped site [Dl, 2, 2 Dr] with column s_out + 2 b: term j
+ *             occupies rows [off_l(j), off_l(j) + Dl(j)) and bond columns [off_r(j), off_r(j) + Dr(j)) -- columns
+ *             [2 off_r(j), 2 off_r(j) + 2 Dr(j)) of the MPS-shaped site.  First tensor: the row of weighted blocks; interior:
+ *             block-diagonal; last: the column stack; n = 1: the single tensor is sum_j c_j W^j.
+ *   exactness as qil_mps_sum: interior and last tensors are copies bit for bit (+0.0 imaginary part for a widened real operand),
+ *             every off-block entry is exactly +0.0, the first tensor carries the one rounding of the multiply.
+ * The kernel is qil_mps_sum's (its site table with doubled column counts; four physical slices on the last and the only site):
+ * one grouped launch, every output element stored exactly once, zeros included, no memset.
+ * Errors, all returned before the context is activated, in qil_mps_sum's order under the name "mpo_sum": QIL_EINVAL_ARG for a
+ * null terms / out / entry, nb < 1, a non-finite coefficient, different contexts or paired flags; QIL_EINVAL_LENGTH;
+ * QIL_EINVAL_SITES (each term against terms[0]).                                                                        */
+QIL_API int qil_mpo_sum(const qil_mpo* const* terms, int64_t nb, const double* coeffs, qil_mpo** out);
+/* The Frobenius overlap <V, W>_F = tr(V^dagger W) = sum_{x,y} conj(V[x,y]) W[x,y].  out: host, one complex double (re, im).
+ * <W, W>_F = |W|_F^2 (qil_mpo_bond_spectra's norm_out squared); <I, W>_F = tr W; <F, F>_F / 2^n = 1 for a unitary F.
+ * V and W: same context, same paired flag (QIL_EINVAL_ARG), same number of sites (QIL_EINVAL_LENGTH), same site ids
+ * (QIL_EINVAL_SITES), after the null check ("mpo_inner: null argument") and before the context is activated; bonds and dtypes
+ * are free, mixed dtypes contract in c64.  V and W are not modified; every temporary is returned to the pool.
+ * Routes, as qil_inner with four physical slices per site: two f64-MFMA GEMMs per site at any bonds (T = E W_i, pl x 4 sr;
+ * E' = V_i^H T, V_i as (4 pl) x pr), or the whole walk in one launch of one workgroup (E and one slice of T in LDS, bonds of
+ * both chains <= 64).  Auto: the one launch while both chains' bonds are <= 12, the measured crossover at n = 24 (past it the
+ * one workgroup loses to the GEMMs in f64, past 20 in c64 too: at D = 64 it is 40x slower; MEASUREMENTS.md section 26).
+ * QIL_MPO_INNER_ROUTE=chain|gemm, read per call, forces a route; chain only where the bonds fit.  Integer-valued operands whose partial sums stay below 2^53 give the exact integer on both routes. */
+QIL_API int qil_mpo_inner(const qil_mpo* V, const qil_mpo* W, double* out);
+
 /* ------------------------------------------------------------------ restriction (no reference counterpart) */
 /* The MPS-valued counterpart of qil_mps_block: spec (host, n_tensors bytes, the vocabulary and layout of qil_mps_block's spec)
  * fixes a site's bit (0 / 1), sums the site (2) or keeps it (3); out is the chain of the KEPT tensors, in order -- one damping

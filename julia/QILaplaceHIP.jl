@@ -21,7 +21,7 @@ export DeviceMPS, DeviceMPO, to_device, to_host, signal_mps_device, marginal, mp
     compress_mpo!, build_dt_mpo_batch, build_qft_mpo_device, build_zt_qft_chain_device, apply_coefficient_sweep, apply!, rsvd_device, svd_device,
     Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm, sample, top_k,
     hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress, restrict, weight_batch, apply_weight_batch, apply_sample, apply_top_k, bond_spectra,
-    signal_mps_cross, ztmps_from_mps, product_batch
+    signal_mps_cross, ztmps_from_mps, product_batch, mpo_linear_combination, mpo_inner
 
 const LIB = get(ENV, "QILHIP_LIB", "libqilhip.so")
 
@@ -363,6 +363,25 @@ function linear_combination_compress(terms::Vector{<:DeviceMPS}, coeffs=nothing;
 end
 Base.:+(phi::DeviceMPS, psi::DeviceMPS) = linear_combination([phi, psi], [1.0, 1.0])
 Base.:-(phi::DeviceMPS, psi::DeviceMPS) = linear_combination([phi, psi], [1.0, -1.0])
+# the same for operators (no reference counterpart).  mpo_linear_combination: sum_j c_j W_j as the direct sum of the chains (bonds
+# add, the weights in the first tensor: MPOs carry no amplitude; the kernel of linear_combination); V + W, V - W on top of it;
+# mpo_inner: the Frobenius overlap tr(V' W), Float64 when both operands are real
+function mpo_linear_combination(terms::Vector{<:DeviceMPO}, coeffs=nothing)
+    isempty(terms) && throw(ArgumentError("mpo_linear_combination: needs at least one term"))
+    hs = Ptr{Cvoid}[t.h for t in terms]
+    c = _coeff_pairs(coeffs, length(terms))
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve terms c check(ccall((:qil_mpo_sum, LIB), Cint, (Ptr{Ptr{Cvoid}}, Int64, Ptr{Cdouble}, Ref{Ptr{Cvoid}}),
+                                     hs, length(terms), c, r))
+    return finalizer(_free!, DeviceMPO(r[], copy(terms[1].sites), terms[1].paired))
+end
+Base.:+(V::DeviceMPO, W::DeviceMPO) = mpo_linear_combination([V, W], [1.0, 1.0])
+Base.:-(V::DeviceMPO, W::DeviceMPO) = mpo_linear_combination([V, W], [1.0, -1.0])
+function mpo_inner(V::DeviceMPO, W::DeviceMPO)
+    v = zeros(Float64, 2)
+    check(ccall((:qil_mpo_inner, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cdouble}), V.h, W.h, v))
+    return _overlap_value(v, V, W)
+end
 # restriction (no reference counterpart; by hand it is psi[i] * onehot(s => b)).  spec: one UInt8 per tensor, 0 / 1 fixes the
 # site's bit, 2 sums the site, 3 keeps it (mps_block's vocabulary); the result is the chain of the kept tensors with the
 # parent's dtype and amplitude, paired when whole (main, copy) pairs are kept

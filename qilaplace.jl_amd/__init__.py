@@ -20,6 +20,8 @@ from .ops import (apply, apply_compress, apply_compress_batch, mpo_compress, com
                   mps_to_vector, norm, inner, apply_norm, distance, apply_distance, bond_spectra, mpo_bond_spectra, entanglement_entropy,
                   truncation_error_bounds, required_maxdim, sample, apply_sample, top_k, apply_top_k, hadamard, hadamard_compress, diagonal_mpo, adjoint, convolve, correlate,
                   power_spectrum, linear_combination, linear_combination_compress, add, sub, scale, exponential_tensors,
+                  mpo_linear_combination, mpo_linear_combination_compress, mpo_add, mpo_sub, mpo_scale, mpo_inner, mpo_norm,
+                  mpo_distance, mpo_trace,
                   exponential_mps, exponential_sum, restrict, zt_row, zt_column, copy_marginal, weight_batch, weight, bit_probabilities,
                   range_weight, weight_quantiles, zt_row_weights, zt_column_weights, apply_weight_batch, apply_weight,
                   apply_bit_probabilities, apply_range_weight, apply_weight_quantiles, apply_zt_row_weights, apply_zt_column_weights, canonicalize, compress, signal_mps, signal_ztmps, signal_mps_batch,
@@ -27,7 +29,8 @@ from .ops import (apply, apply_compress, apply_compress_batch, mpo_compress, com
                   svd_trunc, gemm, gemm_plan, readout_route, gemm_batched, gemm_device_time, qr_positive)
 from .builders import (build_qft_mpo, build_dt_mpo, build_zt_mpo, qft_mpo_tensors,  # noqa: F401
                        dt_mpo_tensors, zt_mpo_tensors, dt_mpo_tensors_many, build_dt_mpo_batch,
-                       build_zt_mpo_batch, zt_qft_chain_tensors, qft_mpo_device, zt_qft_chain_device)
+                       build_zt_mpo_batch, zt_qft_chain_tensors, qft_mpo_device, zt_qft_chain_device,
+                       shift_mpo_tensors, build_shift_mpo, fir_mpo)
 from .interchange import save, load  # noqa: F401
 from .sweep import shard_items, sweep, damping_sweep, gather_results, damping_sample_bits, Comm, unshuffle  # noqa: F401
 
@@ -40,6 +43,8 @@ __all__ = [
     "truncation_error_bounds", "required_maxdim", "sample", "apply_sample", "top_k", "apply_top_k",
     "hadamard", "hadamard_compress", "diagonal_mpo", "adjoint", "convolve", "correlate", "power_spectrum",
     "linear_combination", "linear_combination_compress", "add", "sub", "scale", "exponential_tensors", "exponential_mps",
+    "mpo_linear_combination", "mpo_linear_combination_compress", "mpo_add", "mpo_sub", "mpo_scale", "mpo_inner", "mpo_norm",
+    "mpo_distance", "mpo_trace", "shift_mpo_tensors", "build_shift_mpo", "fir_mpo",
     "exponential_sum", "restrict", "zt_row", "zt_column", "copy_marginal",
     "weight_batch", "weight", "bit_probabilities", "range_weight", "weight_quantiles", "zt_row_weights", "zt_column_weights",
     "apply_weight_batch", "apply_weight", "apply_bit_probabilities", "apply_range_weight", "apply_weight_quantiles", "apply_zt_row_weights",

@@ -147,6 +147,8 @@ PROTOTYPES = {
     "qil_hadamard_compress": [_vp, _int, _vp, _i64, _dbl, _int, _i64, _pvp],
     "qil_mps_sum": [_pvp, _i64, _pdbl, _pvp],
     "qil_mps_sum_compress": [_pvp, _i64, _pdbl, _i64, _dbl, _int, _i64, _pvp],
+    "qil_mpo_sum": [_pvp, _i64, _pdbl, _pvp],
+    "qil_mpo_inner": [_vp, _vp, _pdbl],
     "qil_mps_restrict": [_vp, _pu8, _pvp],
     "qil_weight_batch": [_vp, _i64, _pu8, _pdbl],
     "qil_apply_weight_batch": [_vp, _vp, _i64, _pu8, _pdbl],

@@ -312,6 +312,57 @@ def build_zt_mpo(n_or_psi, wr, cutoff=1e-14, maxdim=1000, ctx=None, device=None)
                          ctx=ctx or (psi.ctx if psi is not None else None))
 
 
+# ------------------------------------------------------------------ shifts and FIR filters (no reference counterpart)
+def shift_mpo_tensors(n, s):
+    """The cyclic shift (S psi)_x = psi_{(x - s) mod 2^n} as an exact real MPO of bond 2, for any integer s: a ripple-carry
+    adder of the constant s.  Site 1 is the MSB; the bond carries the carry, which enters as 0 at the last site, flows to the
+    first and is dropped there.  W[a, s_in, s_out, b] with a = carry out, b = carry in: the one non-zero entry per (x, cin) is
+    W[cout, x, (x + s_i + cin) & 1, cin] = 1, cout = (x + s_i + cin) >> 1, s_i the bit of s at that site."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"shift_mpo_tensors: n must be >= 1, got {n}")
+    s = int(s) % (1 << n)
+    out = []
+    for i in range(n):
+        bit = (s >> (n - 1 - i)) & 1
+        Dl, Dr = (1 if i == 0 else 2), (1 if i == n - 1 else 2)
+        W = np.zeros((Dl, 2, 2, Dr))
+        for cin in range(Dr):
+            for x in range(2):
+                t = x + bit + cin
+                W[(t >> 1) if Dl == 2 else 0, x, t & 1, cin] = 1.0
+        out.append(W)
+    return out
+
+
+def build_shift_mpo(n_or_psi, s, sites=None, ctx=None):
+    """The cyclic shift by s samples as a SingleSiteMPO on the device (`shift_mpo_tensors`), on the sites and context of a
+    SignalMPS when one is given."""
+    psi = n_or_psi if hasattr(n_or_psi, "handle") else None
+    n = _n_of(n_or_psi)
+    if sites is not None and len(sites) != n:
+        raise ValueError(f"build_shift_mpo: Number of sites must be equal to n. Found length(sites)={len(sites)}, n={n}")
+    if psi is not None:
+        sites, ctx = (psi.site_ids if sites is None else sites), ctx or psi.ctx
+    return SingleSiteMPO(shift_mpo_tensors(n, s), sites=sites, ctx=ctx)
+
+
+def fir_mpo(taps, n_or_psi, cutoff=1e-14, maxdim=None, ctx=None):
+    """The FIR filter sum_k taps[k] S^k (S = the cyclic shift by one sample) as a SingleSiteMPO: applied to a state it is the
+    circular convolution y_x = sum_k taps[k] psi_{(x - k) mod 2^n}.  `taps` maps offset -> coefficient (a dict; offsets may be
+    negative) or is a sequence starting at offset 0.  mpo_linear_combination_compress of the shifts (bond 2 each): no QFT and
+    no state for the kernel, unlike `convolve`; a K-tap filter has bond <= 2 K before the compression."""
+    from .ops import mpo_linear_combination_compress, mpo_linear_combination
+    items = sorted(taps.items()) if isinstance(taps, dict) else list(enumerate(taps))
+    if not items:
+        raise ValueError("fir_mpo: needs at least one tap")
+    terms = [build_shift_mpo(n_or_psi, k, ctx=ctx) for k, _ in items]
+    coeffs = [c for _, c in items]
+    if len(terms[0]) == 1:                            # one tensor: nothing to compress
+        return mpo_linear_combination(terms, coeffs)
+    return mpo_linear_combination_compress(terms, coeffs, cutoff=cutoff, maxdim=maxdim)
+
+
 def _dt_worker(args):
     n, w, cutoff, maxdim = args
     return dt_mpo_tensors(n, w, cutoff, maxdim)

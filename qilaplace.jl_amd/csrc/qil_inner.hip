@@ -6,6 +6,7 @@
 //   qil_inner        E[phi, psi]:            E' = A_phi^H (E A_psi)                         (GEMM route, any bonds)
 //                                            the same contraction in ONE launch, E in LDS   (chain route, bonds <= 16)
 //   qil_norm         E[psi, psi]:            the GEMM route of qil_inner with phi = psi
+//   qil_mpo_inner    E[V, W]:                tr(V^H W): both routes of qil_inner with four physical slices per site instead of two
 //   qil_apply_inner  E[phi, a, psi]:         T1 = E A_psi, T2_beta = T1_beta W, E' = A_phi^H T2
 //   qil_apply_norm   E[psi', a', a, psi]:    ket A, ket W, bra conj(W), bra conj(A)
 //
@@ -30,8 +31,8 @@ static int read_scalar(qil_context* ctx, int dt, const void* E, double h[2]) {
 
 // ---- <phi|psi>: chain route -------------------------------------------------------------------------------------
 struct InnerSite {
-    const void* P;   // phi site  (pl, 2, pr)
-    const void* S;   // psi site  (sl, 2, sr)
+    const void* P;   // phi site  (pl, NS, pr): NS = 2 physical slices for states, 4 for operators (s_in + 2 s_out)
+    const void* S;   // psi site  (sl, NS, sr)
     int pl, pr, sl, sr;
 };
 constexpr int kChainMax = 64;        // largest bond of either chain the one-workgroup route holds
@@ -39,10 +40,10 @@ constexpr int kChainThreads = 512;
 constexpr int kChainPer = kChainMax * kChainMax / kChainThreads;   // entries of E' per thread (registers)
 
 // One workgroup walks every site.  E (pl x sl) and one physical slice of T = E A_psi (pl x sr) live in LDS; E' (pr x sr)
-// accumulates in registers over the two slices and replaces E at the end of the site:
+// accumulates in registers over the NS slices and replaces E at the end of the site:
 //   T_s[p, b]   = sum_k E[p, k] A_psi[k, s, b]
 //   E'[q, b]   += sum_p conj(A_phi[p, s, q]) T_s[p, b]
-template <class TP, class TS, class TE>
+template <class TP, class TS, class TE, int NS>
 __global__ __launch_bounds__(kChainThreads) void inner_chain(const InnerSite* __restrict__ sites, int n, double amplitude,
                                                              c64* __restrict__ out) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -58,10 +59,10 @@ __global__ __launch_bounds__(kChainThreads) void inner_chain(const InnerSite* __
 #pragma unroll
         for (int r = 0; r < kChainPer; ++r) acc[r] = TE{};
         const int nT = S.pl * S.sr, nE = S.pr * S.sr;
-        for (int s = 0; s < 2; ++s) {
+        for (int s = 0; s < NS; ++s) {
             for (int t = threadIdx.x; t < nT; t += kChainThreads) {
                 const int p = t % S.pl, b = t / S.pl;
-                const TS* col = A + (long long)S.sl * (s + 2 * b);
+                const TS* col = A + (long long)S.sl * (s + NS * b);
                 TE v{};
                 for (int k = 0; k < S.sl; ++k) v = cmul_add(v, E[p + S.pl * k], col[k]);
                 T[t] = v;
@@ -72,15 +73,16 @@ __global__ __launch_bounds__(kChainThreads) void inner_chain(const InnerSite* __
                 const int t = threadIdx.x + r * kChainThreads;
                 if (t < nE) {
                     const int q = t % S.pr, b = t / S.pr;
-                    const TP* pc = P + (long long)S.pl * (s + 2 * q);
+                    const TP* pc = P + (long long)S.pl * (s + NS * q);
                     const TE* tc = T + S.pl * b;
                     TE v = acc[r];
                     for (int p = 0; p < S.pl; ++p) v = cmul_add(v, conj_t(pc[p]), tc[p]);
                     acc[r] = v;
                 }
             }
-            // slice 0: T is overwritten next; slice 1: every read of E (by the T_1 products) happened before the barrier above
-            if (s == 0) __syncthreads();
+            // before the last slice: T is overwritten next; the last: every read of E (by its T products) happened before the
+            // barrier above
+            if (s + 1 < NS) __syncthreads();
         }
 #pragma unroll
         for (int r = 0; r < kChainPer; ++r) {
@@ -95,12 +97,12 @@ __global__ __launch_bounds__(kChainThreads) void inner_chain(const InnerSite* __
     }
 }
 
-template <class TP, class TS, class TE>
+template <class TP, class TS, class TE, int NS>
 static int launch_inner_chain(qil_context* ctx, const InnerSite* dtab, int n, double amp, c64* dout) {
     static qil_lds_grant grant;
     const size_t lds = 2 * (size_t)kChainMax * kChainMax * sizeof(TE);
-    QIL_HIP(grant.ensure(ctx->device, reinterpret_cast<const void*>(&inner_chain<TP, TS, TE>), lds));
-    hipLaunchKernelGGL((inner_chain<TP, TS, TE>), dim3(1), dim3(kChainThreads), lds, qil_stream(ctx), dtab, n, amp, dout);
+    QIL_HIP(grant.ensure(ctx->device, reinterpret_cast<const void*>(&inner_chain<TP, TS, TE, NS>), lds));
+    hipLaunchKernelGGL((inner_chain<TP, TS, TE, NS>), dim3(1), dim3(kChainThreads), lds, qil_stream(ctx), dtab, n, amp, dout);
     QIL_HIP(hipGetLastError());
     return QIL_OK;
 }
@@ -111,7 +113,17 @@ static int launch_inner_chain(qil_context* ctx, const InnerSite* dtab, int n, do
 // QIL_INNER_ROUTE=chain / gemm forces one (read per call; the chain route only where its bonds fit).
 constexpr long long kChainAutoMax = 16;
 
-static int inner_chain_route(const qil_mps* phi, const qil_mps* psi, double h[2]) {
+// The operator overlap's crossover, measured at n = 24 tensors (f64 / c64, median of 10, tools/_mpo_algebra_time.py): D 8 chain
+// 0.18 / 0.18 ms vs GEMM 0.20 / 0.29 ms, D 12 0.229 / 0.235 vs 0.230 / 0.339, D 16 0.31 / 0.32 vs 0.25 / 0.38, D 20 0.47 / 0.47 vs
+// 0.30 / 0.48, D 24 0.88 / 0.89 vs 0.33 / 0.53, D 32 1.46 / 1.47 vs 0.24 / 0.31, D 64 11.2 / 12.3 vs 0.27 / 0.37.  12 is the largest
+// bond at which the one workgroup is not slower in BOTH dtypes (at 16 it still wins in c64 and loses in f64): below the states'
+// 16, as four slices instead of two double the one-CU arithmetic per site.  QIL_MPO_INNER_ROUTE=chain / gemm forces a route, as
+// QIL_INNER_ROUTE does.
+constexpr long long kMpoChainAutoMax = 12;
+
+// phi, psi: two states (NS = 2) or two operators (NS = 4, amplitude 1)
+template <int NS>
+static int inner_chain_route(const qil_chain* phi, const qil_chain* psi, double h[2]) {
     qil_context* ctx = psi->ctx;
     const int64_t n = psi->n();
     std::vector<InnerSite> tab((size_t)n);
@@ -127,19 +139,21 @@ static int inner_chain_route(const qil_mps* phi, const qil_mps* psi, double h[2]
     const bool pc = phi->dtype == QIL_C64, sc = psi->dtype == QIL_C64;
     const InnerSite* t = dtab.as<InnerSite>();
     c64* o = static_cast<c64*>(dout);
-    if (pc && sc) QIL_TRY((launch_inner_chain<c64, c64, c64>(ctx, t, (int)n, amp, o)));
-    else if (pc) QIL_TRY((launch_inner_chain<c64, double, c64>(ctx, t, (int)n, amp, o)));
-    else if (sc) QIL_TRY((launch_inner_chain<double, c64, c64>(ctx, t, (int)n, amp, o)));
-    else QIL_TRY((launch_inner_chain<double, double, double>(ctx, t, (int)n, amp, o)));
+    if (pc && sc) QIL_TRY((launch_inner_chain<c64, c64, c64, NS>(ctx, t, (int)n, amp, o)));
+    else if (pc) QIL_TRY((launch_inner_chain<c64, double, c64, NS>(ctx, t, (int)n, amp, o)));
+    else if (sc) QIL_TRY((launch_inner_chain<double, c64, c64, NS>(ctx, t, (int)n, amp, o)));
+    else QIL_TRY((launch_inner_chain<double, double, double, NS>(ctx, t, (int)n, amp, o)));
     QIL_TRY(dtab.release());
     return qil_read_back(ctx, h, dout, 16);
 }
 
 // ---- <phi|psi>: GEMM route --------------------------------------------------------------------------------------
-// the contraction alone: the amplitudes are not applied (qil_inner scales, qil_norm takes phi = psi)
-static int inner_gemm_raw(const qil_mps* phi, const qil_mps* psi, double h[2]) {
+// the contraction alone: the amplitudes are not applied (qil_inner scales, qil_norm takes phi = psi); two states, or two
+// operators with ph = 4 physical slices (s_in + 2 s_out, the same order in both operands) in the place of the states' 2
+static int inner_gemm_raw(const qil_chain* phi, const qil_chain* psi, double h[2]) {
     qil_context* ctx = psi->ctx;
     const int64_t n = psi->n();
+    const int64_t ph = psi->phys_rank == 2 ? 4 : 2;
     const int dt = (phi->dtype == QIL_C64 || psi->dtype == QIL_C64) ? QIL_C64 : QIL_F64;
     const size_t e = qil_elem_size(dt);
     long long maxE = 1, maxT = 1, maxP = 1, maxS = 1;
@@ -147,9 +161,9 @@ static int inner_gemm_raw(const qil_mps* phi, const qil_mps* psi, double h[2]) {
         const long long pl = phi->dims[(size_t)i], pr = phi->dims[(size_t)i + 1];
         const long long sl = psi->dims[(size_t)i], sr = psi->dims[(size_t)i + 1];
         maxE = std::max(maxE, std::max(pl * sl, pr * sr));
-        maxT = std::max(maxT, pl * 2 * sr);
-        maxP = std::max(maxP, pl * 2 * pr);
-        maxS = std::max(maxS, sl * 2 * sr);
+        maxT = std::max(maxT, pl * ph * sr);
+        maxP = std::max(maxP, pl * ph * pr);
+        maxS = std::max(maxS, sl * ph * sr);
     }
     qil_scratch tmp(ctx);
     void *E = nullptr, *En = nullptr, *T = nullptr, *Pw = nullptr, *Sw = nullptr;
@@ -165,10 +179,10 @@ static int inner_gemm_raw(const qil_mps* phi, const qil_mps* psi, double h[2]) {
         const void *Ap = nullptr, *As = nullptr;
         QIL_TRY(qil_site_operand(ctx, dt, phi, i, Pw, &Ap));
         QIL_TRY(qil_site_operand(ctx, dt, psi, i, Sw, &As));
-        // T (pl x 2sr) = E (pl x sl) * A_psi (sl x 2sr):  T[p, s, b]
-        QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, pl, 2 * sr, sl, E, pl, As, sl, T, pl));
-        // E' (pr x sr) = A_phi^H ((2pl) x pr)^H * T ((2pl) x sr)
-        QIL_TRY(qil_dev_gemm(ctx, dt, 2, 0, pr, sr, 2 * pl, Ap, 2 * pl, T, 2 * pl, En, pr));
+        // T (pl x ph sr) = E (pl x sl) * A_psi (sl x ph sr):  T[p, s, b]
+        QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, pl, ph * sr, sl, E, pl, As, sl, T, pl));
+        // E' (pr x sr) = A_phi^H ((ph pl) x pr)^H * T ((ph pl) x sr)
+        QIL_TRY(qil_dev_gemm(ctx, dt, 2, 0, pr, sr, ph * pl, Ap, ph * pl, T, ph * pl, En, pr));
         std::swap(E, En);
     }
     return read_scalar(ctx, dt, E, h);
@@ -193,6 +207,16 @@ static long long max_bond(const qil_chain* c) {
 
 }  // namespace
 
+int qil_check_pair(const char* verb, const qil_mpo* V, const qil_mpo* W) {
+    QIL_REQUIRE(V->ctx == W->ctx, QIL_EINVAL_ARG, "%s: MPOs belong to different contexts", verb);
+    QIL_REQUIRE(V->paired == W->paired, QIL_EINVAL_ARG, "%s: cannot mix paired and single-register operands", verb);
+    QIL_REQUIRE(V->n() == W->n(), QIL_EINVAL_LENGTH,
+                "%s: MPOs must have the same number of sites. Found length(V)=%lld, length(W)=%lld", verb, (long long)V->n(),
+                (long long)W->n());
+    QIL_REQUIRE(V->site_ids == W->site_ids, QIL_EINVAL_SITES, "%s: MPOs must have the same site indices.", verb);
+    return QIL_OK;
+}
+
 extern "C" int qil_inner(const qil_mps* phi, const qil_mps* psi, double* out) {
     QIL_REQUIRE(phi && psi && out, QIL_EINVAL_ARG, "inner: null argument");
     QIL_TRY(check_overlap_pair(phi, psi));
@@ -207,13 +231,34 @@ extern "C" int qil_inner(const qil_mps* phi, const qil_mps* psi, double* out) {
     else if (route && !strcmp(route, "gemm")) chain = false;
     double h[2] = {0.0, 0.0};
     if (chain) {
-        QIL_TRY(inner_chain_route(phi, psi, h));   // the amplitudes are applied in the kernel
+        QIL_TRY(inner_chain_route<2>(phi, psi, h));   // the amplitudes are applied in the kernel
     } else {
         QIL_TRY(inner_gemm_raw(phi, psi, h));
         const double amp = phi->amplitude * psi->amplitude;
         h[0] *= amp;
         h[1] *= amp;
     }
+    out[0] = h[0];
+    out[1] = h[1];
+    return QIL_OK;
+}
+
+// <V, W>_F = tr(V^H W): qil_inner's two routes with four physical slices per site; MPOs carry no amplitude
+extern "C" int qil_mpo_inner(const qil_mpo* V, const qil_mpo* W, double* out) {
+    QIL_REQUIRE(V && W && out, QIL_EINVAL_ARG, "mpo_inner: null argument");
+    QIL_TRY(qil_check_pair("mpo_inner", V, W));
+    qil_context* ctx = W->ctx;
+    QIL_TRY(qil_ctx_activate(ctx));
+    qil_call_scope call_scope(ctx);
+    const char* route = getenv("QIL_MPO_INNER_ROUTE");
+    const long long mb = std::max(max_bond(V), max_bond(W));
+    const bool fits = mb <= kChainMax;
+    bool chain = fits && mb <= kMpoChainAutoMax;
+    if (route && !strcmp(route, "chain")) chain = fits;
+    else if (route && !strcmp(route, "gemm")) chain = false;
+    double h[2] = {0.0, 0.0};
+    if (chain) QIL_TRY(inner_chain_route<4>(V, W, h));
+    else QIL_TRY(inner_gemm_raw(V, W, h));
     out[0] = h[0];
     out[1] = h[1];
     return QIL_OK;

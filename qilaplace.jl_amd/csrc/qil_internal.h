@@ -491,6 +491,8 @@ int qil_beam_search(qil_context* ctx, qil_scratch& tmp, qil_beam_rows& rows, int
 // (qil_hadamard.hip) phi against psi under `verb`: context, paired flag (QIL_EINVAL_ARG), length (QIL_EINVAL_LENGTH), site ids
 // (QIL_EINVAL_SITES), in that order; touches no device
 int qil_check_pair(const char* verb, const struct qil_mps* phi, const struct qil_mps* psi);
+// (qil_inner.hip) the same four checks, in the same order and with the same codes, for two operators (qil_mpo_inner, qil_mpo_sum)
+int qil_check_pair(const char* verb, const struct qil_mpo* V, const struct qil_mpo* W);
 // (qil_apply.hip) the site table of the two fused-layout product kernels, site_apply_grouped and site_hadamard_grouped
 // (qil_dev::ProductSite, qil_device_utils.h): result site i = left site i x right site i in row tiles of tile_rows, beta tiles of
 // tb and left-bond chunks of nb.  Returns the workgroup count of the grouped grid.

@@ -1,5 +1,6 @@
 // Linear combinations of MPS for gfx950: qil_mps_sum (the direct sum of the chains), qil_mps_sum_compress (the fused
-// sum-and-truncate, driver in qil_truncate.hip) and the grouped small GEMM the fused route runs its per-term products through.
+// sum-and-truncate, driver in qil_truncate.hip) and the grouped small GEMM the fused route runs its per-term products through;
+// and qil_mpo_sum, the direct sum of operator chains through the same kernel (launch_sum: an MPO site is an MPS-shaped site).
 //
 // out = sum_j c_j terms[j] has the block tensors
 //     first     [ w_1 A^1 | w_2 A^2 | ... ]              1 x 2 x sum(chi)         w_j = c_j amplitude_j
@@ -44,7 +45,7 @@ struct SumSite {
     int row_tiles;         // ceil(R / tile rows)
     int kind;              // kByColumn: first and interior sites; kByRow: the last site; kAccumulate: the only site of n = 1
     int scale;             // multiply by the weight (first site)
-    int pad;
+    int nphys;             // physical slices of a kByRow / kAccumulate site: 2 (MPS), 4 (MPO); kByColumn sites are MPS-shaped
     long long block_begin; // first workgroup of this site in the grouped grid
 };
 
@@ -79,8 +80,8 @@ __global__ __launch_bounds__(kRows) void site_sum_grouped(const SumSite* __restr
     const SumTerm* __restrict__ T = terms + S.term_begin;
     TO* __restrict__ C = static_cast<TO*>(S.C);
     const long long R = S.R;
-    if (S.kind == kAccumulate) {                       // n = 1: the two numbers sum_j w_j A^j[s]
-        if (threadIdx.x < 2) {
+    if (S.kind == kAccumulate) {                       // n = 1: the nphys numbers sum_j w_j A^j[s]
+        if ((int)threadIdx.x < S.nphys) {
             TO acc{};
             for (int j = 0; j < S.nterms; ++j)
                 acc = add_t(acc, wmul(load_term<TA, TO, MIXED>(T[j], threadIdx.x), T[j].wre, T[j].wim));
@@ -108,8 +109,8 @@ __global__ __launch_bounds__(kRows) void site_sum_grouped(const SumSite* __restr
                 const long long r = r_first + k;
                 if (r < R && r >= Tj.row_off && r < (long long)Tj.row_off + Tj.rows) {
                     const long long off = r - Tj.row_off;
-                    store_out<true>(C + r, load_term<TA, TO, MIXED>(Tj, off));
-                    store_out<true>(C + r + R, load_term<TA, TO, MIXED>(Tj, off + Tj.rows));
+                    for (int s = 0; s < S.nphys; ++s)
+                        store_out<true>(C + r + R * s, load_term<TA, TO, MIXED>(Tj, off + (long long)Tj.rows * s));
                 }
             }
         }
@@ -191,9 +192,10 @@ __global__ __launch_bounds__(64) void gemm_grouped_small(const qil_gemm_problem*
     }
 }
 
-// the operand checks of both entries, all of them before the context is activated: arguments, coefficients, then every term
-// against terms[0] in the order of check_pair (context, paired, length, sites)
-int check_terms(const char* verb, const qil_mps* const* terms, int64_t nb, const double* coeffs, qil_mps* const* out) {
+// the operand checks of every entry, all of them before the context is activated: arguments, coefficients, then every term
+// against terms[0] in the order of check_pair (context, paired, length, sites).  H = qil_mps or qil_mpo.
+template <class H>
+int check_terms(const char* verb, const H* const* terms, int64_t nb, const double* coeffs, H* const* out) {
     QIL_REQUIRE(terms && out, QIL_EINVAL_ARG, "%s: null argument", verb);
     QIL_REQUIRE(nb >= 1, QIL_EINVAL_ARG, "%s: needs at least one term, got nb = %lld", verb, (long long)nb);
     for (int64_t j = 0; j < nb; ++j) QIL_REQUIRE(terms[j], QIL_EINVAL_ARG, "%s: null argument", verb);
@@ -205,21 +207,30 @@ int check_terms(const char* verb, const qil_mps* const* terms, int64_t nb, const
 }
 
 // w_j = c_j amplitude_j as (re, im) pairs, and the result dtype: promote(terms), c64 when a coefficient has an imaginary part
-int weights_of(const qil_mps* const* terms, int64_t nb, const double* coeffs, std::vector<double>& w) {
+// (MPOs carry no amplitude: w_j = c_j)
+inline double amplitude_of(const qil_mps* t) { return t->amplitude; }
+inline double amplitude_of(const qil_mpo*) { return 1.0; }
+template <class H>
+int weights_of(const H* const* terms, int64_t nb, const double* coeffs, std::vector<double>& w) {
     int odt = QIL_F64;
     w.resize((size_t)(2 * nb));
     for (int64_t j = 0; j < nb; ++j) {
         const double cre = coeffs ? coeffs[2 * j] : 1.0, cim = coeffs ? coeffs[2 * j + 1] : 0.0;
-        w[(size_t)(2 * j)] = cre * terms[j]->amplitude;
-        w[(size_t)(2 * j + 1)] = cim * terms[j]->amplitude;
+        w[(size_t)(2 * j)] = cre * amplitude_of(terms[j]);
+        w[(size_t)(2 * j + 1)] = cim * amplitude_of(terms[j]);
         if (terms[j]->dtype == QIL_C64 || cim != 0.0) odt = QIL_C64;
     }
     return odt;
 }
 
-int launch_sum(const qil_mps* const* terms, int64_t nb, const std::vector<double>& w, qil_mps* out) {
+// H = qil_mps or qil_mpo.  An MPO site [Dl, 2, 2, Dr] is the MPS-shaped site [Dl, 2, 2 Dr] with column s_out + 2 b, so the first
+// and interior sites of an operator sum are kByColumn sites with the column counts and offsets doubled; the last site and the only
+// site of n = 1 have four physical slices instead of two.
+template <class H>
+int launch_sum(const char* verb, const H* const* terms, int64_t nb, const std::vector<double>& w, H* out) {
     qil_context* ctx = out->ctx;
     const int64_t n = out->n();
+    const int cmul = out->phys_rank == 2 ? 2 : 1;
     const int tile_rows = out->dtype == QIL_F64 ? 2 * kRows : kRows;
     std::vector<SumSite> stab((size_t)n);
     std::vector<SumTerm> ttab((size_t)(n * nb));
@@ -228,12 +239,12 @@ int launch_sum(const qil_mps* const* terms, int64_t nb, const std::vector<double
         SumSite& s = stab[(size_t)i];
         s.C = out->site[(size_t)i];
         s.R = out->dims[(size_t)i];
-        s.ncols = (int)out->dims[(size_t)i + 1];
+        s.ncols = cmul * (int)out->dims[(size_t)i + 1];
         s.nterms = (int)nb;
         s.term_begin = i * nb;
         s.kind = n == 1 ? kAccumulate : i + 1 == n ? kByRow : kByColumn;
         s.scale = i == 0;
-        s.pad = 0;
+        s.nphys = 2 * cmul;
         s.row_tiles = (int)((s.R + tile_rows - 1) / tile_rows);
         s.block_begin = blocks;
         blocks += s.kind == kAccumulate ? 1 : s.kind == kByRow ? s.row_tiles : (long long)s.row_tiles * ((s.ncols + kNC - 1) / kNC);
@@ -242,7 +253,7 @@ int launch_sum(const qil_mps* const* terms, int64_t nb, const std::vector<double
             SumTerm& t = ttab[(size_t)(i * nb + j)];
             t.A = terms[j]->site[(size_t)i];
             t.rows = (int)terms[j]->dims[(size_t)i];
-            t.cols = (int)terms[j]->dims[(size_t)i + 1];
+            t.cols = cmul * (int)terms[j]->dims[(size_t)i + 1];
             t.row_off = i == 0 ? 0 : (int)ro;                 // the edge bonds are shared: every term starts at 0 there
             t.col_off = i + 1 == n ? 0 : (int)co;
             t.wre = w[(size_t)(2 * j)];
@@ -253,7 +264,7 @@ int launch_sum(const qil_mps* const* terms, int64_t nb, const std::vector<double
             co += t.cols;
         }
     }
-    QIL_REQUIRE(blocks < (1LL << 31), QIL_EINVAL_ARG, "mps_sum: grid too large (%lld workgroups)", blocks);
+    QIL_REQUIRE(blocks < (1LL << 31), QIL_EINVAL_ARG, "%s: grid too large (%lld workgroups)", verb, blocks);
     // both tables in one upload, the terms behind the sites (64 terms x 48 sites is past a descriptor slot)
     const size_t sbytes = stab.size() * sizeof(SumSite);
     qil_dev_table dev(ctx);
@@ -313,7 +324,7 @@ extern "C" int qil_mps_sum(const qil_mps* const* terms, int64_t nb, const double
     qil_mps* res = nullptr;
     QIL_TRY(qil_mps_alloc(ctx, n, odt, terms[0]->paired, bonds.data(), terms[0]->site_ids.data(), 1.0, &res));
     qil_result_guard<qil_mps> guard(res);
-    QIL_TRY(launch_sum(terms, nb, w, res));
+    QIL_TRY(launch_sum("mps_sum", terms, nb, w, res));
     *out = guard.release();
     return QIL_OK;
 }
@@ -329,4 +340,23 @@ extern "C" int qil_mps_sum_compress(const qil_mps* const* terms, int64_t nb, con
     std::vector<double> w;
     const int odt = weights_of(terms, nb, coeffs, w);
     return qil_sum_compress_impl(ctx, terms, nb, w.data(), odt, maxdim, tol, sweeps, zip_maxdim, out);
+}
+
+extern "C" int qil_mpo_sum(const qil_mpo* const* terms, int64_t nb, const double* coeffs, qil_mpo** out) {
+    QIL_TRY(check_terms("mpo_sum", terms, nb, coeffs, out));
+    qil_context* ctx = terms[0]->ctx;
+    QIL_TRY(qil_ctx_activate(ctx));
+    qil_call_scope call_scope(ctx);
+    const int64_t n = terms[0]->n();
+    std::vector<double> w;
+    const int odt = weights_of(terms, nb, coeffs, w);
+    std::vector<int64_t> bonds((size_t)(n > 1 ? n - 1 : 0), 0);
+    for (int64_t i = 0; i + 1 < n; ++i)
+        for (int64_t j = 0; j < nb; ++j) bonds[(size_t)i] += terms[j]->dims[(size_t)i + 1];
+    qil_mpo* res = nullptr;
+    QIL_TRY(qil_mpo_alloc(ctx, n, odt, terms[0]->paired, bonds.data(), terms[0]->site_ids.data(), &res));
+    qil_result_guard<qil_mpo> guard(res);
+    QIL_TRY(launch_sum("mpo_sum", terms, nb, w, res));
+    *out = guard.release();
+    return QIL_OK;
 }

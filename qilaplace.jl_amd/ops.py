@@ -11,6 +11,8 @@
                      complex w (laplace_sum, dft_eval, dt_eval, zt_eval, refine_frequencies; no reference counterpart)
   hadamard, adjoint  element-wise products of states and W^dagger; convolve / correlate / power_spectrum on top of them (no
                      reference counterpart)
+  mpo_linear_combination, mpo_inner   sums and Frobenius overlaps of operators, with mpo_norm / mpo_distance / mpo_trace and
+                     `+`, `-`, `c *` on the MPO classes on top of them (no reference counterpart)
   canonicalize       src/mps.jl:787-847, 866-901   (Julia: canonicalize!)
   compress           src/mps.jl:913-999            (Julia: compress!)
   signal_mps         src/signals/SignalConverters.jl:228-233
@@ -1056,16 +1058,18 @@ def power_spectrum(psi, maxdim=None, tol=1e-12, sweeps=1, zip_maxdim=None):
 
 
 # ---------------------------------------------------------------- linear combinations
-def _require_terms(terms, coeffs, what="linear_combination"):
-    """A non-empty sequence of states of one register kind and their coefficients as nb x (re, im) doubles (None: all ones),
-    checked before any native call (context, length and sites are checked natively, as for `hadamard`)."""
-    if isinstance(terms, SignalMPS) or not isinstance(terms, (list, tuple)):
-        raise TypeError(f"{what}: unsupported operand types (expected a list of SignalMPS / ZTMPS)")
+def _require_terms(terms, coeffs, what="linear_combination", cls=SignalMPS, names=("SignalMPS", "ZTMPS")):
+    """A non-empty sequence of states (or, with cls = SingleSiteMPO, operators) of one register kind and their coefficients as
+    nb x (re, im) doubles (None: all ones), checked before any native call (context, length and sites are checked natively, as
+    for `hadamard`)."""
+    single, paired = names
+    if isinstance(terms, cls) or not isinstance(terms, (list, tuple)):
+        raise TypeError(f"{what}: unsupported operand types (expected a list of {single} / {paired})")
     terms = list(terms)
-    if not terms or not all(isinstance(t, SignalMPS) for t in terms):
-        raise TypeError(f"{what}: unsupported operand types (expected a non-empty list of SignalMPS / ZTMPS)")
+    if not terms or not all(isinstance(t, cls) for t in terms):
+        raise TypeError(f"{what}: unsupported operand types (expected a non-empty list of {single} / {paired})")
     if any(t._paired() != terms[0]._paired() for t in terms):
-        raise TypeError(f"{what}: unsupported operand types (ZTMPS combines only with ZTMPS)")
+        raise TypeError(f"{what}: unsupported operand types ({paired} combines only with {paired})")
     if coeffs is None:
         return terms, None
     try:
@@ -1124,6 +1128,121 @@ def scale(psi, c):
         out.amplitude = psi.amplitude * float(np.real(c))
         return out
     return linear_combination([psi], [c])
+
+
+# ---------------------------------------------------------------- operator algebra
+def _require_mpo(W, what):
+    if not isinstance(W, SingleSiteMPO):
+        raise TypeError(f"{what}: unsupported operand types")
+
+
+def _require_mpo_terms(terms, coeffs):
+    """`_require_terms` for operators."""
+    return _require_terms(terms, coeffs, "mpo_linear_combination", SingleSiteMPO, ("SingleSiteMPO", "PairedSiteMPO"))
+
+
+def _is_number(c):
+    return not isinstance(c, (bool, np.bool_)) and isinstance(c, (int, float, complex, np.number))
+
+
+def mpo_linear_combination(terms, coeffs=None):
+    """sum_j coeffs[j] * terms[j] as a new operator of terms[0]'s class, materialised as the direct sum of the chains: every
+    bond is the sum of the terms' bonds, nothing is truncated, the weights sit in the first tensor (MPOs carry no amplitude).
+    `coeffs` may be complex (the result is then complex); None means all ones.  Terms may repeat.  One grouped launch of the
+    kernel of `linear_combination` (include/qilaplace_hip.h, qil_mpo_sum)."""
+    terms, c = _require_mpo_terms(terms, coeffs)
+    _, arr = _handle_array(terms)
+    h = C.c_void_p()
+    L.check(L.lib.qil_mpo_sum(arr, len(terms), None if c is None else c.ctypes.data_as(L._pdbl), C.byref(h)))
+    return type(terms[0])(ctx=terms[0].ctx, _handle=h)
+
+
+def mpo_linear_combination_compress(terms, coeffs=None, direction="down", cutoff=1e-14, maxdim=None):
+    """mpo_compress(mpo_linear_combination(terms, coeffs), direction, cutoff, maxdim).  A plain composition of the two: the
+    direct-sum tensors are formed, then compressed (there is no fused route for operators)."""
+    return mpo_compress(mpo_linear_combination(terms, coeffs), direction=direction, cutoff=cutoff, maxdim=maxdim)
+
+
+def mpo_add(V, W):
+    """V + W (mpo_linear_combination of the two with unit coefficients)."""
+    return mpo_linear_combination([V, W], [1.0, 1.0])
+
+
+def mpo_sub(V, W):
+    """V - W."""
+    return mpo_linear_combination([V, W], [1.0, -1.0])
+
+
+def mpo_scale(W, c):
+    """c * W as a new operator: the one-term sum (MPOs have no amplitude to scale and no clone entry)."""
+    _require_mpo_terms([W], None)
+    if not _is_number(c):
+        raise TypeError("mpo_linear_combination: unsupported operand types (the factor must be a number)")
+    return mpo_linear_combination([W], [c])
+
+
+def _mpo_add(self, other):
+    if not isinstance(other, SingleSiteMPO) or self._paired() != other._paired():
+        return NotImplemented
+    return mpo_add(self, other)
+
+
+def _mpo_sub(self, other):
+    if not isinstance(other, SingleSiteMPO) or self._paired() != other._paired():
+        return NotImplemented
+    return mpo_sub(self, other)
+
+
+def _mpo_neg(self):
+    return mpo_scale(self, -1.0)
+
+
+def _mpo_rmul(self, c):
+    return mpo_scale(self, c) if _is_number(c) else NotImplemented
+
+
+# V + W, V - W, -W, c * W (numbers only, from the left); W * x stays the application (W * psi, W1 * W2)
+SingleSiteMPO.__add__ = _mpo_add
+SingleSiteMPO.__sub__ = _mpo_sub
+SingleSiteMPO.__neg__ = _mpo_neg
+SingleSiteMPO.__rmul__ = _mpo_rmul
+
+
+def _require_mpo_pair(V, W):
+    """Two operators, checked before any native call (register kind, context, length and sites are checked natively, as for
+    `inner`)."""
+    _require_mpo(V, "mpo_inner")
+    _require_mpo(W, "mpo_inner")
+
+
+def mpo_inner(V, W):
+    """The Frobenius overlap <V, W>_F = tr(V^dagger W) = sum_{x,y} conj(V[x,y]) W[x,y] of two operators of one class, without
+    a dense operator (include/qilaplace_hip.h, qil_mpo_inner).  float when both operands are real, complex otherwise."""
+    _require_mpo_pair(V, W)
+    v = (C.c_double * 2)()
+    L.check(L.lib.qil_mpo_inner(V.handle, W.handle, v))
+    return _scalar(v, V, W)
+
+
+def mpo_norm(W) -> float:
+    """The Frobenius norm ||W||_F = sqrt(Re <W, W>_F)."""
+    return float(np.sqrt(max(0.0, np.real(mpo_inner(W, W)))))
+
+
+def mpo_distance(V, W) -> float:
+    """||V - W||_F as sqrt(max(0, ||V||^2 + ||W||^2 - 2 Re<V, W>)), without the difference.
+
+    The same floor as `distance`: the squared distance carries an absolute error of a few eps * (||V||^2 + ||W||^2), so
+    relative distances below about 1e-7 are not resolved (they come out as that floor or as 0)."""
+    _require_mpo_pair(V, W)
+    return _distance(float(np.real(mpo_inner(V, V))), float(np.real(mpo_inner(W, W))), mpo_inner(V, W))
+
+
+def mpo_trace(W):
+    """tr W = <I, W>_F, with the identity of W's class on W's sites and context."""
+    _require_mpo(W, "mpo_trace")
+    eye = type(W).identity(len(W), sites=W.site_ids, ctx=W.ctx)
+    return mpo_inner(eye, W)
 
 
 def _dyadic_powers(z, n):
