@@ -324,6 +324,22 @@ __device__ __forceinline__ double rcp_refined(double x) {
 // sweep on a handful of 1e-15-level rotations and another one on finding nothing to do.  `big` reports whether this
 // pair was above that level.
 constexpr double kQuadraticOff = 1e-9;
+// ... but the argument needs SMALL angles.  A pair of (nearly) equal norms turns by up to 45 degrees however small its overlap
+// is, and such a turn hands the overlaps that its two columns still have with every other column on to pairs the sweep has
+// already visited -- at first order.  A sweep that meets only overlaps below kQuadraticOff can then leave 1e-11 behind: an operand
+// with a KEPT cluster of equal singular values (75 values at 1e-3 below a flat spectrum, 300 columns) came out with
+// max |Q^H Q - 1| = 2.5e-11 between cluster columns and the others.  So a pair that is ROTATED by more than kSmallAngle keeps
+// the iteration going like one above kQuadraticOff; the last sweep then turns by less than that, and what it leaves is below
+// kSmallAngle * kQuadraticOff.  (A cluster stops turning once its pairs are below tol, which they reach like any other pair.)
+// ONLY the rounds of the one-factor SVD of the gauge sweeps honour kSmallAngle so far (svd_left_mid of qil_linalg.hip: the
+// vector rounds jacobi_block_round_nov and the Gram rounds gram_block_round, where the defect was measured).  The general SVD
+// (jacobi_pair, jacobi_fused, the block Jacobi), jacobi_sweeps below, the spectra and the builders still stop on kQuadraticOff
+// alone: `big` of jacobi_rotation / rotation_fast does not know the angle.
+constexpr double kSmallAngle = 1e-4;
+__device__ __forceinline__ bool turns_far(double al, double be, double g2) {
+    const double d = be - al;
+    return 4.0 * g2 > (kSmallAngle * kSmallAngle) * (d * d);             // |tan 2 theta| = 2 |g| / |be - al|
+}
 // Rank-deficient operands (every product bond before its truncation) leave columns that are pure rounding residue:
 // |a|^2 below 1e-30 |A|_F^2.  Such a column has no direction to converge to -- each rotation of the genuine columns
 // re-randomises it -- and keeps full sweeps going (builder slices: 14.7 -> 4.5 sweeps when it is left alone).  When the

@@ -2749,7 +2749,7 @@ __device__ __forceinline__ void jacobi_block_round_nov_body(const uint3 blockIdx
             double c, sr, si, sn, gabs;
             bool big;
             if (!(al < ng || be < ng) && rotation_fast<CX>(al, be, gr, gi, tol, c, sr, si, sn, gabs, big)) {
-                flags |= big ? 3 : 1;
+                flags |= (big || turns_far(al, be, CX ? fma(gr, gr, gi * gi) : gr * gr)) ? 3 : 1;
 #pragma unroll
                 for (int u = 0; u < KM; ++u) {
                     rotate_pair_sg(xs[u], ys[u], c, sr, si);
@@ -3058,7 +3058,7 @@ __device__ __forceinline__ void gram_block_round_body(const gram_round_args<T>& 
             double g2 = G0[r * LDG + c] * G0[r * LDG + c];
             if constexpr (CX) g2 = fma(G0[W * LDG + r * LDG + c], G0[W * LDG + r * LDG + c], g2);
             const double ab = al * be;
-            if (g2 > a.tol * a.tol * ab && g2 != 0.0) fl |= 1;
+            if (g2 > a.tol * a.tol * ab && g2 != 0.0) fl |= turns_far(al, be, g2) ? 3 : 1;
             if (g2 > kQuadraticOff * kQuadraticOff * ab) fl |= 2;
         }
         if (fl) atomicOr(sflag, fl);

@@ -95,6 +95,7 @@ static int svd_trunc_lowrank(qil_context* ctx, int dtype, int64_t m, int64_t n, 
     *done = 0;
     const int64_t r0 = std::min(m, n);
     if (r0 < 384 || !(cutoff > 0)) return QIL_OK;
+    const bool dbg = getenv("QIL_SVD_DEBUG") != nullptr;
     const size_t e = qil_elem_size(dtype);
     const int cj = dtype == QIL_C64 ? 2 : 1;
     const int nre = dtype == QIL_C64 ? 2 : 1;
@@ -126,7 +127,7 @@ static int svd_trunc_lowrank(qil_context* ctx, int dtype, int64_t m, int64_t n, 
             rho += hp[2 * b];
             tot += hp[2 * b + 1];
         }
-        if (getenv("QIL_SVD_DEBUG")) fprintf(stderr, "[svd-lowrank] %lld x %lld, k = %lld: residual^2 / total = %.3e (cutoff %.1e)\n",
+        if (dbg) fprintf(stderr, "[svd-lowrank] %lld x %lld, k = %lld: residual^2 / total = %.3e (cutoff %.1e)\n",
                                              (long long)m, (long long)n, (long long)k, tot > 0 ? rho / tot : 0.0, cutoff);
         if (!(rho <= 1e-8 * cutoff * tot)) {
             // a sketch twice as wide cannot help an operand that is nowhere near low rank (flat spectra leave > 50 % of
@@ -134,6 +135,7 @@ static int svd_trunc_lowrank(qil_context* ctx, int dtype, int64_t m, int64_t n, 
             if (rho > 1e-4 * tot) break;
             continue;
         }
+        if (dbg) fprintf(stderr, "[svd-lowrank] %lld x %lld, k = %lld: sketch accepted\n", (long long)m, (long long)n, (long long)k);
         int64_t r = 0;
         void *Ub = nullptr, *Vh = nullptr;
         std::vector<double> S;
