@@ -485,6 +485,32 @@ struct sumsq_partial_k {
         sumsq_partial_body(b, g, a...);
     }
 };
+// The rescue pass of the norm (signal_mps_impl): per-workgroup partial sums of (s x)^2 with s a power of two, so that s x is
+// exact, or -- sq == 0 -- per-workgroup partial maxima of |x|.  Same grid and reduction tree as sumsq_partial.
+__device__ __forceinline__ void sumsq_rescue_body(const uint3 blockIdx, const uint3 gridDim, const double* __restrict__ x, long long n,
+                                                    double s, int sq, double* __restrict__ part) {
+    __shared__ double red[4];
+    double v = 0;
+    for (long long t = blockIdx.x * 256LL + threadIdx.x; t < n; t += (long long)gridDim.x * 256) {
+        const double a = x[t] * s;
+        v = sq ? v + a * a : fmax(v, fabs(a));
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const double o = __shfl_xor(v, m, 64);
+        v = sq ? v + o : fmax(v, o);
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = sq ? (red[0] + red[1]) + (red[2] + red[3]) : fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+}
+struct sumsq_rescue_k {
+    static constexpr int NT = 256, MINW = 1;
+    template <class... QA>
+    static __device__ __forceinline__ void run(const uint3 b, const uint3 g, QA... a) {
+        sumsq_rescue_body(b, g, a...);
+    }
+};
 __device__ __forceinline__ void scale_inplace_body(const uint3 blockIdx, const uint3 gridDim, double* __restrict__ x, long long n, double s) {
     for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < n;
          t += (long long)gridDim.x * blockDim.x)
@@ -519,13 +545,31 @@ struct scale_copy_k {
 // Steps follow src/linalg/rsvd.jl:72-114; the small SVD is taken of B^T = Z conj(Q) (n x l), whose
 // short side is l, so the Jacobi rotations act on l columns and (S V^h)^T falls out of the rotated
 // work matrix directly.
+//
+// The route line of QIL_RSVD_DEBUG: one per call of rsvd_rowmajor, whatever the size, and no stream synchronisation (nothing
+// it prints comes from the device).  `l` is the sketch width after the deflation, negative for the exact branch:
+//   [rsvd] route m=<m> n=<n> l0=<l0> exact
+//   [rsvd] route m=<m> n=<n> l0=<l0> sketch l=<l>
+// One write per line, so the lines of concurrent sub-trees do not interleave (tests/encode_cases.py parses them).
+static void rsvd_route_line(int64_t m, int64_t n, int64_t l0, int64_t l) {
+    char line[160];
+    if (l < 0)
+        snprintf(line, sizeof line, "[rsvd] route m=%lld n=%lld l0=%lld exact\n", (long long)m, (long long)n, (long long)l0);
+    else
+        snprintf(line, sizeof line, "[rsvd] route m=%lld n=%lld l0=%lld sketch l=%lld\n", (long long)m, (long long)n, (long long)l0,
+                 (long long)l);
+    fputs(line, stderr);
+}
+
 int rsvd_rowmajor(qil_context* ctx, int dt, int64_t m, int64_t n, const void* Z, int64_t k, int64_t p, int q,
                   uint64_t seed, double cutoff, int64_t maxdim, int64_t mindim, int64_t* rank, void** left,
                   void** right, std::vector<double>* S_out) {
     QIL_REQUIRE(m >= 1 && n >= 1, QIL_EEMPTY, "In `rsvd`, left or right index set is empty.");
     const size_t e = qil_elem_size(dt);
     const int64_t l0 = std::min(std::min(k + p, m), n);  // rsvd.jl:72
+    const bool route = getenv("QIL_RSVD_DEBUG") != nullptr;
     if (l0 == std::min(m, n)) {
+        if (route) rsvd_route_line(m, n, l0, -1);
         // The sketch is as wide as the short side: Q spans the whole range of M and the procedure returns the exact
         // truncated SVD (up to rounding) after 2 + 2q products and 1 + 2q QRs of matrices no larger than M itself.
         // Take the SVD directly: Z = M^T = Uz Sz Vz^h  =>  U_M^T = Vz^h,  (S V_M^h)^T = Uz Sz.  Every deep split of
@@ -543,7 +587,7 @@ int rsvd_rowmajor(qil_context* ctx, int dt, int64_t m, int64_t n, const void* Z,
         return QIL_OK;
     }
     void *Om = nullptr, *Y = nullptr, *Zq = nullptr, *Bt = nullptr;
-    const bool dbg = getenv("QIL_RSVD_DEBUG") != nullptr && m * n >= ((1LL << 24));
+    const bool dbg = route && m * n >= ((1LL << 24));                              // the timing laps synchronise: large operands only
     auto t_prev = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
         if (!dbg) return;
@@ -604,6 +648,7 @@ int rsvd_rowmajor(qil_context* ctx, int dt, int64_t m, int64_t n, const void* Z,
         }
         qil_ctx_free(ctx, Rq);
     }
+    if (route) rsvd_route_line(m, n, l0, l);
     if (q > 0) QIL_TRY(qil_ctx_alloc(ctx, (size_t)(n * l) * e, &Zq));
     for (int it = 0; it < q; ++it) {                                                    // :86-95
         QIL_TRY(qil_dev_gemm(ctx, dt, 3, 0, n, l, m, Z, n, Y, m, Zq, n));               // M^H Q = conj(Z) Q
@@ -831,11 +876,33 @@ int signal_mps_impl(qil_context* ctx, const void* x, int64_t len, int dtype, con
     QIL_TRY((qil_klaunch<sumsq_partial_k>(ctx, dim3(kPartBlocks), dim3(256), 0, (const double*)src, (long long)(N * ncomp), (double*)part)));
     std::vector<double> ph(kPartBlocks);
     QIL_TRY(qil_read_back(ctx, ph.data(), part, kPartBlocks * sizeof(double)));   // also completes the upload of caller memory `x`
-    qil_ctx_free(ctx, part);
     double ss = 0;
     for (double v : ph) ss += v;                  // fixed order: deterministic
-    const double amp = std::sqrt(ss);
-    if (!(amp > 0 && std::isfinite(amp))) {
+    double amp = std::sqrt(ss);
+    if (ss == 0.0 || std::isinf(ss)) {
+        // every x^2 underflowed to zero (samples below about 1e-162) or the sum overflowed (samples from about 1e+154), or the
+        // signal is zero or holds an Inf: the reference's norm(x) (SignalConverters.jl:36) scales, so finite samples must
+        // encode.  Two more passes, on this path only: max |x|, then the same sum over s x with s the power of two that brings
+        // the maximum into [1/2, 1) (s x is exact).  A NaN makes ss NaN and never comes here; every other signal takes the
+        // plain sum above, bit for bit as before -- also samples of 1e-155 ... 1e-162, whose squares are subnormal: their sum is
+        // non-zero with few bits, so the amplitude is coarse and the state not normalised, while amplitude * state stays right.
+        QIL_TRY((qil_klaunch<sumsq_rescue_k>(ctx, dim3(kPartBlocks), dim3(256), 0, (const double*)src, (long long)(N * ncomp), 1.0, 0, (double*)part)));
+        QIL_TRY(qil_read_back(ctx, ph.data(), part, kPartBlocks * sizeof(double)));
+        double mx = 0;
+        for (double v : ph) mx = std::max(mx, v);
+        if (mx > 0 && std::isfinite(mx)) {
+            int ex = 0;
+            (void)std::frexp(mx, &ex);
+            const int sh = std::min(-ex, 1023);
+            QIL_TRY((qil_klaunch<sumsq_rescue_k>(ctx, dim3(kPartBlocks), dim3(256), 0, (const double*)src, (long long)(N * ncomp), std::ldexp(1.0, sh), 1, (double*)part)));
+            QIL_TRY(qil_read_back(ctx, ph.data(), part, kPartBlocks * sizeof(double)));
+            ss = 0;
+            for (double v : ph) ss += v;
+            amp = std::ldexp(std::sqrt(ss), -sh);
+        }
+    }
+    qil_ctx_free(ctx, part);
+    if (!(amp > 0 && std::isfinite(amp) && std::isfinite(1.0 / amp))) {
         qil_ctx_free(ctx, X);
         return qil_fail(QIL_EINVAL_ARG, "signal_mps: signal has zero or non-finite norm");
     }
