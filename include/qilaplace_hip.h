@@ -682,7 +682,9 @@ QIL_API int qil_svd_trunc(qil_context* ctx, const void* A, int64_t m, int64_t n,
  * route that pads every MPO of the batch to a common bond profile with zero components (same operators).
  * The persistent builders (this one, qil_build_qft_mpo, qil_build_zt_qft_chain, qil_build_zt_mpo_batch) run their truncation rule
  * at max(cutoff, 1e-28): directions below 1e-28 of a bond's weight are rounding residue of exactly rank-deficient product bonds
- * (the reference's LAPACK SVD would keep them at cutoff = 0 as noise-level singular values; the operator is the same to rounding). */
+ * (the reference's LAPACK SVD would keep them at cutoff = 0 as noise-level singular values; the operator is the same to rounding).
+ * QIL_EINVAL_ARG, naming the index, for a damping value that is NaN or infinite or whose largest gate entry exp(-w 2^(n-2))
+ * (exp(-w) for n <= 2) overflows -- a negative w at large n; checked on the host before anything is allocated or launched. */
 QIL_API int qil_build_dt_mpo_batch(qil_context* ctx, int64_t n, int64_t nb, const double* wrs, double cutoff,
                            int64_t maxdim, const int64_t* site_ids, qil_mpo** out);
 
@@ -707,7 +709,7 @@ QIL_API int qil_build_zt_qft_chain(qil_context* ctx, int64_t n, double cutoff, i
  * (:104; the nb compressions run as one batch).  out[nb] receives PairedSiteMPO handles (complex, 2n tensors) with the bond
  * dimensions of a single build_zt_mpo call each.  site_ids: the 2n labels main_1, copy_1, ... of the operand (build_zt_mpo(
  * psi::ZTMPS, wr), :107-111); NULL => 1..2n.  maxdim <= 0: no cap.  n == 1 returns the bare product (:66-70).
- * QIL_EINVAL_ARG for n < 1 (the reference's ArgumentError, :49).                                                        */
+ * QIL_EINVAL_ARG for n < 1 (the reference's ArgumentError, :49) and for the damping values qil_build_dt_mpo_batch refuses.  */
 QIL_API int qil_build_zt_mpo_batch(qil_context* ctx, int64_t n, int64_t nb, const double* wrs, double cutoff,
                            int64_t maxdim, const int64_t* site_ids, qil_mpo** out);
 

@@ -719,11 +719,27 @@ void dt_copy_site(int n, int k, double w, int site, int* dl, int* dr, std::vecto
 int qil_build_dt_persistent(qil_context* ctx, int64_t n, int64_t nb, const double* wrs, double cutoff, int64_t maxdim,
                             const int64_t* site_ids, qil_mpo** out, int* fallback);
 
+// Every damping value must give finite gate entries: the largest is exp(-w 2^(n-2)) of the copy blocks (exp(-w) for n <= 2,
+// dt_gates.jl:133-229), which overflows for a negative w at large n.  NaN, +-inf and such values are refused here, on the
+// host, before anything is allocated or launched (the host chain fails in LAPACK on the same inputs).
+int qil_check_damping_values(const char* who, int64_t n, int64_t nb, const double* wrs) {
+    const double scale = std::ldexp(1.0, (int)std::min<int64_t>(std::max<int64_t>(n - 2, 0), 1023));
+    for (int64_t b = 0; b < nb; ++b) {
+        const double w = wrs[b];
+        QIL_REQUIRE(std::isfinite(w), QIL_EINVAL_ARG, "%s: damping value %lld is not finite (%g)", who, (long long)b, w);
+        QIL_REQUIRE(std::isfinite(std::exp(-w * scale)), QIL_EINVAL_ARG,
+                    "%s: damping value %lld (%g) overflows the gate exp(-w 2^%lld) at n=%lld", who, (long long)b, w,
+                    (long long)std::max<int64_t>(n - 2, 0), (long long)n);
+    }
+    return QIL_OK;
+}
+
 extern "C" int qil_build_dt_mpo_batch(qil_context* ctx, int64_t n, int64_t nb, const double* wrs, double cutoff,
                                       int64_t maxdim, const int64_t* site_ids, qil_mpo** out) {
     QIL_REQUIRE(ctx && wrs && out, QIL_EINVAL_ARG, "build_dt_mpo: null argument");
     QIL_REQUIRE(n >= 1, QIL_EINVAL_ARG, "build_dt_mpo: n must be >= 1. Found n=%lld", (long long)n);
     QIL_REQUIRE(nb >= 1 && nb <= 4096, QIL_EINVAL_ARG, "build_dt_mpo: batch of %lld damping values", (long long)nb);
+    QIL_TRY(qil_check_damping_values("build_dt_mpo", n, nb, wrs));
     QIL_TRY(qil_ctx_activate(ctx));
     qil_call_scope call_scope(ctx);
     // default route: the persistent kernel (one launch, one workgroup per damping value, true bond dimensions per
@@ -785,19 +801,30 @@ extern "C" int qil_build_dt_mpo_batch(qil_context* ctx, int64_t n, int64_t nb, c
     const int L = (int)M.size();
     std::vector<int64_t> bonds((size_t)std::max(L - 1, 1));
     for (int i = 0; i + 1 < L; ++i) bonds[(size_t)i] = M[(size_t)i].dr;
+    // a failure part-way takes back the handles already stored in out[]: their blocks are owned, so nothing else would
+    int made = 0;
+    auto fail_out = [&](int code) {
+        for (int b = 0; b < made; ++b) {
+            qil_mpo_destroy(out[b]);
+            out[b] = nullptr;
+        }
+        return fail(code);
+    };
     for (int b = 0; b < B; ++b) {
         qil_mpo* W = nullptr;
         st = qil_mpo_alloc(ctx, L, QIL_F64, 1, bonds.data(), site_ids, &W);
-        if (st != QIL_OK) return fail(st);
+        if (st != QIL_OK) return fail_out(st);
+        out[b] = W;
+        ++made;
         for (int i = 0; i < L; ++i) {
             const size_t bytes = (size_t)M[(size_t)i].elems() * sizeof(double);
             hipError_t e = hipMemcpyAsync(W->site[(size_t)i], static_cast<char*>(M[(size_t)i].p) + (size_t)b * bytes, bytes,
                                           hipMemcpyDeviceToDevice, qil_stream(ctx));
-            if (e != hipSuccess) return fail(qil_fail(QIL_EHIP, "copy failed: %s", hipGetErrorString(e)));
+            if (e != hipSuccess) return fail_out(qil_fail(QIL_EHIP, "copy failed: %s", hipGetErrorString(e)));
         }
-        out[b] = W;
     }
-    QIL_HIP(qil_stream_sync(ctx));
+    hipError_t e = qil_stream_sync(ctx);
+    if (e != hipSuccess) return fail_out(qil_fail(QIL_EHIP, "build_dt_mpo: copy-out failed: %s", hipGetErrorString(e)));
     for (auto& s : M) bfree(ctx, s);
     return QIL_OK;
 }

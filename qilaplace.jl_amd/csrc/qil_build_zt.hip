@@ -20,6 +20,7 @@ int qil_build_chain_persistent(qil_context* ctx, int kind, int64_t n, double cut
                                qil_mpo** out, int* fallback);
 int qil_apply_mpo_mpo_shared(const qil_mpo* W1, const qil_mpo* W2, qil_mpo** out);
 int qil_build_zt_qft_chain_generic(qil_context* ctx, int64_t n, double cutoff, int64_t maxdim, const int64_t* site_ids, qil_mpo** out);
+int qil_check_damping_values(const char* who, int64_t n, int64_t nb, const double* wrs);
 
 extern "C" int qil_build_zt_mpo_batch(qil_context* ctx, int64_t n, int64_t nb, const double* wrs, double cutoff,
                                       int64_t maxdim, const int64_t* site_ids, qil_mpo** out) {
@@ -27,6 +28,7 @@ extern "C" int qil_build_zt_mpo_batch(qil_context* ctx, int64_t n, int64_t nb, c
     QIL_REQUIRE(n >= 1, QIL_EINVAL_ARG, "build_zt_mpo: n must be >= 1. Found n=%lld", (long long)n);
     QIL_REQUIRE(nb >= 1 && nb <= 4096, QIL_EINVAL_ARG, "build_zt_mpo: batch of %lld damping values", (long long)nb);
     QIL_REQUIRE(cutoff >= 0, QIL_EINVAL_ARG, "build_zt_mpo: cutoff must be >= 0");
+    QIL_TRY(qil_check_damping_values("build_zt_mpo", n, nb, wrs));
     QIL_TRY(qil_ctx_activate(ctx));
     qil_call_scope call_scope(ctx);
     std::vector<qil_mpo*> dts((size_t)nb, nullptr), prods((size_t)nb, nullptr);
