@@ -25,23 +25,8 @@ struct BSite {
     int dl = 1, dr = 1;
     long long elems() const { return (long long)dl * 4 * dr; }
 };
-struct BChain {
-    qil_context* ctx = nullptr;
-    int B = 0;
-    std::vector<BSite> s;
-};
 
 inline unsigned nblk(long long total) { return (unsigned)std::min<long long>((total + 255) / 256, 4096); }
-
-int balloc(qil_context* ctx, int B, int dl, int dr, BSite* out) {
-    out->dl = dl;
-    out->dr = dr;
-    return qil_ctx_alloc(ctx, (size_t)B * out->elems() * sizeof(double), &out->p);
-}
-void bfree(qil_context* ctx, BSite& s) {
-    if (s.p) qil_ctx_free(ctx, s.p);
-    s.p = nullptr;
-}
 
 // ---------------------------------------------------------------- kernels (one grid.y slice per sigma)
 // core[r, i, o, b1, b2] = sum_{a,c,m} T[r,a,c] M[a,i,m,b1] Bk[c,m,o,b2]      (dt_transformer.jl:54-61)
@@ -318,8 +303,11 @@ __global__ void bgather(const double* __restrict__ src, int rows, int scols, con
 }
 
 // ---------------------------------------------------------------- host orchestration
+// Every pool block of a build -- the batched sites, the gate blocks, the temporaries of a step -- is listed in `tmp`, the entry
+// point's scratch, from its allocation until release() returns it early; what a failing step leaves goes back with the scratch.
 struct Builder {
     qil_context* ctx;
+    qil_scratch& tmp;
     int B;
     double cutoff;
     long long maxdim;
@@ -346,8 +334,12 @@ struct Builder {
         return QIL_OK;
     }
 
+    void release(BSite& s) {
+        tmp.free(s.p);
+        s.p = nullptr;
+    }
     int upload(const std::vector<double>& h, void** dev) {
-        QIL_TRY(qil_ctx_alloc(ctx, h.size() * sizeof(double), dev));
+        QIL_TRY(tmp.alloc(h.size() * sizeof(double), dev));
         QIL_HIP(hipMemcpyAsync(*dev, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, qil_stream(ctx)));
         QIL_HIP(qil_stream_sync(ctx));
         return QIL_OK;
@@ -372,17 +364,17 @@ struct Builder {
         return QIL_OK;
     }
 
-    int qr_tall_or_identity(double* Mat, int m, int n, BSite* Qsite_out_p, void** R_out, int* nb_out) {
-        // Mat: B slices of m x n.  m <= n: Q = I_m, R = Mat (valid factorisation, no work);
-        // m > n: CGS2 in place, R n x n.
-        (void)Qsite_out_p;
+    // The gauge step Mat = Q R of B slices of m x n, bond nb.  m > n: CGS2 in place, Q = Mat, R (n x n) a fresh block.
+    // m <= n, a fat site: *R_out stays null and the caller takes R = Mat itself and Q = identity(m), an isometry (a valid
+    // factorisation, no work); the bond shrinks to m.
+    int qr_tall_or_identity(double* Mat, int m, int n, void** R_out, int* nb_out) {
         if (m <= n) {
             *nb_out = m;
-            *R_out = nullptr;  // caller uses Mat itself as R
+            *R_out = nullptr;
             return QIL_OK;
         }
         void* R = nullptr;
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)B * n * n * sizeof(double), &R));
+        QIL_TRY(tmp.alloc((size_t)B * n * n * sizeof(double), &R));
         const size_t lds = ((size_t)(n + (n & 1)) + (size_t)(m | 1) * n) * sizeof(double);
         if (lds <= 60 * 1024)
             hipLaunchKernelGGL(bgs_fused<true>, dim3(B), dim3(256), lds, qil_stream(ctx), Mat, (double*)R, m, n);
@@ -392,6 +384,11 @@ struct Builder {
         QIL_HIP(hipGetLastError());
         *R_out = R;
         *nb_out = n;
+        return QIL_OK;
+    }
+    int identity(int m, void** Q) {
+        QIL_TRY(tmp.alloc((size_t)B * m * m * sizeof(double), Q));
+        hipLaunchKernelGGL(bidentity, dim3(nblk((long long)m * m), B), dim3(256), 0, qil_stream(ctx), (double*)*Q, m);
         return QIL_OK;
     }
 
@@ -409,24 +406,20 @@ struct Builder {
             QIL_REQUIRE(M[(size_t)k].dl == Da && Blk[(size_t)k].dl == Dc, QIL_EINVAL_ARG, "zip: bond mismatch");
             const int rows = R * 4, cols = B1 * B2;
             void* core = nullptr;
-            QIL_TRY(qil_ctx_alloc(ctx, (size_t)B * rows * cols * sizeof(double), &core));
+            QIL_TRY(tmp.alloc((size_t)B * rows * cols * sizeof(double), &core));
             hipLaunchKernelGGL(bz_core, dim3(nblk((long long)rows * cols), B), dim3(256), 0, qil_stream(ctx),
                                (const double*)T, (const double*)M[(size_t)k].p, (const double*)Blk[(size_t)k].p,
                                (double*)core, R, Da, Dc, B1, B2);
-            qil_ctx_free(ctx, T);
+            tmp.free(T);
             void* Rm = nullptr;
             int nb = 0;
-            QIL_TRY(qr_tall_or_identity((double*)core, rows, cols, nullptr, &Rm, &nb));
-            bfree(ctx, M[(size_t)k]);
+            QIL_TRY(qr_tall_or_identity((double*)core, rows, cols, &Rm, &nb));
+            release(M[(size_t)k]);
             if (Rm) {                       // tall: Q = core (in place), T = R
                 M[(size_t)k].p = core;
                 T = Rm;
             } else {                        // fat/square: Q = I, T = core
-                void* Q = nullptr;
-                QIL_TRY(qil_ctx_alloc(ctx, (size_t)B * rows * rows * sizeof(double), &Q));
-                hipLaunchKernelGGL(bidentity, dim3(nblk((long long)rows * rows), B), dim3(256), 0, qil_stream(ctx),
-                                   (double*)Q, rows);
-                M[(size_t)k].p = Q;
+                QIL_TRY(identity(rows, &M[(size_t)k].p));
                 T = core;
             }
             M[(size_t)k].dl = R;
@@ -440,24 +433,24 @@ struct Builder {
         if (L1 > L2) {
             BSite& nx = M[(size_t)L2];
             void* out = nullptr;
-            QIL_TRY(qil_ctx_alloc(ctx, (size_t)B * R * 4 * nx.dr * sizeof(double), &out));
+            QIL_TRY(tmp.alloc((size_t)B * R * 4 * nx.dr * sizeof(double), &out));
             hipLaunchKernelGGL(bgemm, dim3(nblk((long long)R * 4 * nx.dr), B), dim3(256), 0, qil_stream(ctx),
                                (const double*)T, (const double*)nx.p, (double*)out, R, 4 * nx.dr, Da);
-            bfree(ctx, nx);
+            release(nx);
             nx.p = out;
             nx.dl = R;
         } else {
             BSite& lt = M[(size_t)L2 - 1];
             void* out = nullptr;
-            QIL_TRY(qil_ctx_alloc(ctx, (size_t)B * lt.dl * 4 * Da * sizeof(double), &out));
+            QIL_TRY(tmp.alloc((size_t)B * lt.dl * 4 * Da * sizeof(double), &out));
             hipLaunchKernelGGL(bgemm, dim3(nblk((long long)lt.dl * 4 * Da), B), dim3(256), 0, qil_stream(ctx),
                                (const double*)lt.p, (const double*)T, (double*)out, lt.dl * 4, Da, R);
-            bfree(ctx, lt);
+            release(lt);
             lt.p = out;
             lt.dr = Da;
         }
         QIL_HIP(hipGetLastError());
-        qil_ctx_free(ctx, T);
+        tmp.free(T);
         return QIL_OK;
     }
 
@@ -467,32 +460,24 @@ struct Builder {
         for (int i = 0; i + 1 < L; ++i) {
             const int m = M[(size_t)i].dl * 4, n = M[(size_t)i].dr;
             BSite& nx = M[(size_t)i + 1];
-            if (m <= n) {
-                // fat site: Q = I_m (an isometry), R = the site itself; the bond shrinks to m
-                void *out = nullptr, *Q = nullptr;
-                QIL_TRY(qil_ctx_alloc(ctx, (size_t)B * m * 4 * nx.dr * sizeof(double), &out));
-                hipLaunchKernelGGL(bgemm, dim3(nblk((long long)m * 4 * nx.dr), B), dim3(256), 0, qil_stream(ctx),
-                                   (const double*)M[(size_t)i].p, (const double*)nx.p, (double*)out, m, 4 * nx.dr, n);
-                QIL_TRY(qil_ctx_alloc(ctx, (size_t)B * m * m * sizeof(double), &Q));
-                hipLaunchKernelGGL(bidentity, dim3(nblk((long long)m * m), B), dim3(256), 0, qil_stream(ctx), (double*)Q, m);
-                bfree(ctx, M[(size_t)i]);
-                M[(size_t)i].p = Q;
-                M[(size_t)i].dr = m;
-                bfree(ctx, nx);
-                nx.p = out;
-                nx.dl = m;
-                continue;
-            }
             void* Rm = nullptr;
             int nb = 0;
-            QIL_TRY(qr_tall_or_identity((double*)M[(size_t)i].p, m, n, nullptr, &Rm, &nb));
-            void* out = nullptr;
-            QIL_TRY(qil_ctx_alloc(ctx, (size_t)B * n * 4 * nx.dr * sizeof(double), &out));
-            hipLaunchKernelGGL(bgemm, dim3(nblk((long long)n * 4 * nx.dr), B), dim3(256), 0, qil_stream(ctx),
-                               (const double*)Rm, (const double*)nx.p, (double*)out, n, 4 * nx.dr, n);
-            qil_ctx_free(ctx, Rm);
-            bfree(ctx, nx);
+            QIL_TRY(qr_tall_or_identity((double*)M[(size_t)i].p, m, n, &Rm, &nb));
+            void *out = nullptr, *Q = nullptr;
+            QIL_TRY(tmp.alloc((size_t)B * nb * 4 * nx.dr * sizeof(double), &out));
+            hipLaunchKernelGGL(bgemm, dim3(nblk((long long)nb * 4 * nx.dr), B), dim3(256), 0, qil_stream(ctx),
+                               (const double*)(Rm ? Rm : M[(size_t)i].p), (const double*)nx.p, (double*)out, nb, 4 * nx.dr, n);
+            if (Rm) {                       // tall: Q is the site, factored in place
+                tmp.free(Rm);
+            } else {                        // fat: R was the site itself, Q = I
+                QIL_TRY(identity(m, &Q));
+                release(M[(size_t)i]);
+                M[(size_t)i].p = Q;
+                M[(size_t)i].dr = m;
+            }
+            release(nx);
             nx.p = out;
+            nx.dl = nb;
         }
         // Truncating sweep R -> L.  The reference factorises the two-site core M[i-1] M[i] (:207-229); with
         // everything left of the bond in isometric gauge (the QR sweep above) that core has the SAME singular
@@ -506,7 +491,7 @@ struct Builder {
             const int cols = std::min(d, w), rows = std::max(d, w);
             const bool tall = d > w;                        // rare (only near the right edge)
             void* Wk = nullptr;                             // rows x cols work matrix whose columns get rotated
-            QIL_TRY(qil_ctx_alloc(ctx, (size_t)B * rows * cols * sizeof(double), &Wk));
+            QIL_TRY(tmp.alloc((size_t)B * rows * cols * sizeof(double), &Wk));
             if (!tall)
                 hipLaunchKernelGGL(btranspose, dim3(nblk((long long)d * w), B), dim3(256), 0, qil_stream(ctx),
                                    (const double*)rt.p, (double*)Wk, d, w);                       // Wk = M[i]^T (w x d)
@@ -514,18 +499,14 @@ struct Builder {
                 QIL_HIP(hipMemcpyAsync(Wk, rt.p, (size_t)B * d * w * sizeof(double), hipMemcpyDeviceToDevice,
                                        qil_stream(ctx)));
             void* nrm = nullptr;
-            QIL_TRY(qil_ctx_alloc(ctx, (size_t)B * cols * sizeof(double), &nrm));
+            QIL_TRY(tmp.alloc((size_t)B * cols * sizeof(double), &nrm));
             const size_t lds = (size_t)((rows | 1) * cols) * sizeof(double);
             if (cols <= 32 && rows <= 128 && lds <= 60 * 1024) {
                 hipLaunchKernelGGL((bjacobi<true, 256>), dim3(B), dim3(256), lds, qil_stream(ctx), (double*)Wk,
                                    (double*)nrm, rows, cols, 1e-15);
             } else if (lds <= 150 * 1024) {
-                static bool attr = false;
-                if (!attr) {
-                    QIL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bjacobi<true, 1024>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-                    attr = true;
-                }
+                static qil_lds_grant grant;                // per device (qil_internal.h)
+                QIL_HIP(grant.ensure(ctx->device, reinterpret_cast<const void*>(&bjacobi<true, 1024>), 160 * 1024 - 512));
                 hipLaunchKernelGGL((bjacobi<true, 1024>), dim3(B), dim3(1024), lds, qil_stream(ctx), (double*)Wk,
                                    (double*)nrm, rows, cols, 1e-15);
             } else {
@@ -559,14 +540,14 @@ struct Builder {
                 rmax = std::max(rmax, rank[b]);
             }
             void* dpack = nullptr;
-            QIL_TRY(qil_ctx_alloc(ctx, up_bytes, &dpack));
+            QIL_TRY(tmp.alloc(up_bytes, &dpack));
             QIL_HIP(hipMemcpyAsync(dpack, inv, up_bytes, hipMemcpyHostToDevice, qil_stream(ctx)));
             const double* dinv = static_cast<const double*>(dpack);
             const int* dperm = reinterpret_cast<const int*>(dinv + nsig);
             const int* drank = dperm + nsig;
             void *Vh = nullptr, *US = nullptr, *nl = nullptr;   // Vh: rmax x w ; US: d x rmax
-            QIL_TRY(qil_ctx_alloc(ctx, (size_t)B * rmax * w * sizeof(double), &Vh));
-            QIL_TRY(qil_ctx_alloc(ctx, (size_t)B * d * rmax * sizeof(double), &US));
+            QIL_TRY(tmp.alloc((size_t)B * rmax * w * sizeof(double), &Vh));
+            QIL_TRY(tmp.alloc((size_t)B * d * rmax * sizeof(double), &US));
             if (!tall) {
                 // M[i]^T = (Wk D^-1) D V^T : Vh = (Wk[:, perm] D^-1)^T (rmax x w) ; U S = M[i] Vh^T (d x rmax)
                 hipLaunchKernelGGL(bgather, dim3(nblk((long long)w * rmax), B), dim3(256), 0, qil_stream(ctx),
@@ -584,16 +565,16 @@ struct Builder {
                                    cols);
             }
             // M[i-1] <- M[i-1] (U S)
-            QIL_TRY(qil_ctx_alloc(ctx, (size_t)B * lf.dl * 4 * rmax * sizeof(double), &nl));
+            QIL_TRY(tmp.alloc((size_t)B * lf.dl * 4 * rmax * sizeof(double), &nl));
             hipLaunchKernelGGL(bgemm, dim3(nblk((long long)lf.dl * 4 * rmax), B), dim3(256), 0, qil_stream(ctx),
                                (const double*)lf.p, (const double*)US, (double*)nl, lf.dl * 4, rmax, d);
             QIL_HIP(hipGetLastError());
-            qil_ctx_free(ctx, Wk);
-            qil_ctx_free(ctx, nrm);
-            qil_ctx_free(ctx, dpack);
-            qil_ctx_free(ctx, US);
-            bfree(ctx, lf);
-            bfree(ctx, rt);
+            tmp.free(Wk);
+            tmp.free(nrm);
+            tmp.free(dpack);
+            tmp.free(US);
+            release(lf);
+            release(rt);
             lf.p = nl;
             lf.dr = rmax;
             rt.p = Vh;
@@ -606,12 +587,14 @@ struct Builder {
         std::vector<BSite> out(M.size());
         for (size_t i = 0; i < M.size(); ++i) {
             BSite& src = M[M.size() - 1 - i];
-            QIL_TRY(balloc(ctx, B, src.dr, src.dl, &out[i]));
+            out[i].dl = src.dr;
+            out[i].dr = src.dl;
+            QIL_TRY(tmp.alloc((size_t)B * out[i].elems() * sizeof(double), &out[i].p));
             hipLaunchKernelGGL(bmirror, dim3(nblk(src.elems()), B), dim3(256), 0, qil_stream(ctx), (const double*)src.p,
                                (double*)out[i].p, src.dl, src.dr);
         }
         QIL_HIP(hipGetLastError());
-        for (auto& s : M) bfree(ctx, s);
+        for (auto& s : M) release(s);
         M = out;
         return QIL_OK;
     }
@@ -734,6 +717,8 @@ int qil_check_damping_values(const char* who, int64_t n, int64_t nb, const doubl
     return QIL_OK;
 }
 
+// A call that fails hands out no handle.  The launch-per-step route does not touch out[] unless the call succeeds: out[b] is
+// written after the final stream synchronisation.  (The persistent route destroys and nulls what it had stored.)
 extern "C" int qil_build_dt_mpo_batch(qil_context* ctx, int64_t n, int64_t nb, const double* wrs, double cutoff,
                                       int64_t maxdim, const int64_t* site_ids, qil_mpo** out) {
     QIL_REQUIRE(ctx && wrs && out, QIL_EINVAL_ARG, "build_dt_mpo: null argument");
@@ -752,79 +737,64 @@ extern "C" int qil_build_dt_mpo_batch(qil_context* ctx, int64_t n, int64_t nb, c
     }
     // (the rule never runs below 1e-28: the batched Jacobi leaves rounding residue of rank-deficient bonds un-orthogonalised, see
     // qil_build_persist.hip persist_chunk)
-    Builder bd{ctx, (int)nb, std::max(cutoff, 1e-28), maxdim <= 0 ? INT64_MAX : maxdim};
+    qil_scratch tmp(ctx);                                 // every block of the build: whatever is left goes back on return
+    Builder bd{ctx, tmp, (int)nb, std::max(cutoff, 1e-28), maxdim <= 0 ? INT64_MAX : maxdim};
     const int B = (int)nb;
     std::vector<BSite> M;
-    int st = bd.make_block(2, [&](int b, int site, int* dl, int* dr, std::vector<double>* o) {
+    QIL_TRY(bd.make_block(2, [&](int b, int site, int* dl, int* dr, std::vector<double>* o) {
         dt_main_site(1, wrs[b], site, dl, dr, o);
-    }, &M);
-    if (st != QIL_OK) return st;
-    auto fail = [&](int code) {
-        for (auto& s : M) bfree(ctx, s);
-        return code;
-    };
+    }, &M));
     for (int k = 2; k <= n; ++k) {                                            // part 1 (:351-390)
         for (int t = 0; t < 2; ++t) {                                         // identity pair, dim-1 bonds
             BSite s;
             std::vector<double> eye;
             for (int b = 0; b < B; ++b) eye.insert(eye.end(), {1.0, 0.0, 0.0, 1.0});
             s.dl = s.dr = 1;
-            if ((st = bd.upload(eye, &s.p)) != QIL_OK) return fail(st);
+            QIL_TRY(bd.upload(eye, &s.p));
             M.push_back(s);
         }
         std::vector<BSite> blk;
-        st = bd.make_block(2 * k, [&](int b, int site, int* dl, int* dr, std::vector<double>* o) {
+        QIL_TRY(bd.make_block(2 * k, [&](int b, int site, int* dl, int* dr, std::vector<double>* o) {
             dt_main_site(k, wrs[b], site, dl, dr, o);
-        }, &blk);
-        if (st == QIL_OK) st = bd.zip_lr(M, blk);
-        for (auto& s : blk) bfree(ctx, s);
-        if (st == QIL_OK) st = bd.compress_lr(M);
-        if (st != QIL_OK) return fail(st);
+        }, &blk));
+        QIL_TRY(bd.zip_lr(M, blk));
+        for (auto& s : blk) bd.release(s);
+        QIL_TRY(bd.compress_lr(M));
     }
     if (n > 1) {                                                              // part 2 in the mirrored frame (:396-405)
-        if ((st = bd.mirror(M)) != QIL_OK) return fail(st);
+        QIL_TRY(bd.mirror(M));
         for (int k = 1; k < n; ++k) {
             const int ns = 2 * (int)(n - k + 1);
             std::vector<BSite> blk;
-            st = bd.make_block(ns, [&](int b, int site, int* dl, int* dr, std::vector<double>* o) {
+            QIL_TRY(bd.make_block(ns, [&](int b, int site, int* dl, int* dr, std::vector<double>* o) {
                 dt_copy_site((int)n, k, wrs[b], site, dl, dr, o);
-            }, &blk);
-            if (st == QIL_OK) st = bd.mirror(blk);
-            if (st == QIL_OK) st = bd.zip_lr(M, blk);
-            for (auto& s : blk) bfree(ctx, s);
-            if (st == QIL_OK) st = bd.compress_lr(M);
-            if (st != QIL_OK) return fail(st);
+            }, &blk));
+            QIL_TRY(bd.mirror(blk));
+            QIL_TRY(bd.zip_lr(M, blk));
+            for (auto& s : blk) bd.release(s);
+            QIL_TRY(bd.compress_lr(M));
         }
-        if ((st = bd.mirror(M)) != QIL_OK) return fail(st);
+        QIL_TRY(bd.mirror(M));
     }
     // hand out one PairedSiteMPO per damping value (zero-padded to the batch's common bond profile)
     const int L = (int)M.size();
     std::vector<int64_t> bonds((size_t)std::max(L - 1, 1));
     for (int i = 0; i + 1 < L; ++i) bonds[(size_t)i] = M[(size_t)i].dr;
-    // a failure part-way takes back the handles already stored in out[]: their blocks are owned, so nothing else would
-    int made = 0;
-    auto fail_out = [&](int code) {
-        for (int b = 0; b < made; ++b) {
-            qil_mpo_destroy(out[b]);
-            out[b] = nullptr;
-        }
-        return fail(code);
-    };
+    std::vector<qil_result_guard<qil_mpo>> made;         // a failure part-way destroys the handles made so far
+    made.reserve((size_t)B);
     for (int b = 0; b < B; ++b) {
         qil_mpo* W = nullptr;
-        st = qil_mpo_alloc(ctx, L, QIL_F64, 1, bonds.data(), site_ids, &W);
-        if (st != QIL_OK) return fail_out(st);
-        out[b] = W;
-        ++made;
+        QIL_TRY(qil_mpo_alloc(ctx, L, QIL_F64, 1, bonds.data(), site_ids, &W));
+        made.emplace_back(W);
         for (int i = 0; i < L; ++i) {
             const size_t bytes = (size_t)M[(size_t)i].elems() * sizeof(double);
             hipError_t e = hipMemcpyAsync(W->site[(size_t)i], static_cast<char*>(M[(size_t)i].p) + (size_t)b * bytes, bytes,
                                           hipMemcpyDeviceToDevice, qil_stream(ctx));
-            if (e != hipSuccess) return fail_out(qil_fail(QIL_EHIP, "copy failed: %s", hipGetErrorString(e)));
+            if (e != hipSuccess) return qil_fail(QIL_EHIP, "copy failed: %s", hipGetErrorString(e));
         }
     }
     hipError_t e = qil_stream_sync(ctx);
-    if (e != hipSuccess) return fail_out(qil_fail(QIL_EHIP, "build_dt_mpo: copy-out failed: %s", hipGetErrorString(e)));
-    for (auto& s : M) bfree(ctx, s);
+    if (e != hipSuccess) return qil_fail(QIL_EHIP, "build_dt_mpo: copy-out failed: %s", hipGetErrorString(e));
+    for (int b = 0; b < B; ++b) out[b] = made[(size_t)b].release();
     return QIL_OK;
 }

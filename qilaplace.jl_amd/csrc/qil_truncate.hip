@@ -23,16 +23,6 @@ using namespace qil_dev;
 
 constexpr int64_t kNoCap = INT64_MAX;
 
-template <class F>
-struct Defer {
-    F f;
-    ~Defer() { f(); }
-};
-template <class F>
-Defer<F> defer(F f) {
-    return Defer<F>{f};
-}
-
 // dst (rows x cols, ldd) <- src (rows x cols, lds): strided device copy
 int copy_2d(qil_context* ctx, int dtype, int64_t rows, int64_t cols, const void* src, int64_t lds_, void* dst,
             int64_t ldd) {
@@ -140,13 +130,15 @@ static int svd_trunc_lowrank(qil_context* ctx, int dtype, int64_t m, int64_t n, 
         void *Ub = nullptr, *Vh = nullptr;
         std::vector<double> S;
         QIL_TRY(svd_trunc_dev(ctx, dtype, k, n, B, k, cutoff, true, maxdim, mindim, absorb, &r, &Ub, &Vh, &S));
+        scratch.own(Ub);
+        scratch.own(Vh);
         void* U = nullptr;
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(m * std::min(m, n)) * e, &U));     // callers index U with ld m only
+        QIL_TRY(scratch.alloc((size_t)(m * std::min(m, n)) * e, &U));          // callers index U with ld m only
         QIL_TRY(qil_dev_gemm(ctx, dtype, 0, 0, m, r, k, Y, m, Ub, k, U, m));                         // U = Q U_B
-        qil_ctx_free(ctx, Ub);
+        scratch.free(Ub);
         *rank = r;
-        *U_out = U;
-        *Vh_out = Vh;
+        *U_out = scratch.give(U);
+        *Vh_out = scratch.give(Vh);
         if (S_out) *S_out = std::move(S);
         *done = 1;
         return QIL_OK;
@@ -157,11 +149,13 @@ static int svd_trunc_lowrank(qil_context* ctx, int dtype, int64_t m, int64_t n, 
 // Truncated SVD of the device matrix A (m x n, lda; destroyed).  Outputs are fresh pool blocks:
 //   U  (m x r, ld m)   -- optionally scaled by S (absorb = 1)
 //   Vh (r x n, ld r)   -- optionally scaled by S (absorb = 2)
+// They are the caller's from the return on (qil_scratch::own); a failed call leaves nothing behind.
 int svd_trunc_dev(qil_context* ctx, int dtype, int64_t m, int64_t n, void* A, int64_t lda, double cutoff,
                   bool use_cutoff, int64_t maxdim, int64_t mindim, int absorb, int64_t* rank, void** U_out,
                   void** Vh_out, std::vector<double>* S_out) {
     const int64_t r0 = std::min(m, n);
     const size_t e = qil_elem_size(dtype);
+    qil_scratch tmp(ctx);
     // Gauge sweeps that truncate by cutoff only and do not read the singular values (canonicalize!(cutoff), the first pass of
     // compress!): where the site's triangular factor certifies that nothing can be dropped, the thin QR is the gauge step
     // (qil_linalg.hip, "nothing can be truncated" certificate).  97..639 columns: inside the one-factor SVD, which has the QR
@@ -170,8 +164,8 @@ int svd_trunc_dev(qil_context* ctx, int dtype, int64_t m, int64_t n, void* A, in
     if (cert_cutoff > 0.0 && r0 >= 640) {
         const int64_t rows = std::max(m, n);
         void *Qb = nullptr, *Rb = nullptr;
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(rows * r0) * e, &Qb));
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(r0 * r0) * e, &Rb));
+        QIL_TRY(tmp.alloc((size_t)(rows * r0) * e, &Qb));
+        QIL_TRY(tmp.alloc((size_t)(r0 * r0) * e, &Rb));
         bool certified = false;
         QIL_TRY(qil_dev_qr_certified(ctx, dtype, m, n, A, lda, cert_cutoff, Qb, Rb, &certified));
         if (getenv("QIL_SVD_DEBUG"))
@@ -179,8 +173,8 @@ int svd_trunc_dev(qil_context* ctx, int dtype, int64_t m, int64_t n, void* A, in
                     certified ? "QR gauge" : "declined");
         if (certified) {
             void *U = nullptr, *Vh = nullptr;
-            QIL_TRY(qil_ctx_alloc(ctx, (size_t)(m * r0) * e, &U));
-            QIL_TRY(qil_ctx_alloc(ctx, (size_t)(r0 * n) * e, &Vh));
+            QIL_TRY(tmp.alloc((size_t)(m * r0) * e, &U));
+            QIL_TRY(tmp.alloc((size_t)(r0 * n) * e, &Vh));
             if (absorb == 2) {                       // U isometric, the rest absorbed
                 if (m >= n) {                        // A = Q R
                     QIL_TRY(copy_2d(ctx, dtype, m, r0, Qb, rows, U, m));
@@ -200,15 +194,15 @@ int svd_trunc_dev(qil_context* ctx, int dtype, int64_t m, int64_t n, void* A, in
                     QIL_TRY(copy_2d(ctx, dtype, m, n, A, lda, U, m));
                 }
             }
-            qil_ctx_free(ctx, Qb);
-            qil_ctx_free(ctx, Rb);
+            tmp.free(Qb);
+            tmp.free(Rb);
             *rank = r0;
-            *U_out = U;
-            *Vh_out = Vh;
+            *U_out = tmp.give(U);
+            *Vh_out = tmp.give(Vh);
             return QIL_OK;
         }
-        qil_ctx_free(ctx, Qb);
-        qil_ctx_free(ctx, Rb);
+        tmp.free(Qb);
+        tmp.free(Rb);
     }
     if (use_cutoff) {
         int done = 0;
@@ -216,8 +210,8 @@ int svd_trunc_dev(qil_context* ctx, int dtype, int64_t m, int64_t n, void* A, in
         if (done) return QIL_OK;
     }
     void *U = nullptr, *Vh = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(m * r0) * e, &U));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(r0 * n) * e, &Vh));
+    QIL_TRY(tmp.alloc((size_t)(m * r0) * e, &U));
+    QIL_TRY(tmp.alloc((size_t)(r0 * n) * e, &Vh));
     std::vector<double> S((size_t)r0);
     // with a truncating cutoff, columns 100x below it (and never above 1e-30 |A|_F^2) are not worth rotating
     const double negl_rel = use_cutoff && cutoff > 0 ? std::min(1e-30, 1e-2 * cutoff) : 0.0;
@@ -236,18 +230,18 @@ int svd_trunc_dev(qil_context* ctx, int dtype, int64_t m, int64_t n, void* A, in
         QIL_TRY(qil_dev_svd_left(ctx, dtype, m, n, A, lda, U, m, S.data(), Vh, r0, negl_rel, &handled, cert_cutoff, deflate));
     } else if (absorb == 1) {     // Vh isometric, U S absorbed: the same problem on A^H
         void *At = nullptr, *Vi = nullptr, *SU = nullptr;
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(m * n) * e, &At));
+        QIL_TRY(tmp.alloc((size_t)(m * n) * e, &At));
         QIL_TRY(qil_dev_transpose(ctx, dtype, 1, m, n, A, lda, At, n));                         // A^H (n x m)
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(n * r0) * e, &Vi));
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(r0 * m) * e, &SU));
+        QIL_TRY(tmp.alloc((size_t)(n * r0) * e, &Vi));
+        QIL_TRY(tmp.alloc((size_t)(r0 * m) * e, &SU));
         QIL_TRY(qil_dev_svd_left(ctx, dtype, n, m, At, n, Vi, n, S.data(), SU, r0, negl_rel, &handled, cert_cutoff, deflate));
         if (handled) {
             QIL_TRY(qil_dev_transpose(ctx, dtype, 1, n, r0, Vi, n, Vh, r0));                    // Vh = V^H   (r0 x n)
             QIL_TRY(qil_dev_transpose(ctx, dtype, 1, r0, m, SU, r0, U, m));                     // U S = (S U^H)^H
         }
-        qil_ctx_free(ctx, At);
-        qil_ctx_free(ctx, Vi);
-        qil_ctx_free(ctx, SU);
+        tmp.free(At);
+        tmp.free(Vi);
+        tmp.free(SU);
     }
     if (!handled) QIL_TRY(qil_dev_svd(ctx, dtype, m, n, A, lda, U, m, S.data(), Vh, r0, negl_rel));
     // handled == 2: certified that nothing can be truncated (S was not computed)
@@ -256,15 +250,15 @@ int svd_trunc_dev(qil_context* ctx, int dtype, int64_t m, int64_t n, void* A, in
     if (!handled && absorb == 2) QIL_TRY(qil_dev_scale(ctx, dtype, 0, r, n, Vh, r0, S.data()));
     if (r < r0) {  // compact Vh rows to leading dimension r
         void* Vc = nullptr;
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(r * n) * e, &Vc));
+        QIL_TRY(tmp.alloc((size_t)(r * n) * e, &Vc));
         QIL_TRY(copy_2d(ctx, dtype, r, n, Vh, r0, Vc, r));
-        qil_ctx_free(ctx, Vh);
+        tmp.free(Vh);
         Vh = Vc;
     }
     S.resize((size_t)r);
     *rank = r;
-    *U_out = U;  // first r columns are the kept ones (contiguous)
-    *Vh_out = Vh;
+    *U_out = tmp.give(U);  // first r columns are the kept ones (contiguous)
+    *Vh_out = tmp.give(Vh);
     if (S_out) *S_out = std::move(S);
     return QIL_OK;
 }
@@ -278,8 +272,9 @@ int svd_trunc_dev(qil_context* ctx, int dtype, int64_t m, int64_t n, void* A, in
 // wider than tall has no thin QR that shrinks nothing, so it takes the SVD route with cutoff 0.
 // Every gauge step here and below factors a COPY of site i and replaces the two sites only when nothing can fail any more: a
 // call that runs out of memory half way leaves the chain, and the operator or state it stands for, as the last finished step left it.
-static int site_copy(qil_chain* psi, int64_t i, void** out) {
-    QIL_TRY(qil_ctx_alloc(psi->ctx, psi->site_bytes(i), out));
+// The blocks of a step are its scratch's until the chain takes them.
+static int site_copy(qil_scratch& tmp, qil_chain* psi, int64_t i, void** out) {
+    QIL_TRY(tmp.alloc(psi->site_bytes(i), out));
     return qil_dev_copy(psi->ctx, *out, psi->site[(size_t)i], psi->site_bytes(i));
 }
 
@@ -288,15 +283,16 @@ static int gauge_qr_site_right(qil_chain* psi, int64_t i, int64_t pd) {
     const int dt = psi->dtype;
     const size_t e = qil_elem_size(dt);
     const int64_t cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1], cr2 = psi->dims[(size_t)i + 2];
+    qil_scratch tmp(ctx);
     void *Q = nullptr, *Rf = nullptr, *next = nullptr;
-    QIL_TRY(site_copy(psi, i, &Q));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(cr * cr) * e, &Rf));
+    QIL_TRY(site_copy(tmp, psi, i, &Q));
+    QIL_TRY(tmp.alloc((size_t)(cr * cr) * e, &Rf));
     QIL_TRY(qil_dev_qr_positive(ctx, dt, pd * cl, cr, Q, pd * cl, Rf, cr, true));   // Q in place of the copy
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(cr * pd * cr2) * e, &next));
+    QIL_TRY(tmp.alloc((size_t)(cr * pd * cr2) * e, &next));
     QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, cr, pd * cr2, cr, Rf, cr, psi->site[(size_t)i + 1], cr, next, cr));
-    qil_ctx_free(ctx, Rf);
-    QIL_TRY(qil_chain_set_site(psi, i, Q, cl, cr));
-    QIL_TRY(qil_chain_set_site(psi, i + 1, next, cr, cr2));
+    tmp.free(Rf);
+    QIL_TRY(qil_chain_set_site(psi, i, tmp.give(Q), cl, cr));
+    QIL_TRY(qil_chain_set_site(psi, i + 1, tmp.give(next), cr, cr2));
     return QIL_OK;
 }
 
@@ -306,19 +302,20 @@ static int gauge_qr_site_left(qil_chain* psi, int64_t i, int64_t pd) {
     const size_t e = qil_elem_size(dt);
     const int64_t cl = psi->dims[(size_t)i], cr = psi->dims[(size_t)i + 1], cl0 = psi->dims[(size_t)i - 1];
     // A (cl x pd cr) = L Q with orthonormal rows of Q:  A^H = Qt Rt  =>  Q = Qt^H, L = Rt^H
+    qil_scratch tmp(ctx);
     void *Ah = nullptr, *Rt = nullptr, *prev = nullptr, *Q = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(pd * cr * cl) * e, &Ah));
+    QIL_TRY(tmp.alloc((size_t)(pd * cr * cl) * e, &Ah));
     QIL_TRY(qil_dev_transpose(ctx, dt, 1, cl, pd * cr, psi->site[(size_t)i], cl, Ah, pd * cr));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(cl * cl) * e, &Rt));
+    QIL_TRY(tmp.alloc((size_t)(cl * cl) * e, &Rt));
     QIL_TRY(qil_dev_qr_positive(ctx, dt, pd * cr, cl, Ah, pd * cr, Rt, cl, true));
-    QIL_TRY(qil_ctx_alloc(ctx, psi->site_bytes(i), &Q));
+    QIL_TRY(tmp.alloc(psi->site_bytes(i), &Q));
     QIL_TRY(qil_dev_transpose(ctx, dt, 1, pd * cr, cl, Ah, pd * cr, Q, cl));
-    qil_ctx_free(ctx, Ah);
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(cl0 * pd * cl) * e, &prev));
+    tmp.free(Ah);
+    QIL_TRY(tmp.alloc((size_t)(cl0 * pd * cl) * e, &prev));
     QIL_TRY(qil_dev_gemm(ctx, dt, 0, 2, pd * cl0, cl, cl, psi->site[(size_t)i - 1], pd * cl0, Rt, cl, prev, pd * cl0));
-    qil_ctx_free(ctx, Rt);
-    QIL_TRY(qil_chain_set_site(psi, i, Q, cl, cr));
-    QIL_TRY(qil_chain_set_site(psi, i - 1, prev, cl0, cl));
+    tmp.free(Rt);
+    QIL_TRY(qil_chain_set_site(psi, i, tmp.give(Q), cl, cr));
+    QIL_TRY(qil_chain_set_site(psi, i - 1, tmp.give(prev), cl0, cl));
     return QIL_OK;
 }
 
@@ -334,17 +331,20 @@ static int gauge_site_right(qil_chain* psi, int64_t i, double cutoff, int64_t ma
     const int64_t cr2 = psi->dims[(size_t)i + 2];
     if (gauge_qr && pd * cl >= cr) return gauge_qr_site_right(psi, i, pd);
     int64_t r = 0;
+    qil_scratch tmp(ctx);
     void *A = nullptr, *U = nullptr, *SV = nullptr;
     // rows (alpha, s) | cols beta : the site buffer as it lies
-    QIL_TRY(site_copy(psi, i, &A));
+    QIL_TRY(site_copy(tmp, psi, i, &A));
     QIL_TRY(svd_trunc_dev(ctx, dt, pd * cl, cr, A, pd * cl, cutoff, true, maxdim, 1, 2, &r, &U, &SV, nullptr));
-    qil_ctx_free(ctx, A);
+    tmp.own(U);
+    tmp.own(SV);
+    tmp.free(A);
     void* next = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(r * pd * cr2) * e, &next));
+    QIL_TRY(tmp.alloc((size_t)(r * pd * cr2) * e, &next));
     QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, r, pd * cr2, cr, SV, r, psi->site[(size_t)i + 1], cr, next, r));
-    qil_ctx_free(ctx, SV);
-    QIL_TRY(qil_chain_set_site(psi, i, U, cl, r));
-    QIL_TRY(qil_chain_set_site(psi, i + 1, next, r, cr2));
+    tmp.free(SV);
+    QIL_TRY(qil_chain_set_site(psi, i, tmp.give(U), cl, r));
+    QIL_TRY(qil_chain_set_site(psi, i + 1, tmp.give(next), r, cr2));
     return QIL_OK;
 }
 
@@ -359,17 +359,20 @@ static int gauge_site_left(qil_chain* psi, int64_t i, double cutoff, int64_t max
     const int64_t cl0 = psi->dims[(size_t)i - 1];
     if (gauge_qr && pd * cr >= cl) return gauge_qr_site_left(psi, i, pd);
     int64_t r = 0;
+    qil_scratch tmp(ctx);
     void *A = nullptr, *US = nullptr, *Vh = nullptr;
     // rows alpha | cols (s, beta)
-    QIL_TRY(site_copy(psi, i, &A));
+    QIL_TRY(site_copy(tmp, psi, i, &A));
     QIL_TRY(svd_trunc_dev(ctx, dt, cl, pd * cr, A, cl, cutoff, true, maxdim, 1, 1, &r, &US, &Vh, nullptr));
-    qil_ctx_free(ctx, A);
+    tmp.own(US);
+    tmp.own(Vh);
+    tmp.free(A);
     void* prev = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(cl0 * pd * r) * e, &prev));
+    QIL_TRY(tmp.alloc((size_t)(cl0 * pd * r) * e, &prev));
     QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, pd * cl0, r, cl, psi->site[(size_t)i - 1], pd * cl0, US, cl, prev, pd * cl0));
-    qil_ctx_free(ctx, US);
-    QIL_TRY(qil_chain_set_site(psi, i, Vh, r, cr));
-    QIL_TRY(qil_chain_set_site(psi, i - 1, prev, cl0, r));
+    tmp.free(US);
+    QIL_TRY(qil_chain_set_site(psi, i, tmp.give(Vh), r, cr));
+    QIL_TRY(qil_chain_set_site(psi, i - 1, tmp.give(prev), cl0, r));
     return QIL_OK;
 }
 
@@ -568,6 +571,7 @@ int rsvd_rowmajor(qil_context* ctx, int dt, int64_t m, int64_t n, const void* Z,
     const size_t e = qil_elem_size(dt);
     const int64_t l0 = std::min(std::min(k + p, m), n);  // rsvd.jl:72
     const bool route = getenv("QIL_RSVD_DEBUG") != nullptr;
+    qil_scratch tmp(ctx);
     if (l0 == std::min(m, n)) {
         if (route) rsvd_route_line(m, n, l0, -1);
         // The sketch is as wide as the short side: Q spans the whole range of M and the procedure returns the exact
@@ -575,12 +579,11 @@ int rsvd_rowmajor(qil_context* ctx, int dt, int64_t m, int64_t n, const void* Z,
         // Take the SVD directly: Z = M^T = Uz Sz Vz^h  =>  U_M^T = Vz^h,  (S V_M^h)^T = Uz Sz.  Every deep split of
         // the bisection encoder ends up here (SignalConverters.jl:161: m or n <= k + p).
         void* Zc = nullptr;
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(m * n) * e, &Zc));
+        QIL_TRY(tmp.alloc((size_t)(m * n) * e, &Zc));
         QIL_TRY(qil_dev_copy(ctx, Zc, Z, (size_t)(m * n) * e));
         int64_t r = 0;
         void *UzS = nullptr, *Vzh = nullptr;
-        QIL_TRY(svd_trunc_dev(ctx, dt, n, m, Zc, n, cutoff, true, maxdim, mindim, 1, &r, &UzS, &Vzh, S_out));
-        qil_ctx_free(ctx, Zc);
+        QIL_TRY(svd_trunc_dev(ctx, dt, n, m, Zc, n, cutoff, true, maxdim, mindim, 1, &r, &UzS, &Vzh, S_out));   // the caller's from here
         *rank = r;
         *left = Vzh;    // r x m, ld r
         *right = UzS;   // n x (>= r) columns, ld n
@@ -597,8 +600,8 @@ int rsvd_rowmajor(qil_context* ctx, int dt, int64_t m, int64_t n, const void* Z,
                 std::chrono::duration<double, std::milli>(now - t_prev).count());
         t_prev = now;
     };
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(n * l0) * e, &Om));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(m * l0) * e, &Y));
+    QIL_TRY(tmp.alloc((size_t)(n * l0) * e, &Om));
+    QIL_TRY(tmp.alloc((size_t)(m * l0) * e, &Y));
     QIL_TRY(qil_dev_fill_normal(ctx, dt, Om, n * l0, seed, 1.0));                        // rsvd.jl:74-76
     lap("omega");
     QIL_TRY(qil_dev_gemm(ctx, dt, 1, 0, m, l0, n, Z, n, Om, n, Y, m));                   // Y = M Omega (:79)
@@ -615,7 +618,7 @@ int rsvd_rowmajor(qil_context* ctx, int dt, int64_t m, int64_t n, const void* Z,
     int64_t l = l0;
     {
         void* Rq = nullptr;
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(l0 * l0) * e, &Rq));
+        QIL_TRY(tmp.alloc((size_t)(l0 * l0) * e, &Rq));
         QIL_TRY(qil_dev_qr_positive(ctx, dt, m, l0, Y, m, Rq, l0, q == 0));             // Q (:83)
         lap("qr(Y)");
         if (l0 <= 1024 && l0 >= 8) {
@@ -646,10 +649,10 @@ int rsvd_rowmajor(qil_context* ctx, int dt, int64_t m, int64_t n, const void* Z,
                 if (dbg) fprintf(stderr, "[rsvd] %lld x %lld: sketch of %lld columns has numerical rank %lld: deflated\n", (long long)m, (long long)n, (long long)l0, (long long)l);
             }
         }
-        qil_ctx_free(ctx, Rq);
+        tmp.free(Rq);
     }
     if (route) rsvd_route_line(m, n, l0, l);
-    if (q > 0) QIL_TRY(qil_ctx_alloc(ctx, (size_t)(n * l) * e, &Zq));
+    if (q > 0) QIL_TRY(tmp.alloc((size_t)(n * l) * e, &Zq));
     for (int it = 0; it < q; ++it) {                                                    // :86-95
         QIL_TRY(qil_dev_gemm(ctx, dt, 3, 0, n, l, m, Z, n, Y, m, Zq, n));               // M^H Q = conj(Z) Q
         QIL_TRY(qil_dev_qr_positive(ctx, dt, n, l, Zq, n, nullptr, 0));
@@ -657,26 +660,28 @@ int rsvd_rowmajor(qil_context* ctx, int dt, int64_t m, int64_t n, const void* Z,
         QIL_TRY(qil_dev_qr_positive(ctx, dt, m, l, Y, m, nullptr, 0, it + 1 == q));
         lap("power iteration (2 products + 2 QRs)");
     }
-    qil_ctx_free(ctx, Om);
-    if (Zq) qil_ctx_free(ctx, Zq);
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(n * l) * e, &Bt));
+    tmp.free(Om);
+    tmp.free(Zq);                                                                       // (none without a power iteration)
+    QIL_TRY(tmp.alloc((size_t)(n * l) * e, &Bt));
     QIL_TRY(qil_dev_gemm(ctx, dt, 0, 3, n, l, m, Z, n, Y, m, Bt, n));                   // B^T = Z conj(Q) (:98)
     lap("B^T = Z conj(Q)");
     // B^T = Ub Sb Vbh  =>  Uhat = Vbh^T,  (S V^h)^T = Ub Sb
     int64_t r = 0;
     void *UbS = nullptr, *Vbh = nullptr;
     QIL_TRY(svd_trunc_dev(ctx, dt, n, l, Bt, n, cutoff, true, maxdim, mindim, 1, &r, &UbS, &Vbh, S_out));  // :103
-    qil_ctx_free(ctx, Bt);
+    tmp.own(UbS);
+    tmp.own(Vbh);
+    tmp.free(Bt);
     void* L = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(r * m) * e, &L));
+    QIL_TRY(tmp.alloc((size_t)(r * m) * e, &L));
     lap("svd(B^T)");
     QIL_TRY(qil_dev_gemm(ctx, dt, 0, 1, r, m, l, Vbh, r, Y, m, L, r));                  // U_M^T = Vbh Q^T (:114)
     lap("U^T = Vbh Q^T");
-    qil_ctx_free(ctx, Vbh);
-    qil_ctx_free(ctx, Y);
+    tmp.free(Vbh);
+    tmp.free(Y);
     *rank = r;
-    *left = L;
-    *right = UbS;  // first r columns, ld n
+    *left = tmp.give(L);
+    *right = tmp.give(UbS);  // first r columns, ld n
     return QIL_OK;
 }
 
@@ -697,17 +702,21 @@ struct EncodeParams {
 // Sub-trees of the bisection are independent: with `defer`, the children of the nodes at depth `defer_depth - 1` are not
 // descended into but recorded, and the caller runs them concurrently (qil_run_batch_on) -- below the first splits every
 // node is a short chain of small factorisations.
+// The call consumes X.  What it leaves behind -- the finished sites and the operands of the deferred sub-trees -- belongs to
+// `keep`, a scratch of the same context, so a failure anywhere in the tree strands nothing.
 struct TtTask {
     void* X;
     int64_t lb, rb, first, last;
 };
-int compress_tt(qil_context* ctx, int dt, void* X, int64_t lb, int64_t rb, int64_t first, int64_t last,
+int compress_tt(qil_context* ctx, int dt, qil_scratch& keep, void* X, int64_t lb, int64_t rb, int64_t first, int64_t last,
                 const EncodeParams& P, std::vector<void*>& sites, std::vector<int64_t>& dims, int depth = 0,
                 std::vector<TtTask>* defer = nullptr, int defer_depth = 0) {
+    qil_scratch tmp(ctx);
+    tmp.own(X);
     const size_t e = qil_elem_size(dt);
     if (first == last) {
         void* A = nullptr;
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(lb * 2 * rb) * e, &A));
+        QIL_TRY(keep.alloc((size_t)(lb * 2 * rb) * e, &A));
         if (dt == QIL_C64)
             QIL_TRY((qil_klaunch<site_from_chunk_k<c64>>(ctx, dim3(nblk(2 * lb * rb)), dim3(256), 0, (const c64*)X, (int)lb, (int)rb, (c64*)A)));
         else
@@ -716,7 +725,6 @@ int compress_tt(qil_context* ctx, int dt, void* X, int64_t lb, int64_t rb, int64
         sites[(size_t)first] = A;
         dims[(size_t)first] = lb;
         dims[(size_t)first + 1] = rb;
-        qil_ctx_free(ctx, X);
         return QIL_OK;
     }
     const int64_t mid = (first + last + 1) / 2 - 1;  // 1-based (first+last-1) div 2, SignalConverters.jl:161
@@ -726,14 +734,16 @@ int compress_tt(qil_context* ctx, int dt, void* X, int64_t lb, int64_t rb, int64
     // explicit cutoff/maxdim override the rsvd defaults (SignalConverters.jl:133)
     QIL_TRY(rsvd_rowmajor(ctx, dt, m, n, X, P.k, P.p, P.q, P.seed, P.cutoff, P.maxdim, P.mindim, &r, &L, &R,
                           nullptr));
-    qil_ctx_free(ctx, X);
+    tmp.own(L);
+    tmp.own(R);
+    tmp.free(X);
     if (defer && depth + 1 == defer_depth) {
-        defer->push_back(TtTask{L, lb, r, first, mid});
-        defer->push_back(TtTask{R, r, rb, mid + 1, last});
+        defer->push_back(TtTask{keep.own(tmp.give(L)), lb, r, first, mid});
+        defer->push_back(TtTask{keep.own(tmp.give(R)), r, rb, mid + 1, last});
         return QIL_OK;
     }
-    QIL_TRY(compress_tt(ctx, dt, L, lb, r, first, mid, P, sites, dims, depth + 1, defer, defer_depth));
-    QIL_TRY(compress_tt(ctx, dt, R, r, rb, mid + 1, last, P, sites, dims, depth + 1, defer, defer_depth));
+    QIL_TRY(compress_tt(ctx, dt, keep, tmp.give(L), lb, r, first, mid, P, sites, dims, depth + 1, defer, defer_depth));
+    QIL_TRY(compress_tt(ctx, dt, keep, tmp.give(R), r, rb, mid + 1, last, P, sites, dims, depth + 1, defer, defer_depth));
     return QIL_OK;
 }
 
@@ -741,11 +751,15 @@ int compress_tt(qil_context* ctx, int dt, void* X, int64_t lb, int64_t rb, int64
 // `par_depth` levels run level by level, the nodes of a level concurrently on the context's streams (qil_run_batch_on), and
 // the 2^par_depth sub-trees below them concurrently, each as a sequential recursion.  Same kernels on the same operands in
 // every order, so the MPS is bit-identical to the sequential recursion (QIL_ENCODE_PAR_DEPTH=0).
-static int compress_tt_root(qil_context* ctx, int dt, void* X, int64_t n, const EncodeParams& P, std::vector<void*>& sites,
-                            std::vector<int64_t>& dims) {
+// Who owns what: `keep` is the caller's scratch on the home context; X, every task that has not started and everything a level
+// has brought home are listed there.  A task that starts belongs to its node, whose scratch on the working context holds what
+// the node produces until the node has succeeded.  A block is in no scratch while qil_ctx_transfer moves it.
+static int compress_tt_root(qil_context* ctx, int dt, qil_scratch& keep, void* X, int64_t n, const EncodeParams& P,
+                            std::vector<void*>& sites, std::vector<int64_t>& dims) {
     const int par_depth = getenv("QIL_ENCODE_PAR_DEPTH") ? atoi(getenv("QIL_ENCODE_PAR_DEPTH")) : 3;   // tuning aid (read per call); 0 = off
     // (a context that is already one slot of a batch -- qil_signal_mps_batch -- encodes sequentially)
-    if (par_depth <= 0 || n < 16 || ctx->parent || ctx->lending) return compress_tt(ctx, dt, X, 1, 1, 0, n - 1, P, sites, dims);
+    if (par_depth <= 0 || n < 16 || ctx->parent || ctx->lending)
+        return compress_tt(ctx, dt, keep, keep.give(X), 1, 1, 0, n - 1, P, sites, dims);
     std::vector<TtTask> frontier{TtTask{X, 1, 1, 0, n - 1}};
     int s = QIL_OK;
     for (int level = 0; level <= par_depth && !frontier.empty() && s == QIL_OK; ++level) {
@@ -754,14 +768,23 @@ static int compress_tt_root(qil_context* ctx, int dt, void* X, int64_t n, const 
         std::vector<qil_context*> where((size_t)nt, ctx);
         std::vector<std::vector<int64_t>> tdims((size_t)nt, std::vector<int64_t>(dims.size(), 1));
         std::vector<std::vector<TtTask>> kids((size_t)nt);
+        std::vector<char> started((size_t)nt, 0);            // (the batch skips the tasks of a slot it could not set up)
         auto node = [&](int64_t j, qil_context* work) {
             const TtTask& t = frontier[(size_t)j];
-            const int st = whole ? compress_tt(work, dt, t.X, t.lb, t.rb, t.first, t.last, P, sites, tdims[(size_t)j])
-                                 : compress_tt(work, dt, t.X, t.lb, t.rb, t.first, t.last, P, sites, tdims[(size_t)j], 0,
-                                               &kids[(size_t)j], 1);
-            if (st != QIL_OK) (void)qil_ctx_free(work, t.X);     // "unknown block" if the recursion released it already
+            started[(size_t)j] = 1;
+            qil_scratch made(work);
+            const int st = compress_tt(work, dt, made, t.X, t.lb, t.rb, t.first, t.last, P, sites, tdims[(size_t)j], 0,
+                                       whole ? nullptr : &kids[(size_t)j], 1);
+            if (st == QIL_OK) {                                  // the level's collection takes over what the node made
+                for (int64_t i = t.first; i <= t.last; ++i) made.give(sites[(size_t)i]);
+                for (const TtTask& c : kids[(size_t)j]) made.give(c.X);
+            } else {                                             // `made` frees it
+                std::fill(sites.begin() + t.first, sites.begin() + t.last + 1, nullptr);
+                kids[(size_t)j].clear();
+            }
             return st;
         };
+        for (const TtTask& t : frontier) keep.give(t.X);
         if (nt == 1)
             s = node(0, ctx);
         else
@@ -776,29 +799,36 @@ static int compress_tt_root(qil_context* ctx, int dt, void* X, int64_t n, const 
         std::vector<TtTask> next;
         for (int64_t j = 0; j < nt; ++j) {
             const TtTask& t = frontier[(size_t)j];
+            if (!started[(size_t)j]) {
+                qil_ctx_transfer(where[(size_t)j], ctx, t.X);
+                keep.own(t.X);
+            }
             for (int64_t i = t.first; i <= t.last; ++i)
                 if (sites[(size_t)i] && (whole || t.first == t.last)) {
                     qil_ctx_transfer(where[(size_t)j], ctx, sites[(size_t)i]);
+                    keep.own(sites[(size_t)i]);
                     dims[(size_t)i] = tdims[(size_t)j][(size_t)i];
                     dims[(size_t)i + 1] = tdims[(size_t)j][(size_t)i + 1];
                 }
             for (const TtTask& c : kids[(size_t)j]) {
                 qil_ctx_transfer(where[(size_t)j], ctx, c.X);
+                keep.own(c.X);
                 next.push_back(c);
             }
         }
         frontier.swap(next);
     }
-    if (s != QIL_OK)
-        for (const TtTask& t : frontier) (void)qil_ctx_free(ctx, t.X);
     return s;
 }
 
 // _tensor_to_mps_svd (SignalConverters.jl:77-98).  The carried tensor X[(s_n..s_i), alpha] is viewed
 // for free as Y[low, (s_i, alpha)] = M^T (L x 2r): the Jacobi SVD rotates its 2r columns, the site
 // tensor is V_y^h permuted, and the carry S V^h is U_y S -- already in the layout of the next step.
-int svd_sweep(qil_context* ctx, int dt, void* X, int64_t n, const EncodeParams& P, std::vector<void*>& sites,
+// The sweep consumes X; the finished sites belong to `keep` (as in compress_tt).
+int svd_sweep(qil_context* ctx, int dt, qil_scratch& keep, void* X, int64_t n, const EncodeParams& P, std::vector<void*>& sites,
               std::vector<int64_t>& dims) {
+    qil_scratch tmp(ctx);
+    tmp.own(X);
     const size_t e = qil_elem_size(dt);
     int64_t r = 1;
     dims[0] = 1;
@@ -807,15 +837,17 @@ int svd_sweep(qil_context* ctx, int dt, void* X, int64_t n, const EncodeParams& 
         int64_t k = 0;
         void *UyS = nullptr, *Vyh = nullptr;
         QIL_TRY(svd_trunc_dev(ctx, dt, L, 2 * r, X, L, P.cutoff, true, P.maxdim, 1, 1, &k, &UyS, &Vyh, nullptr));
-        qil_ctx_free(ctx, X);
+        tmp.own(UyS);
+        tmp.own(Vyh);
+        tmp.free(X);
         void* A = nullptr;
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(r * 2 * k) * e, &A));
+        QIL_TRY(keep.alloc((size_t)(r * 2 * k) * e, &A));
         if (dt == QIL_C64)
             QIL_TRY((qil_klaunch<site_from_vh_k<c64>>(ctx, dim3(nblk(2 * r * k)), dim3(256), 0, (const c64*)Vyh, (long long)k, (int)r, (int)k, (c64*)A)));
         else
             QIL_TRY((qil_klaunch<site_from_vh_k<double>>(ctx, dim3(nblk(2 * r * k)), dim3(256), 0, (const double*)Vyh, (long long)k, (int)r, (int)k, (double*)A)));
         QIL_HIP(hipGetLastError());
-        qil_ctx_free(ctx, Vyh);
+        tmp.free(Vyh);
         sites[(size_t)i] = A;
         dims[(size_t)i + 1] = k;
         X = UyS;  // (L x k): X'[(s_n..s_{i+1}), alpha']
@@ -823,13 +855,12 @@ int svd_sweep(qil_context* ctx, int dt, void* X, int64_t n, const EncodeParams& 
     }
     // last site: X[(s_n), alpha] -> A[alpha, s_n, 1]  == chunk layout with rb = 1
     void* A = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(r * 2) * e, &A));
+    QIL_TRY(keep.alloc((size_t)(r * 2) * e, &A));
     if (dt == QIL_C64)
         QIL_TRY((qil_klaunch<site_from_chunk_k<c64>>(ctx, dim3(1), dim3(256), 0, (const c64*)X, (int)r, 1, (c64*)A)));
     else
         QIL_TRY((qil_klaunch<site_from_chunk_k<double>>(ctx, dim3(1), dim3(256), 0, (const double*)X, (int)r, 1, (double*)A)));
     QIL_HIP(hipGetLastError());
-    qil_ctx_free(ctx, X);
     sites[(size_t)n - 1] = A;
     dims[(size_t)n] = 1;
     return QIL_OK;
@@ -844,6 +875,7 @@ int signal_mps_impl(qil_context* ctx, const void* x, int64_t len, int dtype, con
     QIL_REQUIRE(len >= 1, QIL_EINVAL_LENGTH, "signal_mps: empty signal");
     QIL_TRY(qil_ctx_activate(ctx));
     qil_call_scope call_scope(ctx);
+    qil_scratch tmp(ctx);
     // _array_to_tensor (SignalConverters.jl:16-46): n = round(log2 N), zero-fill, normalise
     const int64_t n = std::max<int64_t>(1, (int64_t)std::llround(std::log2((double)len)));
     const int64_t N = 1LL << n;
@@ -854,7 +886,7 @@ int signal_mps_impl(qil_context* ctx, const void* x, int64_t len, int dtype, con
     const int ncomp = dtype == QIL_C64 ? 2 : 1;
     const size_t e = qil_elem_size(dtype);
     void* X = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)N * e, &X));
+    QIL_TRY(tmp.alloc((size_t)N * e, &X));
     // `x` may live on the host or already in HBM (unified addressing resolves the direction).  Samples that are ALREADY on this
     // device and fill the register (an n = 30 signal: 8.6 GB) are not copied first: the norm reads them in place and the scaled
     // copy is written in one pass (r05: copy + norm + scale in place moved 43 GB through HBM, 9 ms; now 26 GB)
@@ -872,7 +904,7 @@ int signal_mps_impl(qil_context* ctx, const void* x, int64_t len, int dtype, con
     const void* src = in_place ? x : X;
     void* part = nullptr;
     constexpr int kPartBlocks = 1024;
-    QIL_TRY(qil_ctx_alloc(ctx, kPartBlocks * sizeof(double), &part));
+    QIL_TRY(tmp.alloc(kPartBlocks * sizeof(double), &part));
     QIL_TRY((qil_klaunch<sumsq_partial_k>(ctx, dim3(kPartBlocks), dim3(256), 0, (const double*)src, (long long)(N * ncomp), (double*)part)));
     std::vector<double> ph(kPartBlocks);
     QIL_TRY(qil_read_back(ctx, ph.data(), part, kPartBlocks * sizeof(double)));   // also completes the upload of caller memory `x`
@@ -901,11 +933,9 @@ int signal_mps_impl(qil_context* ctx, const void* x, int64_t len, int dtype, con
             amp = std::ldexp(std::sqrt(ss), -sh);
         }
     }
-    qil_ctx_free(ctx, part);
-    if (!(amp > 0 && std::isfinite(amp) && std::isfinite(1.0 / amp))) {
-        qil_ctx_free(ctx, X);
-        return qil_fail(QIL_EINVAL_ARG, "signal_mps: signal has zero or non-finite norm");
-    }
+    tmp.free(part);
+    QIL_REQUIRE(amp > 0 && std::isfinite(amp) && std::isfinite(1.0 / amp), QIL_EINVAL_ARG,
+                "signal_mps: signal has zero or non-finite norm");
     if (in_place) {
         QIL_TRY((qil_klaunch<scale_copy_k>(ctx, dim3(nblk(N * ncomp)), dim3(256), 0, (const double*)x, (double*)X, (long long)(N * ncomp), 1.0 / amp)));
         QIL_HIP(qil_stream_sync(ctx));             // `x` is caller memory: read completely before anything else can return
@@ -914,21 +944,14 @@ int signal_mps_impl(qil_context* ctx, const void* x, int64_t len, int dtype, con
     QIL_HIP(hipGetLastError());
     std::vector<void*> sites((size_t)n, nullptr);
     std::vector<int64_t> dims((size_t)n + 1, 1);
-    int s;
-    if (n == 1) {
-        // single site: A[1, s, 1] = x_hat[s]
-        sites[0] = X;
-        s = QIL_OK;
-    } else if (P.method == QIL_METHOD_SVD) {
-        s = svd_sweep(ctx, dtype, X, n, P, sites, dims);
-    } else {
-        s = compress_tt_root(ctx, dtype, X, n, P, sites, dims);
-    }
-    if (s != QIL_OK) {
-        for (void* p : sites)
-            if (p) qil_ctx_free(ctx, p);
-        return s;
-    }
+    // the encoders consume X; the sites they finish are in tmp, on this context, until the handle adopts them
+    if (n == 1)
+        sites[0] = X;                                      // single site: A[1, s, 1] = x_hat[s]
+    else if (P.method == QIL_METHOD_SVD)
+        QIL_TRY(svd_sweep(ctx, dtype, tmp, tmp.give(X), n, P, sites, dims));
+    else
+        QIL_TRY(compress_tt_root(ctx, dtype, tmp, X, n, P, sites, dims));
+    for (void* p : sites) QIL_REQUIRE(p && tmp.give(p), QIL_EHIP, "signal_mps: internal error, a finished site is not in the call's scratch");
     qil_mps* psi = qil_mps_empty(ctx, n, dtype, 0, nullptr, amp);
     psi->dims = dims;
     for (size_t i = 0; i < sites.size(); ++i) qil_chain_adopt(psi, (int64_t)i, sites[i]);
@@ -1009,14 +1032,14 @@ struct zip_stage2_k {
 template <class TO, class TW, class TA>
 int zip_theta(qil_context* ctx, const void* Rm, const void* W, const void* A, int R, int Dl, int Dr, int cl, int cr,
               void** theta_out) {
+    qil_scratch tmp(ctx);
     void *X = nullptr, *th = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)R * Dl * 2 * cr * sizeof(TO), &X));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)R * 2 * cr * Dr * sizeof(TO), &th));
+    QIL_TRY(tmp.alloc((size_t)R * Dl * 2 * cr * sizeof(TO), &X));
+    QIL_TRY(tmp.alloc((size_t)R * 2 * cr * Dr * sizeof(TO), &th));
     QIL_TRY((qil_klaunch<zip_stage1_k<TO, TA>>(ctx, dim3(nblk((long long)R * Dl * 2 * cr)), dim3(256), 0, (const TO*)Rm, (const TA*)A, (TO*)X, R, Dl, cl, cr)));
     QIL_TRY((qil_klaunch<zip_stage2_k<TO, TW>>(ctx, dim3(nblk((long long)R * 2 * cr * Dr)), dim3(256), 0, (const TO*)X, (const TW*)W, (TO*)th, R, Dl, Dr, cr)));
     QIL_HIP(hipGetLastError());
-    qil_ctx_free(ctx, X);
-    *theta_out = th;
+    *theta_out = tmp.give(th);                          // (X goes back with tmp)
     return QIL_OK;
 }
 
@@ -1598,22 +1621,22 @@ extern "C" int qil_svd_trunc(qil_context* ctx, const void* A, int64_t m, int64_t
     QIL_REQUIRE(m >= 1 && n >= 1, QIL_EEMPTY, "svd: empty matrix");
     QIL_TRY(qil_ctx_activate(ctx));
     qil_call_scope call_scope(ctx);
+    qil_scratch tmp(ctx);
     const size_t e = qil_elem_size(dtype);
     void* dA = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(m * n) * e, &dA));
+    QIL_TRY(tmp.alloc((size_t)(m * n) * e, &dA));
     QIL_HIP(hipMemcpyAsync(dA, A, (size_t)(m * n) * e, hipMemcpyHostToDevice, qil_stream(ctx)));
     QIL_HIP(qil_stream_sync(ctx));
     int64_t r = 0;
     void *dU = nullptr, *dVh = nullptr;
     std::vector<double> Sv;
     QIL_TRY(svd_trunc_dev(ctx, dtype, m, n, dA, m, cutoff, cutoff >= 0, maxdim, mindim, 0, &r, &dU, &dVh, &Sv));
+    tmp.own(dU);
+    tmp.own(dVh);
     QIL_HIP(hipMemcpyAsync(U, dU, (size_t)(m * r) * e, hipMemcpyDeviceToHost, qil_stream(ctx)));
     QIL_TRY(qil_read_back(ctx, Vh, dVh, (size_t)(r * n) * e));
     for (int64_t i = 0; i < r; ++i) S[i] = Sv[(size_t)i];
     *rank = r;
-    qil_ctx_free(ctx, dA);
-    qil_ctx_free(ctx, dU);
-    qil_ctx_free(ctx, dVh);
     return QIL_OK;
 }
 
@@ -1627,38 +1650,37 @@ extern "C" int qil_rsvd(qil_context* ctx, const void* A, int64_t m, int64_t n, i
     QIL_REQUIRE(k >= 1 && p >= 0 && q >= 0, QIL_EINVAL_ARG, "rsvd: need k >= 1, p >= 0, q >= 0");
     QIL_TRY(qil_ctx_activate(ctx));
     qil_call_scope call_scope(ctx);
+    qil_scratch tmp(ctx);
     const size_t e = qil_elem_size(dtype);
     void *dA = nullptr, *Z = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(m * n) * e, &dA));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(m * n) * e, &Z));
+    QIL_TRY(tmp.alloc((size_t)(m * n) * e, &dA));
+    QIL_TRY(tmp.alloc((size_t)(m * n) * e, &Z));
     QIL_HIP(hipMemcpyAsync(dA, A, (size_t)(m * n) * e, hipMemcpyHostToDevice, qil_stream(ctx)));
     QIL_HIP(qil_stream_sync(ctx));
     QIL_TRY(qil_dev_transpose(ctx, dtype, 0, m, n, dA, m, Z, n));               // Z = A^T ("A row-major")
-    qil_ctx_free(ctx, dA);
-    if (maxdim <= 0) maxdim = k;                                                 // maxdim = k default (rsvd.jl:47)
+    tmp.free(dA);
+    if (maxdim <= 0) maxdim = k;                                                // maxdim = k default (rsvd.jl:47)
     int64_t r = 0;
     void *L = nullptr, *R = nullptr;
     std::vector<double> Sv;
     QIL_TRY(rsvd_rowmajor(ctx, dtype, m, n, Z, k, p, q, seed, cutoff, maxdim, mindim < 1 ? 1 : mindim, &r, &L, &R,
                           &Sv));
-    qil_ctx_free(ctx, Z);
+    tmp.own(L);
+    tmp.own(R);
+    tmp.free(Z);
     // L = U^T (r x m); R = (S V^h)^T (n x r).  Return U (m x r) and V^h (r x n) = (R diag(1/S))^T.
     std::vector<double> inv((size_t)r);
     for (int64_t i = 0; i < r; ++i) inv[(size_t)i] = Sv[(size_t)i] > 0 ? 1.0 / Sv[(size_t)i] : 0.0;
     QIL_TRY(qil_dev_scale(ctx, dtype, 1, n, r, R, n, inv.data()));
     void *dU = nullptr, *dVh = nullptr;
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(m * r) * e, &dU));
-    QIL_TRY(qil_ctx_alloc(ctx, (size_t)(r * n) * e, &dVh));
+    QIL_TRY(tmp.alloc((size_t)(m * r) * e, &dU));
+    QIL_TRY(tmp.alloc((size_t)(r * n) * e, &dVh));
     QIL_TRY(qil_dev_transpose(ctx, dtype, 0, r, m, L, r, dU, m));
     QIL_TRY(qil_dev_transpose(ctx, dtype, 0, n, r, R, n, dVh, r));
     QIL_HIP(hipMemcpyAsync(U, dU, (size_t)(m * r) * e, hipMemcpyDeviceToHost, qil_stream(ctx)));
     QIL_TRY(qil_read_back(ctx, Vh, dVh, (size_t)(r * n) * e));
     for (int64_t i = 0; i < r; ++i) S[i] = Sv[(size_t)i];
     *rank = r;
-    qil_ctx_free(ctx, L);
-    qil_ctx_free(ctx, R);
-    qil_ctx_free(ctx, dU);
-    qil_ctx_free(ctx, dVh);
     return QIL_OK;
 }
 
@@ -1699,10 +1721,11 @@ static int ztmps_from_sites(qil_context* ctx, const qil_mps* sig, double cutoff,
     const size_t e = qil_elem_size(dtype);
     qil_result_guard<qil_mps> zt_own(qil_mps_empty(ctx, 2 * n, dtype, 1, nullptr, sig->amplitude));
     qil_mps* const zt = zt_own.p;
+    qil_scratch tmp(ctx);
     for (int64_t i = 0; i < n; ++i) {                                             // :261-276
         const int64_t cl = sig->dims[(size_t)i], cr = sig->dims[(size_t)i + 1];
         void* T = nullptr;
-        QIL_TRY(qil_ctx_alloc(ctx, (size_t)(4 * cl * cr) * e, &T));
+        QIL_TRY(tmp.alloc((size_t)(4 * cl * cr) * e, &T));
         if (dtype == QIL_C64)
             QIL_TRY((qil_klaunch<fuse_delta_k<c64>>(ctx, dim3(nblk(4 * cl * cr)), dim3(256), 0, (const c64*)sig->site[(size_t)i], (int)cl, (int)cr, (c64*)T)));
         else
@@ -1710,7 +1733,7 @@ static int ztmps_from_sites(qil_context* ctx, const qil_mps* sig, double cutoff,
         int64_t r = 0;
         void *U = nullptr, *SV = nullptr;
         QIL_TRY(svd_trunc_dev(ctx, dtype, 2 * cl, 2 * cr, T, 2 * cl, cutoff, true, maxdim, 1, 2, &r, &U, &SV, nullptr));
-        qil_ctx_free(ctx, T);
+        tmp.free(T);
         qil_chain_adopt(zt, 2 * i, U);        // core_main [b_{i-1}, s_main, c]
         qil_chain_adopt(zt, 2 * i + 1, SV);   // core_copy [c, s_copy, b_i]
         zt->dims[(size_t)(2 * i)] = cl;

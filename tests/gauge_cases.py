@@ -64,7 +64,7 @@ def shape_class(m, k, dtype):
     kk, rows, e = min(m, k), max(m, k), 16 if dtype == "c64" else 8
     if kk < 17:                                                        # svd_left_mid, `k < 17`, qil_linalg.hip:3441
         return "general"
-    if kk >= 640:                                                      # svd_left_mid `k >= 640` :3441, bj_min :3887, qil_truncate.hip:170
+    if kk >= 640:                                                      # svd_left_mid `k >= 640` :3441, bj_min :3887, svd_trunc_dev in qil_truncate.hip
         return "big"
     if kk < 49:                                                        # fused_below, qil_linalg.hip:3442-3449
         if ((rows | 1) * kk + (kk | 1) * kk) * e <= 150 * 1024 and rows * kk <= 1 << 19:
@@ -78,7 +78,7 @@ def _route(kind, m, k, dtype, cert, rank):
     """The label a case is aimed at, from its kind and shape class."""
     cls, kk = shape_class(m, k, dtype), min(m, k)
     if kind == "deficient" and kk >= 384 and rank <= 128:
-        return "lowrank"                                               # svd_trunc_lowrank, qil_truncate.hip:97-132
+        return "lowrank"                                               # svd_trunc_lowrank in qil_truncate.hip
     if cls == "general":
         return "general"
     if cls == "big":
@@ -391,19 +391,19 @@ def predicted(name):
     margins, ev = {}, set()
     tall = m >= k
     Mt = M if tall else M.conj().T                                                # the tall orientation
-    cert_cutoff = c.cutoff if (c.cutoff > 0 and (c.maxdim is None or kk <= c.maxdim)) else 0.0     # cert_cutoff, qil_truncate.hip:169
-    deflate = min(1e-6 * c.cutoff, 1e-18)                                         # deflate, qil_truncate.hip:234
+    cert_cutoff = c.cutoff if (c.cutoff > 0 and (c.maxdim is None or kk <= c.maxdim)) else 0.0     # cert_cutoff of svd_trunc_dev
+    deflate = min(1e-6 * c.cutoff, 1e-18)                                         # deflate of svd_trunc_dev
     cls = shape_class(m, k, c.dtype)
 
     def done(rounds=None):
         return tuple(x for x in LABELS if x in ev), rounds, margins
 
-    if cert_cutoff > 0 and kk >= 640:                                             # qil_truncate.hip:170-212
+    if cert_cutoff > 0 and kk >= 640:                                             # svd_trunc_dev, the certificate
         if c.cert and _certificate(_triangular(Mt), kk, cert_cutoff, margins, "certificate (>= 640)"):
             ev.add("cert-640")
             return done()
         ev.add("cert-declined")
-    if kk >= 384:                                                                 # svd_trunc_lowrank, qil_truncate.hip:97-138
+    if kk >= 384:                                                                 # svd_trunc_lowrank
         w = reference(name).sigma ** 2
         for ks in (128, 256):
             if ks * 3 > kk:
