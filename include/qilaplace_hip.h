@@ -181,6 +181,7 @@ QIL_API int qil_coefficient_marginal_batch(const qil_mps* psi, int64_t nb, const
  * per tensor for all rows and a kernel that combines each row's two slices; QIL_PRODUCT_ROUTE=chain / gemm (read per call)
  * forces one where it fits. */
 #define QIL_PRODUCT_CHAIN_MAX_BOND 1024
+#define QIL_MPO_ENTRY_CHAIN_MAX_BOND 1024   /* qil_mpo_entry_batch's one-launch route, below */
 QIL_API int qil_product_batch(const qil_mps* psi, int64_t nb, const double* v, double* out);
 /* <bits| W psi> without materialising W*psi (same numbers as
  * qil_coefficient_batch(qil_apply(W, psi))).                                      */
@@ -405,6 +406,65 @@ QIL_API int qil_mpo_inner(const qil_mpo* V, const qil_mpo* W, double* out);
  * Deliberately not here: the lazy form (a slice of W psi without forming it), a batch of specs in one call, Born marginals
  * (tracing a site in |psi|^2).                                                                                            */
 QIL_API int qil_mps_restrict(const qil_mps* psi, const uint8_t* spec, qil_mps** out);
+
+/* ------------------------------------------------------------------ operator read-outs (no reference counterpart) */
+/* Rows, columns, diagonals and entries of an operator on its own bonds, O(n D^2) per number: no basis state, no qil_apply and
+ * no product of bond chi D is formed.  A spec gives two bytes per tensor, (in_i, out_i), for the legs of W_i[a, s_in, s_out, b]:
+ *   0 / 1     fixes the leg's bit;  2 sums the leg;  3 keeps it (qil_mpo_slice only);
+ *   (4, 4)    traces the site, sum_s W_i[:, s, s, :];  (5, 5) keeps its diagonal, A[:, s, :] = W_i[:, s, s, :] (qil_mpo_slice
+ *             only).  4 and 5 tie the legs and must stand in both bytes of a site.
+ * Slice (s_in, s_out) of a site is the D_l x D_r matrix at offset D_l (s_in + 2 s_out) with leading dimension 4 D_l.
+ *   removed   a site that keeps no leg is the D_l x D_r factor S_i, the sum of 1, 2 or 4 slices added in ascending
+ *             s_in + 2 s_out, left-associated, in the operand load; no S_i goes to HBM on the LDS routes.
+ *   kept      a site that keeps exactly one leg (3 in exactly one byte, or (5, 5)) is the MPS-shaped tensor whose slice s is one
+ *             slice of W_i, or the sum of two where the other leg is summed.
+ *
+ * qil_mpo_entry_batch: out[r] = prod_i S_i(r) for nb rows; spec: host, nb x n_tensors x 2 bytes, row-major; out: host, nb complex
+ * values (re, im) for either dtype -- a real operator is contracted in real arithmetic and gives an imaginary part of exactly
+ * zero.  Allowed are 0, 1, 2 and (4, 4): all-fixed rows are the entries W[in, out], 2 gives row sums, column sums and the sum
+ * of all entries, (4, 4) partial traces and the trace.  In exact arithmetic row r depends on (W, row r) only; its rounding
+ * depends on the route, and the route auto takes depends on nb (below).
+ * Routes: "chain", possible while every bond is <= QIL_MPO_ENTRY_CHAIN_MAX_BOND: one launch, one workgroup per row, the carry a
+ * row vector in LDS (two buffers), v <- v S_i left to right.  "gemm", at any bonds: per tensor one f64-MFMA GEMM of the
+ * nb x D_l carry with the site as the plain D_l x 4 D_r matrix it is in memory, and a kernel that adds each row's slices of the
+ * product (qil_product_batch's second route with four slices), rows in chunks under 64 MiB of temporaries.  That route adds
+ * the slices AFTER the product, so its rounding differs from the chain's.
+ * Bits: on the chain route, forced or chosen, a row's result is bit-identical alone, in any batch, and from run to run.  On
+ * the gemm route it is bit-identical from run to run for the same batch.  Under auto the same row may take the chain in a small
+ * batch and the GEMMs in a large one; force a route where bits must not depend on nb.
+ * Auto: the chain while every bond is <= 64 and nb * bond^2 < 2^21 (bond: the widest), the GEMMs otherwise -- the measured
+ * crossover at 24 tensors, chain / gemm in ms (f64): 64 rows, bond 16: 0.09 / 0.21, bond 64: 0.25 / 0.22, bond 96: 0.47 / 0.23,
+ * bond 512: 5.0 / 0.39; 1024 rows, bond 32: 0.17 / 0.25, bond 64: 0.34 / 0.27; 4096 rows, bond 16: 0.31 / 0.40, bond 32:
+ * 0.44 / 0.52, bond 64: 1.02 / 0.62, bond 512: 12.3 / 3.8 (c64 alike, MEASUREMENTS.md section 27).  Every workgroup of the
+ * chain streams the whole operator, so the rule keeps it to the calls it wins or loses by less than a quarter.
+ * QIL_MPO_ENTRY_ROUTE=chain|gemm, read per call, forces a route; chain only where the bonds fit.  Integer-valued operands
+ * whose partial sums stay below 2^53 give the exact integer on both routes.
+ * Errors, all before the context is activated: QIL_EINVAL_ARG ("mpo_entry_batch: null argument") for a null W or, when nb > 0,
+ * a null spec or out; QIL_EINVAL_ARG for nb < 0; QIL_EINVAL_CONFIG for a value 3, 5 or above 5 and for a 4 that is not in both
+ * bytes of its site (the message names the row and the tensor).  nb = 0 is a no-op.  Nothing but `out` outlives the call, also
+ * when an allocation fails midway.                                                                                          */
+QIL_API int qil_mpo_entry_batch(const qil_mpo* W, int64_t nb, const uint8_t* spec, double* out);
+/* qil_mpo_slice: the chain of the KEPT tensors of spec (host, n_tensors x 2 bytes), a state: a column of W (in fixed, out kept:
+ * W applied to a basis state), a row (out fixed, in kept: the functional that produces one transform value), the diagonal (all
+ * (5, 5): the inverse of qil_mpo_diagonal), W applied to the all-ones signal (in summed, out kept), and every mixture.  Runs of
+ * removed sites are absorbed exactly as in qil_mps_restrict: an interior or leading run p..q goes into the kept tensor on its
+ * right as M = ((S_p S_p+1) ...); a trailing run goes from the right into the last kept tensor as c = S_p (... S_q),
+ * A'_k[:, s] = A_k[:, s, :] c; a last kept tensor that takes both is M (A_k c); runs of length 1 are read in place.
+ *   result    W's dtype, amplitude 1.0, the kept sites' ids, bonds = the parent's right bonds of the kept sites but the last;
+ *             paired = 1 iff W is paired and whole (main_i, copy_i) pairs are kept.
+ *   exactness a kept tensor that absorbs nothing is the gather of W's slices bit for bit, where a leg is summed the one IEEE
+ *             addition; results are bit-identical from run to run.
+ * One grouped launch writes all kept tensors, every element exactly once; a kept tensor that absorbs a run is 16 x 16 f64-MFMA
+ * tiles.  Runs of length >= 2 and trailing runs go in one further launch, one workgroup per run with the running product in
+ * LDS, while every bond the run touches is <= 96 (f64) / 64 (c64): two buffers within the 160 KiB of a CU, the limits of
+ * qil_mps_restrict; wider runs go through the GEMM with multi-term factors materialised.  One call may mix the routes; their
+ * roundings differ.  Nothing but the result outlives the call, also when an allocation fails midway.
+ * Errors, all before the context is activated: QIL_EINVAL_ARG ("mpo_slice: null argument") first; QIL_EINVAL_CONFIG for a value
+ * above 5, for 4 / 5 in one byte of a site only, for a site (3, 3) ("keeps both legs: sub-operators are not built") and for a
+ * spec that keeps no site ("that number is what mpo_entry_batch returns").
+ * Deliberately not here: sub-operators (sites that keep both legs), the lazy form (a slice of a product of operators without
+ * forming it), a device-resident out for the entries.                                                                     */
+QIL_API int qil_mpo_slice(const qil_mpo* W, const uint8_t* spec, qil_mps** out);
 
 /* ------------------------------------------------------------------ Born weights (no reference counterpart) */
 /* Energy read-out: out[r] = amplitude^2 * sum over the configurations x that match row r of |psi_x|^2 -- the power in a

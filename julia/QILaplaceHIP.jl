@@ -21,7 +21,7 @@ export DeviceMPS, DeviceMPO, to_device, to_host, signal_mps_device, marginal, mp
     compress_mpo!, build_dt_mpo_batch, build_qft_mpo_device, build_zt_qft_chain_device, apply_coefficient_sweep, apply!, rsvd_device, svd_device,
     Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm, sample, top_k,
     hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress, restrict, weight_batch, apply_weight_batch, apply_sample, apply_top_k, bond_spectra,
-    signal_mps_cross, ztmps_from_mps, product_batch, mpo_linear_combination, mpo_inner
+    signal_mps_cross, ztmps_from_mps, product_batch, mpo_linear_combination, mpo_inner, mpo_entry_batch, mpo_slice
 
 const LIB = get(ENV, "QILHIP_LIB", "libqilhip.so")
 
@@ -394,6 +394,35 @@ function restrict(psi::DeviceMPS, spec::AbstractVector{<:Integer})
     p = Ref{Cint}(0)
     check(ccall((:qil_mps_is_paired, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}), r[], p))
     return finalizer(_free!, DeviceMPS(r[], psi.sites[findall(==(3), sp)], p[] != 0))
+end
+# operator read-outs (no reference counterpart).  A spec gives (in, out) per tensor for the legs of W_i[a, s_in, s_out, b]: 0 / 1 fixes
+# the leg's bit, 2 sums it, 3 keeps it; (4, 4) traces the site, (5, 5) keeps its diagonal.  mpo_entry_batch: specs nb x n_tensors x 2
+# with values 0, 1, 2 and (4, 4); one number per row (entries, row / column sums, partial traces), on the operator's own bonds
+function mpo_entry_batch(W::DeviceMPO, specs::AbstractArray{<:Integer,3})
+    nb, n, two = size(specs)
+    (n == length(W.sites) && two == 2) || throw(ArgumentError("mpo_entry_batch: expected $(length(W.sites)) x 2 entries per row, got $n x $two"))
+    all(s -> 0 <= s <= 2 || s == 4, specs) || throw(ArgumentError("mpo_entry_batch: spec value outside {0, 1, 2, 4}"))
+    all(specs[:, :, 1] .== specs[:, :, 2] .|| (specs[:, :, 1] .!= 4 .&& specs[:, :, 2] .!= 4)) ||
+        throw(ArgumentError("mpo_entry_batch: 4 (trace) must stand in both bytes of a site"))
+    sp = Array{UInt8,3}(permutedims(specs, (3, 2, 1)))                         # the ABI's row-major nb x n x 2
+    out = Vector{ComplexF64}(undef, nb)
+    nb == 0 && return out
+    GC.@preserve sp out check(ccall((:qil_mpo_entry_batch, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{Cdouble}), W.h, nb, sp,
+                                    Ptr{Cdouble}(pointer(out))))
+    return _is_complex(W) ? out : real.(out)
+end
+# mpo_slice: spec n_tensors x 2; the chain of the kept tensors (3 in exactly one byte of a site, or (5, 5)) as a state with
+# amplitude 1: a column (in fixed, out kept), a row (out fixed, in kept), the diagonal (all (5, 5)), W on the all-ones signal
+function mpo_slice(W::DeviceMPO, spec::AbstractMatrix{<:Integer})
+    size(spec) == (length(W.sites), 2) || throw(ArgumentError("mpo_slice: expected $(length(W.sites)) x 2 entries, got $(size(spec))"))
+    all(s -> 0 <= s <= 5, spec) || throw(ArgumentError("mpo_slice: spec value outside [0,5]"))
+    sp = Matrix{UInt8}(permutedims(spec))                                      # the ABI's row-major n x 2
+    keep = [i for i in 1:size(spec, 1) if spec[i, 1] == 5 || ((spec[i, 1] == 3) != (spec[i, 2] == 3))]
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve sp check(ccall((:qil_mpo_slice, LIB), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Ref{Ptr{Cvoid}}), W.h, sp, r))
+    p = Ref{Cint}(0)
+    check(ccall((:qil_mps_is_paired, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}), r[], p))
+    return finalizer(_free!, DeviceMPS(r[], W.sites[keep], p[] != 0))
 end
 # Born weights (no reference counterpart).  specs: nb x n_tensors, 0 / 1 fixes the tensor's bit, 2 traces the site in |psi|^2;
 # returns amplitude^2 * sum |psi_x|^2 over the configurations that match each row (band power, row energy, bit probability)

@@ -21,7 +21,8 @@ from .ops import (apply, apply_compress, apply_compress_batch, mpo_compress, com
                   truncation_error_bounds, required_maxdim, sample, apply_sample, top_k, apply_top_k, hadamard, hadamard_compress, diagonal_mpo, adjoint, convolve, correlate,
                   power_spectrum, linear_combination, linear_combination_compress, add, sub, scale, exponential_tensors,
                   mpo_linear_combination, mpo_linear_combination_compress, mpo_add, mpo_sub, mpo_scale, mpo_inner, mpo_norm,
-                  mpo_distance, mpo_trace,
+                  mpo_distance, mpo_trace, mpo_entry_batch, mpo_slice, mpo_entries, mpo_entry, mpo_to_matrix, mpo_column, mpo_row,
+                  mpo_diagonal_state, mpo_column_sums, mpo_row_sums,
                   exponential_mps, exponential_sum, restrict, zt_row, zt_column, copy_marginal, weight_batch, weight, bit_probabilities,
                   range_weight, weight_quantiles, zt_row_weights, zt_column_weights, apply_weight_batch, apply_weight,
                   apply_bit_probabilities, apply_range_weight, apply_weight_quantiles, apply_zt_row_weights, apply_zt_column_weights, canonicalize, compress, signal_mps, signal_ztmps, signal_mps_batch,
@@ -44,7 +45,8 @@ __all__ = [
     "hadamard", "hadamard_compress", "diagonal_mpo", "adjoint", "convolve", "correlate", "power_spectrum",
     "linear_combination", "linear_combination_compress", "add", "sub", "scale", "exponential_tensors", "exponential_mps",
     "mpo_linear_combination", "mpo_linear_combination_compress", "mpo_add", "mpo_sub", "mpo_scale", "mpo_inner", "mpo_norm",
-    "mpo_distance", "mpo_trace", "shift_mpo_tensors", "build_shift_mpo", "fir_mpo",
+    "mpo_distance", "mpo_trace", "mpo_entry_batch", "mpo_slice", "mpo_entries", "mpo_entry", "mpo_to_matrix", "mpo_column",
+    "mpo_row", "mpo_diagonal_state", "mpo_column_sums", "mpo_row_sums", "shift_mpo_tensors", "build_shift_mpo", "fir_mpo",
     "exponential_sum", "restrict", "zt_row", "zt_column", "copy_marginal",
     "weight_batch", "weight", "bit_probabilities", "range_weight", "weight_quantiles", "zt_row_weights", "zt_column_weights",
     "apply_weight_batch", "apply_weight", "apply_bit_probabilities", "apply_range_weight", "apply_weight_quantiles", "apply_zt_row_weights",

@@ -150,6 +150,8 @@ PROTOTYPES = {
     "qil_mpo_sum": [_pvp, _i64, _pdbl, _pvp],
     "qil_mpo_inner": [_vp, _vp, _pdbl],
     "qil_mps_restrict": [_vp, _pu8, _pvp],
+    "qil_mpo_entry_batch": [_vp, _i64, _pu8, _pdbl],
+    "qil_mpo_slice": [_vp, _pu8, _pvp],
     "qil_weight_batch": [_vp, _i64, _pu8, _pdbl],
     "qil_apply_weight_batch": [_vp, _vp, _i64, _pu8, _pdbl],
     "qil_apply_sample": [_vp, _vp, _i64, _u64, _pdbl, _pu8, _pdbl],

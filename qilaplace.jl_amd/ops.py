@@ -13,6 +13,9 @@
                      reference counterpart)
   mpo_linear_combination, mpo_inner   sums and Frobenius overlaps of operators, with mpo_norm / mpo_distance / mpo_trace and
                      `+`, `-`, `c *` on the MPO classes on top of them (no reference counterpart)
+  mpo_entry_batch, mpo_slice   numbers and state-valued slices of an operator on its own bonds, with mpo_entries / mpo_to_matrix /
+                     mpo_column / mpo_row / mpo_diagonal_state / mpo_column_sums / mpo_row_sums on top of them (no reference
+                     counterpart)
   canonicalize       src/mps.jl:787-847, 866-901   (Julia: canonicalize!)
   compress           src/mps.jl:913-999            (Julia: compress!)
   signal_mps         src/signals/SignalConverters.jl:228-233
@@ -1243,6 +1246,163 @@ def mpo_trace(W):
     _require_mpo(W, "mpo_trace")
     eye = type(W).identity(len(W), sites=W.site_ids, ctx=W.ctx)
     return mpo_inner(eye, W)
+
+
+# ---------------------------------------------------------------- operator read-outs
+TIE, DIAG = 4, 5          # both legs of a site tied: traced (mpo_entry_batch, mpo_slice) / its diagonal kept (mpo_slice)
+
+
+def _mpo_spec(W, spec, what, ndim):
+    """A spec of `W` as contiguous uint8 ([nb,] n_tensors, 2), checked for shape, range 0 .. 5 and whole ties."""
+    _require_mpo(W, what)
+    n = _ntensors(W)
+    sp = np.asarray(spec)
+    if sp.ndim != ndim or sp.shape[-2:] != (n, 2):
+        raise ValueError(f"{what}: expected {n} x 2 entries, got {sp.shape}")
+    if sp.dtype.kind not in "iub":
+        raise TypeError(f"{what}: the spec must hold integers")
+    if sp.size and (sp.min() < 0 or sp.max() > DIAG):
+        bad = int(sp[(sp < 0) | (sp > DIAG)][0])
+        raise ValueError(f"{what}: spec value {bad} outside [0,5]")
+    tied = sp >= TIE
+    if np.any(tied[..., 0] != tied[..., 1]) or np.any((sp[..., 0] != sp[..., 1]) & tied[..., 0]):
+        raise ValueError(f"{what}: 4 (TIE) and 5 (DIAG) must stand in both bytes of a site")
+    return np.ascontiguousarray(sp, dtype=np.uint8)
+
+
+def mpo_entry_batch(W, spec):
+    """One number per row of `spec` (nb, n_tensors, 2), read on the operator's own bonds (qil_mpo_entry_batch): per tensor the
+    pair (in, out) for the legs of W_i[a, s_in, s_out, b], FIX0 / FIX1 fixes the leg's bit, SUM sums it, (TIE, TIE) traces the
+    site.  All-fixed rows are the entries W[in, out]; SUM gives row sums, column sums and the sum of all entries; TIE partial
+    traces and the trace.  float for a real operator, complex otherwise."""
+    sp = _mpo_spec(W, spec, "mpo_entry_batch", 3)
+    if sp.size and np.any((sp == FREE) | (sp == DIAG)):
+        raise ValueError("mpo_entry_batch: a kept leg (3) or a kept diagonal (5) makes no number; mpo_slice returns that state")
+    nb = sp.shape[0]
+    out = np.zeros(nb, dtype=np.complex128)
+    L.check(L.lib.qil_mpo_entry_batch(W.handle, nb, sp.ctypes.data_as(C.POINTER(C.c_uint8)), out.ctypes.data_as(L._pdbl)))
+    return out if W.dtype == np.complex128 else out.real.copy()
+
+
+def mpo_slice(W, spec):
+    """The part of `W` that agrees with `spec` (n_tensors, 2), as a state (qil_mpo_slice): per tensor (in, out); a site keeps
+    exactly one leg (FREE in one byte, or (DIAG, DIAG) for its diagonal) or none (FIX0 / FIX1 / SUM per leg, (TIE, TIE) traced);
+    removed sites are absorbed into their kept neighbours as in `restrict`.  The result has W's dtype, amplitude 1, the kept
+    sites' ids and no bond larger than the parent's; a ZTMPS when W is paired and whole (main_i, copy_i) pairs are kept, a
+    SignalMPS otherwise.  A spec that keeps no site is a number: `mpo_entry_batch` returns it."""
+    sp = _mpo_spec(W, spec, "mpo_slice", 2)
+    if np.any((sp[:, 0] == FREE) & (sp[:, 1] == FREE)):
+        raise ValueError("mpo_slice: a site (3, 3) keeps both legs: sub-operators are not built")
+    if not np.any((sp == FREE) | (sp == DIAG)):
+        raise ValueError("mpo_slice: the spec keeps no site; that number is what mpo_entry_batch returns")
+    h = C.c_void_p()
+    L.check(L.lib.qil_mpo_slice(W.handle, sp.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(h)))
+    paired = C.c_int()
+    status = L.lib.qil_mps_is_paired(h, C.byref(paired))
+    if status != L.QIL_OK:                                # no container owns the handle yet
+        L.lib.qil_mps_destroy(h)
+        L.check(status)
+    return (ZTMPS if paired.value else SignalMPS)(ctx=W.ctx, _handle=h)
+
+
+def _mpo_config(W, cfg, what):
+    """One configuration of W's n_tensors legs as bits, in any form `_parse_config` takes."""
+    n = _ntensors(W)
+    bits = _parse_config(cfg, n)
+    if len(bits) != n:
+        raise ValueError(f"{what}: expected {n} entries, got {len(bits)}")
+    if any(b not in (0, 1) for b in bits):
+        raise ValueError(f"{what}: bit value outside [0,1]")
+    return np.asarray(bits, dtype=np.uint8)
+
+
+def _mpo_configs(W, cfgs, what):
+    """Configurations as an (m, n_tensors) bit array: an integer array (site 1 the most significant bit, as a single integer
+    configuration) or a sequence of configurations."""
+    n = _ntensors(W)
+    if isinstance(cfgs, (str, int, np.integer)):
+        cfgs = [cfgs]
+    a = cfgs if isinstance(cfgs, np.ndarray) else None
+    if a is not None and a.dtype.kind in "iu" and a.ndim == 1 and n <= 62:
+        if a.size and (a.min() < 0 or int(a.max()) >> n):
+            raise ValueError(f"{what}: index outside [0, 2^{n})")
+        return _msb_bits(a, n)
+    if a is not None and a.dtype.kind in "iu" and a.ndim == 2:
+        if a.shape[1] != n:
+            raise ValueError(f"{what}: expected {n} entries, got {a.shape[1]}")
+        if a.size and (a.min() < 0 or a.max() > 1):
+            raise ValueError(f"{what}: bit value outside [0,1]")
+        return a.astype(np.uint8)
+    return np.array([_mpo_config(W, c, what) for c in cfgs], dtype=np.uint8).reshape(-1, n)
+
+
+def mpo_entries(W, ins, outs):
+    """M[in, out] for every (in, out) of `ins` x `outs`, as a (len(ins), len(outs)) array in the convention of the dense
+    operator (out[o] = sum_in M[in, o] psi[in], site 1 the most significant bit): one `mpo_entry_batch` call.  Configurations
+    come in any form `coefficient` takes, or as integer arrays."""
+    _require_mpo(W, "mpo_entries")
+    bi, bo = _mpo_configs(W, ins, "mpo_entries"), _mpo_configs(W, outs, "mpo_entries")
+    n = _ntensors(W)
+    spec = np.empty((len(bi), len(bo), n, 2), dtype=np.uint8)
+    spec[..., 0] = bi[:, None, :]
+    spec[..., 1] = bo[None, :, :]
+    return mpo_entry_batch(W, spec.reshape(-1, n, 2)).reshape(len(bi), len(bo))
+
+
+def mpo_entry(W, i, o):
+    """The entry M[i, o] of the operator: (W psi)[o] = sum_i M[i, o] psi[i]."""
+    _require_mpo(W, "mpo_entry")
+    n = _ntensors(W)
+    spec = np.stack([_mpo_config(W, i, "mpo_entry"), _mpo_config(W, o, "mpo_entry")], axis=-1)
+    return mpo_entry_batch(W, spec.reshape(1, n, 2))[0]
+
+
+def mpo_to_matrix(W):
+    """The dense 2^n x 2^n matrix M[in, out] of an operator of at most 12 tensors: all 4^n entries through mpo_entry_batch."""
+    _require_mpo(W, "mpo_to_matrix")
+    n = _ntensors(W)
+    if n > 12:
+        raise ValueError(f"mpo_to_matrix: {n} tensors make 4^{n} entries; the dense form stops at 12 tensors")
+    idx = np.arange(2 ** n)
+    return mpo_entries(W, idx, idx)
+
+
+def _leg_spec(W, what, fixed_leg, value):
+    """(n_tensors, 2) spec with leg `fixed_leg` (0 = in, 1 = out) set to the bits of configuration `value` (or to SUM where
+    value is None) and the other leg kept"""
+    _require_mpo(W, what)
+    n = _ntensors(W)
+    spec = np.full((n, 2), FREE, dtype=np.uint8)
+    spec[:, fixed_leg] = SUM if value is None else _mpo_config(W, value, what)
+    return spec
+
+
+def mpo_column(W, cfg):
+    """W applied to the basis state `cfg`, as a state: the input legs fixed, the output legs kept.  In exact arithmetic
+    apply(W, basis state), at the operator's own bonds."""
+    return mpo_slice(W, _leg_spec(W, "mpo_column", 0, cfg))
+
+
+def mpo_row(W, cfg):
+    """The state r with r_j = M[j, cfg], so that (W psi)_cfg = sum_j r_j psi_j: the output legs fixed, the input legs kept.  The
+    functional that produces one transform value, usable as a matched filter against any number of signals."""
+    return mpo_slice(W, _leg_spec(W, "mpo_row", 1, cfg))
+
+
+def mpo_diagonal_state(W):
+    """The diagonal M[j, j] as a state (every site (DIAG, DIAG)): the inverse of `diagonal_mpo`."""
+    _require_mpo(W, "mpo_diagonal_state")
+    return mpo_slice(W, np.full((_ntensors(W), 2), DIAG, dtype=np.uint8))
+
+
+def mpo_column_sums(W):
+    """W applied to the all-ones signal, as a state: s_o = sum_j M[j, o]."""
+    return mpo_slice(W, _leg_spec(W, "mpo_column_sums", 0, None))
+
+
+def mpo_row_sums(W):
+    """The state s with s_j = sum_o M[j, o]: the sum of all output values as a functional of the input."""
+    return mpo_slice(W, _leg_spec(W, "mpo_row_sums", 1, None))
 
 
 def _dyadic_powers(z, n):
