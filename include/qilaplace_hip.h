@@ -258,6 +258,37 @@ QIL_API int qil_apply_inner(const qil_mps* phi, const qil_mpo* W, const qil_mps*
 /* norm(W psi) without materialising W psi: the same number as qil_norm(qil_apply(W, psi))
  * (without amplitude, as qil_norm / mps.jl:754-771).  (W, psi) pass the checks of qil_apply.              */
 QIL_API int qil_apply_norm(const qil_mpo* W, const qil_mps* psi, double* out);
+/* ------------------------------------------------------------------ environments (no reference counterpart) */
+/* The partial contraction the overlap verbs carry and never return: E[p, a, s], the contraction of `count` tensors of
+ * <phi|psi> (W null: a has extent 1) or <phi|W|psi> with the bond legs left open -- p the bond of phi, a of W, s of psi.  The
+ * conventions are qil_apply_inner's: the bra is conj(phi) and contracts the operator's s_out, the ket psi contracts s_in.
+ * QIL_ENV_LEFT walks tensors 1 .. count, the open legs are the bonds to the right of tensor `count`; QIL_ENV_RIGHT walks tensors
+ * n - count + 1 .. n, the open legs are the bonds to their left.  The amplitudes are NOT applied, as in qil_norm: count = n
+ * gives <phi|psi> or <phi|W psi> divided by amp_phi amp_psi, count = 0 gives [1].
+ * dims (three values) always receives (p, a, s).  out null: the size query, nothing else happens.  Otherwise out (host) receives p a s
+ * interleaved complex doubles, column-major [p, a, s], whatever the operand dtypes (all f64 / c64 mixes, contracted in c64 when
+ * any operand is complex).  The operands pass the checks of qil_inner (W null) or qil_apply_inner; for paired (ZTMPS) chains
+ * `count` counts tensors of the 2n chain, and n above is that chain's length.
+ * Routes: "chain", possible while both state bonds over the walked tensors are <= 16 and the operator's are
+ * <= QIL_ENV_CHAIN_MAX_OP_BOND: one launch, one workgroup, the environment in LDS for the whole walk in either direction;
+ * "gemm": the per-site f64-MFMA products of qil_inner / qil_apply_inner, on mirrored site copies for QIL_ENV_RIGHT, any bonds.
+ * The chain route is taken where it fits; QIL_ENV_ROUTE=chain / gemm forces one (read per call; the chain only where it fits).
+ * Errors, before the context is activated: QIL_EINVAL_ARG ("environment: null argument") for a null phi, psi or dims,
+ * QIL_EINVAL_ARG for a side that is neither 0 nor 1 and for a count outside [0, n]; then the operand errors of qil_inner /
+ * qil_apply_inner.  Every temporary belongs to the call; a failed call leaves nothing behind.                              */
+#define QIL_ENV_LEFT  0
+#define QIL_ENV_RIGHT 1
+#define QIL_ENV_CHAIN_MAX_OP_BOND 8   /* two ping-pong blocks of 2 * 16 * 8 * 16 c64 and one site's operands: 148 of 160 KiB of LDS */
+QIL_API int qil_environment(const qil_mps* phi, const qil_mpo* W, const qil_mps* psi, int side, int64_t count, double* out,
+                            int64_t* dims);
+/* Which route a qil_environment call takes: THE decision, not a copy of it -- qil_environment switches on the value this function
+ * returns.  Host only: no context, no GPU.  side, count: as in the call; phi_dims, psi_dims: the n + 1 bond dimensions of the two
+ * states, edges included; op_dims: the operator's, or null without one.  *route: 0 = the one-workgroup chain, 1 = the per-site
+ * GEMMs.  Only the bonds of the walked tensors count; QIL_ENV_ROUTE is honoured.  QIL_EINVAL_ARG for a null pointer, a side that
+ * is neither 0 nor 1 or a count outside [0, n].  (Declared here, beside the verb: the symbol set of qilaplace_hip_testing.h is
+ * pinned by tests/test_cabi_symbols.py.) */
+QIL_API int qil_environment_route(int side, int64_t count, int64_t n, const int64_t* phi_dims, const int64_t* psi_dims,
+                                  const int64_t* op_dims, int* route);
 /* Schmidt spectra of every bond (ITensors' svd(...).spec at every cut; no entry of the reference returns them).  S_out: host,
  * sum_k bond_k doubles; bond k (k = 1 .. N - 1 in tensor order, interleaved for paired chains) owns the bond_k slots that start
  * at the sum of the earlier bond dimensions, as qil_mps_bond_dims reports them at the time of the call.  Each block holds the

@@ -21,7 +21,7 @@ export DeviceMPS, DeviceMPO, to_device, to_host, signal_mps_device, marginal, mp
     compress_mpo!, build_dt_mpo_batch, build_qft_mpo_device, build_zt_qft_chain_device, apply_coefficient_sweep, apply!, rsvd_device, svd_device,
     Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm, sample, top_k,
     hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress, restrict, weight_batch, apply_weight_batch, apply_sample, apply_top_k, bond_spectra,
-    signal_mps_cross, ztmps_from_mps, product_batch, mpo_linear_combination, mpo_inner, mpo_entry_batch, mpo_slice
+    signal_mps_cross, ztmps_from_mps, product_batch, mpo_linear_combination, mpo_inner, mpo_entry_batch, mpo_slice, environment
 
 const LIB = get(ENV, "QILHIP_LIB", "libqilhip.so")
 
@@ -246,6 +246,23 @@ function inner(phi::DeviceMPS, W::DeviceMPO, psi::DeviceMPS)                   #
     v = zeros(Float64, 2)
     check(ccall((:qil_apply_inner, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cdouble}), phi.h, W.h, psi.h, v))
     return _overlap_value(v, phi, W, psi)
+end
+# environment: the partial contraction E[p, a, s] of `count` tensors of <phi|psi> (W = nothing: E[p, s]) or <phi|W|psi> with the bond
+# legs open -- side = :left walks tensors 1 .. count, :right the last `count`; amplitudes are not applied (as in norm); for a paired
+# chain `count` counts tensors of the 2n chain.  Two calls: the size query (out = NULL), then the values, column-major [p, a, s].
+function environment(phi::DeviceMPS, psi::DeviceMPS; W::Union{DeviceMPO,Nothing}=nothing, side::Symbol=:right,
+                     count::Integer=length(psi.sites))
+    side in (:left, :right) || throw(ArgumentError("environment: side must be :left or :right, got $(side)"))
+    0 <= count <= length(psi.sites) || throw(ArgumentError("environment: count $(count) outside [0, $(length(psi.sites))]"))
+    wh = W === nothing ? C_NULL : W.h
+    code = side == :left ? Cint(0) : Cint(1)
+    dims = zeros(Int64, 3)
+    check(ccall((:qil_environment, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Ptr{Cdouble}, Ptr{Int64}),
+                phi.h, wh, psi.h, code, Int64(count), C_NULL, dims))
+    out = Array{ComplexF64,3}(undef, dims[1], dims[2], dims[3])
+    GC.@preserve out check(ccall((:qil_environment, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Ptr{Cdouble}, Ptr{Int64}),
+                                 phi.h, wh, psi.h, code, Int64(count), Ptr{Cdouble}(pointer(out)), dims))
+    return W === nothing ? out[:, 1, :] : out
 end
 function apply_norm(W::DeviceMPO, psi::DeviceMPS)                              # norm(W * psi) without the product
     v = Ref{Cdouble}(0)

@@ -137,6 +137,7 @@ PROTOTYPES = {
     "qil_inner": [_vp, _vp, _pdbl],
     "qil_apply_inner": [_vp, _vp, _vp, _pdbl],
     "qil_apply_norm": [_vp, _vp, _pdbl],
+    "qil_environment": [_vp, _vp, _vp, _int, _i64, _pdbl, _pi64],
     "qil_bond_spectra": [_vp, _pdbl, _pdbl],
     "qil_mpo_bond_spectra": [_vp, _pdbl, _pdbl],
     "qil_sample": [_vp, _i64, _u64, _pdbl, _pu8, _pdbl],
@@ -183,6 +184,7 @@ PROTOTYPES = {
     "qil_gemm": [_vp, _int, _int, _int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64],
     "qil_gemm_plan": [_int, _int, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, C.POINTER(GemmPlanInfo)],
     "qil_readout_route": [_int, _int, _i64, _i64, _pi64, _pi64, _pint, _pi64],
+    "qil_environment_route": [_int, _i64, _i64, _pi64, _pi64, _pi64, _pint],
     "qil_gemm_batched_host": [_vp, _int, _int, _int, _i64, _i64, _i64, _pop, _pop, _pop, _i64, _int, _int, _pu8, _i64, _i64,
                               C.POINTER(C.c_int32), _i64],
     "qil_qr_positive": [_vp, _int, _i64, _i64, _vp, _vp, _vp],

@@ -4,7 +4,9 @@
 //   qil_put_mpo_site     returns the site itself where it already has that dtype
 //   qil_norm_env_ket /   the four-product environment step of |W psi|^2, E' = A^H ((E A) W) conj(Wr), on nslots packed environments
 //   qil_norm_env_bra
-//   qil_upload_bytes     caller memory into a block of the call's qil_scratch
+//   qil_overlap_env_step /        the environment steps of <phi|psi> and <phi|W psi> (qil_inner, qil_apply_inner, qil_environment):
+//   qil_apply_overlap_env_step    two and three products per site
+//   qil_upload_bytes    caller memory into a block of the call's qil_scratch
 //   qil_download         device memory to the caller, complete when it returns
 // Declared in qil_internal.h.  The f64 MFMA tile step and the small type helpers of the kernels are in qil_device_utils.h.
 #include "qil_internal.h"
@@ -135,6 +137,24 @@ int qil_norm_env_bra(qil_context* ctx, int dt, int64_t cl, int64_t cr, int64_t D
     b3.count = nslots * Dr * cr, b3.a_bs = cl * 2 * Dl, b3.c_bs = cl * 2 * Dr;
     QIL_TRY(qil_dev_gemm_batched(ctx, dt, 0, 3, cl, 2 * Dr, 2 * Dl, s2, cl, Wr, 2 * Dl, s1, cl, &b3));
     return qil_dev_gemm(ctx, dt, 2, 0, cr, nslots * Dr * Dr * cr, 2 * cl, As, 2 * cl, s1, 2 * cl, out, cr);
+}
+
+//   T[p, s, b]  = E A_psi,   E'[q, b] = A_phi^H T        (ph physical slices: 2 for states, 4 for operators)
+int qil_overlap_env_step(qil_context* ctx, int dt, int64_t ph, int64_t pl, int64_t pr, int64_t sl, int64_t sr, const void* Ap,
+                         const void* As, const void* E, void* T, void* En) {
+    // T (pl x ph sr) = E (pl x sl) * A_psi (sl x ph sr):  T[p, s, b]
+    QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, pl, ph * sr, sl, E, pl, As, sl, T, pl));
+    // E' (pr x sr) = A_phi^H ((ph pl) x pr)^H * T ((ph pl) x sr)
+    return qil_dev_gemm(ctx, dt, 2, 0, pr, sr, ph * pl, Ap, ph * pl, T, ph * pl, En, pr);
+}
+//   T1[p, a, s_in, beta] = E A_psi,   T2[p, s_out, b, beta] = T1_beta W (batch = beta),   E'[q, b, beta] = A_phi^H T2
+int qil_apply_overlap_env_step(qil_context* ctx, int dt, int64_t pl, int64_t pr, int64_t sl, int64_t sr, int64_t Dl, int64_t Dr,
+                               const void* Ap, const void* As, const void* Wd, const void* E, void* T1, void* T2, void* En) {
+    QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, pl * Dl, 2 * sr, sl, E, pl * Dl, As, sl, T1, pl * Dl));
+    qil_gemm_batch bt;                             // batch = beta
+    bt.count = sr, bt.a_bs = pl * 2 * Dl, bt.c_bs = pl * 2 * Dr;
+    QIL_TRY(qil_dev_gemm_batched(ctx, dt, 0, 0, pl, 2 * Dr, 2 * Dl, T1, pl, Wd, 2 * Dl, T2, pl, &bt));
+    return qil_dev_gemm(ctx, dt, 2, 0, pr, Dr * sr, 2 * pl, Ap, 2 * pl, T2, 2 * pl, En, pr);
 }
 
 int qil_upload_bytes(qil_scratch& tmp, const void* host, size_t bytes, void** dev) {

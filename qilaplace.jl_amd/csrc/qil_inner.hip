@@ -179,24 +179,10 @@ static int inner_gemm_raw(const qil_chain* phi, const qil_chain* psi, double h[2
         const void *Ap = nullptr, *As = nullptr;
         QIL_TRY(qil_site_operand(ctx, dt, phi, i, Pw, &Ap));
         QIL_TRY(qil_site_operand(ctx, dt, psi, i, Sw, &As));
-        // T (pl x ph sr) = E (pl x sl) * A_psi (sl x ph sr):  T[p, s, b]
-        QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, pl, ph * sr, sl, E, pl, As, sl, T, pl));
-        // E' (pr x sr) = A_phi^H ((ph pl) x pr)^H * T ((ph pl) x sr)
-        QIL_TRY(qil_dev_gemm(ctx, dt, 2, 0, pr, sr, ph * pl, Ap, ph * pl, T, ph * pl, En, pr));
+        QIL_TRY(qil_overlap_env_step(ctx, dt, ph, pl, pr, sl, sr, Ap, As, E, T, En));
         std::swap(E, En);
     }
     return read_scalar(ctx, dt, E, h);
-}
-
-// phi against psi (or against the product W psi, which has psi's chain shape): same context, register kind, length, sites
-static int check_overlap_pair(const qil_mps* phi, const qil_mps* psi) {
-    QIL_REQUIRE(phi->ctx == psi->ctx, QIL_EINVAL_ARG, "inner: MPS belong to different contexts");
-    QIL_REQUIRE(phi->paired == psi->paired, QIL_EINVAL_ARG, "inner: cannot mix paired and single-register operands");
-    QIL_REQUIRE(phi->n() == psi->n(), QIL_EINVAL_LENGTH,
-                "inner: MPS must have the same number of sites. Found length(phi)=%lld, length(psi)=%lld",
-                (long long)phi->n(), (long long)psi->n());
-    QIL_REQUIRE(phi->site_ids == psi->site_ids, QIL_EINVAL_SITES, "inner: MPS must have the same site indices.");
-    return QIL_OK;
 }
 
 static long long max_bond(const qil_chain* c) {
@@ -206,6 +192,17 @@ static long long max_bond(const qil_chain* c) {
 }
 
 }  // namespace
+
+// phi against psi (or against the product W psi, which has psi's chain shape): same context, register kind, length, sites
+int qil_check_overlap_pair(const qil_mps* phi, const qil_mps* psi) {
+    QIL_REQUIRE(phi->ctx == psi->ctx, QIL_EINVAL_ARG, "inner: MPS belong to different contexts");
+    QIL_REQUIRE(phi->paired == psi->paired, QIL_EINVAL_ARG, "inner: cannot mix paired and single-register operands");
+    QIL_REQUIRE(phi->n() == psi->n(), QIL_EINVAL_LENGTH,
+                "inner: MPS must have the same number of sites. Found length(phi)=%lld, length(psi)=%lld",
+                (long long)phi->n(), (long long)psi->n());
+    QIL_REQUIRE(phi->site_ids == psi->site_ids, QIL_EINVAL_SITES, "inner: MPS must have the same site indices.");
+    return QIL_OK;
+}
 
 int qil_check_pair(const char* verb, const qil_mpo* V, const qil_mpo* W) {
     QIL_REQUIRE(V->ctx == W->ctx, QIL_EINVAL_ARG, "%s: MPOs belong to different contexts", verb);
@@ -219,7 +216,7 @@ int qil_check_pair(const char* verb, const qil_mpo* V, const qil_mpo* W) {
 
 extern "C" int qil_inner(const qil_mps* phi, const qil_mps* psi, double* out) {
     QIL_REQUIRE(phi && psi && out, QIL_EINVAL_ARG, "inner: null argument");
-    QIL_TRY(check_overlap_pair(phi, psi));
+    QIL_TRY(qil_check_overlap_pair(phi, psi));
     qil_context* ctx = psi->ctx;
     QIL_TRY(qil_ctx_activate(ctx));
     qil_call_scope call_scope(ctx);
@@ -283,7 +280,7 @@ extern "C" int qil_norm(const qil_mps* psi, double* out) {
 extern "C" int qil_apply_inner(const qil_mps* phi, const qil_mpo* W, const qil_mps* psi, double* out) {
     QIL_REQUIRE(phi && W && psi && out, QIL_EINVAL_ARG, "apply_inner: null argument");
     QIL_TRY(qil_check_apply_operands(W, psi));
-    QIL_TRY(check_overlap_pair(phi, psi));
+    QIL_TRY(qil_check_overlap_pair(phi, psi));
     qil_context* ctx = psi->ctx;
     QIL_TRY(qil_ctx_activate(ctx));
     qil_call_scope call_scope(ctx);
@@ -320,11 +317,7 @@ extern "C" int qil_apply_inner(const qil_mps* phi, const qil_mpo* W, const qil_m
         QIL_TRY(qil_site_operand(ctx, dt, phi, i, Pw, &Ap));
         QIL_TRY(qil_site_operand(ctx, dt, psi, i, Sw, &As));
         QIL_TRY(qil_site_operand(ctx, dt, W, i, Ww, &Wd));
-        QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, pl * Dl, 2 * sr, sl, E, pl * Dl, As, sl, T1, pl * Dl));
-        qil_gemm_batch bt;                             // batch = beta
-        bt.count = sr, bt.a_bs = pl * 2 * Dl, bt.c_bs = pl * 2 * Dr;
-        QIL_TRY(qil_dev_gemm_batched(ctx, dt, 0, 0, pl, 2 * Dr, 2 * Dl, T1, pl, Wd, 2 * Dl, T2, pl, &bt));
-        QIL_TRY(qil_dev_gemm(ctx, dt, 2, 0, pr, Dr * sr, 2 * pl, Ap, 2 * pl, T2, 2 * pl, En, pr));
+        QIL_TRY(qil_apply_overlap_env_step(ctx, dt, pl, pr, sl, sr, Dl, Dr, Ap, As, Wd, E, T1, T2, En));
         std::swap(E, En);
     }
     double h[2];

@@ -410,6 +410,17 @@ inline int qil_norm_env_step(qil_context* ctx, int dt, int64_t cl, int64_t cr, i
     QIL_TRY(qil_norm_env_ket(ctx, dt, cl, cr, Dl, Dr, nslots, As, Wd, in, s1, s2));
     return qil_norm_env_bra(ctx, dt, cl, cr, Dl, Dr, nslots, As, Wr, s2, s1, out);
 }
+// The environment step of <phi|psi>: T = E A_psi, E' = A_phi^H T with E (pl x sl), E' (pr x sr) column-major and ph physical slices
+// per site (2 for states, 4 for operators); Ap, As: the sites in dt.  The mirrored (right-to-left) step is the same call with
+// pl <-> pr, sl <-> sr and the REVERSED operands.
+int qil_overlap_env_step(qil_context* ctx, int dt, int64_t ph, int64_t pl, int64_t pr, int64_t sl, int64_t sr, const void* Ap,
+                         const void* As, const void* E, void* T, void* En);
+// ... and of <phi|W psi>: T1 = E A_psi, T2_beta = T1_beta W, E' = A_phi^H T2 with E[p, a, s] (pl x Dl x sl); mirrored likewise
+int qil_apply_overlap_env_step(qil_context* ctx, int dt, int64_t pl, int64_t pr, int64_t sl, int64_t sr, int64_t Dl, int64_t Dr,
+                               const void* Ap, const void* As, const void* Wd, const void* E, void* T1, void* T2, void* En);
+// (qil_inner.hip) phi against psi (or against W psi, which has psi's chain shape) for the overlap verbs: context, paired flag
+// (QIL_EINVAL_ARG), length (QIL_EINVAL_LENGTH), site ids (QIL_EINVAL_SITES), under the name "inner"; touches no device
+int qil_check_overlap_pair(const struct qil_mps* phi, const struct qil_mps* psi);
 // `bytes` of caller memory into a new block of tmp (stream-synchronised: the source may go away when this returns)
 int qil_upload_bytes(qil_scratch& tmp, const void* host, size_t bytes, void** dev);
 // `bytes` of device memory to the caller, ordered after everything ctx has enqueued and complete on return (stream-synchronised)

@@ -16,6 +16,9 @@
   mpo_entry_batch, mpo_slice   numbers and state-valued slices of an operator on its own bonds, with mpo_entries / mpo_to_matrix /
                      mpo_column / mpo_row / mpo_diagonal_state / mpo_column_sums / mpo_row_sums on top of them (no reference
                      counterpart)
+  environment, esprit   the partial contraction <phi|...|psi> / <phi|W|...|psi> with open bond legs, and on top of it shift_pencil /
+                     esprit_from_pencil / esprit: the poles of a sum of exponentials from the bond basis, no scan (no reference
+                     counterpart)
   canonicalize       src/mps.jl:787-847, 866-901   (Julia: canonicalize!)
   compress           src/mps.jl:913-999            (Julia: compress!)
   signal_mps         src/signals/SignalConverters.jl:228-233
@@ -649,6 +652,57 @@ def apply_distance(phi, W, psi) -> float:
     nphi = phi.amplitude * norm(phi)
     nwpsi = psi.amplitude * apply_norm(W, psi)
     return _distance(nphi * nphi, nwpsi * nwpsi, inner(phi, W, psi))
+
+
+# ---------------------------------------------------------------- environments
+ENV_SIDES = {"left": 0, "right": 1}              # QIL_ENV_LEFT / QIL_ENV_RIGHT (include/qilaplace_hip.h)
+ENV_CHAIN_MAX_OP_BOND = 8                        # QIL_ENV_CHAIN_MAX_OP_BOND
+
+
+def environment(phi, psi, W=None, side="right", count=None):
+    """The partial contraction the overlap verbs carry and never return (qil_environment): `count` tensors of <phi|psi>, or of
+    <phi|W|psi> with an operator, with the bond legs left open.  side="left" walks tensors 1 .. count and leaves the bonds to
+    their right open, side="right" walks the last `count` tensors and leaves the bonds to their left open; count=None walks the
+    whole chain.  For a ZTMPS `count` counts tensors of the interleaved 2n chain.
+
+    Returns a complex128 array E[p, s] (p: the bond of phi, s: of psi), or E[p, a, s] with an operator (a: its bond).  The bra is
+    conj(phi) and contracts the operator's output leg, as in inner(phi, W, psi).  The amplitudes are NOT applied (as in `norm`):
+    count = all tensors gives inner(...) / (phi.amplitude * psi.amplitude), count = 0 gives [[1]]."""
+    _require_mps(phi, "environment")
+    _require_mps(psi, "environment")
+    if W is not None:
+        _require_operator(W, psi)
+    if side not in ENV_SIDES:
+        raise ValueError(f"environment: side must be 'left' or 'right', got {side!r}")
+    n = _ntensors(psi)
+    if count is None:
+        count = n
+    if isinstance(count, (bool, np.bool_)) or not isinstance(count, (int, np.integer)):
+        raise TypeError(f"environment: count must be an integer, got {type(count).__name__}")
+    if not 0 <= count <= n:
+        raise ValueError(f"environment: count {int(count)} outside [0, {n}]")
+    dims = (C.c_int64 * 3)()
+    wh = None if W is None else W.handle
+    L.check(L.lib.qil_environment(phi.handle, wh, psi.handle, ENV_SIDES[side], int(count), None, dims))
+    out = np.zeros(tuple(dims), dtype=np.complex128, order="F")
+    L.check(L.lib.qil_environment(phi.handle, wh, psi.handle, ENV_SIDES[side], int(count), out.ctypes.data_as(L._pdbl), dims))
+    return out if W is not None else out[:, 0, :]
+
+
+def environment_route(side, count, phi_dims, psi_dims, op_dims=None):
+    """Which route an `environment` call takes (needs no GPU): qil_environment_route, the host function
+    qil_environment switches on.  *_dims: the n + 1 bond dimensions, edges included.  Returns "CHAIN" or "GEMM"."""
+    pd, sd = np.ascontiguousarray(phi_dims, dtype=np.int64), np.ascontiguousarray(psi_dims, dtype=np.int64)
+    od = None if op_dims is None else np.ascontiguousarray(op_dims, dtype=np.int64)
+    if pd.ndim != 1 or pd.size < 1 or sd.shape != pd.shape or (od is not None and od.shape != pd.shape):
+        raise ValueError("environment_route: bond dimensions are n + 1 entries per chain")
+    if side not in ENV_SIDES:
+        raise ValueError(f"environment: side must be 'left' or 'right', got {side!r}")
+    route = C.c_int()
+    p64 = C.POINTER(C.c_int64)
+    L.check(L.lib.qil_environment_route(ENV_SIDES[side], int(count), pd.size - 1, pd.ctypes.data_as(p64), sd.ctypes.data_as(p64),
+                                        od.ctypes.data_as(p64) if od is not None else None, C.byref(route)))
+    return "CHAIN" if route.value == 0 else "GEMM"
 
 
 # ---------------------------------------------------------------- Schmidt spectra
@@ -1649,6 +1703,127 @@ def refine_frequencies(psi, f0, half_width=0.5, sigma=0.0, tol=1e-6):
     N = 2.0 ** len(psi)
     f = _golden_maximise(lambda x: np.abs(laplace_sum(psi, float(sigma), x / N)), f0 - half_width, f0 + half_width, float(tol))
     return f, laplace_sum(psi, float(sigma), f / N)
+
+
+# ---------------------------------------------------------------- ESPRIT on the bond basis: poles without a scan
+def _require_signal(psi, what):
+    if not isinstance(psi, SignalMPS):
+        raise TypeError(f"{what}: unsupported operand types")
+    if isinstance(psi, ZTMPS):
+        raise TypeError(f"{what}: unsupported operand types (a ZTMPS has no single sample register to shift; pass the SignalMPS)")
+
+
+def _low_register(psi, count, what):
+    """`count` as an int, after the range check: the low register has 1 .. n - 1 tensors (a cut inside the chain)."""
+    n = len(psi)
+    if isinstance(count, (bool, np.bool_)) or not isinstance(count, (int, np.integer)):
+        raise TypeError(f"{what}: count must be an integer, got {type(count).__name__}")
+    if not 1 <= count <= n - 1:
+        raise ValueError(f"{what}: count {int(count)} outside [1, {n - 1}] (the low register is cut off inside the chain)")
+    return int(count)
+
+
+def shift_pencil(psi, count):
+    """The shift pencil of the low register: with R (chi x 2^count) the matrix of the last `count` tensors of the SignalMPS psi
+    (R[:, l]: the bond vector of the low bits l, site 1 being the most significant bit), returns (G, P, r_last) with
+    G = R R^H, P = R[:, 1:] R[:, :-1]^H and r_last = R[:, -1] -- three right `environment`s over those tensors, O(count chi^3),
+    never 2^count columns: psi with itself; psi with the one-sample shift `build_shift_mpo(psi, 1)`, of which the carry-out-0
+    component is the shifted Gram matrix; the all-ones basis state against psi.  Amplitudes are not applied."""
+    _require_signal(psi, "shift_pencil")
+    count = _low_register(psi, count, "shift_pencil")
+    from .builders import build_shift_mpo
+    n = len(psi)
+    one = np.zeros((1, 2, 1))
+    one[0, 1, 0] = 1.0
+    ones = SignalMPS([one] * n, sites=psi.site_ids, ctx=psi.ctx)
+    G = environment(psi, psi, side="right", count=count).conj()                 # E[p, s] = sum_l conj(R[p, l]) R[s, l]
+    P = environment(psi, psi, W=build_shift_mpo(psi, 1), side="right", count=count)[:, 0, :].conj()   # conj(R[p, l + 1]) R[s, l]
+    r_last = environment(ones, psi, side="right", count=count)[0, :].copy()
+    return G, P, r_last
+
+
+def esprit_from_pencil(G, P, r_last, rcond=1e-12):
+    """The poles from a shift pencil (host only; public so that it can be checked without a device): for R[:, l] = T diag(c) z^l
+    the columns satisfy R[:, 1:] = Phi R[:, :-1] with Phi = T diag(z) T^-1, and the least-squares Phi is
+    P pinv(G - r_last r_last^H): its eigenvalues are the poles.  The pencil is first scaled to a unit diagonal of G (a
+    similarity of Phi); pinv drops directions below rcond of the largest.  Returns chi complex numbers: a bond that carries
+    less than chi modes returns spurious ones among them (`esprit` gives those negligible amplitudes)."""
+    G, P = np.asarray(G, dtype=np.complex128), np.asarray(P, dtype=np.complex128)
+    r = np.asarray(r_last, dtype=np.complex128).reshape(-1)
+    chi = r.size
+    if G.shape != (chi, chi) or P.shape != (chi, chi):
+        raise ValueError(f"esprit_from_pencil: expected G and P of shape ({chi}, {chi}), got {G.shape} and {P.shape}")
+    if not (np.isfinite(G).all() and np.isfinite(P).all() and np.isfinite(r).all()):
+        raise ValueError("esprit_from_pencil: the pencil is not finite")
+    d = np.sqrt(np.abs(np.real(np.diag(G))))
+    d = 1.0 / np.where(d > 0, d, 1.0)
+    H = (G - np.outer(r, r.conj())) * np.outer(d, d)
+    H = 0.5 * (H + H.conj().T)
+    Phi = (P * np.outer(d, d)) @ np.linalg.pinv(H, rcond=float(rcond), hermitian=True)
+    return np.linalg.eigvals(Phi)
+
+
+def _esprit_amplitudes(psi, poles):
+    """The least-squares amplitudes of x_j ~ sum_k a_k z_k^j over all 2^n samples, from the normal equations: the right-hand
+    side <z_k^j | x> is one `product_batch`, the Gram entries sum_j q^j = prod_b (1 + q^(2^b)), q = conj(z_k) z_k', from the
+    correctly rounded dyadic powers of the poles (stable at q ~ 1, where (1 - q^N) / (1 - q) is not)."""
+    n, K = len(psi), len(poles)
+    pw = np.array([_dyadic_powers(z, n) for z in poles], dtype=np.complex128).reshape(K, n)      # pw[k, b] = z_k^(2^b)
+    if not np.isfinite(pw).all():
+        k, b = np.argwhere(~np.isfinite(pw))[0]
+        raise ValueError(f"esprit: z^(2^{int(b)}) overflows for the pole z = {complex(poles[k])!r} (|z| > 1: the limits of exponential_mps)")
+    w = np.ones((K, n, 2), dtype=np.complex128)
+    w[:, :, 1] = pw[:, ::-1]                                                   # tensor i carries bit n - 1 - i
+    h = np.asarray(product_batch(psi, w, conj=True), dtype=np.complex128)
+    with np.errstate(over="ignore", invalid="ignore"):
+        M = np.prod(1.0 + pw.conj()[:, None, :] * pw[None, :, :], axis=2)
+    if not np.isfinite(M).all():
+        raise ValueError("esprit: the Gram matrix of the modes overflows (|z| > 1: the limits of exponential_mps)")
+    return np.linalg.lstsq(M, h, rcond=None)[0]
+
+
+def esprit(psi, maxdim=None, tol=None, count=None, return_model=False):
+    """Poles and amplitudes of x_j = sum_k a_k z_k^j from the SignalMPS of x, without a scan and without a window: the bond basis of
+    the state already holds the signal subspace, and `shift_pencil` + `esprit_from_pencil` read the poles off the last `count`
+    tensors (ESPRIT with the Hankel SVD replaced by the truncation the encoder has done).  O(count chi^3).
+
+    maxdim / tol: `compress` a copy first (either one given; tol defaults to 1e-12) -- the rank selection is the truncation's: one
+    pole per unit of bond dimension at the cut.  count: the tensors of the low register; default: everything right of the
+    leftmost bond that attains the state's largest bond dimension, the longest register that still carries the full rank
+    (a long baseline is what buys accuracy).  ValueError when 2^count - 1 columns cannot determine a bond of that size.
+    Returns (poles, amplitudes) sorted by |amplitude| descending; the amplitudes are the least-squares fit over all 2^n
+    samples of psi (amplitude included).  A bond inflated by rounding-level junk returns spurious poles with negligible amplitudes.
+    Modes with |z| > 1 inherit the overflow limits of `exponential_mps` (ValueError when a dyadic power overflows).
+    return_model=True adds exponential_sum(amplitudes, poles, n) untruncated and its relative distance to psi (through the exact
+    gauge of the difference: no 1e-7 floor)."""
+    _require_signal(psi, "esprit")
+    n = len(psi)
+    if n < 2:
+        raise ValueError("esprit: needs at least 2 sites")
+    if count is not None:
+        count = _low_register(psi, count, "esprit")
+    work = psi
+    if maxdim is not None or tol is not None:
+        work = compress(psi.copy(), maxdim=maxdim, tol=1e-12 if tol is None else tol)
+    bonds = work.bond_dims
+    if count is None:
+        count = n - 1 - bonds.index(max(bonds))
+    chi = bonds[n - 1 - count]
+    if (1 << count) - 1 < chi:
+        raise ValueError(f"esprit: a register of {count} tensors has {(1 << count) - 1} shifted columns, fewer than the bond {chi} at its cut")
+    poles = esprit_from_pencil(*shift_pencil(work, count))
+    amps = _esprit_amplitudes(psi, poles)
+    order = np.argsort(-np.abs(amps), kind="stable")
+    poles, amps = poles[order], amps[order]
+    if not return_model:
+        return poles, amps
+    model = exponential_sum(amps, poles, n, maxdim=None, tol=None)
+    diff = sub(model, psi)
+    try:
+        _, nd = bond_spectra(diff, return_norm=True)
+    except L.QilDomainError:                                                   # the difference is exactly zero
+        nd = 0.0
+    return poles, amps, model, abs(diff.amplitude) * nd / (abs(psi.amplitude) * norm(psi))
 
 
 # ---------------------------------------------------------------- encode
