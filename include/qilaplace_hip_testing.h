@@ -95,6 +95,55 @@ QIL_API int qil_gemm_batched_host(qil_context* ctx, int dtype, int opA, int opB,
                                   int64_t count, int subtract, int skinny_m, const uint8_t* b_sel, int64_t b_sel_step,
                                   int64_t b_sel_stride, const int32_t* cmap, int64_t cmap_blk);
 
+/* Everything the thin QR (qr_impl: under every gauge sweep, zip-up, the RSVD encoder and the Schmidt spectra) decides on the host before
+ * it launches: THE decision, not a copy of it -- qr_impl switches on this struct, and the launchers of the panel kernels take
+ * their LDS size, KM variant and chunk length from the same helpers that fill it.
+ *   cholesky_eligible: CholeskyQR2 is tried first (unless a refusal earlier in the same call makes qr_impl skip it); the other
+ *     fields describe the route taken when it is not tried, is skipped or refuses.
+ *   route: one launch of the CGS2 kernel, one Householder panel, one row-chunk tree, or the blocked driver.
+ *   panel_width: columns per panel (blocked: 16 or 32; single routes: n); last_panel_width: of the last panel.
+ *   panel_kind / last_panel_kind: the kernel of the full-width panels / of the last panel (equal when there is one panel or n is a
+ *     multiple of panel_width); has_hh, has_tree, has_cgs2_lds, has_cgs2_global: the table of panels contains that kind.
+ *   fused_in_lds: a CGS2 kernel runs on the operand's rows and every such launch keeps its panel in LDS; fused_short_rows: ... and
+ *     m <= 256, where a 16-lane row, not a wave, takes each previous column.
+ *   hh_km, hh_waves: the rows-per-lane variant (2, 4, 6, 8, 9, 13, 19) and waves of the Householder panel kernel; 0 without one.
+ *   tree_chunk rows per chunk, tree_chunks of them, the last one tree_last_rows long; tree_in_lds: a chunk x 16 (single tree
+ *     panel: x n) slice of the first level stays in LDS; tree_top_in_lds: so do the stacked triangles of the second level.  All 0
+ *     without a tree panel. */
+enum { QIL_QR_SINGLE_CGS2 = 0, QIL_QR_SINGLE_HH = 1, QIL_QR_SINGLE_TREE = 2, QIL_QR_BLOCKED = 3 };
+enum { QIL_QR_PANEL_NONE = 0, QIL_QR_PANEL_HH = 1, QIL_QR_PANEL_TREE = 2, QIL_QR_PANEL_CGS2_LDS = 3, QIL_QR_PANEL_CGS2_GLOBAL = 4 };
+typedef struct qil_qr_plan_info {
+    int cholesky_eligible;
+    int route;
+    int panel_width, last_panel_width;
+    int panel_kind, last_panel_kind;
+    int has_hh, has_tree, has_cgs2_lds, has_cgs2_global;
+    int fused_in_lds, fused_short_rows;
+    int hh_km, hh_waves;
+    int64_t tree_chunk, tree_chunks, tree_last_rows;
+    int tree_in_lds, tree_top_in_lds;
+} qil_qr_plan_info;
+/* The plan of the thin QR of an m x n operand (m >= n >= 1).  Host only: no context, no GPU. */
+QIL_API int qil_qr_plan(int dtype, int64_t m, int64_t n, qil_qr_plan_info* plan);
+
+/* What one qil_qr_host call did.  plan: as qr_impl filled it for the outer factorisation.  cholesky: 0 not eligible; 1 done, first-
+ * order second pass; 2 done, full second factorisation; 3 refused in the first pass; 4 refused in the second; 5 skipped after an
+ * earlier refusal.  repairs: re-factorisations qr_reorthogonalise ran (0..2); passes: how often it measured Q^H Q, worst[i] the
+ * off-diagonal maximum of pass i; skipped_check: it returned early because Q was known orthonormal (outcome 1). */
+typedef struct qil_qr_report {
+    qil_qr_plan_info plan;
+    int cholesky, repairs, passes, skipped_check;
+    double worst[3];
+} qil_qr_report;
+/* The thin QR with non-negative diagonal on host operands: uploads the parent buffer of A whole (a_elems elements; the operand is
+ * m x n at a_base + a_off with leading dimension lda >= m) and, unless r_base is null, that of R (n x n at r_off, ldr >= n), runs
+ * qil_dev_qr_positive on the offset device addresses and downloads both parents whole: Q in place of A.  reorth: the `orthonormal`
+ * flag (measure Q^H Q, factor again while it is off).  cholesky_skip: CholeskyQR2 attempts to skip, as after a refusal earlier in
+ * the same call.  Every element of both windows must lie inside its buffer (QIL_EINVAL_ARG otherwise). */
+QIL_API int qil_qr_host(qil_context* ctx, int dtype, int64_t m, int64_t n, void* a_base, int64_t a_elems, int64_t a_off, int64_t lda,
+                        void* r_base, int64_t r_elems, int64_t r_off, int64_t ldr, int reorth, int cholesky_skip,
+                        qil_qr_report* report);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,6 +80,21 @@ class GemmHostOperand(C.Structure):
 
 _pop = C.POINTER(GemmHostOperand)
 
+
+class QrPlanInfo(C.Structure):
+    """qil_qr_plan_info of include/qilaplace_hip_testing.h."""
+    _fields_ = [("cholesky_eligible", _int), ("route", _int), ("panel_width", _int), ("last_panel_width", _int),
+                ("panel_kind", _int), ("last_panel_kind", _int), ("has_hh", _int), ("has_tree", _int),
+                ("has_cgs2_lds", _int), ("has_cgs2_global", _int), ("fused_in_lds", _int), ("fused_short_rows", _int),
+                ("hh_km", _int), ("hh_waves", _int), ("tree_chunk", _i64), ("tree_chunks", _i64), ("tree_last_rows", _i64),
+                ("tree_in_lds", _int), ("tree_top_in_lds", _int)]
+
+
+class QrReport(C.Structure):
+    """qil_qr_report of include/qilaplace_hip_testing.h."""
+    _fields_ = [("plan", QrPlanInfo), ("cholesky", _int), ("repairs", _int), ("passes", _int), ("skipped_check", _int),
+                ("worst", _dbl * 3)]
+
 # name -> argtypes; every function returns int (qil_status) unless listed in _RET
 PROTOTYPES = {
     "qil_device_count": [_pint],
@@ -188,6 +203,8 @@ PROTOTYPES = {
     "qil_gemm_batched_host": [_vp, _int, _int, _int, _i64, _i64, _i64, _pop, _pop, _pop, _i64, _int, _int, _pu8, _i64, _i64,
                               C.POINTER(C.c_int32), _i64],
     "qil_qr_positive": [_vp, _int, _i64, _i64, _vp, _vp, _vp],
+    "qil_qr_plan": [_int, _i64, _i64, C.POINTER(QrPlanInfo)],
+    "qil_qr_host": [_vp, _int, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _int, _int, C.POINTER(QrReport)],
     "qil_gemm_device_time": [_vp, _int, _int, _int, _i64, _i64, _i64, _int, _pdbl],
     "qil_hbm_store_peak": [_vp, _i64, _int, _pdbl, _pint],
     "qil_svd_trunc": [_vp, _vp, _i64, _i64, _int, _dbl, _i64, _i64, _pi64, _vp, _pdbl, _vp],

@@ -87,6 +87,7 @@ struct qil_context {
     hipEvent_t sync_event = nullptr;   // qil_stream_sync inside a lock-step batch
     uint64_t progress_key = 0;    // where the chain driven through this context is (qil_progress)
     int cholqr_skip = 0;          // Cholesky QR attempts to skip after a refusal (qr_impl)
+    struct qil_qr_report* qr_report = nullptr;   // where qr_impl, cholqr2 and qr_reorthogonalise say what they did; null outside qil_qr_host
     // small device -> host read-backs without a copy command or a stream synchronisation (qil_read_back): kRbSlots slots of
     // kRbSlotBytes in pinned, device-visible memory + a ticket word a kernel writes behind the data; the host polls the word
     static constexpr int kRbSlots = 4;

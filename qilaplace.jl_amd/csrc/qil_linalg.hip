@@ -1531,27 +1531,59 @@ struct hh_panel_k {
     }
 };
 
+// The sizes the QR's panel kernels are launched with.  qr_plan (below: what qil_qr_plan hands to the tests) and the launchers
+// read the same functions, so the plan cannot drift from what runs.  esz: bytes per element.
+constexpr size_t QR_LDS_BUDGET = 150 * 1024;
+inline size_t hh_panel_lds_bytes(size_t esz, long long m, int b) { return (size_t)((m + 1) | 1) * b * esz + 2048; }
+inline bool hh_panel_fits_sized(size_t esz, long long m, int b) {
+    return b <= 32 && m <= 64 * 19 && hh_panel_lds_bytes(esz, m, b) <= QR_LDS_BUDGET;
+}
+// the rows-per-lane variant hh_panel_launch instantiates for m rows
+inline int hh_panel_km(long long m) {
+    const int km = (int)((m + 63) / 64);
+    return km <= 2 ? 2 : km <= 4 ? 4 : km <= 6 ? 6 : km <= 8 ? 8 : km <= 9 ? 9 : km <= 13 ? 13 : 19;
+}
+template <class T>
+int hh_panel_waves_of(int km) {
+    switch (km) {
+        case 2: return hh_panel_waves<T, 2>();
+        case 4: return hh_panel_waves<T, 4>();
+        case 6: return hh_panel_waves<T, 6>();
+        case 8: return hh_panel_waves<T, 8>();
+        case 9: return hh_panel_waves<T, 9>();
+        case 13: return hh_panel_waves<T, 13>();
+        default: return hh_panel_waves<T, 19>();
+    }
+}
+// LDS of the CGS2 kernel with its rows x n slice staged (gs_fused_k<T, true>)
+inline size_t gs_fused_lds_bytes(size_t esz, long long rows, long long n) {
+    return ((size_t)2 * (n + (n & 1)) + (size_t)(rows | 1) * n) * esz;
+}
+// rows per chunk of the tall-skinny tree
+inline long long tsqr_chunk_rows(long long m) { return std::max<long long>(512, (m / 512 + 255) / 256 * 256); }
+
 // true when the panel fits (LDS and rows-per-lane budget); launches it
 template <class T>
 bool hh_panel_fits(long long m, int b) {
-    return b <= 32 && m <= 64 * 19 && (size_t)((m + 1) | 1) * b * sizeof(T) + 2048 <= 150 * 1024;
+    return hh_panel_fits_sized(sizeof(T), m, b);
 }
 template <class T>
 int hh_panel_launch(qil_context* ctx, T* P, long long lda, long long m, int b, T* R, long long ldr, const double* ref_norm) {
-    const size_t lds = (size_t)((m + 1) | 1) * b * sizeof(T) + 2048;
-    const int km = (int)((m + 63) / 64);
+    const size_t lds = hh_panel_lds_bytes(sizeof(T), m, b);
 #define QIL_HHP(KMv)                                                                                                   \
-    do {                                                                                                               \
+    case KMv:                                                                                                          \
         QIL_TRY((qil_klaunch<hh_panel_k<T, KMv>>(ctx, dim3(1), dim3(64 * hh_panel_waves<T, KMv>()), lds, P, lda, (int)m, b, R, \
                            ldr, ref_norm, (long long*)nullptr)));                                                                             \
-    } while (0)
-    if (km <= 2) QIL_HHP(2);
-    else if (km <= 4) QIL_HHP(4);
-    else if (km <= 6) QIL_HHP(6);
-    else if (km <= 8) QIL_HHP(8);
-    else if (km <= 9) QIL_HHP(9);
-    else if (km <= 13) QIL_HHP(13);
-    else QIL_HHP(19);
+        break
+    switch (hh_panel_km(m)) {
+        QIL_HHP(2);
+        QIL_HHP(4);
+        QIL_HHP(6);
+        QIL_HHP(8);
+        QIL_HHP(9);
+        QIL_HHP(13);
+        QIL_HHP(19);
+    }
 #undef QIL_HHP
     QIL_HIP(hipGetLastError());
     return QIL_OK;
@@ -1562,8 +1594,8 @@ template <class T>
 int gs_fused_launch(qil_context* ctx, unsigned nwg, T* A, long long lda, long long mtot, int n, T* R, long long ldr,
                     const double* ref_norm, long long chunk_rows) {
     const long long rows = chunk_rows > 0 ? std::min(chunk_rows, mtot) : mtot;
-    const size_t lds = ((size_t)2 * (n + (n & 1)) + (size_t)(rows | 1) * n) * sizeof(T);
-    if (lds <= 150 * 1024) {
+    const size_t lds = gs_fused_lds_bytes(sizeof(T), rows, n);
+    if (lds <= QR_LDS_BUDGET) {
         QIL_TRY((qil_klaunch<gs_fused_k<T, true>>(ctx, dim3(nwg), dim3(1024), lds, A, lda, mtot, n, R, ldr, ref_norm, chunk_rows)));
     } else {
         QIL_TRY((qil_klaunch<gs_fused_k<T, false>>(ctx, dim3(nwg), dim3(1024), (size_t)n * sizeof(T), A, lda, mtot, n, R, ldr, ref_norm, chunk_rows)));
@@ -1941,7 +1973,11 @@ int qr_reorthogonalise(qil_context* ctx, long long m, long long n, T* Q, long lo
     if (n < 2) return QIL_OK;
     // r06: nothing to measure after a CholeskyQR2 whose second pass was the first-order one (A/B with the check forced on,
     // profiles/r06_qr_recheck_ab.txt: bit-identical results, zT compression 64.2 -> 62.6 ms, compress! chi 256 45.2 -> 44.4 ms)
-    if (known_orthonormal) return QIL_OK;
+    qil_qr_report* const rep = ctx->qr_report;               // null outside qil_qr_host
+    if (known_orthonormal) {
+        if (rep) rep->skipped_check = 1;
+        return QIL_OK;
+    }
     void *gbuf = nullptr, *mx = nullptr;
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)(n * n) * sizeof(T), &gbuf));
     QIL_TRY(qil_ctx_alloc(ctx, 256, &mx));
@@ -1953,8 +1989,13 @@ int qr_reorthogonalise(qil_context* ctx, long long m, long long n, T* Q, long lo
         QIL_TRY(qil_read_back(ctx, &worst, mx, sizeof(double)));
         if (dbg) fprintf(stderr, "[qr] max |Q^H Q - I| off-diagonal %.3g\n", worst);
         if (orthonormal) *orthonormal = !(worst > 1e-9);
+        if (rep) rep->worst[pass] = worst, rep->passes = pass + 1;
         if (!(worst > 1e-11) || pass == 2) break;
-        QIL_TRY(qr_impl<T>(ctx, m, n, Q, ldq, static_cast<T*>(gbuf), n));                  // Q <- Q2, gbuf = R2
+        if (rep) ++rep->repairs;
+        ctx->qr_report = nullptr;                            // the report describes the outer factorisation
+        const int st2 = qr_impl<T>(ctx, m, n, Q, ldq, static_cast<T*>(gbuf), n);           // Q <- Q2, gbuf = R2
+        ctx->qr_report = rep;
+        QIL_TRY(st2);
         if (R) {
             if (rinv && *rinv) {                                 // R changes: an inverse kept for the certificate is stale
                 qil_ctx_free(ctx, *rinv);
@@ -2525,11 +2566,13 @@ int cholqr2(qil_context* ctx, long long m, long long n, T* A, long long lda, T* 
     int bad = 0;
     QIL_TRY(qil_read_back(ctx, &bad, fl, sizeof(int)));
     const bool first_order = bad == 0;                           // no bad pivot, every |e_ik| <= 3e-8 / n
+    const bool refused_first = (bad & 1) != 0;
     if (!(bad & 1) && (bad & 2)) {
         QIL_TRY(qil_dev_zero(ctx, fl, sizeof(int)));
         QIL_TRY(chol_inv<T>(ctx, G, (int)n, R2, X2, (int*)fl));
         QIL_TRY(qil_read_back(ctx, &bad, fl, sizeof(int)));
     }
+    if (ctx->qr_report) ctx->qr_report->cholesky = bad ? (refused_first ? 3 : 4) : (first_order ? 1 : 2);
     if (bad) {
         release();
         return QIL_OK;
@@ -4222,8 +4265,7 @@ struct tsqr_apply_q2_k {
 template <class T>
 int tsqr_panel(qil_context* ctx, long long m, int b, T* P, long long lda, T* R, long long ldr,
                const double* ref_norm) {
-    static const long long min_chunk = 512;
-    const long long chunk = std::max<long long>(min_chunk, (m / 512 + 255) / 256 * 256);
+    const long long chunk = tsqr_chunk_rows(m);
     const long long nch = (m + chunk - 1) / chunk;
     void *rs = nullptr, *r2 = nullptr;
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)(nch * b * b) * sizeof(T), &rs));
@@ -4241,36 +4283,24 @@ int tsqr_panel(qil_context* ctx, long long m, int b, T* P, long long lda, T* R, 
     return QIL_OK;
 }
 
-// Thin QR with non-negative diagonal (qr(...; positive=true), rsvd.jl:83,90,94).
-//   * small panels: ONE launch (gs_fused);
-//   * otherwise blocked CGS2: panels of 16 columns are projected against all previous columns with two
-//     MFMA GEMMs per pass (C = Q^H P, then P -= Q C in the second GEMM's epilogue) and orthonormalised internally by gs_fused -- the work is
-//     spread over the chip by the GEMMs and the launch count drops from ~5 n to ~7 n / 16.
-template <class T>
-int qr_impl(qil_context* ctx, long long m, long long n, T* A, long long lda, T* R, long long ldr, bool* orthonormal, void** rinv) {
+// Which kernels factor an m x n operand: every size rule of the thin QR in one place.  qr_impl below switches on the struct this
+// fills and qil_qr_plan hands it to the tests.  cx: complex elements.
+void qr_plan(bool cx, long long m, long long n, qil_qr_plan_info* p) {
     static const long long TALL = 2048;
-    if (orthonormal) *orthonormal = false;
+    const size_t esz = cx ? 16 : 8;
+    *p = qil_qr_plan_info{};
     // Cholesky QR first where it pays (from a few panels on) and while it keeps succeeding on this context: a numerically
     // rank-deficient operand (product bonds, deficient sketches) costs the attempt a Gram product, a partial factorisation and
     // one synchronisation, so after a refusal the next attempts are skipped
     // (r05: skinny tall panels up to 2^24 entries too -- the 32768 x 133 sketch bases of the n = 30 encoder's root split sat just
     // above 2^22 and took the Householder tree at 2.2 ms each, five per split)
-    if (n >= 64 && n <= 1024 && m >= n && (m * n <= (1LL << 22) || (n <= 256 && m * n <= (1LL << 24)))) {
-        if (ctx->cholqr_skip > 0) {
-            --ctx->cholqr_skip;
-        } else {
-            bool done = false;
-            QIL_TRY(cholqr2<T>(ctx, m, n, A, lda, R, ldr, &done, orthonormal, rinv));
-            if (done) return QIL_OK;
-            ctx->cholqr_skip = 8;
-        }
-    }
+    p->cholesky_eligible = n >= 64 && n <= 1024 && m >= n && (m * n <= (1LL << 22) || (n <= 256 && m * n <= (1LL << 24)));
     // one launch for the whole factorisation: single panels, and anything whose slice fits one CU's LDS
-    const bool fits_lds = ((size_t)2 * (n + (n & 1)) + (size_t)(m | 1) * n) * sizeof(T) <= 150 * 1024;
+    const bool fits_lds = gs_fused_lds_bytes(esz, m, n) <= QR_LDS_BUDGET;
     // panels go through the row-chunk tree from TALL rows on, and already from 640 rows when a rows x 16 panel does
     // not fit LDS (complex panels above ~580 rows): its 512-row chunks do, and a single workgroup factoring such a
     // panel out of L2 takes ~220-290 us instead of three short launches
-    const bool panel16_fits = ((size_t)32 + (size_t)(m | 1) * 16) * sizeof(T) <= 150 * 1024;
+    const bool panel16_fits = gs_fused_lds_bytes(esz, m, 16) <= QR_LDS_BUDGET;
     static const long long tree_min = 640;        // (1024 -> 600: exact compress! of the bond-1008 product 476 -> 455 ms, neutral elsewhere)
     const bool tree = m >= TALL || (!panel16_fits && m >= tree_min);
     // up to `fused_max` columns the CGS2 kernel does the whole factorisation in one launch; beyond, whenever a Householder
@@ -4278,23 +4308,103 @@ int qr_impl(qil_context* ctx, long long m, long long n, T* A, long long lda, T* 
     // (128 x 64: 274 -> ~140 us -- the CGS2 kernel pays ~4 us per column, the Householder panel ~1.5; compress! chi 64 -> 32
     // 28 -> 24.5 ms, 128 -> 64 50 -> 42 ms; narrower panels measured equal within noise either way)
     static const long long fused_max = 16;
-    const bool hh_ok = !tree && n > fused_max && hh_panel_fits<T>(m, (int)std::min<long long>(n, 32));
-    if (hh_ok && n <= 32) return hh_panel_launch<T>(ctx, A, lda, m, (int)n, R, ldr, (const double*)nullptr);
-    if (n <= 16 || (fits_lds && !hh_ok)) {
-        if (tree && n <= 16) {
-            void* nb0 = nullptr;
-            QIL_TRY(qil_ctx_alloc(ctx, (size_t)n * sizeof(double), &nb0));
-            QIL_TRY(col_norms_any<T>(ctx, A, lda, m, n, (double*)nb0));
-            QIL_TRY(tsqr_panel<T>(ctx, m, (int)n, A, lda, R, ldr, (const double*)nb0));
-            qil_ctx_free(ctx, nb0);
-            return QIL_OK;
+    const bool hh_ok = !tree && n > fused_max && hh_panel_fits_sized(esz, m, (int)std::min<long long>(n, 32));
+    // the kernel of one m x b panel, and what its launcher will derive from (m, b)
+    bool cgs2_all_lds = true;
+    auto panel = [&](int b) -> int {
+        if (tree && b <= 16) {
+            p->has_tree = 1;
+            p->tree_chunk = tsqr_chunk_rows(m);
+            p->tree_chunks = (m + p->tree_chunk - 1) / p->tree_chunk;
+            p->tree_last_rows = m - (p->tree_chunks - 1) * p->tree_chunk;
+            return QIL_QR_PANEL_TREE;
         }
-        return gs_fused_launch<T>(ctx, 1u, A, lda, m, (int)n, R, ldr, (const double*)nullptr, 0LL);
+        if (p->route != QIL_QR_SINGLE_CGS2 && hh_panel_fits_sized(esz, m, b)) {
+            p->has_hh = 1;
+            p->hh_km = hh_panel_km(m);
+            p->hh_waves = cx ? hh_panel_waves_of<c64>(p->hh_km) : hh_panel_waves_of<double>(p->hh_km);
+            return QIL_QR_PANEL_HH;
+        }
+        if (gs_fused_lds_bytes(esz, m, b) <= QR_LDS_BUDGET) {
+            p->has_cgs2_lds = 1;
+            return QIL_QR_PANEL_CGS2_LDS;
+        }
+        p->has_cgs2_global = 1;
+        cgs2_all_lds = false;
+        return QIL_QR_PANEL_CGS2_GLOBAL;
+    };
+    if (hh_ok && n <= 32) {
+        p->route = QIL_QR_SINGLE_HH;
+    } else if (n <= 16 || (fits_lds && !hh_ok)) {
+        p->route = tree && n <= 16 ? QIL_QR_SINGLE_TREE : QIL_QR_SINGLE_CGS2;
+    } else {
+        p->route = QIL_QR_BLOCKED;
     }
-    // panel width: 32 columns while a rows x 32 panel still fits one CU's LDS (half the launches), else 16
-    const bool wide = !tree && ((size_t)64 + (size_t)(m | 1) * 32) * sizeof(T) <= 150 * 1024;
-    const int PB = wide ? 32 : 16;
-    if (R) QIL_TRY(qil_dev_zero(ctx, R, (size_t)(ldr * n) * sizeof(T)));
+    if (p->route != QIL_QR_BLOCKED) {
+        p->panel_width = p->last_panel_width = (int)n;
+        p->panel_kind = p->last_panel_kind = panel((int)n);
+    } else {
+        // panel width: 32 columns while a rows x 32 panel still fits one CU's LDS (half the launches), else 16
+        const bool wide = !tree && gs_fused_lds_bytes(esz, m, 32) <= QR_LDS_BUDGET;
+        p->panel_width = wide ? 32 : 16;
+        p->last_panel_width = (int)(n - (n - 1) / p->panel_width * p->panel_width);
+        p->panel_kind = panel(p->panel_width);
+        p->last_panel_kind = panel(p->last_panel_width);
+    }
+    p->fused_in_lds = p->has_cgs2_lds && cgs2_all_lds;
+    p->fused_short_rows = p->has_cgs2_lds && m <= 256;
+    if (p->has_tree) {
+        const long long b = std::min<long long>(n, 16);        // the widest tree panel of this operand
+        p->tree_in_lds = gs_fused_lds_bytes(esz, std::min<long long>(p->tree_chunk, m), b) <= QR_LDS_BUDGET;
+        p->tree_top_in_lds = gs_fused_lds_bytes(esz, p->tree_chunks * b, b) <= QR_LDS_BUDGET;
+    }
+}
+
+template <class T>
+int qr_panel_launch(qil_context* ctx, int kind, long long m, int b, T* P, long long lda, T* R, long long ldr, const double* ref_norm) {
+    switch (kind) {
+        case QIL_QR_PANEL_TREE: return tsqr_panel<T>(ctx, m, b, P, lda, R, ldr, ref_norm);
+        case QIL_QR_PANEL_HH: return hh_panel_launch<T>(ctx, P, lda, m, b, R, ldr, ref_norm);
+        default: return gs_fused_launch<T>(ctx, 1u, P, lda, m, b, R, ldr, ref_norm, 0LL);
+    }
+}
+
+// Thin QR with non-negative diagonal (qr(...; positive=true), rsvd.jl:83,90,94).
+//   * small panels: ONE launch (gs_fused);
+//   * otherwise blocked CGS2: panels of 16 columns are projected against all previous columns with two
+//     MFMA GEMMs per pass (C = Q^H P, then P -= Q C in the second GEMM's epilogue) and orthonormalised internally by gs_fused -- the work is
+//     spread over the chip by the GEMMs and the launch count drops from ~5 n to ~7 n / 16.
+// Which of these runs, and with which panel kernels, is qr_plan's decision.
+template <class T>
+int qr_impl(qil_context* ctx, long long m, long long n, T* A, long long lda, T* R, long long ldr, bool* orthonormal, void** rinv) {
+    if (orthonormal) *orthonormal = false;
+    qil_qr_plan_info p;
+    qr_plan(sizeof(T) == 16, m, n, &p);
+    qil_qr_report* const rep = ctx->qr_report;               // null outside qil_qr_host
+    if (rep) rep->plan = p;
+    if (p.cholesky_eligible) {
+        if (ctx->cholqr_skip > 0) {
+            --ctx->cholqr_skip;
+            if (rep) rep->cholesky = 5;
+        } else {
+            bool done = false;
+            QIL_TRY(cholqr2<T>(ctx, m, n, A, lda, R, ldr, &done, orthonormal, rinv));
+            if (done) return QIL_OK;
+            ctx->cholqr_skip = 8;
+        }
+    }
+    if (p.route == QIL_QR_SINGLE_TREE) {
+        void* nb0 = nullptr;
+        QIL_TRY(qil_ctx_alloc(ctx, (size_t)n * sizeof(double), &nb0));
+        QIL_TRY(col_norms_any<T>(ctx, A, lda, m, n, (double*)nb0));
+        QIL_TRY(tsqr_panel<T>(ctx, m, (int)n, A, lda, R, ldr, (const double*)nb0));
+        qil_ctx_free(ctx, nb0);
+        return QIL_OK;
+    }
+    if (p.route != QIL_QR_BLOCKED) return qr_panel_launch<T>(ctx, p.panel_kind, m, (int)n, A, lda, R, ldr, (const double*)nullptr);
+    const int PB = p.panel_width;
+    // (the n x n window only: R may sit inside a wider buffer whose rows beyond n are not this call's)
+    if (R) QIL_TRY(qil_dev_zero2d(ctx, R, (size_t)ldr * sizeof(T), (size_t)n * sizeof(T), (size_t)n));
     void *cbuf = nullptr, *nbuf = nullptr;
     QIL_TRY(qil_ctx_alloc(ctx, (size_t)n * sizeof(double), &nbuf));
     // original column norms, measured before any projection (reference for the dependence test)
@@ -4315,12 +4425,7 @@ int qr_impl(qil_context* ctx, long long m, long long n, T* A, long long lda, T* 
         }
         // intra-panel CGS2 (one launch); its b x b triangular factor goes straight to R[j0:, j0:]
         T* Rjj = R ? R + j0 + ldr * j0 : (T*)nullptr;
-        if (tree)
-            QIL_TRY(tsqr_panel<T>(ctx, m, b, P, lda, Rjj, ldr, (const double*)nbuf + j0));
-        else if (hh_panel_fits<T>(m, b))
-            QIL_TRY(hh_panel_launch<T>(ctx, P, lda, m, b, Rjj, ldr, (const double*)nbuf + j0));
-        else
-            QIL_TRY(gs_fused_launch<T>(ctx, 1u, P, lda, m, b, Rjj, ldr, (const double*)nbuf + j0, 0LL));
+        QIL_TRY(qr_panel_launch<T>(ctx, b == PB ? p.panel_kind : p.last_panel_kind, m, b, P, lda, Rjj, ldr, (const double*)nbuf + j0));
     }
     QIL_HIP(hipGetLastError());
     qil_ctx_free(ctx, cbuf);
@@ -4697,6 +4802,57 @@ extern "C" int qil_qr_positive(qil_context* ctx, int dtype, int64_t m, int64_t n
     QIL_TRY(qil_read_back(ctx, R, dR, (size_t)(n * n) * e));
     qil_ctx_free(ctx, dA);
     qil_ctx_free(ctx, dR);
+    return QIL_OK;
+}
+
+// What qr_impl would decide for this operand (testing hook; host only)
+extern "C" int qil_qr_plan(int dtype, int64_t m, int64_t n, qil_qr_plan_info* plan) {
+    QIL_REQUIRE(plan, QIL_EINVAL_ARG, "qr: null argument");
+    QIL_REQUIRE(dtype == QIL_F64 || dtype == QIL_C64, QIL_EINVAL_ARG, "qr: bad dtype %d", dtype);
+    QIL_REQUIRE(m >= n && n >= 1, QIL_EINVAL_ARG, "qr: needs m >= n >= 1 (got %lld x %lld)", (long long)m, (long long)n);
+    qr_plan(dtype == QIL_C64, m, n, plan);
+    return QIL_OK;
+}
+
+// The thin QR on host operands (testing hook): whole parent buffers up, qil_dev_qr_positive on base + off, whole parents down
+extern "C" int qil_qr_host(qil_context* ctx, int dtype, int64_t m, int64_t n, void* a_base, int64_t a_elems, int64_t a_off, int64_t lda,
+                           void* r_base, int64_t r_elems, int64_t r_off, int64_t ldr, int reorth, int cholesky_skip,
+                           qil_qr_report* report) {
+    QIL_REQUIRE(ctx && a_base && report, QIL_EINVAL_ARG, "qr: null argument");
+    QIL_REQUIRE(dtype == QIL_F64 || dtype == QIL_C64, QIL_EINVAL_ARG, "qr: bad dtype %d", dtype);
+    QIL_REQUIRE(m >= n && n >= 1, QIL_EINVAL_ARG, "qr: needs m >= n >= 1 (got %lld x %lld)", (long long)m, (long long)n);
+    QIL_REQUIRE(m <= INT32_MAX, QIL_EINVAL_ARG, "qr: %lld rows exceed the panel kernels' row index", (long long)m);
+    QIL_REQUIRE(lda >= m, QIL_EINVAL_ARG, "qr: lda %lld is smaller than the %lld rows of A", (long long)lda, (long long)m);
+    QIL_REQUIRE(a_off >= 0 && a_off + (m - 1) + lda * (n - 1) < a_elems, QIL_EINVAL_ARG, "qr: A reaches beyond its buffer");
+    QIL_REQUIRE(cholesky_skip >= 0, QIL_EINVAL_ARG, "qr: negative cholesky_skip");
+    if (r_base) {
+        QIL_REQUIRE(ldr >= n, QIL_EINVAL_ARG, "qr: ldr %lld is smaller than the %lld rows of R", (long long)ldr, (long long)n);
+        QIL_REQUIRE(r_off >= 0 && r_off + (n - 1) + ldr * (n - 1) < r_elems, QIL_EINVAL_ARG, "qr: R reaches beyond its buffer");
+    }
+    QIL_TRY(qil_ctx_activate(ctx));
+    qil_call_scope call_scope(ctx);
+    ctx->cholqr_skip = cholesky_skip;
+    *report = qil_qr_report{};
+    struct report_guard {                                    // the pointer never outlives the call, however it ends
+        qil_context* c;
+        ~report_guard() { c->qr_report = nullptr; }
+    } guard{ctx};
+    ctx->qr_report = report;
+    const size_t e = qil_elem_size(dtype);
+    void *dA = nullptr, *dR = nullptr;
+    QIL_TRY(qil_ctx_alloc(ctx, (size_t)a_elems * e, &dA));
+    QIL_HIP(hipMemcpyAsync(dA, a_base, (size_t)a_elems * e, hipMemcpyHostToDevice, qil_stream(ctx)));
+    if (r_base) {
+        QIL_TRY(qil_ctx_alloc(ctx, (size_t)r_elems * e, &dR));
+        QIL_HIP(hipMemcpyAsync(dR, r_base, (size_t)r_elems * e, hipMemcpyHostToDevice, qil_stream(ctx)));
+    }
+    QIL_HIP(qil_stream_sync(ctx));
+    QIL_TRY(qil_dev_qr_positive(ctx, dtype, m, n, static_cast<char*>(dA) + (size_t)a_off * e, lda,
+                                dR ? static_cast<char*>(dR) + (size_t)r_off * e : nullptr, ldr, reorth != 0));
+    if (r_base) QIL_TRY(qil_read_back(ctx, r_base, dR, (size_t)r_elems * e));
+    QIL_TRY(qil_read_back(ctx, a_base, dA, (size_t)a_elems * e));
+    qil_ctx_free(ctx, dA);
+    if (dR) qil_ctx_free(ctx, dR);
     return QIL_OK;
 }
 

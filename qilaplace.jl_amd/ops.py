@@ -2166,6 +2166,44 @@ def gemm_batched(A, B, Cbuf, m, n, k, opA="N", opB="N", a=(0, None, 0), b=(0, No
     return Cbuf
 
 
+QR_ROUTES = ("SINGLE_CGS2", "SINGLE_HH", "SINGLE_TREE", "BLOCKED")
+QR_PANELS = ("NONE", "HH", "TREE", "CGS2_LDS", "CGS2_GLOBAL")
+
+
+def _qr_plan_dict(info):
+    d = {name: int(getattr(info, name)) for name, _ in info._fields_}
+    d["route"] = QR_ROUTES[d["route"]]
+    d["panel_kind"], d["last_panel_kind"] = QR_PANELS[d["panel_kind"]], QR_PANELS[d["last_panel_kind"]]
+    return d
+
+
+def qr_plan(dtype, m, n):
+    """What the thin QR decides for an m x n operand (testing hook; needs no GPU): a dict of the fields of qil_qr_plan_info, the
+    route and the panel kinds by name (QR_ROUTES, QR_PANELS)."""
+    code = L.QIL_C64 if np.dtype(dtype) == np.complex128 else L.QIL_F64
+    info = L.QrPlanInfo()
+    L.check(L.lib.qil_qr_plan(code, int(m), int(n), C.byref(info)))
+    return _qr_plan_dict(info)
+
+
+def qr_host(A, m, n, a=(0, None), R=None, r=(0, None), reorth=False, cholesky_skip=0, ctx=None):
+    """The thin QR with non-negative diagonal on host buffers (testing hook).  A (and R, optional) are flat parent buffers of one
+    dtype; a, r = (element offset, leading dimension) of the m x n operand and of the n x n factor inside them.  Both buffers are
+    uploaded whole and come back in place, Q where the operand was.  reorth: measure Q^H Q and factor again while it is off;
+    cholesky_skip: CholeskyQR2 attempts to skip.  Returns the fields of qil_qr_report as a dict ("plan": as qr_plan returns it)."""
+    ctx = ctx or default_context()
+    code = L.QIL_C64 if A.dtype == np.complex128 else L.QIL_F64
+    for x in (A,) if R is None else (A, R):
+        if not (isinstance(x, np.ndarray) and x.ndim == 1 and x.dtype == _np_dtype(code) and x.flags.c_contiguous):
+            raise ValueError("qr_host: operands are flat contiguous arrays of one dtype (float64 or complex128)")
+    rep = L.QrReport()
+    L.check(L.lib.qil_qr_host(ctx.handle, code, int(m), int(n), A.ctypes.data, A.size, int(a[0]), int(m if a[1] is None else a[1]),
+                              None if R is None else R.ctypes.data, 0 if R is None else R.size, int(r[0]),
+                              int(n if r[1] is None else r[1]), int(bool(reorth)), int(cholesky_skip), C.byref(rep)))
+    return {"plan": _qr_plan_dict(rep.plan), "cholesky": rep.cholesky, "repairs": rep.repairs, "passes": rep.passes,
+            "skipped_check": rep.skipped_check, "worst": [float(w) for w in rep.worst]}
+
+
 def gemm_device_time(m, n, k, dtype=np.float64, opA="N", opB="N", reps=10, ctx=None):
     """ms per call of the device-resident MFMA GEMM (diagnostic)."""
     ctx = ctx or default_context()

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 TESTING_HOOKS = {"qil_context_fail_alloc_after", "qil_context_unowned_bytes", "qil_timer_start", "qil_timer_stop",
                  "qil_profile_enable", "qil_profile_read", "qil_gemm_device_time", "qil_hbm_store_peak",
-                 "qil_gemm_plan", "qil_gemm_batched_host", "qil_readout_route"}
+                 "qil_gemm_plan", "qil_gemm_batched_host", "qil_readout_route", "qil_qr_plan", "qil_qr_host"}
 
 
 def _symbols_of(header):
