@@ -183,6 +183,25 @@ QIL_API int qil_coefficient_marginal_batch(const qil_mps* psi, int64_t nb, const
 #define QIL_PRODUCT_CHAIN_MAX_BOND 1024
 #define QIL_MPO_ENTRY_CHAIN_MAX_BOND 1024   /* qil_mpo_entry_batch's one-launch route, below */
 QIL_API int qil_product_batch(const qil_mps* psi, int64_t nb, const double* v, double* out);
+/* Read-out by index, device to device:
+ *   out_dev[j] = amplitude * prod_i A_i[:, bit_i(idx_dev[j]), :],  j < count,
+ * tensor 1 the most significant bit of the index, as in qil_signal_mps; for a paired state the bits are the 2n interleaved
+ * tensors main_1, copy_1, ...  idx_dev: count int64 indices in HBM.  out_dev: count values of psi's dtype in HBM -- a real
+ * state gives doubles, not (re, im) pairs: the layout qil_cross_supply takes.
+ * Errors, before the context is activated: QIL_EINVAL_ARG for a null psi, count < 0, a null idx_dev or out_dev with count > 0,
+ * and for a chain of more than 62 tensors.  count = 0 is a no-op.  An index outside [0, 2^n) is NOT an error (finding it would
+ * need a read-back): out_dev holds NaN at that position, in both parts for a complex state.
+ * Stream rule, that of qil_cross_indices / qil_cross_supply: the caller orders the producer of idx_dev before the call; the
+ * verb runs on the context's stream and synchronises it before returning.  No index or value is copied to or from the host;
+ * every temporary is a pool block that returns before the call does.
+ * Route: bonds up to QIL_COEFFICIENT_AT_WAVE_MAX_BOND: one launch, one wave per index with the carry vector in LDS private to
+ * the wave; wider chains: the indices are expanded to device bits and take the marginal read-out's routes (one workgroup per
+ * index, or one f64-MFMA GEMM per tensor for all of them).  QIL_COEFFICIENT_AT_ROUTE=wave / bits (read per call) forces one;
+ * wave only while the carry fits the LDS (bonds up to 1024).  The cap is measured (MEASUREMENTS section 29): up to bond 8 the
+ * wave route never loses (equal at 64 indices, 2.9x faster at 262144); at bond 16 it wins near 4096 indices only, from bond
+ * 32 on it loses at all counts but a tie near 4096 (4x to 5x at 262144 indices, 9x to 11x at bond 64). */
+#define QIL_COEFFICIENT_AT_WAVE_MAX_BOND 8
+QIL_API int qil_coefficient_at(const qil_mps* psi, int64_t count, const int64_t* idx_dev, void* out_dev);
 /* <bits| W psi> without materialising W*psi (same numbers as
  * qil_coefficient_batch(qil_apply(W, psi))).                                      */
 QIL_API int qil_apply_coefficient_batch(const qil_mpo* W, const qil_mps* psi, int64_t nb,
@@ -751,6 +770,33 @@ QIL_API int qil_signal_mps_cross(qil_context* ctx, const void* x, int64_t len, i
  * a state that exists already, so that qil_ztmps_from_mps(qil_signal_mps(x, cutoff), cutoff) is qil_signal_ztmps(x, cutoff).
  * psi is left intact; a paired psi is QIL_EINVAL_ARG.  maxdim <= 0: no cap.                                          */
 QIL_API int qil_ztmps_from_mps(const qil_mps* psi, double cutoff, int64_t maxdim, qil_mps** out);
+/* An element-wise function of up to four states as a new state: out_x = f(states[0]_x, states[1]_x, ..), by the cross
+ * interpolation of qil_signal_mps_cross with the samples read from the operands on the device (one launch per block reads
+ * every operand at the block's indices and applies f; nothing of a block crosses the host).  Each value includes its state's
+ * amplitude.  The result carries the site ids of states[0] and obeys the encoder's invariants: a unit-norm chain whose
+ * amplitude is the norm.
+ *   op               states  params[0]    value                                    result dtype
+ *   QIL_MAP_ABS      1       --           |a|                                      f64
+ *   QIL_MAP_POWER    1       p > 0        |a|^p                                    f64
+ *   QIL_MAP_LOG      1       eps > 0      log(|a|^2 + eps)                         f64
+ *   QIL_MAP_DIVIDE   2       lambda >= 0  a conj(b) / (|b|^2 + lambda)  (0: a / b) c64 when a or b is, else f64
+ *   QIL_MAP_SHRINK   1       tau >= 0     a max(0, 1 - tau / |a|), 0 at a = 0      dtype of a
+ * maxdim, tol, max_sweeps, seeds, nseeds and the outputs est, nevals, sweeps, converged: as in qil_signal_mps_cross.
+ * Errors, before the context is activated and before a state is read: QIL_EINVAL_ARG for a null argument (states, a state,
+ * out, params of an op that takes one), an unknown op, nstates not matching the op, a parameter outside its range or not
+ * finite, and maxdim, tol, max_sweeps or seeds outside the ranges of qil_cross_begin.  Then: QIL_EINVAL_ARG for states of
+ * different contexts, for a paired state ("map: paired states are not supported; map the SignalMPS and call ztmps_from_mps"),
+ * for a chain of more than 62 tensors, for a seed >= 2^n and for a bond above 1024 (the carry of the sampler lives in LDS);
+ * QIL_EINVAL_LENGTH for states of different lengths; QIL_EINVAL_SITES for site ids that differ from states[0]'s.
+ * QIL_EDOMAIN when a sampled value is not finite (QIL_MAP_DIVIDE with lambda = 0 where b vanishes: every non-finite quotient
+ * is sampled as +inf) and when every sampled value is 0, both through the session's own checks.  A failed call leaves the
+ * pool as it was.
+ * The blind spot of cross interpolation is inherited: a feature of f(psi) that no pivot's row or column touches is invisible
+ * to the interpolation and to its estimate; pass its index among the seeds (the features of f(psi) usually sit where psi's do). */
+enum { QIL_MAP_ABS = 0, QIL_MAP_POWER = 1, QIL_MAP_LOG = 2, QIL_MAP_DIVIDE = 3, QIL_MAP_SHRINK = 4 };
+QIL_API int qil_mps_map(const qil_mps* const* states, int64_t nstates, int op, const double* params,
+                int64_t maxdim, double tol, int max_sweeps, const int64_t* seeds, int64_t nseeds,
+                qil_mps** out, double* est, int64_t* nevals, int* sweeps, int* converged);
 /* rsvd(A, Linds...; k, p, q, random_seed, cutoff, maxdim, mindim) src/linalg/rsvd.jl:38-121
  * on the matricised operand A (m x n, host, column-major).  Outputs (host, caller
  * allocated for rank min(k+p, m, n)): U m x r, S r, Vh r x n; *rank = r kept.        */

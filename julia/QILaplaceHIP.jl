@@ -21,7 +21,7 @@ export DeviceMPS, DeviceMPO, to_device, to_host, signal_mps_device, marginal, mp
     compress_mpo!, build_dt_mpo_batch, build_qft_mpo_device, build_zt_qft_chain_device, apply_coefficient_sweep, apply!, rsvd_device, svd_device,
     Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm, sample, top_k,
     hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress, restrict, weight_batch, apply_weight_batch, apply_sample, apply_top_k, bond_spectra,
-    signal_mps_cross, ztmps_from_mps, product_batch, mpo_linear_combination, mpo_inner, mpo_entry_batch, mpo_slice, environment
+    signal_mps_cross, ztmps_from_mps, coefficient_at!, map_states, product_batch, mpo_linear_combination, mpo_inner, mpo_entry_batch, mpo_slice, environment
 
 const LIB = get(ENV, "QILHIP_LIB", "libqilhip.so")
 
@@ -614,6 +614,30 @@ function ztmps_from_mps(psi::DeviceMPS; cutoff::Real=1e-10, maxdim::Int=typemax(
     n = length(psi.sites)
     sites = [Index(2; tags="site-$i") for i in 1:2n]
     return finalizer(_free!, DeviceMPS(r[], sites, true))
+end
+
+# read-out at `count` Int64 indices of the device buffer `idx` into the device buffer `out` (count values of psi's dtype);
+# an index outside [0, 2^n) gives NaN.  The caller orders the producer of idx before the call.
+function coefficient_at!(out::Ptr{Cvoid}, psi::DeviceMPS, idx::Ptr{Int64}, count::Integer)
+    check(ccall((:qil_coefficient_at, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cvoid}), psi.h, count, idx, out))
+    return out
+end
+
+# element-wise functions of states as new states, by cross interpolation with the samples read on the device:
+# op = :abs, :power (p > 0), :log (eps > 0), :divide (two states, lambda >= 0), :shrink (tau >= 0).  (psi, info)
+const _MAP_OPS = Dict(:abs => 0, :power => 1, :log => 2, :divide => 3, :shrink => 4)
+function map_states(op::Symbol, states::DeviceMPS...; param::Real=0.0, maxdim::Int=64, tol::Real=1e-10, max_sweeps::Int=8,
+                    seeds=nothing, random_seed::Int=1234)
+    n = length(states[1].sites)
+    sd = _cross_seeds(n, seeds, random_seed)
+    hs = Ptr{Cvoid}[s.h for s in states]
+    ps = Cdouble[param]
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    est, nevals, sweeps, converged = Ref{Cdouble}(0), Ref{Int64}(0), Ref{Cint}(0), Ref{Cint}(0)
+    GC.@preserve states check(ccall((:qil_mps_map, LIB), Cint,
+        (Ptr{Ptr{Cvoid}}, Int64, Cint, Ptr{Cdouble}, Int64, Cdouble, Cint, Ptr{Int64}, Int64, Ref{Ptr{Cvoid}}, Ref{Cdouble}, Ref{Int64}, Ref{Cint}, Ref{Cint}),
+        hs, length(hs), _MAP_OPS[op], ps, maxdim, tol, max_sweeps, sd, length(sd), r, est, nevals, sweeps, converged))
+    return finalizer(_free!, DeviceMPS(r[], copy(states[1].sites), false)), _cross_info(est, nevals, sweeps, converged)
 end
 
 # ---------------------------------------------------------------- back to the reference's host types

@@ -26,7 +26,7 @@ from .ops import (apply, apply_compress, apply_compress_batch, mpo_compress, com
                   exponential_mps, exponential_sum, restrict, zt_row, zt_column, copy_marginal, weight_batch, weight, bit_probabilities,
                   range_weight, weight_quantiles, zt_row_weights, zt_column_weights, apply_weight_batch, apply_weight,
                   apply_bit_probabilities, apply_range_weight, apply_weight_quantiles, apply_zt_row_weights, apply_zt_column_weights, canonicalize, compress, signal_mps, signal_ztmps, signal_mps_batch,
-                  signal_ztmps_batch, signal_mps_cross, ztmps_from_mps, rsvd,
+                  signal_ztmps_batch, signal_mps_cross, ztmps_from_mps, coefficient_at, coefficient_at_route, map_states, cross_map, magnitude, log_power, shrink, divide, deconvolve, rsvd,
                   svd_trunc, gemm, gemm_plan, readout_route, gemm_batched, gemm_device_time, qr_positive, qr_plan, qr_host)
 from .builders import (build_qft_mpo, build_dt_mpo, build_zt_mpo, qft_mpo_tensors,  # noqa: F401
                        dt_mpo_tensors, zt_mpo_tensors, dt_mpo_tensors_many, build_dt_mpo_batch,
@@ -52,6 +52,7 @@ __all__ = [
     "apply_weight_batch", "apply_weight", "apply_bit_probabilities", "apply_range_weight", "apply_weight_quantiles", "apply_zt_row_weights",
     "apply_zt_column_weights",
     "canonicalize", "compress", "signal_mps", "signal_ztmps", "signal_mps_batch", "signal_ztmps_batch", "signal_mps_cross", "ztmps_from_mps",
+    "coefficient_at", "coefficient_at_route", "map_states", "cross_map", "magnitude", "log_power", "shrink", "divide", "deconvolve",
     "rsvd", "svd_trunc", "gemm",
     "build_qft_mpo", "build_dt_mpo", "build_zt_mpo", "qft_mpo_tensors", "dt_mpo_tensors", "zt_mpo_tensors",
     "dt_mpo_tensors_many", "build_dt_mpo_batch", "build_zt_mpo_batch", "zt_qft_chain_tensors", "qft_mpo_device", "zt_qft_chain_device", "mpo_compress", "compress_batch", "mpo_compress_batch", "mps_block",

@@ -14,6 +14,8 @@ QIL_F64, QIL_C64 = 0, 1
 QIL_METHOD_SVD, QIL_METHOD_RSVD = 0, 1
 QIL_DIR_RIGHT, QIL_DIR_LEFT = 0, 1
 QIL_MAXDIM_NONE = 2 ** 63 - 1
+QIL_MAP_ABS, QIL_MAP_POWER, QIL_MAP_LOG, QIL_MAP_DIVIDE, QIL_MAP_SHRINK = range(5)
+QIL_COEFFICIENT_AT_WAVE_MAX_BOND = 8
 
 (QIL_OK, QIL_EINVAL_LENGTH, QIL_EINVAL_SITES, QIL_EINVAL_CONFIG, QIL_EDOMAIN, QIL_ENOMEM, QIL_EHIP,
  QIL_EINVAL_ARG, QIL_EEMPTY) = range(9)
@@ -191,6 +193,8 @@ PROTOTYPES = {
     "qil_cross_destroy": [_vp],
     "qil_signal_mps_cross": [_vp, _vp, _i64, _int, _i64, _dbl, _int, _pi64, _i64, _pvp, _pdbl, _pi64, _pint, _pint],
     "qil_ztmps_from_mps": [_vp, _dbl, _i64, _pvp],
+    "qil_coefficient_at": [_vp, _i64, _vp, _vp],
+    "qil_mps_map": [_pvp, _i64, _int, _pdbl, _i64, _dbl, _int, _pi64, _i64, _pvp, _pdbl, _pi64, _pint, _pint],
     "qil_rsvd": [_vp, _vp, _i64, _i64, _int, _i64, _i64, _int, _u64, _dbl, _i64, _i64, _pi64, _vp, _pdbl, _vp],
     "qil_build_dt_mpo_batch": [_vp, _i64, _i64, _pdbl, _dbl, _i64, _pi64, _pvp],
     "qil_build_zt_mpo_batch": [_vp, _i64, _i64, _pdbl, _dbl, _i64, _pi64, _pvp],

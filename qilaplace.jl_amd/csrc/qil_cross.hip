@@ -102,9 +102,9 @@ struct cross_index_k {
 // ---- the dense-signal evaluator -------------------------------------------------------------------------------------------
 template <class T>
 __device__ __forceinline__ void cross_gather_body(const uint3 blockIdx, const uint3 gridDim, const T* __restrict__ x, long long len,
-                                                    const long long* __restrict__ idx, const CrossState* __restrict__ st,
+                                                    const long long* __restrict__ idx, const int* __restrict__ cnt,
                                                     T* __restrict__ out) {
-    const long long total = st->cnt;
+    const long long total = *cnt;
     for (long long q = blockIdx.x * 256LL + threadIdx.x; q < total; q += gridDim.x * 256LL) {
         const long long j = idx[q];
         out[q] = j < len ? x[j] : T{};
@@ -591,6 +591,27 @@ int cross_check_args(const char* verb, qil_context* ctx, int64_t n, int dtype, i
 
 }  // namespace
 
+int qil_cross_check_args(const char* verb, qil_context* ctx, int64_t n, int dtype, int64_t maxdim, double tol, int max_sweeps,
+                         const int64_t* seeds, int64_t nseeds, const void* out) {
+    return cross_check_args(verb, ctx, n, dtype, maxdim, tol, max_sweeps, seeds, nseeds, out);
+}
+
+// The session with its evaluator inside the library (qil_signal_mps_cross: a gather from the signal; qil_mps_map: the index
+// read-out of the operands): the sample count stays in CrossState::cnt, the grids are sized by the host's bounds.
+int qil_cross_run(qil_context* ctx, int64_t n, int dtype, int64_t maxdim, double tol, int max_sweeps, const int64_t* seeds,
+                  int64_t nseeds, const qil_cross_eval& eval, qil_mps** out, double* est, int64_t* nevals, int* sweeps,
+                  int* converged) {
+    qil_cross* s = nullptr;
+    QIL_TRY(cross_begin_impl(ctx, n, dtype, maxdim, tol, max_sweeps, seeds, nseeds, false, &s));
+    cross_guard guard{s};
+    while (s->phase < kPhDone) {
+        const long long bound = s->phase == kPhBlock ? 4LL * s->ubI[(size_t)s->l - 1] * s->ubJ[(size_t)s->l + 1] : std::max<long long>(nseeds, 2);
+        QIL_TRY(eval((const long long*)s->idx, (const int*)&s->st->cnt, bound, s->vals));
+        QIL_TRY(cross_consume(s, s->vals));
+    }
+    return cross_finish_impl(s, out, est, nevals, sweeps, converged);
+}
+
 extern "C" int qil_cross_begin(qil_context* ctx, int64_t n, int dtype, int64_t maxdim, double tol, int max_sweeps,
                                const int64_t* seeds, int64_t nseeds, qil_cross** out) {
     QIL_TRY(cross_check_args("cross_begin", ctx, n, dtype, maxdim, tol, max_sweeps, seeds, nseeds, out));
@@ -666,20 +687,14 @@ extern "C" int qil_signal_mps_cross(qil_context* ctx, const void* x, int64_t len
         QIL_TRY(qil_upload_bytes(tmp, x, (size_t)len * e, &up));
         xd = up;
     }
-    qil_cross* s = nullptr;
-    QIL_TRY(cross_begin_impl(ctx, n, dtype, maxdim, tol, max_sweeps, seeds, nseeds, false, &s));
-    cross_guard guard{s};
-    while (s->phase < kPhDone) {
-        const long long bound = s->phase == kPhBlock ? 4LL * s->ubI[(size_t)s->l - 1] * s->ubJ[(size_t)s->l + 1] : std::max<long long>(nseeds, 2);
+    const qil_cross_eval gather = [&](const long long* idx, const int* cnt, long long bound, void* vals) {
         if (dtype == QIL_C64)
-            QIL_TRY((qil_klaunch<cross_gather_k<c64>>(ctx, dim3(qil_grid_for(bound)), dim3(256), 0, static_cast<const c64*>(xd), (long long)len,
-                                                      (const long long*)s->idx, (const CrossState*)s->st, static_cast<c64*>(s->vals))));
-        else
-            QIL_TRY((qil_klaunch<cross_gather_k<double>>(ctx, dim3(qil_grid_for(bound)), dim3(256), 0, static_cast<const double*>(xd), (long long)len,
-                                                         (const long long*)s->idx, (const CrossState*)s->st, static_cast<double*>(s->vals))));
-        QIL_TRY(cross_consume(s, s->vals));
-    }
-    QIL_TRY(cross_finish_impl(s, out, est, nevals, sweeps, converged));
+            return qil_klaunch<cross_gather_k<c64>>(ctx, dim3(qil_grid_for(bound)), dim3(256), 0, static_cast<const c64*>(xd), (long long)len,
+                                                    idx, cnt, static_cast<c64*>(vals));
+        return qil_klaunch<cross_gather_k<double>>(ctx, dim3(qil_grid_for(bound)), dim3(256), 0, static_cast<const double*>(xd), (long long)len,
+                                                   idx, cnt, static_cast<double*>(vals));
+    };
+    QIL_TRY(qil_cross_run(ctx, n, dtype, maxdim, tol, max_sweeps, seeds, nseeds, gather, out, est, nevals, sweeps, converged));
     QIL_HIP(qil_stream_sync(ctx));                 // `x` is caller memory: read completely before the call returns
     return QIL_OK;
 }

@@ -383,6 +383,34 @@ int qil_lazy_row_step(qil_context* ctx, int dt, const struct qil_mpo* W, const s
                       void* Mn, void* X, void* Wc, void* Ac, int64_t nq, const uint8_t* sel, int64_t sel_step);
 // (qil_readout.hip) dout[t] = amplitude * v[t] (complex out, v of dtype dt), t < nb: the last step of a GEMM-form read-out
 int qil_dev_finish_coeff(qil_context* ctx, int dt, const void* v, int64_t nb, double amplitude, void* dout);
+// (qil_readout.hip) the read-out of nb rows of DEVICE bits (nb x n bytes, values 0 / 1 / 2) into dout (nb complex, device) under
+// the marginal verb: its routes, CHAIN and GEMM_SELECT, need no host plan.  Only enqueues; temporaries go back in stream order.
+int qil_coefficient_enqueue_select(const struct qil_mps* psi, int64_t nb, const uint8_t* dbits, void* dout);
+// ---- (qil_index.hip) the wave-per-index reader: up to QIL_MAP_MAX_STATES chains of one length read at the same int64 device
+// indices, the values (amplitudes included) optionally through an element-wise function (op = a QIL_MAP_* value, < 0: the value
+// of state 0).  begin() uploads the site table into a block of tmp (stream-synchronised) and refuses a bond above what the LDS
+// holds; enqueue() launches for `bound` indices or, with cnt_dev, for the device-side count *cnt_dev <= bound.  The carry dtype
+// is c64 when any state is; out holds doubles for QIL_MAP_ABS / POWER / LOG and for all-real states, c64 otherwise.
+constexpr int QIL_MAP_MAX_STATES = 4;
+struct qil_index_reader {
+    const void* tab = nullptr;
+    int n = 0, nstates = 0, maxchi = 1;
+    bool cx = false;
+    double amp[QIL_MAP_MAX_STATES] = {};
+};
+int qil_index_reader_begin(qil_scratch& tmp, const struct qil_mps* const* states, int nstates, qil_index_reader* r);
+int qil_index_reader_enqueue(qil_context* ctx, const qil_index_reader& r, int op, double param, const long long* idx,
+                             const int* cnt_dev, int64_t bound, void* out);
+// ---- (qil_cross.hip) the cross-interpolation session driven inside the library: cross_begin_impl, then per request
+// eval(idx, cnt_dev, bound, vals) -- enqueue the evaluation of the *cnt_dev <= bound pending sample indices idx into vals
+// (device, `dtype`) -- and cross_consume, then cross_finish_impl.  No host round trip per block.  Context active, call scope
+// open, arguments checked (qil_cross_check_args: the ranges of qil_cross_begin under the caller's verb).
+using qil_cross_eval = std::function<int(const long long* idx, const int* cnt_dev, long long bound, void* vals)>;
+int qil_cross_check_args(const char* verb, qil_context* ctx, int64_t n, int dtype, int64_t maxdim, double tol, int max_sweeps,
+                         const int64_t* seeds, int64_t nseeds, const void* out);
+int qil_cross_run(qil_context* ctx, int64_t n, int dtype, int64_t maxdim, double tol, int max_sweeps, const int64_t* seeds,
+                  int64_t nseeds, const qil_cross_eval& eval, struct qil_mps** out, double* est, int64_t* nevals, int* sweeps,
+                  int* converged);
 // ---- (qil_contract.hip) the steps the overlap and Born-weight verbs share
 // blocks of 256 threads for `work` items of a grid-stride kernel
 inline unsigned qil_grid_for(long long work, long long cap = 4096) {

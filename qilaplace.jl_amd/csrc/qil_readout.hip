@@ -521,6 +521,11 @@ static int coefficient_enqueue(const qil_mps* psi, int64_t nb, const uint8_t* db
     }
 }
 
+// the device-to-device form for qil_coefficient_at (qil_index.hip): the marginal verb's routes take device bits as they are
+int qil_coefficient_enqueue_select(const qil_mps* psi, int64_t nb, const uint8_t* dbits, void* dout) {
+    return coefficient_enqueue(psi, nb, dbits, dout, QIL_READOUT_MARGINAL, nullptr);
+}
+
 static int coefficient_impl(const qil_mps* psi, int64_t nb, const uint8_t* bits, double* out, int max_bit) {
     QIL_REQUIRE(psi && (nb == 0 || (bits && out)), QIL_EINVAL_ARG, "coefficient: null argument");
     if (nb == 0) return QIL_OK;

@@ -1072,7 +1072,8 @@ def adjoint(W):
     return type(W)(ctx=W.ctx, _handle=h)
 
 
-def _spectral_product(x, h, F, maxdim, tol, conj, what):
+def _spectral_operands(x, h, F, what):
+    """The operand checks of the spectral verbs and the transform they use: `F`, or build_qft_mpo(x)."""
     if not (isinstance(x, SignalMPS) and isinstance(h, SignalMPS)) or x._paired() or h._paired():
         raise TypeError(f"{what}: unsupported operand types")
     if F is not None and not (isinstance(F, SingleSiteMPO) and not F._paired()):
@@ -1082,6 +1083,11 @@ def _spectral_product(x, h, F, maxdim, tol, conj, what):
     if F is None:
         from .builders import build_qft_mpo
         F = build_qft_mpo(x)
+    return F
+
+
+def _spectral_product(x, h, F, maxdim, tol, conj, what):
+    F = _spectral_operands(x, h, F, what)
     X = apply_compress(F, x, maxdim=maxdim, tol=tol)
     H = apply_compress(F, h, maxdim=maxdim, tol=tol)
     P = hadamard_compress(X, H, conj=conj, maxdim=maxdim, tol=tol)
@@ -2026,6 +2032,173 @@ def ztmps_from_mps(psi, cutoff=1e-10, maxdim=None):
     h = C.c_void_p()
     L.check(L.lib.qil_ztmps_from_mps(psi.handle, float(cutoff), _maxdim(maxdim), C.byref(h)))
     return ZTMPS(ctx=psi.ctx, _handle=h)
+
+
+# ---------------------------------------------------------------- read-out by index on the device, element-wise functions
+def coefficient_at_route(dims, forced=None):
+    """The route qil_coefficient_at takes for a chain with the bond dimensions `dims` (the decision of csrc/qil_index.hip,
+    mirrored): "wave" while every bond is <= QIL_COEFFICIENT_AT_WAVE_MAX_BOND, "bits" above.  forced: the value of
+    QIL_COEFFICIENT_AT_ROUTE; "wave" holds while the carry fits the LDS (bonds <= 1024), "bits" always."""
+    top = max([1] + [int(d) for d in dims])
+    if forced == "bits":
+        return "bits"
+    if forced == "wave":
+        return "wave" if top <= 1024 else "bits"
+    return "wave" if top <= L.QIL_COEFFICIENT_AT_WAVE_MAX_BOND else "bits"
+
+
+def coefficient_at(psi, idx):
+    """psi at the indices idx, device to device (include/qilaplace_hip.h, qil_coefficient_at): idx is a 1-D int64 torch tensor
+    on the context's device or any `__cuda_array_interface__` object; the result is a torch tensor on that device, float64 for
+    a real state and complex128 otherwise, amplitude included.  Site 1 is the most significant bit of an index (for a ZTMPS:
+    of the 2n interleaved tensors main_1, copy_1, ..).  An index outside [0, 2^n) gives NaN.  Host configurations go through
+    coefficient_batch."""
+    if not isinstance(psi, SignalMPS):
+        raise TypeError("coefficient_at: unsupported operand types")
+    import torch
+    if isinstance(idx, torch.Tensor):
+        if idx.device.type != "cuda":
+            raise TypeError("coefficient_at: idx must live on the device; for host configurations use coefficient_batch")
+        t = idx
+    elif hasattr(idx, "__cuda_array_interface__"):
+        t = torch.as_tensor(idx, device=torch.device("cuda", psi.ctx.device))
+    else:
+        raise TypeError("coefficient_at: idx must be a device tensor or a __cuda_array_interface__ object; for host "
+                        "configurations use coefficient_batch")
+    dev = torch.device("cuda", psi.ctx.device)
+    if t.dtype != torch.int64 or t.dim() != 1:
+        raise ValueError(f"coefficient_at: idx must be a 1-D int64 tensor, got {t.dtype} with {t.dim()} dimensions")
+    if t.device != dev:
+        raise ValueError(f"coefficient_at: idx lives on {t.device}, the state on {dev}")
+    t = t.contiguous()
+    out = torch.empty(t.numel(), dtype=torch.complex128 if psi.dtype == np.complex128 else torch.float64, device=dev)
+    if t.numel():
+        torch.cuda.current_stream(dev).synchronize()
+        L.check(L.lib.qil_coefficient_at(psi.handle, t.numel(), C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr())))
+    return out
+
+
+_MAP_OPS = {"abs": (L.QIL_MAP_ABS, 1, 0), "power": (L.QIL_MAP_POWER, 1, 1), "log": (L.QIL_MAP_LOG, 1, 1),
+            "divide": (L.QIL_MAP_DIVIDE, 2, 1), "shrink": (L.QIL_MAP_SHRINK, 1, 1)}      # name: (code, states, parameters)
+
+
+def _map_operands(what, states, count=None):
+    """Unpaired SignalMPS of one length, checked before any native verb; returns the number of sites."""
+    if not states or not all(isinstance(s, SignalMPS) for s in states) or (count is not None and len(states) != count):
+        raise TypeError(f"{what}: unsupported operand types")
+    if any(s._paired() for s in states):
+        raise ValueError("map: paired states are not supported; map the SignalMPS and call ztmps_from_mps")
+    n = len(states[0])
+    for s in states[1:]:
+        if len(s) != n:
+            raise ValueError(f"{what}: states must have the same number of sites. Found {n} and {len(s)}")
+    return n
+
+
+def _map_seeds(states, n, seeds, seed_peaks, random_seed):
+    """Explicit seeds as given; otherwise _cross_seeds' defaults and, per operand, the indices of its seed_peaks largest entries."""
+    if seeds is not None or n > 62:
+        return _cross_seeds(min(n, 62), seeds, random_seed)
+    parts = [_cross_seeds(n, None, random_seed)[0]]
+    if seed_peaks:
+        for s in states:
+            parts.append(np.asarray(top_k(s, k=min(int(seed_peaks), 2 ** n))[0], dtype=np.int64))
+    return _cross_seeds(n, np.concatenate(parts), random_seed)
+
+
+def map_states(op, *states, params=(), maxdim=64, tol=1e-10, max_sweeps=8, seeds=None, seed_peaks=8, random_seed=1234,
+               return_info=False):
+    """An element-wise function of states as a new SignalMPS, by cross interpolation with the samples read from the operands on
+    the device (include/qilaplace_hip.h, qil_mps_map).  op: "abs" |a|, "power" |a|^p (params = (p,), p > 0), "log"
+    log(|a|^2 + eps) (eps > 0), "divide" a conj(b) / (|b|^2 + lambda) of two states (lambda >= 0; 0 is a / b), "shrink"
+    a max(0, 1 - tau / |a|) (tau >= 0).  Amplitudes are included.  abs, power and log give a real state, divide a complex one
+    when either operand is, shrink its operand's dtype.
+
+    maxdim, tol, max_sweeps, seeds, random_seed, return_info: as in signal_mps_cross.  By default the seeds are
+    signal_mps_cross' and the indices of the seed_peaks largest entries of every operand (top_k): the features of f(psi)
+    usually sit where psi's do.  seed_peaks=0 turns that off; explicit seeds are used as given.
+
+    The blind spot of cross interpolation is inherited: a feature of the result that no pivot's row or column touches is
+    invisible, and the estimate does not see it either; the remedy is to pass its index in `seeds`."""
+    if op not in _MAP_OPS:
+        raise ValueError(f"map_states: unknown op {op!r}; one of {sorted(_MAP_OPS)}")
+    code, count, nparams = _MAP_OPS[op]
+    n = _map_operands("map_states", states, count)
+    if not isinstance(maxdim, (int, np.integer)) or isinstance(maxdim, bool):
+        raise ValueError("map_states: maxdim must be an integer, 1 .. 256")
+    par = np.ascontiguousarray(np.atleast_1d(np.asarray(params, dtype=np.float64)).reshape(-1))
+    if len(par) != nparams:
+        raise ValueError(f"map_states: {op} takes {nparams} parameter(s), got {len(par)}")
+    seeds_np, seeds_p = _map_seeds(states, n, seeds, seed_peaks, random_seed)
+    handles = (C.c_void_p * len(states))(*[s.handle for s in states])
+    h = C.c_void_p()
+    est, nevals, sweeps, converged = C.c_double(), C.c_int64(), C.c_int(), C.c_int()
+    L.check(L.lib.qil_mps_map(handles, len(states), code, par.ctypes.data_as(L._pdbl) if nparams else None, int(maxdim),
+                              float(tol), int(max_sweeps), seeds_p, len(seeds_np), C.byref(h), C.byref(est), C.byref(nevals),
+                              C.byref(sweeps), C.byref(converged)))
+    out = SignalMPS(ctx=states[0].ctx, _handle=h)
+    return (out, _cross_info(est, nevals, sweeps, converged)) if return_info else out
+
+
+def cross_map(f, *states, n=None, maxdim=64, tol=1e-10, max_sweeps=8, seeds=None, seed_peaks=8, random_seed=1234,
+              return_info=False):
+    """The SignalMPS of f(psi_1[x], psi_2[x], ..) for an arbitrary torch function f of device value tensors (float64 for a real
+    state, complex128 otherwise; f returns float64 or complex128 of the same length): the pull session of signal_mps_cross
+    with every request answered by coefficient_at on the operands.  The arguments and the blind spot are map_states'.  The
+    five built-in functions are faster through map_states, which never leaves the library, while the operands' bonds are small
+    (1.6x at bond 8); at bond 32 and above this route is the faster one for them too, because coefficient_at then reads
+    through MFMA GEMMs and map_states' sampler does not (MEASUREMENTS section 29)."""
+    if not callable(f):
+        raise TypeError("cross_map: f must be callable")
+    nn = _map_operands("cross_map", states)
+    if n is not None and int(n) != nn:
+        raise ValueError(f"cross_map: n = {n} does not match states of {nn} sites")
+    if not isinstance(maxdim, (int, np.integer)) or isinstance(maxdim, bool):
+        raise ValueError("cross_map: maxdim must be an integer, 1 .. 256")
+    seeds_np, _ = _map_seeds(states, nn, seeds, seed_peaks, random_seed)
+    psi, info = _cross_from_callable(lambda idx: f(*[coefficient_at(s, idx) for s in states]), nn, maxdim, tol, max_sweeps,
+                                     seeds_np, random_seed, states[0].ctx)
+    return (psi, info) if return_info else psi
+
+
+def magnitude(psi, **kwargs):
+    """|psi_x| as a real state: map_states("abs", psi, ...)."""
+    return map_states("abs", psi, **kwargs)
+
+
+def log_power(psi, eps, **kwargs):
+    """log(|psi_x|^2 + eps) as a real state (a spectrum in dB is 10 / ln 10 times it): map_states("log", psi, params=(eps,), ...)."""
+    return map_states("log", psi, params=(eps,), **kwargs)
+
+
+def shrink(psi, tau, **kwargs):
+    """Soft thresholding psi_x max(0, 1 - tau / |psi_x|): map_states("shrink", psi, params=(tau,), ...)."""
+    return map_states("shrink", psi, params=(tau,), **kwargs)
+
+
+def divide(a, b, reg=0.0, **kwargs):
+    """a_x conj(b_x) / (|b_x|^2 + reg); reg = 0 is the plain quotient a_x / b_x, which raises QilDomainError where a sampled
+    b_x vanishes: map_states("divide", a, b, params=(reg,), ...)."""
+    return map_states("divide", a, b, params=(reg,), **kwargs)
+
+
+def deconvolve(y, h, reg=0.0, F=None, maxdim=None, tol=1e-12, map_tol=1e-10, map_maxdim=64):
+    """The inverse of `convolve` in MPS form: x = (1 / sqrt(N)) F^dagger((F y) conj(F h) / (|F h|^2 + reg)), the x with
+    convolve(x, h) = y when reg = 0 and F h vanishes nowhere.  The stages and the `F` handling are convolve's (F y, F h and
+    F^dagger through apply_compress with `maxdim` and `tol`; F's bit reversal cancels between F and F^dagger); the quotient is
+    divide(F y, F h, reg, tol=map_tol, maxdim=map_maxdim), a cross interpolation.
+
+    As for convolve, the QFT MPO at its default cutoff 1e-14 is unitary only to 3e-9 (n = 6) ... 3e-7 (n = 10), and here that
+    error is divided by min |F h|: the result matches the dense deconvolution to about 1e-7 max|F y| / min|F h| relative to
+    the spectrum, whatever `tol` is.  Pass F = build_qft_mpo(y, cutoff=...) with a tighter cutoff for a tighter result, and
+    reg > 0 where F h comes close to zero."""
+    F = _spectral_operands(y, h, F, "deconvolve")
+    Y = apply_compress(F, y, maxdim=maxdim, tol=tol)
+    H = apply_compress(F, h, maxdim=maxdim, tol=tol)
+    Q = divide(Y, H, reg, tol=map_tol, maxdim=map_maxdim)
+    x = apply_compress(adjoint(F), Q, maxdim=maxdim, tol=tol)
+    x.amplitude = x.amplitude / float(np.sqrt(2.0) ** len(y))
+    return x
 
 
 def _factor_out(m, n, r0, code):
