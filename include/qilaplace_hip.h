@@ -308,6 +308,47 @@ QIL_API int qil_environment(const qil_mps* phi, const qil_mpo* W, const qil_mps*
  * pinned by tests/test_cabi_symbols.py.) */
 QIL_API int qil_environment_route(int side, int64_t count, int64_t n, const int64_t* phi_dims, const int64_t* psi_dims,
                                   const int64_t* op_dims, int* route);
+/* ------------------------------------------------------------------ linear solver (no reference counterpart) */
+/* Solves (A + shift I) x = c for A + shift I Hermitian positive definite, by the alternating two-site solver (ALS / DMRG for
+ * linear systems) with a conjugate-gradient local solve.  HERMITICITY IS THE CALLER'S PROMISE: it cannot be checked cheaply and
+ * is not; a non-Hermitian operator gives a wrong answer, not an error.  (A, c) pass the checks of qil_apply; x0, the initial
+ * guess, may be null (a clone of c, compressed to maxdim where it is wider) and otherwise passes the checks of qil_inner against
+ * c.  Single-register and paired chains (their 2n tensors) both work; every f64 / c64 mix is accepted, and the contraction and
+ * the result are c64 when any operand is complex.  The solve runs on the tensors; *out carries c's amplitude (the solver factors
+ * no scalar out of the tensors: the weight sits in the first tensor), so that qil_mps_to_vector(*out) is the solution.
+ * Per bond k and half-sweep (a full sweep goes left to right, then right to left): the local right-hand side
+ * g = Lc c_k c_{k+1} Rc and the local operator H v = L_A A_k A_{k+1} R_A v + shift v are formed from environments that are
+ * updated one tensor at a time; CG runs from the current two-site tensor until |r| <= tol |g| or cg_iters iterations; the
+ * result is split by the SVD under the project's truncation rule (drop the tail while the dropped weight <= cutoff * total,
+ * at most maxdim, at least 1).  Each local step records |g - H y| / |g| before its CG; the verb stops after the first full
+ * sweep whose largest such value is <= tol, or after max_sweeps (converged = 0; not an error: a truncation coarser than tol
+ * keeps the value above tol).  With maxdim below the solution's rank and a right-hand side that does not compress, truncation
+ * by SVD does not converge to the best approximation: the verb is for solutions that compress.
+ * info (8 doubles, may be null): full sweeps done; converged (0 / 1); the largest pre-solve local residual of the last sweep;
+ * matvecs in total; the largest bond of *out; local solves by the one-launch route; by the GEMM route; 0.
+ * Routes of the local solve, per bond: "local", one launch of one workgroup with the whole CG in it, where
+ * qil_mps_solve_local_fits says so (it fits the LDS and is small enough to win); "gemm", four f64-MFMA products per matvec and CG's scalars in device memory, any bonds.
+ * QIL_SOLVE_ROUTE=local / gemm forces one (read per call; local only where the bond fits, else gemm, and info shows it).
+ * Errors, before the context is activated: QIL_EINVAL_ARG for a null A, c or out, for maxdim, max_sweeps or cg_iters < 1, for
+ * a shift, cutoff or tol that is not finite, for cutoff < 0 or tol <= 0; the operand errors of qil_apply and qil_inner;
+ * QIL_EINVAL_LENGTH for a chain of one tensor (the two-site step needs a bond).  During the solve: QIL_EDOMAIN, "solve: operator
+ * not positive definite on the local space (bond k)".  Every temporary belongs to the call; a failed call leaves nothing behind
+ * and *out untouched. */
+QIL_API int qil_mps_solve(const qil_mpo* A, double shift, const qil_mps* c, const qil_mps* x0 /* may be null */,
+                          int64_t maxdim, double cutoff, double tol, int max_sweeps, int cg_iters,
+                          qil_mps** out, double* info /* 8 doubles, may be null */);
+/* Whether the local solve of a bond takes the one-launch route: THE decision, not a copy of it -- qil_mps_solve switches on this
+ * value for every bond.  Host only: no context, no GPU.  complex_: the contraction type is c64; xl, xr: the outer bonds of x at
+ * the two tensors; dl, dm, dr: the operator's three bonds there; cl, cm, cr: those of c.  *fits = 1 when the LDS the kernel needs,
+ *     128 + e * (xl^2 dl + xr^2 dr + 4 dl dm + 4 dm dr + 12 xl xr + 2 blk) bytes,   e = 8 (f64) / 16 (c64),
+ *     blk = max(4 xl xr max(dl, dm, dr), 2 xl cm, 4 xl cr)
+ * (both environments, both operator tensors, y, r, p and two ping-pong blocks), is within 160 KiB, QIL_SOLVE_ROUTE is not
+ * gemm, and -- unless QIL_SOLVE_ROUTE is local -- one matvec is at most 200000 multiply-adds,
+ *     4 xl^2 xr dl + 8 xl xr dm (dl + dr) + 4 xl xr^2 dr,
+ * the size up to which the one workgroup was measured to beat the GEMMs (MEASUREMENTS.md).  Growing a dimension never turns 0
+ * into 1.  QIL_EINVAL_ARG for a null fits or a dimension < 1. */
+QIL_API int qil_mps_solve_local_fits(int complex_, int64_t xl, int64_t xr, int64_t dl, int64_t dm, int64_t dr,
+                                     int64_t cl, int64_t cm, int64_t cr, int* fits);
 /* Schmidt spectra of every bond (ITensors' svd(...).spec at every cut; no entry of the reference returns them).  S_out: host,
  * sum_k bond_k doubles; bond k (k = 1 .. N - 1 in tensor order, interleaved for paired chains) owns the bond_k slots that start
  * at the sum of the earlier bond dimensions, as qil_mps_bond_dims reports them at the time of the call.  Each block holds the

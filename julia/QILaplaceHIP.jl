@@ -21,7 +21,7 @@ export DeviceMPS, DeviceMPO, to_device, to_host, signal_mps_device, marginal, mp
     compress_mpo!, build_dt_mpo_batch, build_qft_mpo_device, build_zt_qft_chain_device, apply_coefficient_sweep, apply!, rsvd_device, svd_device,
     Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm, sample, top_k,
     hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress, restrict, weight_batch, apply_weight_batch, apply_sample, apply_top_k, bond_spectra,
-    signal_mps_cross, ztmps_from_mps, coefficient_at!, map_states, product_batch, mpo_linear_combination, mpo_inner, mpo_entry_batch, mpo_slice, environment
+    signal_mps_cross, ztmps_from_mps, coefficient_at!, map_states, product_batch, mpo_linear_combination, mpo_inner, mpo_entry_batch, mpo_slice, environment, solve, solve_local_fits
 
 const LIB = get(ENV, "QILHIP_LIB", "libqilhip.so")
 
@@ -263,6 +263,27 @@ function environment(phi::DeviceMPS, psi::DeviceMPS; W::Union{DeviceMPO,Nothing}
     GC.@preserve out check(ccall((:qil_environment, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Ptr{Cdouble}, Ptr{Int64}),
                                  phi.h, wh, psi.h, code, Int64(count), Ptr{Cdouble}(pointer(out)), dims))
     return W === nothing ? out[:, 1, :] : out
+end
+# solve: x with (A + shift I) x = c for a Hermitian positive definite A + shift I (the caller's promise; not checked), by the
+# alternating two-site solver with a CG local solve.  x0 = nothing starts from c.  Returns (x, info); info = (sweeps, converged,
+# residual, matvecs, max_bond, local_solves, gemm_solves).  solve_local_fits: whether a bond takes the one-launch local route.
+function solve(A::DeviceMPO, c::DeviceMPS; x0::Union{DeviceMPS,Nothing}=nothing, shift::Float64=0.0, maxdim::Int=64,
+               cutoff::Float64=1e-20, tol::Float64=1e-10, max_sweeps::Int=6, cg_iters::Int=100)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    info = zeros(Float64, 8)
+    check(ccall((:qil_mps_solve, LIB), Cint,
+                (Ptr{Cvoid}, Cdouble, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cdouble, Cdouble, Cint, Cint, Ref{Ptr{Cvoid}}, Ptr{Cdouble}),
+                A.h, shift, c.h, x0 === nothing ? C_NULL : x0.h, maxdim, cutoff, tol, max_sweeps, cg_iters, r, info))
+    x = finalizer(_free!, DeviceMPS(r[], copy(c.sites), c.paired))
+    return x, (sweeps=Int(info[1]), converged=info[2] != 0, residual=info[3], matvecs=Int(info[4]), max_bond=Int(info[5]),
+               local_solves=Int(info[6]), gemm_solves=Int(info[7]))
+end
+function solve_local_fits(complex::Bool, xl::Integer, xr::Integer, dl::Integer, dm::Integer, dr::Integer, cl::Integer, cm::Integer,
+                          cr::Integer)
+    f = Ref{Cint}(0)
+    check(ccall((:qil_mps_solve_local_fits, LIB), Cint, (Cint, Int64, Int64, Int64, Int64, Int64, Int64, Int64, Int64, Ref{Cint}),
+                complex, xl, xr, dl, dm, dr, cl, cm, cr, f))
+    return f[] != 0
 end
 function apply_norm(W::DeviceMPO, psi::DeviceMPS)                              # norm(W * psi) without the product
     v = Ref{Cdouble}(0)

@@ -17,7 +17,7 @@ from .containers import (Context, default_context, set_default_context, device_c
 from .ops import (apply, apply_compress, apply_compress_batch, mpo_compress, compress_batch, mpo_compress_batch, mps_block, coefficient, coefficient_batch, apply_coefficient_batch, apply_coefficient_sweep,  # noqa: F401
                   marginal_batch, coefficient_grid, laplace_values, product_batch, laplace_weights, laplace_sum, power_sum, dft_eval, dt_eval,
                   zt_eval, refine_frequencies,
-                  mps_to_vector, norm, inner, environment, environment_route, shift_pencil, esprit_from_pencil, esprit, apply_norm, distance, apply_distance, bond_spectra, mpo_bond_spectra, entanglement_entropy,
+                  mps_to_vector, norm, inner, environment, environment_route, shift_pencil, esprit_from_pencil, esprit, solve, solve_local_fits, solve_residual, least_squares, smooth, apply_norm, distance, apply_distance, bond_spectra, mpo_bond_spectra, entanglement_entropy,
                   truncation_error_bounds, required_maxdim, sample, apply_sample, top_k, apply_top_k, hadamard, hadamard_compress, diagonal_mpo, adjoint, convolve, correlate,
                   power_spectrum, linear_combination, linear_combination_compress, add, sub, scale, exponential_tensors,
                   mpo_linear_combination, mpo_linear_combination_compress, mpo_add, mpo_sub, mpo_scale, mpo_inner, mpo_norm,
@@ -31,7 +31,7 @@ from .ops import (apply, apply_compress, apply_compress_batch, mpo_compress, com
 from .builders import (build_qft_mpo, build_dt_mpo, build_zt_mpo, qft_mpo_tensors,  # noqa: F401
                        dt_mpo_tensors, zt_mpo_tensors, dt_mpo_tensors_many, build_dt_mpo_batch,
                        build_zt_mpo_batch, zt_qft_chain_tensors, qft_mpo_device, zt_qft_chain_device,
-                       shift_mpo_tensors, build_shift_mpo, fir_mpo)
+                       shift_mpo_tensors, build_shift_mpo, fir_mpo, laplacian_mpo_tensors, build_laplacian_mpo)
 from .interchange import save, load  # noqa: F401
 from .sweep import shard_items, sweep, damping_sweep, gather_results, damping_sample_bits, Comm, unshuffle  # noqa: F401
 
@@ -40,13 +40,13 @@ __all__ = [
     "SignalMPS", "ZTMPS", "SingleSiteMPO", "PairedSiteMPO",
     "apply", "apply_compress", "apply_compress_batch", "coefficient", "coefficient_batch", "apply_coefficient_batch", "apply_coefficient_sweep", "marginal_batch", "coefficient_grid", "laplace_values", "mps_to_vector", "norm",
     "product_batch", "laplace_weights", "laplace_sum", "power_sum", "dft_eval", "dt_eval", "zt_eval", "refine_frequencies",
-    "inner", "environment", "shift_pencil", "esprit_from_pencil", "esprit", "apply_norm", "distance", "apply_distance", "bond_spectra", "mpo_bond_spectra", "entanglement_entropy",
+    "inner", "environment", "shift_pencil", "esprit_from_pencil", "esprit", "solve", "solve_local_fits", "solve_residual", "least_squares", "smooth", "apply_norm", "distance", "apply_distance", "bond_spectra", "mpo_bond_spectra", "entanglement_entropy",
     "truncation_error_bounds", "required_maxdim", "sample", "apply_sample", "top_k", "apply_top_k",
     "hadamard", "hadamard_compress", "diagonal_mpo", "adjoint", "convolve", "correlate", "power_spectrum",
     "linear_combination", "linear_combination_compress", "add", "sub", "scale", "exponential_tensors", "exponential_mps",
     "mpo_linear_combination", "mpo_linear_combination_compress", "mpo_add", "mpo_sub", "mpo_scale", "mpo_inner", "mpo_norm",
     "mpo_distance", "mpo_trace", "mpo_entry_batch", "mpo_slice", "mpo_entries", "mpo_entry", "mpo_to_matrix", "mpo_column",
-    "mpo_row", "mpo_diagonal_state", "mpo_column_sums", "mpo_row_sums", "shift_mpo_tensors", "build_shift_mpo", "fir_mpo",
+    "mpo_row", "mpo_diagonal_state", "mpo_column_sums", "mpo_row_sums", "shift_mpo_tensors", "build_shift_mpo", "fir_mpo", "laplacian_mpo_tensors", "build_laplacian_mpo",
     "exponential_sum", "restrict", "zt_row", "zt_column", "copy_marginal",
     "weight_batch", "weight", "bit_probabilities", "range_weight", "weight_quantiles", "zt_row_weights", "zt_column_weights",
     "apply_weight_batch", "apply_weight", "apply_bit_probabilities", "apply_range_weight", "apply_weight_quantiles", "apply_zt_row_weights",

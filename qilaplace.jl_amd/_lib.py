@@ -155,6 +155,8 @@ PROTOTYPES = {
     "qil_apply_inner": [_vp, _vp, _vp, _pdbl],
     "qil_apply_norm": [_vp, _vp, _pdbl],
     "qil_environment": [_vp, _vp, _vp, _int, _i64, _pdbl, _pi64],
+    "qil_mps_solve": [_vp, _dbl, _vp, _vp, _i64, _dbl, _dbl, _int, _int, _pvp, _pdbl],
+    "qil_mps_solve_local_fits": [_int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _pint],
     "qil_bond_spectra": [_vp, _pdbl, _pdbl],
     "qil_mpo_bond_spectra": [_vp, _pdbl, _pdbl],
     "qil_sample": [_vp, _i64, _u64, _pdbl, _pu8, _pdbl],

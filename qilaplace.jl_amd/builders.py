@@ -347,6 +347,41 @@ def build_shift_mpo(n_or_psi, s, sites=None, ctx=None):
     return SingleSiteMPO(shift_mpo_tensors(n, s), sites=sites, ctx=ctx)
 
 
+def laplacian_mpo_tensors(n):
+    """The periodic second difference L = 2 I - S - S^T (S = the cyclic shift by one sample) as host tensors: the direct sum of
+    the identity (bond 1) and the two shifts (bond 2 each, `shift_mpo_tensors`), the weights 2, -1, -1 in the first tensor.
+    Exact and integer-valued, bond 5; the tensors `build_laplacian_mpo` builds on the device."""
+    n = int(n)
+    if n < 2:
+        raise ValueError(f"laplacian_mpo_tensors: n must be >= 2, got {n}")
+    eye = np.eye(2).reshape(1, 2, 2, 1)
+    terms = [(2.0, [eye] * n), (-1.0, shift_mpo_tensors(n, 1)), (-1.0, shift_mpo_tensors(n, -1))]
+    out = []
+    for i in range(n):
+        Dl = 1 if i == 0 else sum(t[i].shape[0] for _, t in terms)
+        Dr = 1 if i == n - 1 else sum(t[i].shape[3] for _, t in terms)
+        W = np.zeros((Dl, 2, 2, Dr))
+        a = b = 0
+        for w, t in terms:
+            da, db = t[i].shape[0], t[i].shape[3]
+            a0, b0 = (0 if i == 0 else a), (0 if i == n - 1 else b)
+            W[a0:a0 + da, :, :, b0:b0 + db] += (w if i == 0 else 1.0) * t[i]
+            a, b = a + da, b + db
+        out.append(W)
+    return out
+
+
+def build_laplacian_mpo(n_or_psi, ctx=None):
+    """The periodic second difference 2 I - S - S^dagger as a SingleSiteMPO on the device: mpo_linear_combination of the identity,
+    build_shift_mpo(n, 1) and its adjoint, on the sites and context of a SignalMPS when one is given.  Exact and integer-valued
+    (bond 5, the tensors of `laplacian_mpo_tensors`); its spectrum is 2 - 2 cos(2 pi m / 2^n), so I + alpha L is the Helmholtz
+    operator of `smooth`."""
+    from .ops import adjoint, mpo_linear_combination
+    S = build_shift_mpo(n_or_psi, 1, ctx=ctx)
+    eye = SingleSiteMPO.identity(len(S), sites=S.site_ids, ctx=S.ctx)
+    return mpo_linear_combination([eye, S, adjoint(S)], [2.0, -1.0, -1.0])
+
+
 def fir_mpo(taps, n_or_psi, cutoff=1e-14, maxdim=None, ctx=None):
     """The FIR filter sum_k taps[k] S^k (S = the cyclic shift by one sample) as a SingleSiteMPO: applied to a state it is the
     circular convolution y_x = sum_k taps[k] psi_{(x - k) mod 2^n}.  `taps` maps offset -> coefficient (a dict; offsets may be

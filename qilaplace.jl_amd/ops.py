@@ -19,6 +19,8 @@
   environment, esprit   the partial contraction <phi|...|psi> / <phi|W|...|psi> with open bond legs, and on top of it shift_pencil /
                      esprit_from_pencil / esprit: the poles of a sum of exponentials from the bond basis, no scan (no reference
                      counterpart)
+  solve              (A + shift I) x = c by the alternating two-site solver with a CG local solve, and least_squares / smooth /
+                     solve_residual on top of it (no reference counterpart)
   canonicalize       src/mps.jl:787-847, 866-901   (Julia: canonicalize!)
   compress           src/mps.jl:913-999            (Julia: compress!)
   signal_mps         src/signals/SignalConverters.jl:228-233
@@ -703,6 +705,110 @@ def environment_route(side, count, phi_dims, psi_dims, op_dims=None):
     L.check(L.lib.qil_environment_route(ENV_SIDES[side], int(count), pd.size - 1, pd.ctypes.data_as(p64), sd.ctypes.data_as(p64),
                                         od.ctypes.data_as(p64) if od is not None else None, C.byref(route)))
     return "CHAIN" if route.value == 0 else "GEMM"
+
+
+# ---------------------------------------------------------------- linear solver
+def _solve_info(v):
+    return {"sweeps": int(v[0]), "converged": bool(v[1]), "residual": float(v[2]), "matvecs": int(v[3]), "max_bond": int(v[4]),
+            "local_solves": int(v[5]), "gemm_solves": int(v[6])}
+
+
+def solve(A, c, x0=None, shift=0.0, maxdim=64, cutoff=1e-20, tol=1e-10, max_sweeps=6, cg_iters=100, return_info=False):
+    """x with (A + shift I) x = c for a Hermitian positive definite A + shift I, as a new state of c's class, without a dense
+    vector: the alternating two-site solver with a conjugate-gradient local solve (include/qilaplace_hip.h, qil_mps_solve).
+    Hermiticity is the caller's promise and is not checked.  `x0` is the initial guess (default: c, compressed to `maxdim`);
+    `cutoff` and `maxdim` truncate every two-site split by the project's rule; `tol` is both CG's relative residual and the
+    stopping test of the sweeps (the largest local residual met before a local solve); `cg_iters` caps CG per bond.
+    mps_to_vector(solve(A, c)) is the solution, amplitudes included.
+
+    return_info=True also returns a dict: sweeps, converged, residual, matvecs, max_bond, local_solves, gemm_solves (how many
+    local solves took the one-launch route and the GEMM route).  converged=False after max_sweeps is not an error: a truncation
+    coarser than `tol` keeps the local residual above it.
+
+    The verb is for solutions that compress.  With `maxdim` below the solution's rank and a right-hand side that does not
+    compress (random), truncation by SVD does not converge to the best approximation at that rank: errors of 0.1 to 0.5 were
+    seen in a numpy restatement."""
+    _require_operator(A, c)
+    if x0 is not None:
+        _require_mps(x0, "solve")
+    if isinstance(maxdim, (bool, np.bool_)) or (maxdim is not None and not isinstance(maxdim, (int, np.integer))):
+        raise TypeError(f"solve: maxdim must be an integer, got {type(maxdim).__name__}")
+    h = C.c_void_p()
+    info = (C.c_double * 8)()
+    L.check(L.lib.qil_mps_solve(A.handle, float(shift), c.handle, None if x0 is None else x0.handle, _maxdim(maxdim), float(cutoff),
+                                float(tol), int(max_sweeps), int(cg_iters), C.byref(h), info))
+    x = _wrap_like(c, h)
+    return (x, _solve_info(info)) if return_info else x
+
+
+def solve_local_fits(xl, xr, dl, dm, dr, cl, cm, cr, dtype=np.float64):
+    """Whether the local solve of a bond takes the one-launch route (needs no GPU): qil_mps_solve_local_fits, the host function
+    qil_mps_solve switches on.  xl, xr: the outer bonds of x at the two tensors; dl, dm, dr: the operator's bonds there;
+    cl, cm, cr: the right-hand side's.  True where the kernel's operands fit 160 KiB of LDS and one matvec is at most 200 000
+    multiply-adds (beyond that the GEMM route was measured faster; MEASUREMENTS.md section 30).  QIL_SOLVE_ROUTE=gemm makes it
+    False, QIL_SOLVE_ROUTE=local drops the size rule and keeps the LDS one."""
+    fits = C.c_int()
+    L.check(L.lib.qil_mps_solve_local_fits(1 if np.dtype(dtype) == np.complex128 else 0, int(xl), int(xr), int(dl), int(dm), int(dr),
+                                           int(cl), int(cm), int(cr), C.byref(fits)))
+    return bool(fits.value)
+
+
+def solve_residual(A, x, c, shift=0.0) -> float:
+    """||(A + shift I) x - c|| / ||c||, amplitudes included, without the product: the expansion of the squared norm from
+    `apply_norm`, `inner` and `norm`.
+
+    The floor of `apply_distance`: the squared residual carries an absolute error of a few eps times the squared norms of its
+    terms, so relative residuals below about 1e-7 are not resolved (they come out as that floor or as 0)."""
+    _require_operator(A, x)
+    _require_mps(c, "solve_residual")
+    s = float(shift)
+    nax = x.amplitude * apply_norm(A, x)
+    nx = x.amplitude * norm(x)
+    nc = c.amplitude * norm(c)
+    r2 = nax * nax + nc * nc - 2.0 * np.real(inner(c, A, x))
+    if s != 0.0:
+        r2 += s * s * nx * nx + 2.0 * s * np.real(inner(x, A, x)) - 2.0 * s * np.real(inner(c, x))
+    return float(np.sqrt(max(0.0, r2)) / nc)
+
+
+def least_squares(W, b, reg=0.0, **solve_kwargs):
+    """argmin_x ||W x - b||^2 + reg ||x||^2 by the normal equations (W^dagger W + reg I) x = W^dagger b, solved with `solve`: the
+    operator is mpo_compress(apply(W, adjoint(W))) ("W first, then W^dagger"), the right-hand side apply(adjoint(W), b), the
+    shift `reg`.  W need not be Hermitian or symmetric.  THE CONDITION NUMBER IS SQUARED: kappa(W^dagger W) = kappa(W)^2, so the
+    attainable accuracy and CG's iteration count are those of the squared problem; `reg` > 0 bounds it by
+    (|W|^2 + reg) / reg.  Keyword arguments go to `solve`."""
+    _require_operator(W, b)
+    Wd = adjoint(W)
+    A = apply(W, Wd)
+    if _ntensors(b) > 1:
+        A = mpo_compress(A)
+    return solve(A, apply(Wd, b), shift=float(reg), **solve_kwargs)
+
+
+def smooth(y, alpha, order=1, mask=None, **solve_kwargs):
+    """The Whittaker smoother and gap filler: argmin_x ||M (x - y)||^2 + alpha ||Delta^order x||^2 with the periodic second
+    difference L = Delta^T Delta = 2 I - S - S^dagger (build_laplacian_mpo), i.e. (M + alpha L^order) x = M y.  `mask` is a state
+    of 0 / 1 weights (M = diagonal_mpo(mask), c = hadamard(mask, y)): samples with weight 0 are filled in from their neighbours.
+    Without a mask M = I enters as shift = 1 and c = y.  Keyword arguments go to `solve`; with a mask the operator is only
+    positive definite where the mask leaves no run of hidden samples that the null space of L^order (the constants) fits, which
+    any mask with one visible sample satisfies."""
+    from .builders import build_laplacian_mpo
+    _require_mps(y, "smooth")
+    if y._paired():
+        raise TypeError("smooth: unsupported operand types (a SignalMPS is needed)")
+    if isinstance(order, (bool, np.bool_)) or not isinstance(order, (int, np.integer)) or order < 1:
+        raise ValueError(f"smooth: order must be a positive integer, got {order!r}")
+    if not float(alpha) >= 0.0:
+        raise ValueError(f"smooth: alpha must be >= 0, got {alpha!r}")
+    lap = build_laplacian_mpo(y)
+    P = lap
+    for _ in range(int(order) - 1):
+        P = mpo_compress(apply(P, lap))
+    if mask is None:
+        return solve(mpo_scale(P, float(alpha)), y, shift=1.0, **solve_kwargs)
+    _require_mps(mask, "smooth")
+    A = mpo_linear_combination([diagonal_mpo(mask), P], [1.0, float(alpha)])
+    return solve(A, hadamard(mask, y), **solve_kwargs)
 
 
 # ---------------------------------------------------------------- Schmidt spectra
