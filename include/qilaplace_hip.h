@@ -349,6 +349,65 @@ QIL_API int qil_mps_solve(const qil_mpo* A, double shift, const qil_mps* c, cons
  * into 1.  QIL_EINVAL_ARG for a null fits or a dimension < 1. */
 QIL_API int qil_mps_solve_local_fits(int complex_, int64_t xl, int64_t xr, int64_t dl, int64_t dm, int64_t dr,
                                      int64_t cl, int64_t cm, int64_t cr, int* fits);
+/* ------------------------------------------------------------------ extremal eigenpairs (no reference counterpart) */
+/* The smallest (which = 0) or largest (which = 1, both algebraic) eigenpair of a Hermitian operator A in MPS form, by the
+ * alternating two-site sweep of qil_mps_solve with the local linear solve replaced by a local eigenvalue solve (two-site DMRG).
+ * Sweep structure, gauge handling and operand rules are those of qil_mps_solve: (A, x0) pass the checks of qil_apply, every
+ * ortho[i] those of qil_inner against x0; single-register and paired chains (their 2n tensors) both work; every f64 / c64 mix is
+ * accepted and the contraction and the result are c64 when any operand is complex.  x0, the start, is mandatory (this layer
+ * invents no start vector): it is copied, widened, truncated to maxdim where it is wider and normalised; its amplitude is ignored.
+ * A full sweep goes left to right, then right to left.
+ * The local problem at bond k: H v = L_A A_k A_{k+1} R_A v + s weight sum_i g_i (g_i^H v), g_i = Lphi_i phi_i,k phi_i,k+1 Rphi_i
+ * the projection of the deflation state ortho[i] onto the local space, s = +1 for which = 0 and -1 for which = 1: the penalty
+ * pushes states found already away from the wanted end, so that a second call with the first result in `ortho` returns the next
+ * eigenpair (ortho states should have norm 1 with their amplitude 1: the tensors alone enter; n_ortho <= 8).
+ * The local solver is restarted Lanczos with full reorthogonalisation from the current two-site tensor y (unit norm): at most
+ * `krylov` vectors (2 .. 16), each new one orthogonalised twice against all earlier ones, the tridiagonal projected matrix
+ * diagonalised, the Ritz pair at the wanted end the next start, at most `restarts` times.  A restart begins with
+ * theta = <y|H y> and r = H y - theta y and the iteration stops when |r| <= tol * scale or on a breakdown
+ * (beta <= 1e-14 * scale: an invariant subspace, e.g. A = I).  scale is the largest |Ritz value| any local solve of this call
+ * has seen, a lower bound of |A|_2 that Lanczos delivers for free (with deflation states only Ritz values at the wanted end count,
+ * since the penalty moves the other end by up to `weight`); it keeps the test meaningful where theta ~ 0.  After the local solve
+ * y is split by the SVD under the project's truncation rule (cutoff, maxdim), the kept singular values are rescaled to norm 1
+ * and the sweep moves on.  The call ends after the first full sweep whose largest pre-solve |r| / scale is <= tol, otherwise after
+ * max_sweeps with converged = 0, which is not an error.
+ * *out has amplitude 1 and norm 1 (the weight sits in tensor 0); its phase is not fixed.  *theta is the Rayleigh quotient of the
+ * last local solve, of the PENALISED local operator: with deflation states it is <x|A|x> + s weight sum_i |<ortho_i|x>|^2, and the
+ * last term is the square of how far *out is from orthogonal to them (rounding level for converged, well separated pairs).  info (8 doubles, may be null): full sweeps done; converged (0 / 1); the largest pre-solve |r| / scale of the
+ * last sweep; matvecs; the largest bond of *out; local solves by the one-launch route; by the GEMM route; scale.
+ * Routes of the local solve, per bond: "local", one launch of one 256-thread workgroup with the whole restarted iteration in LDS,
+ * where qil_mps_eigs_local_fits says so; "gemm", four f64-MFMA products per matvec, the basis in device memory, the vector steps
+ * and the projected problem as small kernels, one read-back of the flags per restart, any bonds.  QIL_EIGS_ROUTE=local / gemm
+ * forces one (read per call; local only where the bond fits, else gemm, and info shows it).
+ * THREE LIMITS.  (1) HERMITICITY IS THE CALLER'S PROMISE: it cannot be checked cheaply and is not; a non-Hermitian operator
+ * gives a wrong answer, not an error.  (2) The sweep converges to an eigenvector, NOT PROVABLY THE EXTREMAL ONE: an eigenvector
+ * of small bond is a fixed point.  For circulant operators (shift, FIR, the periodic Laplacian) every Fourier mode is one: a numpy
+ * restatement started from a random bond-2 state on I + 4 L at n = 8 stopped 9 % of |A| from lambda_min with a residual of 1e-13.
+ * For those operators the spectrum is top_k of the transfer function's magnitude.  (3) CLUSTERED ENDS CONVERGE SLOWLY: the small
+ * end of a random Gram operator, with relative gaps of 1e-8, did not converge in 10 sweeps in the restatement.
+ * Errors, before the context is activated: QIL_EINVAL_ARG for a null A, x0, out or theta, a `which` that is not 0 / 1, n_ortho
+ * outside 0 .. 8, a null ortho or entry with n_ortho > 0, krylov outside 2 .. 16, restarts < 1, maxdim or max_sweeps < 1, a
+ * weight, cutoff or tol that is not finite, weight < 0, cutoff < 0 or tol <= 0; the operand errors of qil_apply for (A, x0) and
+ * of qil_inner for (ortho[i], x0); QIL_EINVAL_LENGTH for a chain of one tensor.  During the call: QIL_EDOMAIN for a zero or
+ * non-finite x0 and for a Ritz value that is not finite (the message names the bond).  Every temporary belongs to the call; a
+ * failed call leaves nothing behind and *out and *theta untouched. */
+QIL_API int qil_mps_eigs(const qil_mpo* A, int which /* 0 smallest, 1 largest (algebraic) */,
+                         const qil_mps* x0, const qil_mps* const* ortho /* may be null */, int n_ortho, double weight,
+                         int64_t maxdim, double cutoff, double tol, int max_sweeps, int krylov, int restarts,
+                         qil_mps** out, double* theta, double* info /* 8 doubles, may be null */);
+/* Whether the local eigen-solve of a bond takes the one-launch route: THE decision, not a copy of it -- qil_mps_eigs switches on
+ * this value for every bond.  Host only: no context, no GPU.  complex_: the contraction type is c64; xl, xr: the outer bonds of
+ * x at the two tensors; dl, dm, dr: the operator's three bonds there; krylov, n_ortho: as in the call.  *fits = 1 when the LDS the
+ * kernel needs,
+ *     128 + 4608 + e * (xl^2 dl + xr^2 dr + 4 dl dm + 4 dm dr + (krylov + 1 + n_ortho) * 4 xl xr + 2 * 4 xl xr max(dl, dm, dr))
+ * bytes, e = 8 (f64) / 16 (c64) (the reduction scratch, the projected problem, both environments, both operator tensors, the
+ * Krylov basis, the work vector, the projected deflation states and two ping-pong blocks), is within 160 KiB, krylov <= 16,
+ * n_ortho <= 8, QIL_EIGS_ROUTE is not gemm, and -- unless QIL_EIGS_ROUTE is local -- one matvec is at most 200000 multiply-adds,
+ *     4 xl^2 xr dl + 8 xl xr dm (dl + dr) + 4 xl xr^2 dr
+ * (MEASUREMENTS.md).  Growing any argument never turns 0 into 1.  QIL_EINVAL_ARG for a null fits, a dimension < 1, krylov < 1
+ * or n_ortho < 0. */
+QIL_API int qil_mps_eigs_local_fits(int complex_, int64_t xl, int64_t xr, int64_t dl, int64_t dm, int64_t dr,
+                                    int krylov, int n_ortho, int* fits);
 /* Schmidt spectra of every bond (ITensors' svd(...).spec at every cut; no entry of the reference returns them).  S_out: host,
  * sum_k bond_k doubles; bond k (k = 1 .. N - 1 in tensor order, interleaved for paired chains) owns the bond_k slots that start
  * at the sum of the earlier bond dimensions, as qil_mps_bond_dims reports them at the time of the call.  Each block holds the

@@ -21,7 +21,7 @@ export DeviceMPS, DeviceMPO, to_device, to_host, signal_mps_device, marginal, mp
     compress_mpo!, build_dt_mpo_batch, build_qft_mpo_device, build_zt_qft_chain_device, apply_coefficient_sweep, apply!, rsvd_device, svd_device,
     Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm, sample, top_k,
     hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress, restrict, weight_batch, apply_weight_batch, apply_sample, apply_top_k, bond_spectra,
-    signal_mps_cross, ztmps_from_mps, coefficient_at!, map_states, product_batch, mpo_linear_combination, mpo_inner, mpo_entry_batch, mpo_slice, environment, solve, solve_local_fits
+    signal_mps_cross, ztmps_from_mps, coefficient_at!, map_states, product_batch, mpo_linear_combination, mpo_inner, mpo_entry_batch, mpo_slice, environment, solve, solve_local_fits, eigs, eigs_local_fits
 
 const LIB = get(ENV, "QILHIP_LIB", "libqilhip.so")
 
@@ -283,6 +283,33 @@ function solve_local_fits(complex::Bool, xl::Integer, xr::Integer, dl::Integer, 
     f = Ref{Cint}(0)
     check(ccall((:qil_mps_solve_local_fits, LIB), Cint, (Cint, Int64, Int64, Int64, Int64, Int64, Int64, Int64, Int64, Ref{Cint}),
                 complex, xl, xr, dl, dm, dr, cl, cm, cr, f))
+    return f[] != 0
+end
+# eigs: the smallest (which = :smallest) or largest eigenpair of a Hermitian operator (the caller's promise; not checked) by two-site
+# DMRG with a restarted Lanczos local solve; x0 is mandatory, ortho are unit states to deflate against (at most 8) with the penalty
+# `weight`.  Returns (theta, x, info); x has norm 1.  The sweep converges to an eigenvector, not provably the extremal one, and
+# clustered ends converge slowly.  eigs_local_fits: whether a bond takes the one-launch local route.
+function eigs(A::DeviceMPO, x0::DeviceMPS; which::Symbol=:smallest, ortho::Vector{DeviceMPS}=DeviceMPS[], weight::Float64=0.0,
+              maxdim::Int=64, cutoff::Float64=1e-20, tol::Float64=1e-10, max_sweeps::Int=10, krylov::Int=8, restarts::Int=4)
+    which in (:smallest, :largest) || throw(ArgumentError("eigs: which must be :smallest or :largest, got $(which)"))
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    theta = Ref{Cdouble}(0)
+    info = zeros(Float64, 8)
+    hs = Ptr{Cvoid}[phi.h for phi in ortho]
+    GC.@preserve ortho hs check(ccall((:qil_mps_eigs, LIB), Cint,
+                (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Ptr{Cvoid}}, Cint, Cdouble, Int64, Cdouble, Cdouble, Cint, Cint, Cint, Ref{Ptr{Cvoid}},
+                 Ref{Cdouble}, Ptr{Cdouble}),
+                A.h, which == :smallest ? Cint(0) : Cint(1), x0.h, isempty(hs) ? C_NULL : pointer(hs), length(hs), weight, maxdim, cutoff, tol,
+                max_sweeps, krylov, restarts, r, theta, info))
+    x = finalizer(_free!, DeviceMPS(r[], copy(x0.sites), x0.paired))
+    return theta[], x, (sweeps=Int(info[1]), converged=info[2] != 0, residual=info[3], matvecs=Int(info[4]), max_bond=Int(info[5]),
+                        local_solves=Int(info[6]), gemm_solves=Int(info[7]), scale=info[8])
+end
+function eigs_local_fits(complex::Bool, xl::Integer, xr::Integer, dl::Integer, dm::Integer, dr::Integer; krylov::Integer=8,
+                         n_ortho::Integer=0)
+    f = Ref{Cint}(0)
+    check(ccall((:qil_mps_eigs_local_fits, LIB), Cint, (Cint, Int64, Int64, Int64, Int64, Int64, Cint, Cint, Ref{Cint}),
+                complex, xl, xr, dl, dm, dr, krylov, n_ortho, f))
     return f[] != 0
 end
 function apply_norm(W::DeviceMPO, psi::DeviceMPS)                              # norm(W * psi) without the product

@@ -5,12 +5,7 @@
 //     H y = g,   H v = L_A A_k A_{k+1} R_A v + shift v,   g = Lc c_k c_{k+1} Rc
 // by conjugate gradients, is split by the SVD under the project's truncation rule, and the sweep moves on by one site.
 //
-// The matvec is four dependent products (the operands lie so that none needs a layout copy):
-//     T1[p, a, s1, s2, l]   = sum_k      L_A[p, a, k] v[k, s1, s2, l]
-//     T2[p, t1, m, s2, l]   = sum_{a,s1} T1[p, a, s1, s2, l] A_k[a, s1, t1, m]
-//     T3[p, t1, t2, b, l]   = sum_{m,s2} T2[p, t1, m, s2, l] A_{k+1}[m, s2, t2, b]
-//     (Hv)[p, t1, t2, q]    = sum_{b,l}  T3[p, t1, t2, b, l] R_A[q, b, l]
-//
+// The matvec is the four dependent products of qil_twosite.h (its host steps, shared with qil_eigs.hip, are defined below):
 //   local route   ONE launch, one workgroup (solve_local): L_A, R_A, both operator sites, y, r, p and two ping-pong blocks in LDS,
 //                 g, the first residual and the whole CG in it; the iteration count is bounded inside the kernel
 //   gemm route    the four products as qil_dev_gemm / qil_dev_gemm_batched, CG's scalars in device memory (cg_start, cg_step), the
@@ -19,21 +14,12 @@
 // The local problem is the same for both sweep directions (the direction only decides which SVD factor keeps the weights and
 // which environment grows), so the kernel needs no re-indexing; operands are widened while they are staged.
 // Every temporary belongs to the call's qil_scratch; the working copy of x is the result handle.
-#include "qil_internal.h"
-#include "qil_device_utils.h"
-
-#include <algorithm>
-#include <cmath>
-#include <cstdlib>
+#include "qil_twosite.h"
 
 namespace {
 
-using namespace qil_dev;
+using namespace qil_twosite;
 
-constexpr int kThreads = 256;
-constexpr long long kLdsBudget = 160 * 1024;        // one workgroup may claim all of it
-constexpr long long kRedBytes = 128;                // block_sum's scratch, at the base
-constexpr long long kDimCap = 1 << 20;              // beyond this nothing fits; keeps the byte formula far from overflow
 constexpr int kPoll = 8;                            // gemm route: iterations enqueued per read-back of the flags
 
 // what a local solve reports (doubles, one read-back)
@@ -52,10 +38,6 @@ long long local_lds_bytes(bool cx, long long xl, long long xr, long long dl, lon
                             2 * local_block_elems(xl, xr, dl, dm, dr, cm, cr));
 }
 
-// multiply-adds of one matvec (the four products): what the single workgroup of the local route runs through per CG iteration
-long long local_matvec_macs(long long xl, long long xr, long long dl, long long dm, long long dr) {
-    return xl * dl * 4 * xr * xl + xl * 2 * dm * 2 * xr * 2 * dl + 2 * xl * 2 * dr * xr * 2 * dm + 4 * xl * xr * dr * xr;
-}
 // The auto rule inside the fit.  One full sweep, local vs gemm, same operands (tools/_solve_time.py, median of 10, one MI355X, ms,
 // 40 tensors, f64 / c64): chi 4, D 2 .. 8: 10.9 - 13.1 vs 22.8 - 26.5 / 12.8 - 15.5 vs 28.2 - 34.7; chi 8, D 8 (98 k multiply-adds
 // per matvec): 30.0 vs 39.1 / 38.4 vs 52.0; chi 16, D 3 (135 k): 47.5 vs 52.2; chi 16, D 5 (266 k, f64 only: c64 does not fit):
@@ -63,14 +45,6 @@ long long local_matvec_macs(long long xl, long long xr, long long dl, long long 
 // whatever the element type (the products are latency-bound).  So auto takes the local route up to 200 k; QIL_SOLVE_ROUTE=local
 // takes it wherever it fits.
 constexpr long long kLocalMaxMacs = 200000;
-
-enum { ROUTE_AUTO = 0, ROUTE_LOCAL = 1, ROUTE_GEMM = 2 };
-int forced_route() {
-    const char* r = getenv("QIL_SOLVE_ROUTE");
-    if (r && !strcmp(r, "local")) return ROUTE_LOCAL;
-    if (r && !strcmp(r, "gemm")) return ROUTE_GEMM;
-    return ROUTE_AUTO;
-}
 
 struct LocalArgs {
     const void *LA, *RA, *A0, *A1;     // environments (TE), operator sites (TA)
@@ -81,55 +55,6 @@ struct LocalArgs {
     int blk, cg_iters;
     double shift, tol;
 };
-
-// sum over the workgroup of one double per thread, the same value in every thread (it went through LDS)
-__device__ __forceinline__ double wg_sum(double v, double* red) {
-    double a[1] = {v};
-    block_sum<1>(a, red);
-    return a[0];
-}
-
-// out (block Y) = H v, v in LDS; X, Y the ping-pong blocks.  Ends behind a barrier.
-template <class TE>
-__device__ __forceinline__ void local_matvec(const LocalArgs& g, const TE* Ls, const TE* Rs, const TE* W0, const TE* W1, const TE* v,
-                                             TE* X, TE* Y) {
-    const int xl = g.xl, xr = g.xr, dl = g.dl, dm = g.dm, dr = g.dr;
-    const int PA = xl * dl;
-    for (int t = threadIdx.x; t < PA * 4 * xr; t += kThreads) {          // T1 -> X
-        const int pa = t % PA, u = t / PA;
-        const TE* vc = v + xl * u;
-        TE acc{};
-        for (int k = 0; k < xl; ++k) acc = cmul_add(acc, Ls[pa + PA * k], vc[k]);
-        X[t] = acc;
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < xl * 2 * dm * 2 * xr; t += kThreads) {   // T2 -> Y
-        const int p = t % xl, u = t / xl, c = u % (2 * dm), bc = u / (2 * dm);
-        const TE* t1 = X + p + xl * 2 * dl * bc;
-        const TE* w = W0 + 2 * dl * c;
-        TE acc{};
-        for (int j = 0; j < 2 * dl; ++j) acc = cmul_add(acc, t1[xl * j], w[j]);
-        Y[t] = acc;
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < 2 * xl * 2 * dr * xr; t += kThreads) {   // T3 -> X
-        const int pt = t % (2 * xl), u = t / (2 * xl), c = u % (2 * dr), l = u / (2 * dr);
-        const TE* t2 = Y + pt + 2 * xl * 2 * dm * l;
-        const TE* w = W1 + 2 * dm * c;
-        TE acc{};
-        for (int j = 0; j < 2 * dm; ++j) acc = cmul_add(acc, t2[2 * xl * j], w[j]);
-        X[t] = acc;
-    }
-    __syncthreads();
-    const TE sh = cast_elem<TE>(g.shift);
-    for (int t = threadIdx.x; t < 4 * xl * xr; t += kThreads) {           // H v -> Y
-        const int ptt = t % (4 * xl), q = t / (4 * xl);
-        TE acc = cmul_add(TE{}, sh, v[t]);
-        for (int j = 0; j < dr * xr; ++j) acc = cmul_add(acc, X[ptt + 4 * xl * j], Rs[q + xr * j]);
-        Y[t] = acc;
-    }
-    __syncthreads();
-}
 
 // One workgroup solves H y = g for one bond.  Every loop around a barrier has uniform bounds; alpha, beta and the stopping test
 // come out of wg_sum, which hands every thread the same bits, so all threads take the same branches.  No spin, no atomics: the
@@ -315,92 +240,23 @@ __global__ __launch_bounds__(kThreads) void cg_step(const TE* __restrict__ Hp, T
     }
 }
 
-struct Solver {
-    qil_context* ctx;
-    qil_scratch& tmp;
-    const qil_mpo* A;
+struct Solver : Sweep {
     const qil_mps* c;
-    qil_mps* x;                        // the working copy, in dt; becomes the result
-    int dt;
-    size_t e;
-    double shift, cutoff, tol;
-    int64_t maxdim;
+    double shift, tol;
     int cg_iters;
-    int64_t n;
-    std::vector<void*> LA, RA, Lc, Rc; // [j]: LA / Lc contract the tensors < j, RA / Rc the tensors >= j
     void* stat = nullptr;
     double sweep_res = 0.0;
-    long long matvecs = 0, n_local = 0, n_gemm = 0;
 
     Solver(qil_context* ctx_, qil_scratch& tmp_, const qil_mpo* A_, const qil_mps* c_, qil_mps* x_, int dt_)
-        : ctx(ctx_), tmp(tmp_), A(A_), c(c_), x(x_), dt(dt_), e(qil_elem_size(dt_)), n(c_->n()) {}
+        : Sweep(ctx_, tmp_, A_, x_, dt_), c(c_) {
+        phi.push_back(c_);
+    }
 
-    int64_t xd(int64_t j) const { return x->dims[(size_t)j]; }
-    int64_t ad(int64_t j) const { return A->dims[(size_t)j]; }
     int64_t cd(int64_t j) const { return c->dims[(size_t)j]; }
 
-    int replace(std::vector<void*>& v, int64_t j, void* p) {
-        if (v[(size_t)j]) tmp.free(v[(size_t)j]);
-        v[(size_t)j] = p;
-        return QIL_OK;
-    }
-
     int init() {
-        LA.assign((size_t)n + 1, nullptr), RA = LA, Lc = LA, Rc = LA;
         QIL_TRY(tmp.alloc(ST_WORDS * sizeof(double), &stat));
-        for (std::vector<void*>* v : {&LA, &Lc}) {
-            QIL_TRY(tmp.alloc(e, &(*v)[0]));
-            QIL_TRY(qil_dev_fill_ones(ctx, dt, (*v)[0], 1));
-        }
-        for (std::vector<void*>* v : {&RA, &Rc}) {
-            QIL_TRY(tmp.alloc(e, &(*v)[(size_t)n]));
-            QIL_TRY(qil_dev_fill_ones(ctx, dt, (*v)[(size_t)n], 1));
-        }
-        for (int64_t j = n - 1; j >= 2; --j) QIL_TRY(extend(j, true));
-        return QIL_OK;
-    }
-
-    // the environments grow by tensor j: LA[j + 1], Lc[j + 1] from the left, RA[j], Rc[j] from the right (the same steps on
-    // REVERSED copies with the bonds exchanged, as qil_environment's GEMM route)
-    int extend(int64_t j, bool right) {
-        int64_t xi = xd(j), xo = xd(j + 1), di = ad(j), dq = ad(j + 1), ci = cd(j), co = cd(j + 1);
-        const long long nx = 2 * xi * xo, na = 4 * di * dq, nc = 2 * ci * co;
-        void *Xw = nullptr, *Aw = nullptr, *Cw = nullptr, *T1 = nullptr, *T2 = nullptr, *En = nullptr, *Ecn = nullptr;
-        const void *Xs = nullptr, *As = nullptr, *Cs = nullptr;
-        if (right) QIL_TRY(tmp.alloc((size_t)nx * e, &Xw));
-        if (right || A->dtype != dt) QIL_TRY(tmp.alloc((size_t)na * e, &Aw));
-        if (right || c->dtype != dt) QIL_TRY(tmp.alloc((size_t)nc * e, &Cw));
-        if (right) {
-            std::swap(xi, xo), std::swap(di, dq), std::swap(ci, co);
-            QIL_TRY(qil_put_mps_site(ctx, dt, x, j, QIL_SITE_REVERSED, Xw));
-            QIL_TRY(qil_put_mpo_site(ctx, dt, A, j, QIL_SITE_REVERSED, Aw));
-            QIL_TRY(qil_put_mps_site(ctx, dt, c, j, QIL_SITE_REVERSED, Cw));
-            Xs = Xw, As = Aw, Cs = Cw;
-        } else {
-            Xs = x->site[(size_t)j];
-            QIL_TRY(qil_site_operand(ctx, dt, A, j, Aw, &As));
-            QIL_TRY(qil_site_operand(ctx, dt, c, j, Cw, &Cs));
-        }
-        const long long nT = 2 * std::max(xi, xo) * std::max(di, dq) * std::max(xi, xo);
-        QIL_TRY(tmp.alloc((size_t)nT * e, &T1));
-        QIL_TRY(tmp.alloc((size_t)nT * e, &T2));
-        QIL_TRY(tmp.alloc((size_t)(xo * dq * xo) * e, &En));
-        QIL_TRY(tmp.alloc((size_t)(xo * co) * e, &Ecn));
-        const void* E = right ? RA[(size_t)j + 1] : LA[(size_t)j];
-        const void* Ec = right ? Rc[(size_t)j + 1] : Lc[(size_t)j];
-        QIL_TRY(qil_apply_overlap_env_step(ctx, dt, xi, xo, xi, xo, di, dq, Xs, Xs, As, E, T1, T2, En));
-        tmp.free(T2);
-        tmp.free(T1);
-        QIL_TRY(tmp.alloc((size_t)(2 * xi * co) * e, &T1));
-        QIL_TRY(qil_overlap_env_step(ctx, dt, 2, xi, xo, ci, co, Xs, Cs, Ec, T1, Ecn));
-        tmp.free(T1);
-        if (Cw) tmp.free(Cw);
-        if (Aw) tmp.free(Aw);
-        if (Xw) tmp.free(Xw);
-        const int64_t to = right ? j : j + 1;
-        replace(right ? RA : LA, to, En);
-        replace(right ? Rc : Lc, to, Ecn);
-        return QIL_OK;
+        return init_envs();
     }
 
     template <class TA, class TC, class TE>
@@ -415,7 +271,7 @@ struct Solver {
     int solve_bond_local(int64_t k, void* y, double* hst) {
         LocalArgs g{};
         g.LA = LA[(size_t)k], g.RA = RA[(size_t)k + 2], g.A0 = A->site[(size_t)k], g.A1 = A->site[(size_t)k + 1];
-        g.Lc = Lc[(size_t)k], g.Rc = Rc[(size_t)k + 2], g.C0 = c->site[(size_t)k], g.C1 = c->site[(size_t)k + 1];
+        g.Lc = Lp[0][(size_t)k], g.Rc = Rp[0][(size_t)k + 2], g.C0 = c->site[(size_t)k], g.C1 = c->site[(size_t)k + 1];
         g.y = y, g.stat = static_cast<double*>(stat);
         g.xl = (int)xd(k), g.xr = (int)xd(k + 2), g.dl = (int)ad(k), g.dm = (int)ad(k + 1), g.dr = (int)ad(k + 2);
         g.cl = (int)cd(k), g.cm = (int)cd(k + 1), g.cr = (int)cd(k + 2);
@@ -436,26 +292,13 @@ struct Solver {
         return qil_read_back_wait(ctx, ticket, hst, ST_WORDS * sizeof(double));
     }
 
-    // out (nv) = L_A A_k A_{k+1} R_A v without the shift; T1, T2: the call's blocks
-    int gemm_matvec(int64_t k, const void* A0, const void* A1, const void* v, void* T1, void* T2, void* out) {
-        const int64_t xl = xd(k), xr = xd(k + 2), dl = ad(k), dm = ad(k + 1), dr = ad(k + 2);
-        QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, xl * dl, 4 * xr, xl, LA[(size_t)k], xl * dl, v, xl, T1, xl * dl));
-        qil_gemm_batch b2, b3;
-        b2.count = 2 * xr, b2.a_bs = xl * 2 * dl, b2.c_bs = xl * 2 * dm;
-        QIL_TRY(qil_dev_gemm_batched(ctx, dt, 0, 0, xl, 2 * dm, 2 * dl, T1, xl, A0, 2 * dl, T2, xl, &b2));
-        b3.count = xr, b3.a_bs = 2 * xl * 2 * dm, b3.c_bs = 2 * xl * 2 * dr;
-        QIL_TRY(qil_dev_gemm_batched(ctx, dt, 0, 0, 2 * xl, 2 * dr, 2 * dm, T2, 2 * xl, A1, 2 * dm, T1, 2 * xl, &b3));
-        return qil_dev_gemm(ctx, dt, 0, 1, 4 * xl, xr, dr * xr, T1, 4 * xl, RA[(size_t)k + 2], xr, out, 4 * xl);
-    }
-
     int solve_bond_gemm(int64_t k, void* y, double* hst) {
         const int64_t xl = xd(k), xr = xd(k + 2), dl = ad(k), dm = ad(k + 1), dr = ad(k + 2);
-        const int64_t cl = cd(k), cm = cd(k + 1), cr = cd(k + 2), nv = 4 * xl * xr;
+        const int64_t cm = cd(k + 1), cr = cd(k + 2), nv = 4 * xl * xr;
         QIL_REQUIRE(nv < (1LL << 31), QIL_EINVAL_ARG, "solve: a two-site tensor of %lld elements", (long long)nv);
         const long long blk = local_block_elems(xl, xr, dl, dm, dr, cm, cr);
-        void *T1 = nullptr, *T2 = nullptr, *H = nullptr, *r = nullptr, *p = nullptr, *Aw0 = nullptr, *Aw1 = nullptr, *Cw0 = nullptr,
-             *Cw1 = nullptr;
-        const void *A0 = nullptr, *A1 = nullptr, *C0 = nullptr, *C1 = nullptr;
+        void *T1 = nullptr, *T2 = nullptr, *H = nullptr, *r = nullptr, *p = nullptr, *Aw0 = nullptr, *Aw1 = nullptr;
+        const void *A0 = nullptr, *A1 = nullptr;
         QIL_TRY(tmp.alloc((size_t)blk * e, &T1));
         QIL_TRY(tmp.alloc((size_t)blk * e, &T2));
         QIL_TRY(tmp.alloc((size_t)nv * e, &H));
@@ -465,18 +308,9 @@ struct Solver {
             QIL_TRY(tmp.alloc((size_t)(4 * dl * dm) * e, &Aw0));
             QIL_TRY(tmp.alloc((size_t)(4 * dm * dr) * e, &Aw1));
         }
-        if (c->dtype != dt) {
-            QIL_TRY(tmp.alloc((size_t)(2 * cl * cm) * e, &Cw0));
-            QIL_TRY(tmp.alloc((size_t)(2 * cm * cr) * e, &Cw1));
-        }
         QIL_TRY(qil_site_operand(ctx, dt, A, k, Aw0, &A0));
         QIL_TRY(qil_site_operand(ctx, dt, A, k + 1, Aw1, &A1));
-        QIL_TRY(qil_site_operand(ctx, dt, c, k, Cw0, &C0));
-        QIL_TRY(qil_site_operand(ctx, dt, c, k + 1, Cw1, &C1));
-        // g = Lc c_k c_{k+1} Rc -> r
-        QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, xl, 2 * cm, cl, Lc[(size_t)k], xl, C0, cl, T1, xl));
-        QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, 2 * xl, 2 * cr, cm, T1, 2 * xl, C1, cm, T2, 2 * xl));
-        QIL_TRY(qil_dev_gemm(ctx, dt, 0, 1, 4 * xl, xr, cr, T2, 4 * xl, Rc[(size_t)k + 2], xr, r, 4 * xl));
+        QIL_TRY(overlap_local(0, k, T1, T2, r));                           // g = Lc c_k c_{k+1} Rc -> r
         QIL_TRY(gemm_matvec(k, A0, A1, y, T1, T2, H));
         double* st = static_cast<double*>(stat);
         const bool cx = dt == QIL_C64;
@@ -504,18 +338,16 @@ struct Solver {
             enq += batch;
             QIL_TRY(qil_read_back(ctx, hst, stat, ST_WORDS * sizeof(double)));
         }
-        for (void* q : {Cw1, Cw0, Aw1, Aw0, p, r, H, T2, T1})
+        for (void* q : {Aw1, Aw0, p, r, H, T2, T1})
             if (q) tmp.free(q);
         return QIL_OK;
     }
 
     // one local step at bond k; to_right: the isometry stays at k and S V^H moves on, else U S moves to k
     int step(int64_t k, bool to_right) {
-        const int64_t xl = xd(k), xm = xd(k + 1), xr = xd(k + 2);
-        const int64_t m = 2 * xl, nn = 2 * xr, r0 = std::min(m, nn);
-        void *y = nullptr, *U = nullptr, *Vh = nullptr;
-        QIL_TRY(tmp.alloc((size_t)(m * nn) * e, &y));
-        QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, m, nn, xm, x->site[(size_t)k], m, x->site[(size_t)k + 1], xm, y, m));
+        const int64_t xl = xd(k), xr = xd(k + 2);
+        void* y = nullptr;
+        QIL_TRY(two_site(k, &y));
         int fits = 0;
         QIL_TRY(qil_mps_solve_local_fits(dt == QIL_C64, xl, xr, ad(k), ad(k + 1), ad(k + 2), cd(k), cd(k + 1), cd(k + 2), &fits));
         double st[ST_WORDS] = {};
@@ -533,42 +365,163 @@ struct Solver {
                     "solve: the local solve at bond %lld is not finite", (long long)(k + 1));
         const double rel = st[ST_GNORM] > 0.0 ? st[ST_RES0] / st[ST_GNORM] : (st[ST_RES0] > 0.0 ? INFINITY : 0.0);
         sweep_res = std::max(sweep_res, rel);
-        // split
-        QIL_TRY(tmp.alloc((size_t)(m * r0) * e, &U));
-        QIL_TRY(tmp.alloc((size_t)(r0 * nn) * e, &Vh));
-        std::vector<double> S((size_t)r0, 0.0);
-        QIL_TRY(qil_dev_svd(ctx, dt, m, nn, y, m, U, m, S.data(), Vh, r0));
-        const int64_t r = qil_truncation_rank(S.data(), r0, cutoff, true, maxdim, 1);
-        void *s0 = nullptr, *s1 = nullptr;
-        QIL_TRY(tmp.alloc((size_t)(m * r) * e, &s0));
-        QIL_TRY(tmp.alloc((size_t)(r * nn) * e, &s1));
-        QIL_TRY(qil_dev_copy(ctx, s0, U, (size_t)(m * r) * e));
-        QIL_TRY(qil_dev_copy2d(ctx, s1, (size_t)r * e, Vh, (size_t)r0 * e, (size_t)r * e, (size_t)nn));
-        if (to_right) QIL_TRY(qil_dev_scale(ctx, dt, 0, r, nn, s1, r, S.data()));
-        else QIL_TRY(qil_dev_scale(ctx, dt, 1, m, r, s0, m, S.data()));
-        QIL_TRY(qil_chain_set_site(x, k, tmp.give(s0), xl, r));
-        QIL_TRY(qil_chain_set_site(x, k + 1, tmp.give(s1), r, xr));
-        tmp.free(Vh);
-        tmp.free(U);
-        tmp.free(y);
-        return QIL_OK;
+        return split(k, to_right, y, false);
     }
 
     int sweep() {
         sweep_res = 0.0;
-        for (int64_t k = 0; k + 1 < n; ++k) {
-            QIL_TRY(step(k, true));
-            if (k + 2 < n) QIL_TRY(extend(k, false));
-        }
-        for (int64_t k = n - 2; k >= 0; --k) {
-            QIL_TRY(step(k, false));
-            if (k >= 1) QIL_TRY(extend(k + 1, true));
-        }
-        return QIL_OK;
+        return Sweep::sweep([&](int64_t k, bool to_right) { return step(k, to_right); });
     }
 };
 
 }  // namespace
+
+// ---- the host steps of qil_twosite.h (declared there, used by this file and by qil_eigs.hip)
+namespace qil_twosite {
+
+int Sweep::init_envs() {
+    LA.assign((size_t)n + 1, nullptr), RA = LA;
+    Lp.assign(phi.size(), LA), Rp = Lp;
+    std::vector<std::vector<void*>*> left{&LA}, right{&RA};
+    for (size_t i = 0; i < phi.size(); ++i) left.push_back(&Lp[i]), right.push_back(&Rp[i]);
+    for (std::vector<void*>* v : left) {
+        QIL_TRY(tmp.alloc(e, &(*v)[0]));
+        QIL_TRY(qil_dev_fill_ones(ctx, dt, (*v)[0], 1));
+    }
+    for (std::vector<void*>* v : right) {
+        QIL_TRY(tmp.alloc(e, &(*v)[(size_t)n]));
+        QIL_TRY(qil_dev_fill_ones(ctx, dt, (*v)[(size_t)n], 1));
+    }
+    for (int64_t j = n - 1; j >= 2; --j) QIL_TRY(extend(j, true));
+    return QIL_OK;
+}
+
+int Sweep::extend(int64_t j, bool right) {
+    int64_t xi = xd(j), xo = xd(j + 1), di = ad(j), dq = ad(j + 1);
+    const long long nx = 2 * xi * xo, na = 4 * di * dq;
+    void *Xw = nullptr, *Aw = nullptr, *T1 = nullptr, *T2 = nullptr, *En = nullptr;
+    const void *Xs = nullptr, *As = nullptr;
+    if (right) QIL_TRY(tmp.alloc((size_t)nx * e, &Xw));
+    if (right || A->dtype != dt) QIL_TRY(tmp.alloc((size_t)na * e, &Aw));
+    if (right) {
+        std::swap(xi, xo), std::swap(di, dq);
+        QIL_TRY(qil_put_mps_site(ctx, dt, x, j, QIL_SITE_REVERSED, Xw));
+        QIL_TRY(qil_put_mpo_site(ctx, dt, A, j, QIL_SITE_REVERSED, Aw));
+        Xs = Xw, As = Aw;
+    } else {
+        Xs = x->site[(size_t)j];
+        QIL_TRY(qil_site_operand(ctx, dt, A, j, Aw, &As));
+    }
+    const long long nT = 2 * std::max(xi, xo) * std::max(di, dq) * std::max(xi, xo);
+    QIL_TRY(tmp.alloc((size_t)nT * e, &T1));
+    QIL_TRY(tmp.alloc((size_t)nT * e, &T2));
+    QIL_TRY(tmp.alloc((size_t)(xo * dq * xo) * e, &En));
+    QIL_TRY(qil_apply_overlap_env_step(ctx, dt, xi, xo, xi, xo, di, dq, Xs, Xs, As, right ? RA[(size_t)j + 1] : LA[(size_t)j], T1,
+                                       T2, En));
+    tmp.free(T2);
+    tmp.free(T1);
+    const int64_t to = right ? j : j + 1;
+    replace(right ? RA : LA, to, En);
+    for (size_t i = 0; i < phi.size(); ++i) {
+        int64_t ci = pd(i, j), co = pd(i, j + 1);
+        void *Cw = nullptr, *Ecn = nullptr;
+        const void* Cs = nullptr;
+        if (right || phi[i]->dtype != dt) QIL_TRY(tmp.alloc((size_t)(2 * ci * co) * e, &Cw));
+        if (right) {
+            std::swap(ci, co);
+            QIL_TRY(qil_put_mps_site(ctx, dt, phi[i], j, QIL_SITE_REVERSED, Cw));
+            Cs = Cw;
+        } else {
+            QIL_TRY(qil_site_operand(ctx, dt, phi[i], j, Cw, &Cs));
+        }
+        QIL_TRY(tmp.alloc((size_t)(xo * co) * e, &Ecn));
+        QIL_TRY(tmp.alloc((size_t)(2 * xi * co) * e, &T1));
+        QIL_TRY(qil_overlap_env_step(ctx, dt, 2, xi, xo, ci, co, Xs, Cs, right ? Rp[i][(size_t)j + 1] : Lp[i][(size_t)j], T1, Ecn));
+        tmp.free(T1);
+        if (Cw) tmp.free(Cw);
+        replace(right ? Rp[i] : Lp[i], to, Ecn);
+    }
+    if (Aw) tmp.free(Aw);
+    if (Xw) tmp.free(Xw);
+    return QIL_OK;
+}
+
+int Sweep::overlap_local(size_t i, int64_t k, void* T1, void* T2, void* out) {
+    const int64_t xl = xd(k), xr = xd(k + 2), cl = pd(i, k), cm = pd(i, k + 1), cr = pd(i, k + 2);
+    void *Cw0 = nullptr, *Cw1 = nullptr;
+    const void *C0 = nullptr, *C1 = nullptr;
+    if (phi[i]->dtype != dt) {
+        QIL_TRY(tmp.alloc((size_t)(2 * cl * cm) * e, &Cw0));
+        QIL_TRY(tmp.alloc((size_t)(2 * cm * cr) * e, &Cw1));
+    }
+    QIL_TRY(qil_site_operand(ctx, dt, phi[i], k, Cw0, &C0));
+    QIL_TRY(qil_site_operand(ctx, dt, phi[i], k + 1, Cw1, &C1));
+    QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, xl, 2 * cm, cl, Lp[i][(size_t)k], xl, C0, cl, T1, xl));
+    QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, 2 * xl, 2 * cr, cm, T1, 2 * xl, C1, cm, T2, 2 * xl));
+    QIL_TRY(qil_dev_gemm(ctx, dt, 0, 1, 4 * xl, xr, cr, T2, 4 * xl, Rp[i][(size_t)k + 2], xr, out, 4 * xl));
+    for (void* q : {Cw1, Cw0})
+        if (q) tmp.free(q);
+    return QIL_OK;
+}
+
+int Sweep::gemm_matvec(int64_t k, const void* A0, const void* A1, const void* v, void* T1, void* T2, void* out) {
+    const int64_t xl = xd(k), xr = xd(k + 2), dl = ad(k), dm = ad(k + 1), dr = ad(k + 2);
+    QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, xl * dl, 4 * xr, xl, LA[(size_t)k], xl * dl, v, xl, T1, xl * dl));
+    qil_gemm_batch b2, b3;
+    b2.count = 2 * xr, b2.a_bs = xl * 2 * dl, b2.c_bs = xl * 2 * dm;
+    QIL_TRY(qil_dev_gemm_batched(ctx, dt, 0, 0, xl, 2 * dm, 2 * dl, T1, xl, A0, 2 * dl, T2, xl, &b2));
+    b3.count = xr, b3.a_bs = 2 * xl * 2 * dm, b3.c_bs = 2 * xl * 2 * dr;
+    QIL_TRY(qil_dev_gemm_batched(ctx, dt, 0, 0, 2 * xl, 2 * dr, 2 * dm, T2, 2 * xl, A1, 2 * dm, T1, 2 * xl, &b3));
+    return qil_dev_gemm(ctx, dt, 0, 1, 4 * xl, xr, dr * xr, T1, 4 * xl, RA[(size_t)k + 2], xr, out, 4 * xl);
+}
+
+int Sweep::two_site(int64_t k, void** y) {
+    const int64_t m = 2 * xd(k), nn = 2 * xd(k + 2), xm = xd(k + 1);
+    QIL_TRY(tmp.alloc((size_t)(m * nn) * e, y));
+    return qil_dev_gemm(ctx, dt, 0, 0, m, nn, xm, x->site[(size_t)k], m, x->site[(size_t)k + 1], xm, *y, m);
+}
+
+int Sweep::split(int64_t k, bool to_right, void* y, bool unit) {
+    const int64_t xl = xd(k), xr = xd(k + 2);
+    const int64_t m = 2 * xl, nn = 2 * xr, r0 = std::min(m, nn);
+    void *U = nullptr, *Vh = nullptr;
+    QIL_TRY(tmp.alloc((size_t)(m * r0) * e, &U));
+    QIL_TRY(tmp.alloc((size_t)(r0 * nn) * e, &Vh));
+    std::vector<double> S((size_t)r0, 0.0);
+    QIL_TRY(qil_dev_svd(ctx, dt, m, nn, y, m, U, m, S.data(), Vh, r0));
+    const int64_t r = qil_truncation_rank(S.data(), r0, cutoff, true, maxdim, 1);
+    if (unit) {
+        double s2 = 0.0;
+        for (int64_t i = 0; i < r; ++i) s2 += S[(size_t)i] * S[(size_t)i];
+        const double f = s2 > 0.0 ? 1.0 / std::sqrt(s2) : 1.0;
+        for (int64_t i = 0; i < r; ++i) S[(size_t)i] *= f;
+    }
+    void *s0 = nullptr, *s1 = nullptr;
+    QIL_TRY(tmp.alloc((size_t)(m * r) * e, &s0));
+    QIL_TRY(tmp.alloc((size_t)(r * nn) * e, &s1));
+    QIL_TRY(qil_dev_copy(ctx, s0, U, (size_t)(m * r) * e));
+    QIL_TRY(qil_dev_copy2d(ctx, s1, (size_t)r * e, Vh, (size_t)r0 * e, (size_t)r * e, (size_t)nn));
+    if (to_right) QIL_TRY(qil_dev_scale(ctx, dt, 0, r, nn, s1, r, S.data()));
+    else QIL_TRY(qil_dev_scale(ctx, dt, 1, m, r, s0, m, S.data()));
+    QIL_TRY(qil_chain_set_site(x, k, tmp.give(s0), xl, r));
+    QIL_TRY(qil_chain_set_site(x, k + 1, tmp.give(s1), r, xr));
+    tmp.free(Vh);
+    tmp.free(U);
+    tmp.free(y);
+    return QIL_OK;
+}
+
+int start_gauge(qil_mps* xh, int64_t maxdim) {
+    int64_t widest = 1;
+    for (int64_t d : xh->dims) widest = std::max(widest, d);
+    if (widest > maxdim) {                                   // left-orthonormal, then the truncating sweep back
+        QIL_TRY(qil_gauge_exact(xh, QIL_DIR_RIGHT, 0));
+        return qil_canonicalize(xh, QIL_DIR_LEFT, 0, 0.0, maxdim);
+    }
+    return qil_gauge_exact(xh, QIL_DIR_LEFT, 0);
+}
+
+}  // namespace qil_twosite
 
 // The decision qil_mps_solve switches on for every bond: 1 when the LDS solve_local needs for these dimensions (local_lds_bytes
 // above) is within the 160 KiB budget, QIL_SOLVE_ROUTE does not say gemm and -- unless it says local -- a matvec stays within
@@ -579,7 +532,7 @@ extern "C" int qil_mps_solve_local_fits(int complex_, int64_t xl, int64_t xr, in
     QIL_REQUIRE(xl >= 1 && xr >= 1 && dl >= 1 && dm >= 1 && dr >= 1 && cl >= 1 && cm >= 1 && cr >= 1, QIL_EINVAL_ARG,
                 "solve_local_fits: dimensions must be positive");
     *fits = 0;
-    const int route = forced_route();
+    const int route = route_from(getenv("QIL_SOLVE_ROUTE"));
     if (route == ROUTE_GEMM) return QIL_OK;
     if (std::max({xl, xr, dl, dm, dr, cl, cm, cr}) > kDimCap) return QIL_OK;
     if (local_lds_bytes(complex_ != 0, xl, xr, dl, dm, dr, cm, cr) > kLdsBudget) return QIL_OK;
@@ -608,9 +561,8 @@ extern "C" int qil_mps_solve(const qil_mpo* A, double shift, const qil_mps* c, c
     // the working copy: x0 (or c) in dt, in units of c's amplitude
     const qil_mps* src = x0 ? x0 : c;
     qil_mps* xh = nullptr;
-    QIL_TRY(qil_mps_alloc(ctx, n, dt, c->paired, src->dims.data() + 1, c->site_ids.data(), c->amplitude, &xh));
+    QIL_TRY(start_chain(ctx, src, dt, c->amplitude, &xh));
     qil_result_guard<qil_mps> x_own(xh);
-    for (int64_t i = 0; i < n; ++i) QIL_TRY(qil_put_mps_site(ctx, dt, src, i, QIL_SITE_PLAIN, xh->site[(size_t)i]));
     if (x0 && c->amplitude != 0.0 && x0->amplitude != c->amplitude) {
         const double f = x0->amplitude / c->amplitude;
         if (std::isfinite(f)) {
@@ -618,14 +570,7 @@ extern "C" int qil_mps_solve(const qil_mpo* A, double shift, const qil_mps* c, c
             QIL_TRY(qil_dev_scale(ctx, dt, 1, 2 * xh->dims[0], xh->dims[1], xh->site[0], 2 * xh->dims[0], s.data()));
         }
     }
-    int64_t widest = 1;
-    for (int64_t d : xh->dims) widest = std::max(widest, d);
-    if (widest > maxdim) {                                   // left-orthonormal, then the truncating sweep back
-        QIL_TRY(qil_gauge_exact(xh, QIL_DIR_RIGHT, 0));
-        QIL_TRY(qil_canonicalize(xh, QIL_DIR_LEFT, 0, 0.0, maxdim));
-    } else {
-        QIL_TRY(qil_gauge_exact(xh, QIL_DIR_LEFT, 0));
-    }
+    QIL_TRY(start_gauge(xh, maxdim));
 
     qil_scratch tmp(ctx);
     Solver sv(ctx, tmp, A, c, xh, dt);

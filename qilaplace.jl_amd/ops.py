@@ -21,6 +21,8 @@
                      counterpart)
   solve              (A + shift I) x = c by the alternating two-site solver with a CG local solve, and least_squares / smooth /
                      solve_residual on top of it (no reference counterpart)
+  eigs               the smallest / largest eigenpairs of a Hermitian operator by two-site DMRG with a Lanczos local solve, and
+                     eig_residual / operator_norm / condition_number on top of it (no reference counterpart)
   canonicalize       src/mps.jl:787-847, 866-901   (Julia: canonicalize!)
   compress           src/mps.jl:913-999            (Julia: compress!)
   signal_mps         src/signals/SignalConverters.jl:228-233
@@ -778,11 +780,18 @@ def least_squares(W, b, reg=0.0, **solve_kwargs):
     attainable accuracy and CG's iteration count are those of the squared problem; `reg` > 0 bounds it by
     (|W|^2 + reg) / reg.  Keyword arguments go to `solve`."""
     _require_operator(W, b)
+    A, Wd = _normal_operator(W)
+    return solve(A, apply(Wd, b), shift=float(reg), **solve_kwargs)
+
+
+def _normal_operator(W):
+    """(W^dagger W, W^dagger) as least_squares and operator_norm form them: mpo_compress(apply(W, adjoint(W))), "W first, then
+    W^dagger"; a single tensor has no bond to compress."""
     Wd = adjoint(W)
     A = apply(W, Wd)
-    if _ntensors(b) > 1:
+    if _ntensors(W) > 1:
         A = mpo_compress(A)
-    return solve(A, apply(Wd, b), shift=float(reg), **solve_kwargs)
+    return A, Wd
 
 
 def smooth(y, alpha, order=1, mask=None, **solve_kwargs):
@@ -809,6 +818,143 @@ def smooth(y, alpha, order=1, mask=None, **solve_kwargs):
     _require_mps(mask, "smooth")
     A = mpo_linear_combination([diagonal_mpo(mask), P], [1.0, float(alpha)])
     return solve(A, hadamard(mask, y), **solve_kwargs)
+
+
+# ---------------------------------------------------------------- extremal eigenpairs
+EIGS_WHICH = {"smallest": 0, "largest": 1}
+EIGS_MAX_ORTHO = 8
+
+
+def _eigs_info(v):
+    return {"sweeps": int(v[0]), "converged": bool(v[1]), "residual": float(v[2]), "matvecs": int(v[3]), "max_bond": int(v[4]),
+            "local_solves": int(v[5]), "gemm_solves": int(v[6]), "scale": float(v[7])}
+
+
+def _random_start(A, rng):
+    """A random bond-2 state on A's sites, of A's kind (ZTMPS for a PairedSiteMPO), complex when A is."""
+    n = _ntensors(A)
+    cx = np.dtype(A.dtype) == np.complex128
+    dims = [1] + [2] * (n - 1) + [1]
+    data = []
+    for i in range(n):
+        shp = (dims[i], 2, dims[i + 1])
+        t = rng.standard_normal(shp)
+        if cx:
+            t = t + 1j * rng.standard_normal(shp)
+        data.append(t / np.sqrt(2.0 * dims[i]))
+    return (ZTMPS if A.paired else SignalMPS)(data, sites=A.site_ids, ctx=A.ctx)
+
+
+def eigs(A, k=1, which="smallest", x0=None, seed=0, ortho=(), weight=None, maxdim=64, cutoff=1e-20, tol=1e-10, max_sweeps=10,
+         krylov=8, restarts=4, return_info=False):
+    """The k smallest or largest (algebraic) eigenpairs of a Hermitian operator A as (values, states), without a dense object:
+    two-site DMRG with a restarted Lanczos local solve (include/qilaplace_hip.h, qil_mps_eigs).  `values` is a float array, `states`
+    a list of unit-norm states of amplitude 1 (their phase is not fixed).  It makes k calls, each deflated against `ortho` (unit
+    states) plus the states found so far by a penalty `weight` that pushes them away from the wanted end; at most 8 deflation
+    states in all.  `weight=None` uses 2 * scale of the first call, scale being the lower bound of |A|_2 that call returns (with a
+    non-empty `ortho` the first call is deflated too, so scale then comes from one undeflated probe sweep before it): A
+    GUESS THE CALLER MAY OVERRIDE -- it must exceed the distance from the wanted end to the k-th eigenvalue.  With deflation
+    states a returned value is the Rayleigh quotient of the PENALISED operator, <x|A|x> + s * weight * sum_i |<phi_i|x>|^2: the
+    last term is rounding-level for converged, well separated pairs; inner(x, A, x) is the plain quotient.  `x0` starts the first
+    call; x0=None, and every later call, draws a random bond-2 state from np.random.default_rng(seed) (complex when A is), a fresh
+    draw per call.  `cutoff` and `maxdim` truncate every two-site split; `tol` is the relative residual |A x - theta x| / scale of
+    the local solves and of the stopping test of the sweeps; `krylov` (2 .. 16) and `restarts` bound the local Lanczos.
+
+    return_info=True also returns a list of dicts, one per call: sweeps, converged, residual, matvecs, max_bond, local_solves,
+    gemm_solves, scale.  converged=False after max_sweeps is not an error.
+
+    THREE LIMITS.  Hermiticity is the caller's promise and is not checked.  The sweep converges to an eigenvector, not provably
+    the extremal one: an eigenvector of small bond is a fixed point, and for circulant operators (shift, FIR, the periodic
+    Laplacian) every Fourier mode is one -- a numpy restatement started from a random bond-2 state on I + 4 L at n = 8 stopped 9 %
+    of |A| from lambda_min with a residual of 1e-13; for those operators the spectrum is top_k of the transfer function's
+    magnitude.  Clustered ends converge slowly: the small end of a random Gram operator (relative gaps of 1e-8) did not converge
+    in 10 sweeps in the restatement.  Check a result with eig_residual."""
+    if not isinstance(A, SingleSiteMPO):
+        raise TypeError("eigs: unsupported operand types (an operator is needed)")
+    if which not in EIGS_WHICH:
+        raise ValueError(f"eigs: which must be 'smallest' or 'largest', got {which!r}")
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError(f"eigs: k must be a positive integer, got {k!r}")
+    if isinstance(maxdim, (bool, np.bool_)) or (maxdim is not None and not isinstance(maxdim, (int, np.integer))):
+        raise TypeError(f"eigs: maxdim must be an integer, got {type(maxdim).__name__}")
+    found = list(ortho)
+    for phi in found:
+        _require_mps(phi, "eigs")
+    if len(found) + int(k) - 1 > EIGS_MAX_ORTHO:
+        raise ValueError(f"eigs: at most {EIGS_MAX_ORTHO} deflation states (got {len(found)} in ortho and k = {int(k)})")
+    if x0 is not None:
+        _require_operator(A, x0)
+    rng = np.random.default_rng(seed)
+    values, states, infos = [], [], []
+    w = None if weight is None else float(weight)
+
+    def call(start, deflate, penalty, sweeps, n_restarts):
+        handles = (C.c_void_p * max(len(deflate), 1))(*[phi.handle for phi in deflate])
+        h, theta, info = C.c_void_p(), C.c_double(), (C.c_double * 8)()
+        L.check(L.lib.qil_mps_eigs(A.handle, EIGS_WHICH[which], start.handle, handles if deflate else None, len(deflate), penalty,
+                                   _maxdim(maxdim), float(cutoff), float(tol), sweeps, int(krylov), n_restarts, C.byref(h),
+                                   C.byref(theta), info))
+        return _wrap_like(start, h), theta.value, info
+
+    for j in range(int(k)):
+        start = x0 if (j == 0 and x0 is not None) else _random_start(A, rng)
+        if w is None and found:
+            # deflation states and no weight yet: `scale` from ONE undeflated sweep of one restart per bond (its state is dropped)
+            w = 2.0 * float(call(start, [], 0.0, 1, 1)[2][7])
+        x, theta, info = call(start, found, 0.0 if w is None else w, int(max_sweeps), int(restarts))
+        if w is None:
+            w = 2.0 * float(info[7])
+        values.append(theta)
+        states.append(x)
+        infos.append(_eigs_info(info))
+        found.append(x)
+    values = np.array(values, dtype=np.float64)
+    return (values, states, infos) if return_info else (values, states)
+
+
+def eigs_local_fits(xl, xr, dl, dm, dr, krylov=8, n_ortho=0, dtype=np.float64):
+    """Whether the local eigen-solve of a bond takes the one-launch route (needs no GPU): qil_mps_eigs_local_fits, the host
+    function qil_mps_eigs switches on.  xl, xr: the outer bonds of x at the two tensors; dl, dm, dr: the operator's bonds there;
+    krylov, n_ortho: as in the call.  True where the kernel's operands fit 160 KiB of LDS and one matvec is at most 200 000
+    multiply-adds (MEASUREMENTS.md).  QIL_EIGS_ROUTE=gemm makes it False, QIL_EIGS_ROUTE=local drops the size rule and keeps the
+    LDS one."""
+    fits = C.c_int()
+    L.check(L.lib.qil_mps_eigs_local_fits(1 if np.dtype(dtype) == np.complex128 else 0, int(xl), int(xr), int(dl), int(dm), int(dr),
+                                          int(krylov), int(n_ortho), C.byref(fits)))
+    return bool(fits.value)
+
+
+def eig_residual(A, x, theta) -> float:
+    """||A x - theta x|| / ||x||, without the product: the expansion of the squared norm from `apply_norm`, `inner` and `norm`.
+
+    The floor of `apply_distance`: the squared residual carries an absolute error of a few eps times the squared norms of its
+    terms, so residuals below about 1e-7 * |theta| are not resolved (they come out as that floor or as 0)."""
+    _require_operator(A, x)
+    t = float(theta)
+    nax = x.amplitude * apply_norm(A, x)
+    nx = x.amplitude * norm(x)
+    r2 = nax * nax - 2.0 * t * np.real(inner(x, A, x)) + t * t * nx * nx
+    return float(np.sqrt(max(0.0, r2)) / nx)
+
+
+def operator_norm(W, **eigs_kwargs):
+    """The spectral norm |W|_2: the square root of the largest eigenvalue of W^dagger W, which is formed exactly as
+    `least_squares` forms it and handed to `eigs` (keyword arguments go there).  W need not be Hermitian.  The value is a
+    Rayleigh quotient, so it never exceeds |W|_2; the limits of `eigs` apply."""
+    if not isinstance(W, SingleSiteMPO):
+        raise TypeError("operator_norm: unsupported operand types (an operator is needed)")
+    A, _ = _normal_operator(W)
+    values, _ = eigs(A, 1, "largest", **eigs_kwargs)
+    return float(np.sqrt(max(0.0, values[0])))
+
+
+def condition_number(A, **eigs_kwargs):
+    """theta_max / theta_min of a Hermitian positive definite A from two `eigs` calls (keyword arguments go there).  The value is
+    always a LOWER bound of kappa: both Rayleigh quotients lie inside the spectrum.  The small end is the slow one: its relative
+    gaps are the small ones, so look at return_info of eigs(A, which="smallest") before trusting it."""
+    hi, _ = eigs(A, 1, "largest", **eigs_kwargs)
+    lo, _ = eigs(A, 1, "smallest", **eigs_kwargs)
+    return float(hi[0] / lo[0])
 
 
 # ---------------------------------------------------------------- Schmidt spectra
