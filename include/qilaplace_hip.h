@@ -408,6 +408,70 @@ QIL_API int qil_mps_eigs(const qil_mpo* A, int which /* 0 smallest, 1 largest (a
  * or n_ortho < 0. */
 QIL_API int qil_mps_eigs_local_fits(int complex_, int64_t xl, int64_t xr, int64_t dl, int64_t dm, int64_t dr,
                                     int krylov, int n_ortho, int* fits);
+/* ------------------------------------------------------------------ time evolution (no reference counterpart) */
+/* *out ~ exp(steps * tau * A) x0, tau = tau_re + i tau_im, for a Hermitian operator A in MPS form (the caller's promise, not
+ * checked, as in qil_mps_eigs) by two-site TDVP, the projector-splitting integrator, on the sweep of qil_mps_solve and
+ * qil_mps_eigs.  Operand rules are those of qil_apply; single-register and paired chains both work.  The contraction type is c64
+ * when A or x0 is c64 or tau_im != 0, else f64; *out has that type, x0's kind and x0's site ids.
+ * One step is a sweep left to right, then right to left.  At bond k the two-site tensor goes through exp(+tau/2 H2),
+ * H2 = L_A A_k A_{k+1} R_A, and is split by the SVD under the project's truncation rule (maxdim, cutoff).  Unless the bond is the
+ * last of its half sweep, the centre tensor that moves on then goes through exp(-tau/2 H1), H1 = L_A A_j R_A at the tensor the
+ * centre now sits on: that tensor was advanced as part of bond k and will be advanced again as part of the next bond, so it is
+ * taken back once.  The start: x0 is copied, widened, cut to maxdim where it is wider, with the centre at tensor 0.
+ * Norm: every local exponential starts from v / |v| and reports |v| g, g the growth of the unit vector; the host sums the
+ * logarithms.  The tensors of *out have norm 1 to rounding, out->amplitude = x0->amplitude * exp(sum log); what a truncation
+ * drops enters the sum at its split.
+ * The local exponential is a Lanczos exponential: a basis with full reorthogonalisation (each vector orthogonalised twice against
+ * all earlier ones) from the unit start, at most `krylov` vectors (2 .. 16); after every vector from the second on the tridiagonal
+ * T_m is diagonalised, c = exp(delta T_m) e_1 with delta the remaining local time, est = beta_m |c_m| / |c|.  A pass ends when
+ * est <= tol, when beta_m <= 1e-14 scale (the space is invariant and the result exact; also at m = 1; scale = the largest
+ * |alpha|, beta of this exponential) or at m = krylov.  There, with est > tol and passes left (at most `substeps` passes), delta is
+ * halved, at most 30 times, until est <= tol (the small exponential alone, no matvec), the vector advances by that part and the
+ * next pass takes the rest.  The last permitted pass takes all that remains and the call reports converged = 0, which is not an
+ * error.
+ * Routes, per local exponential: "local", one launch of one 256-thread workgroup with every pass in LDS, where
+ * qil_mps_evolve_local_fits says so; "gemm", four (two-site) or three (one-site) f64-MFMA products per matvec, the basis in device
+ * memory, the vector steps as small kernels, every launch of a pass issued and a no-op behind the stop, one read-back per pass.
+ * QIL_EVOLVE_ROUTE=local / gemm forces one (read per call; local only where the tensor fits).
+ * WHAT THE ERROR IS.  With every bond of x0 at its full value the step is exact to N_loc * tol, N_loc = steps (4 n - 6); an
+ * eigenvector of small bond and any state under a sum of one-site terms are evolved exactly.  A start narrower than the bonds it
+ * grows to costs first order in tau once (from the first sweep alone).  The error with a binding maxdim is the projection error
+ * and does not fall with the step.
+ * THE STIFF LIMIT.  The backward one-site step is exp(-tau/2 H1): for Re tau < 0 it amplifies rounding by
+ * exp(|Re tau| / 2 * spread(A)).  On the periodic Laplacian (spread 4) a numpy restatement reached 4e-13 at tau = -1.25, 6e-12
+ * at -2.5, 4e-10 at -5 and returned garbage (error 1e12) at tau = -20 in one step.  The verb is for |Re tau| * spread(A) of order
+ * one per step and for any imaginary tau; strong smoothing stays with qil_mps_solve (implicit) and the Fourier route.  info[8]
+ * reports the exponent met.
+ * info (10 doubles, may be null): steps done; converged (1 when every local exponential met tol); the worst accepted estimate;
+ * matvecs; the largest bond of *out; exponentials by the one-launch route; by the GEMM route; passes beyond the first; the
+ * largest |Re tau| / 2 * (theta_max - theta_min) over the Ritz values of the one-site steps; the sum of the logarithms.
+ * Errors, before the context is activated, in this order: QIL_EINVAL_ARG for a null A, x0 or out; steps, maxdim or substeps < 1;
+ * krylov outside 2 .. 16; a tau, cutoff or tol that is not finite; cutoff < 0 or tol <= 0; tau = 0; the operand errors of
+ * qil_apply; QIL_EINVAL_LENGTH for a chain of one tensor.  During the call: QIL_EDOMAIN for a zero or non-finite start and for a
+ * Lanczos coefficient that is not finite (the message names the bond).  Every temporary belongs to the call; a failed call leaves
+ * nothing behind and *out untouched. */
+QIL_API int qil_mps_evolve(const qil_mpo* A, const qil_mps* x0, double tau_re, double tau_im, int steps,
+                           int64_t maxdim, double cutoff, double tol, int krylov, int substeps,
+                           qil_mps** out, double* info /* 10 doubles, may be null */);
+/* Whether a local exponential takes the one-launch route: THE decision, not a copy of it -- qil_mps_evolve switches on this value
+ * for every two-site and one-site step.  Host only: no context, no GPU.  sites = 2: xl, xr the outer bonds of x at the two
+ * tensors, dl, dm, dr the operator's three bonds there.  sites = 1: xl, xr, dl, dr the bonds at the one tensor, dm is ignored.
+ * *fits = 1 when the LDS the kernel needs,
+ *     sites = 2:  128 + 4736 + e * (xl^2 dl + xr^2 dr + 4 dl dm + 4 dm dr + (krylov + 1) * 4 xl xr + 2 * 4 xl xr max(dl, dm, dr))
+ *     sites = 1:  128 + 4736 + e * (xl^2 dl + xr^2 dr + 4 dl dr + (krylov + 1) * 2 xl xr + 2 * 2 xl xr max(dl, dr))
+ * bytes, e = 8 (f64) / 16 (c64) (the reduction scratch, the small area, both environments, the operator tensor or tensors, the
+ * Krylov basis, the work vector and two ping-pong blocks), is within 160 KiB, krylov <= 16, QIL_EVOLVE_ROUTE is not gemm, and --
+ * unless QIL_EVOLVE_ROUTE is local -- one matvec is at most 200000 multiply-adds,
+ *     sites = 2:  4 xl^2 xr dl + 8 xl xr dm (dl + dr) + 4 xl xr^2 dr
+ *     sites = 1:  2 xl^2 xr dl + 4 xl xr dl dr + 2 xl xr^2 dr
+ * (the solver's rule; the one-launch route measured 2.1 to 1.08 times faster than the GEMM route wherever it fits, x bond 4 to
+ * 16, operator bond 2 to 5, so no shape class is excluded: MEASUREMENTS.md section 32).  Growing any argument never turns 0
+ * into 1, and for dm >= min(dl, dr) sites = 1 fits wherever sites = 2 does
+ * (every term of both formulas is then no larger).  QIL_EINVAL_ARG for a null fits, sites not 1 or 2, a dimension < 1 or
+ * krylov < 1. */
+QIL_API int qil_mps_evolve_local_fits(int complex_, int sites /* 1 or 2 */, int64_t xl, int64_t xr,
+                                      int64_t dl, int64_t dm /* ignored for sites == 1 */, int64_t dr,
+                                      int krylov, int* fits);
 /* Schmidt spectra of every bond (ITensors' svd(...).spec at every cut; no entry of the reference returns them).  S_out: host,
  * sum_k bond_k doubles; bond k (k = 1 .. N - 1 in tensor order, interleaved for paired chains) owns the bond_k slots that start
  * at the sum of the earlier bond dimensions, as qil_mps_bond_dims reports them at the time of the call.  Each block holds the

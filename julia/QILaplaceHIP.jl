@@ -21,7 +21,8 @@ export DeviceMPS, DeviceMPO, to_device, to_host, signal_mps_device, marginal, mp
     compress_mpo!, build_dt_mpo_batch, build_qft_mpo_device, build_zt_qft_chain_device, apply_coefficient_sweep, apply!, rsvd_device, svd_device,
     Comm, comm_unique_id, gather_coefficients, damping_sweep, shard_items, inner, apply_norm, sample, top_k,
     hadamard, hadamard_compress, diagonal_mpo, linear_combination, linear_combination_compress, restrict, weight_batch, apply_weight_batch, apply_sample, apply_top_k, bond_spectra,
-    signal_mps_cross, ztmps_from_mps, coefficient_at!, map_states, product_batch, mpo_linear_combination, mpo_inner, mpo_entry_batch, mpo_slice, environment, solve, solve_local_fits, eigs, eigs_local_fits
+    signal_mps_cross, ztmps_from_mps, coefficient_at!, map_states, product_batch, mpo_linear_combination, mpo_inner, mpo_entry_batch, mpo_slice, environment, solve, solve_local_fits, eigs, eigs_local_fits,
+    evolve, evolve_local_fits
 
 const LIB = get(ENV, "QILHIP_LIB", "libqilhip.so")
 
@@ -310,6 +311,29 @@ function eigs_local_fits(complex::Bool, xl::Integer, xr::Integer, dl::Integer, d
     f = Ref{Cint}(0)
     check(ccall((:qil_mps_eigs_local_fits, LIB), Cint, (Cint, Int64, Int64, Int64, Int64, Int64, Cint, Cint, Ref{Cint}),
                 complex, xl, xr, dl, dm, dr, krylov, n_ortho, f))
+    return f[] != 0
+end
+# evolve: exp(steps * tau * A) x0 for a Hermitian operator (the caller's promise; not checked) by two-site TDVP with a Lanczos
+# exponential as the local step; tau may be complex.  Returns (x, info); the tensors of x have norm 1, the factor is its amplitude.
+# THE STIFF LIMIT: for Re tau < 0 the backward one-site step amplifies rounding by exp(|Re tau| / 2 * spread(A)); keep
+# |Re tau| * spread(A) of order one per step (any imaginary tau is fine) and leave strong smoothing to solve.
+# evolve_local_fits: whether a two-site (sites = 2) or one-site (sites = 1) exponential takes the one-launch local route.
+function evolve(A::DeviceMPO, x0::DeviceMPS, tau::Number; steps::Int=1, maxdim::Int=64, cutoff::Float64=1e-20, tol::Float64=1e-10,
+                krylov::Int=8, substeps::Int=4)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    info = zeros(Float64, 10)
+    check(ccall((:qil_mps_evolve, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Cint, Int64, Cdouble, Cdouble, Cint, Cint, Ref{Ptr{Cvoid}}, Ptr{Cdouble}),
+                A.h, x0.h, Float64(real(tau)), Float64(imag(tau)), steps, maxdim, cutoff, tol, krylov, substeps, r, info))
+    x = finalizer(_free!, DeviceMPS(r[], copy(x0.sites), x0.paired))
+    return x, (steps=Int(info[1]), converged=info[2] != 0, estimate=info[3], matvecs=Int(info[4]), max_bond=Int(info[5]),
+               local_exps=Int(info[6]), gemm_exps=Int(info[7]), substeps=Int(info[8]), backward_growth=info[9], log_norm=info[10])
+end
+function evolve_local_fits(complex::Bool, xl::Integer, xr::Integer, dl::Integer, dm::Integer, dr::Integer; sites::Integer=2,
+                           krylov::Integer=8)
+    f = Ref{Cint}(0)
+    check(ccall((:qil_mps_evolve_local_fits, LIB), Cint, (Cint, Cint, Int64, Int64, Int64, Int64, Int64, Cint, Ref{Cint}),
+                complex, sites, xl, xr, dl, dm, dr, krylov, f))
     return f[] != 0
 end
 function apply_norm(W::DeviceMPO, psi::DeviceMPS)                              # norm(W * psi) without the product

@@ -17,7 +17,7 @@ from .containers import (Context, default_context, set_default_context, device_c
 from .ops import (apply, apply_compress, apply_compress_batch, mpo_compress, compress_batch, mpo_compress_batch, mps_block, coefficient, coefficient_batch, apply_coefficient_batch, apply_coefficient_sweep,  # noqa: F401
                   marginal_batch, coefficient_grid, laplace_values, product_batch, laplace_weights, laplace_sum, power_sum, dft_eval, dt_eval,
                   zt_eval, refine_frequencies,
-                  mps_to_vector, norm, inner, environment, environment_route, shift_pencil, esprit_from_pencil, esprit, solve, solve_local_fits, solve_residual, least_squares, smooth, eigs, eigs_local_fits, eig_residual, operator_norm, condition_number, apply_norm, distance, apply_distance, bond_spectra, mpo_bond_spectra, entanglement_entropy,
+                  mps_to_vector, norm, inner, environment, environment_route, shift_pencil, esprit_from_pencil, esprit, solve, solve_local_fits, solve_residual, least_squares, smooth, eigs, eigs_local_fits, eig_residual, operator_norm, condition_number, evolve, propagate, diffuse, evolve_local_fits, apply_norm, distance, apply_distance, bond_spectra, mpo_bond_spectra, entanglement_entropy,
                   truncation_error_bounds, required_maxdim, sample, apply_sample, top_k, apply_top_k, hadamard, hadamard_compress, diagonal_mpo, adjoint, convolve, correlate,
                   power_spectrum, linear_combination, linear_combination_compress, add, sub, scale, exponential_tensors,
                   mpo_linear_combination, mpo_linear_combination_compress, mpo_add, mpo_sub, mpo_scale, mpo_inner, mpo_norm,
@@ -40,7 +40,7 @@ __all__ = [
     "SignalMPS", "ZTMPS", "SingleSiteMPO", "PairedSiteMPO",
     "apply", "apply_compress", "apply_compress_batch", "coefficient", "coefficient_batch", "apply_coefficient_batch", "apply_coefficient_sweep", "marginal_batch", "coefficient_grid", "laplace_values", "mps_to_vector", "norm",
     "product_batch", "laplace_weights", "laplace_sum", "power_sum", "dft_eval", "dt_eval", "zt_eval", "refine_frequencies",
-    "inner", "environment", "shift_pencil", "esprit_from_pencil", "esprit", "solve", "solve_local_fits", "solve_residual", "least_squares", "smooth", "eigs", "eigs_local_fits", "eig_residual", "operator_norm", "condition_number", "apply_norm", "distance", "apply_distance", "bond_spectra", "mpo_bond_spectra", "entanglement_entropy",
+    "inner", "environment", "shift_pencil", "esprit_from_pencil", "esprit", "solve", "solve_local_fits", "solve_residual", "least_squares", "smooth", "eigs", "eigs_local_fits", "eig_residual", "operator_norm", "condition_number", "evolve", "propagate", "diffuse", "evolve_local_fits", "apply_norm", "distance", "apply_distance", "bond_spectra", "mpo_bond_spectra", "entanglement_entropy",
     "truncation_error_bounds", "required_maxdim", "sample", "apply_sample", "top_k", "apply_top_k",
     "hadamard", "hadamard_compress", "diagonal_mpo", "adjoint", "convolve", "correlate", "power_spectrum",
     "linear_combination", "linear_combination_compress", "add", "sub", "scale", "exponential_tensors", "exponential_mps",

@@ -159,6 +159,8 @@ PROTOTYPES = {
     "qil_mps_solve_local_fits": [_int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _pint],
     "qil_mps_eigs": [_vp, _int, _vp, _pvp, _int, _dbl, _i64, _dbl, _dbl, _int, _int, _int, _pvp, _pdbl, _pdbl],
     "qil_mps_eigs_local_fits": [_int, _i64, _i64, _i64, _i64, _i64, _int, _int, _pint],
+    "qil_mps_evolve": [_vp, _vp, _dbl, _dbl, _int, _i64, _dbl, _dbl, _int, _int, _pvp, _pdbl],
+    "qil_mps_evolve_local_fits": [_int, _int, _i64, _i64, _i64, _i64, _i64, _int, _pint],
     "qil_bond_spectra": [_vp, _pdbl, _pdbl],
     "qil_mpo_bond_spectra": [_vp, _pdbl, _pdbl],
     "qil_sample": [_vp, _i64, _u64, _pdbl, _pu8, _pdbl],

@@ -78,98 +78,11 @@ struct EigArgs {
     double tol, scale;
 };
 
-// <a|b> over the workgroup, the same bits in every thread
-template <class TE>
-__device__ __forceinline__ void wg_dot(const TE* a, const TE* b, int nv, double* red, double& re, double& im) {
-    double s[2] = {0.0, 0.0};
-    for (int t = threadIdx.x; t < nv; t += kThreads) dot_parts(a[t], b[t], s[0], s[1]);
-    if constexpr (sizeof(TE) == 16) {
-        block_sum<2>(s, red);
-    } else {
-        double one[1] = {s[0]};
-        block_sum<1>(one, red);
-        s[0] = one[0];
-    }
-    re = s[0], im = s[1];
-}
-template <class TE>
-__device__ __forceinline__ double wg_norm(const TE* a, int nv, double* red) {
-    double part = 0.0;
-    for (int t = threadIdx.x; t < nv; t += kThreads) part += abs2_t(a[t]);
-    return sqrt(wg_sum(part, red));
-}
-// w -= (cr + i ci) v on the thread's own elements
-template <class TE>
-__device__ __forceinline__ void axpy_own(TE* w, const TE* v, int nv, double cr, double ci) {
-    const TE c = make_elem(-cr, -ci, (TE*)nullptr);
-    for (int t = threadIdx.x; t < nv; t += kThreads) w[t] = cmul_add(w[t], c, v[t]);
-}
-
-// One Lanczos step: w holds L_A A_k A_{k+1} R_A v_j on entry.  Adds the penalty, takes alpha_j, orthogonalises w twice against
-// v_0 .. v_j (modified Gram-Schmidt; the coefficient against v_j of both passes is alpha_j) and returns beta_j = |w|.  Every thread
-// works on its own elements t = threadIdx.x (mod 256) between the sums, and every sum hands all threads the same bits.
-template <class TE>
-__device__ __forceinline__ void lanczos_step(int j, int nv, const TE* V, TE* w, const TE* G, int n_ortho, double sw, double* red,
-                                             double& alpha, double& beta) {
-    const TE* vj = V + (size_t)j * nv;
-    for (int i = 0; i < n_ortho; ++i) {
-        const TE* gi = G + (size_t)i * nv;
-        double cr, ci;
-        wg_dot<TE>(gi, vj, nv, red, cr, ci);
-        axpy_own<TE>(w, gi, nv, -sw * cr, -sw * ci);
-    }
-    alpha = 0.0;
-    for (int pass = 0; pass < 2; ++pass)
-        for (int i = 0; i <= j; ++i) {
-            const TE* vi = V + (size_t)i * nv;
-            double cr, ci;
-            wg_dot<TE>(vi, w, nv, red, cr, ci);
-            axpy_own<TE>(w, vi, nv, cr, ci);
-            if (i == j) alpha += cr;
-        }
-    beta = wg_norm<TE>(w, nv, red);
-}
-
-// Eigenpairs of the m x m tridiagonal matrix (alpha, beta) by cyclic Jacobi rotations, in plain C++ by ONE thread: T and Z are
-// 16 x 16 work areas; the eigenvector at the wanted end goes to coef, out = {its value, the largest |eigenvalue|}.
+// The eigenpair of the m x m tridiagonal matrix (alpha, beta) at the wanted end, by ONE thread (tridiagonal_eig): the eigenvector
+// goes to coef, out = {its value, the largest |eigenvalue|}.
 __device__ inline void tridiagonal_ritz(int m, const double* alpha, const double* beta, int which, double* T, double* Z, double* coef,
                                         double* out) {
-    for (int i = 0; i < m; ++i)
-        for (int k = 0; k < m; ++k) {
-            T[i * 16 + k] = i == k ? alpha[i] : ((i == k + 1) ? beta[k] : ((k == i + 1) ? beta[i] : 0.0));
-            Z[i * 16 + k] = i == k ? 1.0 : 0.0;
-        }
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        double off = 0.0, diag = 0.0;
-        for (int p = 0; p < m; ++p) {
-            diag += T[p * 16 + p] * T[p * 16 + p];
-            for (int q = p + 1; q < m; ++q) off += T[p * 16 + q] * T[p * 16 + q];
-        }
-        if (!(off > 1e-34 * (diag + off))) break;                          // also leaves on a NaN
-        for (int p = 0; p < m - 1; ++p)
-            for (int q = p + 1; q < m; ++q) {
-                const double apq = T[p * 16 + q];
-                if (apq == 0.0) continue;
-                const double zeta = (T[q * 16 + q] - T[p * 16 + p]) / (2.0 * apq);
-                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                for (int k = 0; k < m; ++k) {                              // columns p, q
-                    const double akp = T[k * 16 + p], akq = T[k * 16 + q];
-                    T[k * 16 + p] = c * akp - s * akq;
-                    T[k * 16 + q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < m; ++k) {                              // rows p, q
-                    const double apk = T[p * 16 + k], aqk = T[q * 16 + k];
-                    T[p * 16 + k] = c * apk - s * aqk;
-                    T[q * 16 + k] = s * apk + c * aqk;
-                }
-                for (int k = 0; k < m; ++k) {
-                    const double zkp = Z[k * 16 + p], zkq = Z[k * 16 + q];
-                    Z[k * 16 + p] = c * zkp - s * zkq;
-                    Z[k * 16 + q] = s * zkp + c * zkq;
-                }
-            }
-    }
+    tridiagonal_eig(m, alpha, beta, T, Z);
     int best = 0;
     double amax = 0.0;
     for (int i = 0; i < m; ++i) {

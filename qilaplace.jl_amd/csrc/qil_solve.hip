@@ -475,6 +475,15 @@ int Sweep::gemm_matvec(int64_t k, const void* A0, const void* A1, const void* v,
     return qil_dev_gemm(ctx, dt, 0, 1, 4 * xl, xr, dr * xr, T1, 4 * xl, RA[(size_t)k + 2], xr, out, 4 * xl);
 }
 
+int Sweep::gemm_matvec1(int64_t j, const void* A0, const void* v, void* T1, void* T2, void* out) {
+    const int64_t xl = xd(j), xr = xd(j + 1), dl = ad(j), dr = ad(j + 1);
+    QIL_TRY(qil_dev_gemm(ctx, dt, 0, 0, xl * dl, 2 * xr, xl, LA[(size_t)j], xl * dl, v, xl, T1, xl * dl));
+    qil_gemm_batch b2;
+    b2.count = xr, b2.a_bs = xl * 2 * dl, b2.c_bs = xl * 2 * dr;
+    QIL_TRY(qil_dev_gemm_batched(ctx, dt, 0, 0, xl, 2 * dr, 2 * dl, T1, xl, A0, 2 * dl, T2, xl, &b2));
+    return qil_dev_gemm(ctx, dt, 0, 1, 2 * xl, xr, dr * xr, T2, 2 * xl, RA[(size_t)j + 1], xr, out, 2 * xl);
+}
+
 int Sweep::two_site(int64_t k, void** y) {
     const int64_t m = 2 * xd(k), nn = 2 * xd(k + 2), xm = xd(k + 1);
     QIL_TRY(tmp.alloc((size_t)(m * nn) * e, y));
@@ -490,9 +499,10 @@ int Sweep::split(int64_t k, bool to_right, void* y, bool unit) {
     std::vector<double> S((size_t)r0, 0.0);
     QIL_TRY(qil_dev_svd(ctx, dt, m, nn, y, m, U, m, S.data(), Vh, r0));
     const int64_t r = qil_truncation_rank(S.data(), r0, cutoff, true, maxdim, 1);
+    double s2 = 0.0;
+    for (int64_t i = 0; i < r; ++i) s2 += S[(size_t)i] * S[(size_t)i];
+    kept = std::sqrt(s2);
     if (unit) {
-        double s2 = 0.0;
-        for (int64_t i = 0; i < r; ++i) s2 += S[(size_t)i] * S[(size_t)i];
         const double f = s2 > 0.0 ? 1.0 / std::sqrt(s2) : 1.0;
         for (int64_t i = 0; i < r; ++i) S[(size_t)i] *= f;
     }

@@ -957,6 +957,109 @@ def condition_number(A, **eigs_kwargs):
     return float(hi[0] / lo[0])
 
 
+# ---------------------------------------------------------------- time evolution
+DIFFUSE_MAX_STEPS = 4096
+
+
+def _evolve_info(v):
+    return {"steps": int(v[0]), "converged": bool(v[1]), "estimate": float(v[2]), "matvecs": int(v[3]), "max_bond": int(v[4]),
+            "local_exps": int(v[5]), "gemm_exps": int(v[6]), "substeps": int(v[7]), "backward_growth": float(v[8]),
+            "log_norm": float(v[9])}
+
+
+def _positive_int(what, name, v):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 1:
+        raise ValueError(f"{what}: {name} must be a positive integer, got {v!r}")
+    return int(v)
+
+
+def evolve(A, x, t, steps=1, maxdim=64, cutoff=1e-20, tol=1e-10, krylov=8, substeps=4, return_info=False):
+    """exp(t A) x for a Hermitian operator A as a new state of x's class, without a dense object: two-site TDVP, the
+    projector-splitting integrator, with a Lanczos exponential as the local step (include/qilaplace_hip.h, qil_mps_evolve).
+    `t` is the total, real or complex, taken in `steps` steps of tau = t / steps; the result is complex when A, x or t is.
+    Hermiticity is the caller's promise and is not checked.  `cutoff` and `maxdim` truncate every two-site split; `tol` is the
+    error estimate every local exponential must meet; `krylov` (2 .. 16) bounds its basis and `substeps` the passes it may take.
+    mps_to_vector(evolve(A, x, t)) is the result, amplitudes included.
+
+    return_info=True also returns a dict: steps, converged, estimate, matvecs, max_bond, local_exps, gemm_exps (how many local
+    exponentials took the one-launch route and the GEMM route), substeps, backward_growth, log_norm.  converged=False is not an
+    error.
+
+    What the error is: with every bond of x at its full value the step is exact to tol per local exponential; an eigenvector of
+    small bond and any state under a sum of one-site terms are evolved exactly.  A start narrower than the bonds it grows to costs
+    first order in tau once.  The error with a binding maxdim is the projection error and does not fall with the step.
+
+    THE STIFF LIMIT: the backward one-site step exp(-tau/2 H1) amplifies rounding by exp(|Re tau| / 2 * spread(A)) for
+    Re tau < 0 (`backward_growth` reports the exponent met).  On the Laplacian (spread 4) tau = -2.5 is right to 6e-12 and
+    tau = -20 in one step returns garbage.  Use evolve for |Re tau| * spread(A) of order one per step and for any imaginary tau;
+    strong smoothing stays with `smooth` (implicit), and circulant operators have the Fourier route (`hadamard` with a transfer
+    function)."""
+    if not (isinstance(A, SingleSiteMPO) and isinstance(x, SignalMPS)):
+        raise TypeError("evolve: unsupported operand types (an operator and a state are needed)")
+    if A._paired() != x._paired():
+        raise TypeError("evolve: PairedSiteMPO acts on ZTMPS, SingleSiteMPO on SignalMPS")
+    if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, float, complex, np.number)):
+        raise TypeError(f"evolve: t must be a real or complex number, got {type(t).__name__}")
+    n_steps = _positive_int("evolve", "steps", steps)
+    _positive_int("evolve", "krylov", krylov)
+    _positive_int("evolve", "substeps", substeps)
+    if isinstance(maxdim, (bool, np.bool_)) or (maxdim is not None and not isinstance(maxdim, (int, np.integer))):
+        raise TypeError(f"evolve: maxdim must be an integer, got {type(maxdim).__name__}")
+    tau = complex(t) / n_steps
+    if not np.isfinite(tau) or tau == 0:
+        raise ValueError(f"evolve: t must be finite and not zero, got {t!r}")
+    h = C.c_void_p()
+    info = (C.c_double * 10)()
+    L.check(L.lib.qil_mps_evolve(A.handle, x.handle, tau.real, tau.imag, n_steps, _maxdim(maxdim), float(cutoff), float(tol),
+                                 int(krylov), int(substeps), C.byref(h), info))
+    y = _wrap_like(x, h)
+    return (y, _evolve_info(info)) if return_info else y
+
+
+def propagate(H, x, t, **evolve_kwargs):
+    """exp(-i t H) x, the unitary propagation under a Hermitian H for a real time t: evolve(H, x, -1j * t).  Keyword arguments go
+    to `evolve`; the norm is kept to the local tolerance and to what a binding maxdim projects away."""
+    if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, float, np.integer, np.floating)):
+        raise TypeError(f"evolve: propagate needs a real time t, got {type(t).__name__}")
+    return evolve(H, x, -1j * float(t), **evolve_kwargs)
+
+
+def diffuse(y, t, order=1, steps=None, **evolve_kwargs):
+    """exp(-t L^order) y with the periodic second difference L = 2 I - S - S^dagger (build_laplacian_mpo): explicit diffusion for a
+    time t >= 0.  The spectrum of L^order spans 4^order, so the default steps = ceil(t * 4^order / 8) keeps the backward growth
+    exponent of THE STIFF LIMIT (see `evolve`) at or below 4 per step.  More than 4096 steps raise ValueError: that is strong
+    smoothing, which is `smooth` (implicit) or the Fourier route.  Keyword arguments go to `evolve`."""
+    from .builders import build_laplacian_mpo
+    if not isinstance(y, SignalMPS) or y._paired():
+        raise TypeError("evolve: diffuse: unsupported operand types (a SignalMPS is needed)")
+    if isinstance(order, (bool, np.bool_)) or not isinstance(order, (int, np.integer)) or order < 1:
+        raise ValueError(f"evolve: diffuse: order must be a positive integer, got {order!r}")
+    if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, float, np.integer, np.floating)) or not (0.0 < float(t) < np.inf):
+        raise ValueError(f"evolve: diffuse: t must be a positive real number, got {t!r}")
+    if steps is None:
+        steps = max(1, int(np.ceil(float(t) * 4.0 ** int(order) / 8.0)))
+        if steps > DIFFUSE_MAX_STEPS:
+            raise ValueError(f"evolve: diffuse: t = {t!r} at order {int(order)} needs {steps} explicit steps (more than "
+                             f"{DIFFUSE_MAX_STEPS}); this is strong smoothing: call smooth (implicit) or use the Fourier route")
+    lap = build_laplacian_mpo(y)
+    P = lap
+    for _ in range(int(order) - 1):
+        P = mpo_compress(apply(P, lap))
+    return evolve(P, y, -float(t), steps=steps, **evolve_kwargs)
+
+
+def evolve_local_fits(xl, xr, dl, dm, dr, sites=2, krylov=8, dtype=np.float64):
+    """Whether a local exponential of `evolve` takes the one-launch route (needs no GPU): qil_mps_evolve_local_fits, the host
+    function qil_mps_evolve switches on.  sites=2: xl, xr the outer bonds of x at the two tensors, dl, dm, dr the operator's bonds
+    there; sites=1: the bonds at the one tensor, dm is ignored.  True where the kernel's operands fit 160 KiB of LDS and one matvec
+    is at most 200 000 multiply-adds (MEASUREMENTS.md).  QIL_EVOLVE_ROUTE=gemm makes it False, QIL_EVOLVE_ROUTE=local drops the
+    size rule and keeps the LDS one."""
+    fits = C.c_int()
+    L.check(L.lib.qil_mps_evolve_local_fits(1 if np.dtype(dtype) == np.complex128 else 0, int(sites), int(xl), int(xr), int(dl),
+                                            int(dm), int(dr), int(krylov), C.byref(fits)))
+    return bool(fits.value)
+
+
 # ---------------------------------------------------------------- Schmidt spectra
 def _spectra(entry, x, return_norm):
     dims = x.bond_dims
