@@ -1,6 +1,6 @@
 // The eigen-solver (qil_mps_eigs): the smallest or largest eigenpair of a Hermitian operator in MPS form by the alternating
-// two-site sweep (two-site DMRG).  The sweep, the environments, the matvec and the split are those of the linear solver
-// (qil_twosite.h); the local problem at bond k is
+// two-site sweep (two-site DMRG).  The sweep, the environments, the matvec, the split and the frame of both routes are shared with
+// the linear solver and the time evolution (qil_twosite.h, qil_twosite.hip); the local problem at bond k is
 //     H v = L_A A_k A_{k+1} R_A v + s weight sum_i g_i (g_i^H v),   g_i = Lphi_i phi_i,k phi_i,k+1 Rphi_i,   s = +1 / -1,
 // the penalty pushing the deflation states phi_i away from the wanted end, and it is solved by restarted Lanczos with full
 // reorthogonalisation from the current two-site tensor y: at most `krylov` vectors, each orthogonalised twice against all earlier
@@ -24,16 +24,8 @@ namespace {
 
 using namespace qil_twosite;
 
-constexpr int kMaxKrylov = 16, kMaxOrtho = 8;
+constexpr int kMaxOrtho = 8;
 constexpr long long kSmallBytes = 4608;             // alpha, beta, the Ritz coefficients and two 16 x 16 matrices, behind block_sum's 128
-// one dimension beyond this alone needs more than 160 KiB (8 * 2^14 * 4 bytes in every term it enters), and below it every
-// term of the byte and multiply-add formulas stays under 2^50: no overflow for any arguments of the public host entry
-constexpr long long kEigsDimCap = 1 << 14;
-constexpr double kBreakdown = 1e-14;                // beta <= kBreakdown * scale: the Krylov space is invariant
-
-// The auto rule inside the fit starts from the solver's (the same matvec, measured there): the one workgroup up to 200 k
-// multiply-adds per matvec; QIL_EIGS_ROUTE=local takes it wherever it fits.
-constexpr long long kLocalMaxMacs = 200000;
 
 // what a local solve reports and, on the gemm route, carries between its kernels (doubles)
 enum {
@@ -61,21 +53,15 @@ static_assert(SM_WORDS * 8 <= kSmallBytes, "the small area");
 //   e = 8 (f64) / 16 (c64)
 long long local_lds_bytes(bool cx, long long xl, long long xr, long long dl, long long dm, long long dr, long long krylov,
                           long long n_ortho) {
-    const long long e = cx ? 16 : 8;
-    return kRedBytes + kSmallBytes + e * (xl * xl * dl + xr * xr * dr + 4 * dl * dm + 4 * dm * dr + (krylov + 1 + n_ortho) * 4 * xl * xr +
-                                          2 * 4 * xl * xr * std::max({dl, dm, dr}));
+    const long long nv = 4 * xl * xr;
+    return local_bytes(cx, kSmallBytes, frame_elems(2, xl, xr, dl, dm, dr), krylov + 1 + n_ortho, nv, nv * std::max({dl, dm, dr}));
 }
 
-struct EigArgs {
-    const void *LA, *RA, *A0, *A1;     // environments (TE), operator sites (TA)
+struct EigArgs : FrameArgs {           // y: (xl, 2, 2, xr), the Ritz vector on return; stat: ST_WORDS doubles; shift 0
     const void* G;                     // n_ortho projected deflation states (TE), 4 xl xr each
-    void* y;                           // (xl, 2, 2, xr) TE: the start on entry, the Ritz vector on return
-    double* stat;                      // ST_WORDS doubles
-    int xl, xr, dl, dm, dr;
-    int blk, krylov, restarts, n_ortho, which;
-    double shift;                      // 0: the matvec's identity term is not used here
-    double sw;                         // s * weight
+    int krylov, restarts, n_ortho, which;
     double tol, scale;
+    double sw;                         // s * weight
 };
 
 // The eigenpair of the m x m tridiagonal matrix (alpha, beta) at the wanted end, by ONE thread (tridiagonal_eig): the eigenvector
@@ -129,40 +115,19 @@ __global__ __launch_bounds__(kThreads) void eigs_local(const EigArgs g) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     double* red = reinterpret_cast<double*>(lds_raw);
     double* sm = reinterpret_cast<double*>(lds_raw + kRedBytes);
-    const int xl = g.xl, xr = g.xr, dl = g.dl, dm = g.dm, dr = g.dr, nv = 4 * xl * xr;
-    TE* Ls = reinterpret_cast<TE*>(lds_raw + kRedBytes + kSmallBytes);
-    TE* Rs = Ls + xl * dl * xl;
-    TE* W0 = Rs + xr * dr * xr;
-    TE* W1 = W0 + 4 * dl * dm;
-    TE* V = W1 + 4 * dm * dr;
+    const int nv = 4 * g.xl * g.xr;
+    const auto [Ls, Rs, W0, W1, V] = stage_frame<TA, TE, 2>(g, lds_raw + kRedBytes + kSmallBytes);
     TE* wv = V + g.krylov * nv;
     TE* Gs = wv + nv;
     TE* X = Gs + g.n_ortho * nv;
     TE* Y = X + g.blk;
-    {   // stage: the operator sites are widened on the way
-        const TE* LA = static_cast<const TE*>(g.LA);
-        const TE* RA = static_cast<const TE*>(g.RA);
-        const TA* A0 = static_cast<const TA*>(g.A0);
-        const TA* A1 = static_cast<const TA*>(g.A1);
-        const TE* y0 = static_cast<const TE*>(g.y);
-        const TE* G0 = static_cast<const TE*>(g.G);
-        for (int t = threadIdx.x; t < xl * dl * xl; t += kThreads) Ls[t] = LA[t];
-        for (int t = threadIdx.x; t < xr * dr * xr; t += kThreads) Rs[t] = RA[t];
-        for (int t = threadIdx.x; t < 4 * dl * dm; t += kThreads) W0[t] = cast_elem<TE>(A0[t]);
-        for (int t = threadIdx.x; t < 4 * dm * dr; t += kThreads) W1[t] = cast_elem<TE>(A1[t]);
-        for (int t = threadIdx.x; t < nv; t += kThreads) V[t] = y0[t];
-        for (int t = threadIdx.x; t < g.n_ortho * nv; t += kThreads) Gs[t] = G0[t];
-    }
+    const TE* G0 = static_cast<const TE*>(g.G);
+    for (int t = threadIdx.x; t < g.n_ortho * nv; t += kThreads) Gs[t] = G0[t];
     __syncthreads();
-    const double ynorm = wg_norm<TE>(V, nv, red);
+    bool bad;
+    const double ynorm = unit_start<TE>(V, V, nv, red, bad);
     double scale = g.scale, theta = 0.0, res0 = 0.0;
-    int status = 0, matvecs = 0, done = 0, restarts = 0;
-    if (!(ynorm > 0.0) || !isfinite(ynorm)) {
-        status = 2;
-    } else {
-        const double f = 1.0 / ynorm;
-        for (int t = threadIdx.x; t < nv; t += kThreads) V[t] = scale_t(V[t], f);
-    }
+    int status = bad ? 2 : 0, matvecs = 0, done = 0, restarts = 0;
     for (int rs = 0; rs < g.restarts && status == 0 && !done; ++rs) {
         int m = 0;
         for (int j = 0; j < g.krylov; ++j) {
@@ -188,11 +153,7 @@ __global__ __launch_bounds__(kThreads) void eigs_local(const EigArgs g) {
                 }
             }
             if (beta <= kBreakdown * scale) break;
-            if (j + 1 < g.krylov) {
-                const double f = 1.0 / beta;
-                TE* vn = V + (j + 1) * nv;
-                for (int t = threadIdx.x; t < nv; t += kThreads) vn[t] = scale_t(wv[t], f);
-            }
+            if (j + 1 < g.krylov) next_vector<TE>(V + (j + 1) * nv, wv, nv, beta);
         }
         if (status != 0 || done) break;
         __syncthreads();                                                   // alpha, beta and the basis are complete
@@ -223,10 +184,8 @@ template <class TE>
 __global__ __launch_bounds__(kThreads) void eigs_begin(const TE* __restrict__ y, TE* __restrict__ V, int nv, double scale,
                                                        double* __restrict__ st) {
     __shared__ double red[8];
-    const double ynorm = wg_norm<TE>(y, nv, red);
-    const bool bad = !(ynorm > 0.0) || !isfinite(ynorm);
-    const double f = bad ? 0.0 : 1.0 / ynorm;
-    for (int t = threadIdx.x; t < nv; t += kThreads) V[t] = scale_t(y[t], f);
+    bool bad;
+    const double ynorm = unit_start<TE>(y, V, nv, red, bad);
     for (int t = threadIdx.x; t < ST_WORDS; t += kThreads) st[t] = 0.0;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -253,11 +212,7 @@ __global__ __launch_bounds__(kThreads) void eigs_step(TE* __restrict__ V, TE* __
         done = beta <= tol * scale;
     }
     const bool halted = !finite || done || beta <= kBreakdown * scale;
-    if (!halted && j + 1 < krylov) {
-        const double f = 1.0 / beta;
-        TE* vn = V + (size_t)(j + 1) * nv;
-        for (int t = threadIdx.x; t < nv; t += kThreads) vn[t] = scale_t(w[t], f);
-    }
+    if (!halted && j + 1 < krylov) next_vector<TE>(V + (size_t)(j + 1) * nv, w, nv, beta);
     if (threadIdx.x == 0) {
         st[ST_MATVECS] += 1.0;
         if (!finite) {
@@ -334,71 +289,31 @@ struct EigSolver : Sweep {
         return QIL_OK;
     }
 
-    template <class TA, class TE>
-    int launch_local(const EigArgs& g, size_t lds) {
-        static qil_lds_grant grant;
-        QIL_HIP(grant.ensure(ctx->device, reinterpret_cast<const void*>(&eigs_local<TA, TE>), lds));
-        hipLaunchKernelGGL((eigs_local<TA, TE>), dim3(1), dim3(kThreads), lds, qil_stream(ctx), g);
-        QIL_HIP(hipGetLastError());
-        return QIL_OK;
-    }
-
     int bond_local(int64_t k, void* y, const void* G, double* hst) {
-        EigArgs g{};
-        g.LA = LA[(size_t)k], g.RA = RA[(size_t)k + 2], g.A0 = A->site[(size_t)k], g.A1 = A->site[(size_t)k + 1];
-        g.G = G, g.y = y, g.stat = static_cast<double*>(stat);
-        g.xl = (int)xd(k), g.xr = (int)xd(k + 2), g.dl = (int)ad(k), g.dm = (int)ad(k + 1), g.dr = (int)ad(k + 2);
-        g.blk = 4 * g.xl * g.xr * std::max({g.dl, g.dm, g.dr});
-        g.krylov = krylov, g.restarts = restarts, g.n_ortho = (int)phi.size(), g.which = which;
-        g.shift = 0.0, g.sw = sw(), g.tol = tol, g.scale = scale;
+        EigArgs g{frame(2, k, y, stat)};
+        g.G = G, g.krylov = krylov, g.restarts = restarts, g.n_ortho = (int)phi.size(), g.which = which;
+        g.sw = sw(), g.tol = tol, g.scale = scale;
         const bool cx = dt == QIL_C64;
         const size_t lds = (size_t)local_lds_bytes(cx, g.xl, g.xr, g.dl, g.dm, g.dr, krylov, g.n_ortho);
         QIL_REQUIRE((long long)lds <= kLdsBudget, QIL_EINVAL_ARG, "eigs: bond %lld does not fit the local route", (long long)k);
-        if (!cx) QIL_TRY((launch_local<double, double>(g, lds)));
-        else if (A->dtype == QIL_C64) QIL_TRY((launch_local<c64, c64>(g, lds)));
-        else QIL_TRY((launch_local<double, c64>(g, lds)));
-        uint64_t ticket = 0;
-        QIL_TRY(qil_read_back_post(ctx, stat, ST_READ * sizeof(double), &ticket));
-        return qil_read_back_wait(ctx, ticket, hst, ST_READ * sizeof(double));
+        return for_sweep_types(A->dtype == QIL_C64, cx, [&](auto a, auto t) {
+            return launch_local<eigs_local<decltype(a), decltype(t)>>(g, lds, ST_READ, hst);
+        });
     }
 
     int bond_gemm(int64_t k, void* y, const void* G, double* hst) {
-        const int64_t xl = xd(k), xr = xd(k + 2), dl = ad(k), dm = ad(k + 1), dr = ad(k + 2), nv = 4 * xl * xr;
+        const Dims d = dims_of(2, k);
+        const int64_t nv = 4 * d.xl * d.xr;
         QIL_REQUIRE(nv < (1LL << 31) / kMaxKrylov, QIL_EINVAL_ARG, "eigs: a two-site tensor of %lld elements", (long long)nv);
-        const long long blk = 4 * xl * xr * std::max({dl, dm, dr});
-        void *T1 = nullptr, *T2 = nullptr, *H = nullptr, *V = nullptr, *Aw0 = nullptr, *Aw1 = nullptr;
-        const void *A0 = nullptr, *A1 = nullptr;
-        QIL_TRY(tmp.alloc((size_t)blk * e, &T1));
-        QIL_TRY(tmp.alloc((size_t)blk * e, &T2));
-        QIL_TRY(tmp.alloc((size_t)nv * e, &H));
-        QIL_TRY(tmp.alloc((size_t)(krylov * nv) * e, &V));
-        QIL_TRY(qil_dev_zero(ctx, V, (size_t)(krylov * nv) * e));
-        if (A->dtype != dt) {
-            QIL_TRY(tmp.alloc((size_t)(4 * dl * dm) * e, &Aw0));
-            QIL_TRY(tmp.alloc((size_t)(4 * dm * dr) * e, &Aw1));
-        }
-        QIL_TRY(qil_site_operand(ctx, dt, A, k, Aw0, &A0));
-        QIL_TRY(qil_site_operand(ctx, dt, A, k + 1, Aw1, &A1));
-        double* st = static_cast<double*>(stat);
-        const bool cx = dt == QIL_C64;
+        Work w;
+        QIL_TRY(work_alloc(2, k, nv * std::max({d.dl, d.dm, d.dr}), krylov, &w));
+        const void *A0 = w.A0, *A1 = w.A1;
+        void *V = w.V, *H = w.H;
         const int no = (int)phi.size();
-        const hipStream_t s = qil_stream(ctx);
-        for_elem_type(cx, [&](auto t) {
-            using TE = decltype(t);
-            hipLaunchKernelGGL((eigs_begin<TE>), dim3(1), dim3(kThreads), 0, s, (const TE*)y, (TE*)V, (int)nv, scale, st);
-            return 0;
-        });
-        QIL_HIP(hipGetLastError());
+        QIL_TRY(launch_wg([](auto t) { return &eigs_begin<decltype(t)>; }, y, V, (int)nv, scale, stat));
         auto step = [&](int j) -> int {
-            QIL_TRY(gemm_matvec(k, A0, A1, static_cast<char*>(V) + (size_t)(j * nv) * e, T1, T2, H));
-            for_elem_type(cx, [&](auto t) {
-                using TE = decltype(t);
-                hipLaunchKernelGGL((eigs_step<TE>), dim3(1), dim3(kThreads), 0, s, (TE*)V, (TE*)H, (const TE*)G, (int)nv, no, sw(), tol,
-                                   krylov, st);
-                return 0;
-            });
-            QIL_HIP(hipGetLastError());
-            return QIL_OK;
+            QIL_TRY(gemm_matvec(k, A0, A1, static_cast<char*>(V) + (size_t)(j * nv) * e, w.T1, w.T2, H));
+            return launch_wg([](auto t) { return &eigs_step<decltype(t)>; }, V, H, G, (int)nv, no, sw(), tol, krylov, stat);
         };
         // The one read-back of a restart follows its FIRST step, the stopping test: a bond that has converged (every bond of a
         // sweep's last pass) then costs one matvec and one step, not krylov of each.  What the rest of a restart leaves in the
@@ -410,17 +325,11 @@ struct EigSolver : Sweep {
             over = hst[ST_STATUS] != 0.0 || hst[ST_DONE] != 0.0;
             if (over) break;
             for (int j = 1; j < krylov; ++j) QIL_TRY(step(j));
-            for_elem_type(cx, [&](auto t) {
-                using TE = decltype(t);
-                hipLaunchKernelGGL((eigs_ritz<TE>), dim3(1), dim3(kThreads), 0, s, (TE*)V, (TE*)H, (int)nv, which, no, st);
-                return 0;
-            });
-            QIL_HIP(hipGetLastError());
+            QIL_TRY(launch_wg([](auto t) { return &eigs_ritz<decltype(t)>; }, V, H, (int)nv, which, no, stat));
         }
         if (!over) QIL_TRY(qil_read_back(ctx, hst, stat, ST_READ * sizeof(double)));
         QIL_TRY(qil_dev_copy(ctx, y, V, (size_t)nv * e));
-        for (void* q : {Aw1, Aw0, V, H, T2, T1})
-            if (q) tmp.free(q);
+        work_free(w);
         return QIL_OK;
     }
 
@@ -458,21 +367,17 @@ struct EigSolver : Sweep {
 
 }  // namespace
 
-// The decision qil_mps_eigs switches on for every bond: 1 when the LDS eigs_local needs for these dimensions (local_lds_bytes
-// above) is within the 160 KiB budget, QIL_EIGS_ROUTE does not say gemm and -- unless it says local -- a matvec stays within
-// kLocalMaxMacs multiply-adds.
+// The decision qil_mps_eigs switches on for every bond: local_route_fits with the LDS eigs_local needs for these dimensions
+// (local_lds_bytes above).
 extern "C" int qil_mps_eigs_local_fits(int complex_, int64_t xl, int64_t xr, int64_t dl, int64_t dm, int64_t dr, int krylov,
                                        int n_ortho, int* fits) {
     QIL_REQUIRE(fits, QIL_EINVAL_ARG, "eigs_local_fits: null argument");
     QIL_REQUIRE(xl >= 1 && xr >= 1 && dl >= 1 && dm >= 1 && dr >= 1, QIL_EINVAL_ARG, "eigs_local_fits: dimensions must be positive");
     QIL_REQUIRE(krylov >= 1 && n_ortho >= 0, QIL_EINVAL_ARG, "eigs_local_fits: krylov must be >= 1 and n_ortho >= 0 (got %d, %d)",
                 krylov, n_ortho);
-    *fits = 0;
-    const int route = route_from(getenv("QIL_EIGS_ROUTE"));
-    if (route == ROUTE_GEMM) return QIL_OK;
-    if (std::max({xl, xr, dl, dm, dr}) > kEigsDimCap || krylov > kMaxKrylov || n_ortho > kMaxOrtho) return QIL_OK;
-    if (local_lds_bytes(complex_ != 0, xl, xr, dl, dm, dr, krylov, n_ortho) > kLdsBudget) return QIL_OK;
-    *fits = route == ROUTE_LOCAL || local_matvec_macs(xl, xr, dl, dm, dr) <= kLocalMaxMacs ? 1 : 0;
+    const bool over = std::max({xl, xr, dl, dm, dr}) > kKrylovDimCap || krylov > kMaxKrylov || n_ortho > kMaxOrtho;
+    const long long bytes = over ? 0 : local_lds_bytes(complex_ != 0, xl, xr, dl, dm, dr, krylov, n_ortho);
+    *fits = local_route_fits(getenv("QIL_EIGS_ROUTE"), over, bytes, over ? 0 : local_matvec_macs(xl, xr, dl, dm, dr));
     return QIL_OK;
 }
 
@@ -518,20 +423,8 @@ extern "C" int qil_mps_eigs(const qil_mpo* A, int which, const qil_mps* x0, cons
     sv.cutoff = cutoff, sv.maxdim = maxdim;
     QIL_TRY(sv.init());
     int sweeps = 0, converged = 0;
-    while (sweeps < max_sweeps) {
-        QIL_TRY(sv.sweep());
-        ++sweeps;
-        if (sv.sweep_res <= tol) {
-            converged = 1;
-            break;
-        }
-    }
-    if (info) {
-        int64_t bond = 1;
-        for (int64_t d : xh->dims) bond = std::max(bond, d);
-        info[0] = sweeps, info[1] = converged, info[2] = sv.sweep_res, info[3] = (double)sv.matvecs, info[4] = (double)bond;
-        info[5] = (double)sv.n_local, info[6] = (double)sv.n_gemm, info[7] = sv.scale;
-    }
+    QIL_TRY(sweep_until([&] { return sv.sweep(); }, sv.sweep_res, tol, max_sweeps, &sweeps, &converged));
+    if (info) sv.info_head(info, sweeps, converged, sv.sweep_res), info[7] = sv.scale;
     *theta = sv.theta;
     *out = x_own.release();
     return QIL_OK;

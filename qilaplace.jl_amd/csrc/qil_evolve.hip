@@ -1,6 +1,7 @@
 // Time evolution (qil_mps_evolve): y = exp(steps tau A) x0 for a Hermitian operator in MPS form by two-site TDVP, the
-// projector-splitting integrator.  The sweep, the environments, the matvecs and the split are those of the linear solver and the
-// eigen-solver (qil_twosite.h).  One step is a sweep left to right and a sweep right to left; at bond k the two-site tensor goes
+// projector-splitting integrator.  The sweep, the environments, the matvecs, the split and the frame of both routes are shared with
+// the linear solver and the eigen-solver (qil_twosite.h, qil_twosite.hip).
+// One step is a sweep left to right and a sweep right to left; at bond k the two-site tensor goes
 // through exp(+tau/2 H2), H2 = L_A A_k A_{k+1} R_A, and is split; unless the bond is the last of its half sweep the centre tensor
 // that moves on goes through exp(-tau/2 H1), H1 = L_A A_j R_A at the tensor the centre now sits on: the two-site step has advanced
 // that tensor in time as part of bond k, and the next bond will advance it again, so it is taken back once in between.
@@ -26,13 +27,8 @@ namespace {
 
 using namespace qil_twosite;
 
-constexpr int kMaxKrylov = 16, kMaxHalvings = 30;
+constexpr int kMaxHalvings = 30;
 constexpr long long kSmallBytes = 4736;             // alpha, beta, c (re, im), the decision and two 16 x 16 matrices
-constexpr long long kEvolveDimCap = 1 << 14;        // beyond this one dimension alone exceeds the budget; every term stays below 2^50
-constexpr double kBreakdown = 1e-14;
-// The auto rule inside the fit is the solver's: the one workgroup up to 200 k multiply-adds per matvec (the two-site count for
-// sites = 2, the one-site count for sites = 1); QIL_EVOLVE_ROUTE=local takes it wherever it fits.
-constexpr long long kLocalMaxMacs = 200000;
 
 enum {
     ST_STATUS = 0,   // 0 fine, 1 a Lanczos coefficient or the growth is not finite, 2 the start is zero or not finite
@@ -60,21 +56,13 @@ static_assert(SM_WORDS * 8 <= kSmallBytes, "the small area");
 //   sites = 2: 128 + 4736 + e * (xl^2 dl + xr^2 dr + 4 dl dm + 4 dm dr + (krylov + 1) * 4 xl xr + 2 * 4 xl xr max(dl, dm, dr))
 //   sites = 1: 128 + 4736 + e * (xl^2 dl + xr^2 dr + 4 dl dr + (krylov + 1) * 2 xl xr + 2 * 2 xl xr max(dl, dr))
 long long local_lds_bytes(bool cx, int sites, long long xl, long long xr, long long dl, long long dm, long long dr, long long krylov) {
-    const long long e = cx ? 16 : 8;
-    if (sites == 1)
-        return kRedBytes + kSmallBytes +
-               e * (xl * xl * dl + xr * xr * dr + 4 * dl * dr + (krylov + 1) * 2 * xl * xr + 2 * 2 * xl * xr * std::max(dl, dr));
-    return kRedBytes + kSmallBytes + e * (xl * xl * dl + xr * xr * dr + 4 * dl * dm + 4 * dm * dr + (krylov + 1) * 4 * xl * xr +
-                                          2 * 4 * xl * xr * std::max({dl, dm, dr}));
+    const long long nv = (sites == 2 ? 4 : 2) * xl * xr;
+    return local_bytes(cx, kSmallBytes, frame_elems(sites, xl, xr, dl, dm, dr), krylov + 1, nv,
+                       nv * (sites == 2 ? std::max({dl, dm, dr}) : std::max(dl, dr)));
 }
 
-struct EvoArgs {
-    const void *LA, *RA, *A0, *A1;     // environments (TE), operator tensor(s) (TA); A1 unused for one site
-    void* y;                           // the local tensor (TE): the start on entry, the unit result on return
-    double* stat;                      // ST_WORDS doubles
-    int xl, xr, dl, dm, dr;
-    int blk, krylov, substeps;
-    double shift;                      // 0: the matvec's identity term is not used here
+struct EvoArgs : FrameArgs {           // y: the unit result on return; stat: ST_WORDS doubles; shift 0
+    int krylov, substeps;
     double dre, dim, tol;
 };
 
@@ -153,39 +141,16 @@ __global__ __launch_bounds__(kThreads) void evolve_local(const EvoArgs g) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     double* red = reinterpret_cast<double*>(lds_raw);
     double* sm = reinterpret_cast<double*>(lds_raw + kRedBytes);
-    const int xl = g.xl, xr = g.xr, dl = g.dl, dm = g.dm, dr = g.dr, nv = (SITES == 2 ? 4 : 2) * xl * xr;
-    const int n0 = SITES == 2 ? 4 * dl * dm : 4 * dl * dr, n1 = SITES == 2 ? 4 * dm * dr : 0;
-    TE* Ls = reinterpret_cast<TE*>(lds_raw + kRedBytes + kSmallBytes);
-    TE* Rs = Ls + xl * dl * xl;
-    TE* W0 = Rs + xr * dr * xr;
-    TE* W1 = W0 + n0;
-    TE* V = W1 + n1;
+    const int nv = (SITES == 2 ? 4 : 2) * g.xl * g.xr;
+    const auto [Ls, Rs, W0, W1, V] = stage_frame<TA, TE, SITES>(g, lds_raw + kRedBytes + kSmallBytes);
     TE* wv = V + g.krylov * nv;
     TE* X = wv + nv;
     TE* Y = X + g.blk;
-    {
-        const TE* LA = static_cast<const TE*>(g.LA);
-        const TE* RA = static_cast<const TE*>(g.RA);
-        const TA* A0 = static_cast<const TA*>(g.A0);
-        const TA* A1 = static_cast<const TA*>(g.A1);
-        const TE* y0 = static_cast<const TE*>(g.y);
-        for (int t = threadIdx.x; t < xl * dl * xl; t += kThreads) Ls[t] = LA[t];
-        for (int t = threadIdx.x; t < xr * dr * xr; t += kThreads) Rs[t] = RA[t];
-        for (int t = threadIdx.x; t < n0; t += kThreads) W0[t] = cast_elem<TE>(A0[t]);
-        for (int t = threadIdx.x; t < n1; t += kThreads) W1[t] = cast_elem<TE>(A1[t]);
-        for (int t = threadIdx.x; t < nv; t += kThreads) V[t] = y0[t];
-    }
     __syncthreads();
-    const double ynorm = wg_norm<TE>(V, nv, red);
-    double dre = g.dre, dim = g.dim, scale = 0.0, lognorm = 0.0, worst = 0.0, spread = 0.0;
-    int status = 0, matvecs = 0, conv = 1, passes = 0, fin = 0;
-    if (!(ynorm > 0.0) || !isfinite(ynorm)) {
-        status = 2;
-    } else {
-        const double f = 1.0 / ynorm;
-        for (int t = threadIdx.x; t < nv; t += kThreads) V[t] = scale_t(V[t], f);
-        lognorm = log(ynorm);
-    }
+    bool bad;
+    const double ynorm = unit_start<TE>(V, V, nv, red, bad);
+    double dre = g.dre, dim = g.dim, scale = 0.0, lognorm = bad ? 0.0 : log(ynorm), worst = 0.0, spread = 0.0;
+    int status = bad ? 2 : 0, matvecs = 0, conv = 1, passes = 0, fin = 0;
     for (int pass = 0; pass < g.substeps && status == 0 && !fin; ++pass) {
         ++passes;
         for (int j = 0; j < g.krylov; ++j) {
@@ -231,9 +196,7 @@ __global__ __launch_bounds__(kThreads) void evolve_local(const EvoArgs g) {
                 else dre -= pre, dim -= pim;
                 break;
             }
-            const double f = 1.0 / beta;
-            TE* vn = V + (j + 1) * nv;
-            for (int t = threadIdx.x; t < nv; t += kThreads) vn[t] = scale_t(wv[t], f);
+            next_vector<TE>(V + (j + 1) * nv, wv, nv, beta);
         }
     }
     __syncthreads();
@@ -256,10 +219,8 @@ template <class TE>
 __global__ __launch_bounds__(kThreads) void evolve_begin(const TE* __restrict__ y, TE* __restrict__ V, int nv, double dre, double dim,
                                                          double* __restrict__ st) {
     __shared__ double red[8];
-    const double ynorm = wg_norm<TE>(y, nv, red);
-    const bool bad = !(ynorm > 0.0) || !isfinite(ynorm);
-    const double f = bad ? 0.0 : 1.0 / ynorm;
-    for (int t = threadIdx.x; t < nv; t += kThreads) V[t] = scale_t(y[t], f);
+    bool bad;
+    const double ynorm = unit_start<TE>(y, V, nv, red, bad);
     for (int t = threadIdx.x; t < ST_WORDS; t += kThreads) st[t] = 0.0;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -298,9 +259,7 @@ __global__ __launch_bounds__(kThreads) void evolve_step(TE* __restrict__ V, TE* 
     if (!bad && ended) {
         gf = pass_finish<TE>(j + 1, nv, V, w, sm, red);
     } else if (!bad && j + 1 < krylov) {
-        const double f = 1.0 / beta;
-        TE* vn = V + (size_t)(j + 1) * nv;
-        for (int t = threadIdx.x; t < nv; t += kThreads) vn[t] = scale_t(w[t], f);
+        next_vector<TE>(V + (size_t)(j + 1) * nv, w, nv, beta);
     }
     if (threadIdx.x == 0) {
         st[ST_MATVECS] += 1.0;
@@ -340,42 +299,16 @@ struct Evolver : Sweep {
         return init_envs();
     }
 
-    template <class TA, class TE, int SITES>
-    int launch_local(const EvoArgs& g, size_t lds) {
-        static qil_lds_grant grant;
-        QIL_HIP(grant.ensure(ctx->device, reinterpret_cast<const void*>(&evolve_local<TA, TE, SITES>), lds));
-        hipLaunchKernelGGL((evolve_local<TA, TE, SITES>), dim3(1), dim3(kThreads), lds, qil_stream(ctx), g);
-        QIL_HIP(hipGetLastError());
-        return QIL_OK;
-    }
-
-    // the dimensions of a local problem: the two-site tensor of bond j (sites 2) or the tensor j (sites 1)
-    struct Dims {
-        int64_t xl, xr, dl, dm, dr;
-    };
-    Dims dims_of(int sites, int64_t j) const {
-        if (sites == 2) return {xd(j), xd(j + 2), ad(j), ad(j + 1), ad(j + 2)};
-        return {xd(j), xd(j + 1), ad(j), ad(j + 1), ad(j + 1)};
-    }
-
     template <int SITES>
     int exp_local(int64_t j, void* y, double dre, double dim, double* hst) {
-        const Dims d = dims_of(SITES, j);
-        EvoArgs g{};
-        g.LA = LA[(size_t)j], g.RA = RA[(size_t)j + SITES], g.A0 = A->site[(size_t)j], g.A1 = SITES == 2 ? A->site[(size_t)j + 1] : nullptr;
-        g.y = y, g.stat = static_cast<double*>(stat);
-        g.xl = (int)d.xl, g.xr = (int)d.xr, g.dl = (int)d.dl, g.dm = (int)d.dm, g.dr = (int)d.dr;
-        g.blk = (SITES == 2 ? 4 : 2) * g.xl * g.xr * (int)std::max({d.dl, d.dm, d.dr});
-        g.krylov = krylov, g.substeps = substeps, g.shift = 0.0, g.dre = dre, g.dim = dim, g.tol = tol;
+        EvoArgs g{frame(SITES, j, y, stat)};
+        g.krylov = krylov, g.substeps = substeps, g.dre = dre, g.dim = dim, g.tol = tol;
         const bool cx = dt == QIL_C64;
-        const size_t lds = (size_t)local_lds_bytes(cx, SITES, d.xl, d.xr, d.dl, d.dm, d.dr, krylov);
+        const size_t lds = (size_t)local_lds_bytes(cx, SITES, g.xl, g.xr, g.dl, g.dm, g.dr, krylov);
         QIL_REQUIRE((long long)lds <= kLdsBudget, QIL_EINVAL_ARG, "evolve: tensor %lld does not fit the local route", (long long)j);
-        if (!cx) QIL_TRY((launch_local<double, double, SITES>(g, lds)));
-        else if (A->dtype == QIL_C64) QIL_TRY((launch_local<c64, c64, SITES>(g, lds)));
-        else QIL_TRY((launch_local<double, c64, SITES>(g, lds)));
-        uint64_t ticket = 0;
-        QIL_TRY(qil_read_back_post(ctx, stat, ST_READ * sizeof(double), &ticket));
-        return qil_read_back_wait(ctx, ticket, hst, ST_READ * sizeof(double));
+        return for_sweep_types(A->dtype == QIL_C64, cx, [&](auto a, auto t) {
+            return launch_local<evolve_local<decltype(a), decltype(t), SITES>>(g, lds, ST_READ, hst);
+        });
     }
 
     template <int SITES>
@@ -383,51 +316,25 @@ struct Evolver : Sweep {
         const Dims d = dims_of(SITES, j);
         const int64_t nv = (SITES == 2 ? 4 : 2) * d.xl * d.xr;
         QIL_REQUIRE(nv < (1LL << 31) / kMaxKrylov, QIL_EINVAL_ARG, "evolve: a local tensor of %lld elements", (long long)nv);
-        const long long blk = nv * std::max({d.dl, d.dm, d.dr});
-        void *T1 = nullptr, *T2 = nullptr, *H = nullptr, *V = nullptr, *Aw0 = nullptr, *Aw1 = nullptr;
-        const void *A0 = nullptr, *A1 = nullptr;
-        QIL_TRY(tmp.alloc((size_t)blk * e, &T1));
-        QIL_TRY(tmp.alloc((size_t)blk * e, &T2));
-        QIL_TRY(tmp.alloc((size_t)nv * e, &H));
-        QIL_TRY(tmp.alloc((size_t)(krylov * nv) * e, &V));
-        QIL_TRY(qil_dev_zero(ctx, V, (size_t)(krylov * nv) * e));
-        if (A->dtype != dt) {
-            QIL_TRY(tmp.alloc((size_t)(4 * ad(j) * ad(j + 1)) * e, &Aw0));
-            if (SITES == 2) QIL_TRY(tmp.alloc((size_t)(4 * ad(j + 1) * ad(j + 2)) * e, &Aw1));
-        }
-        QIL_TRY(qil_site_operand(ctx, dt, A, j, Aw0, &A0));
-        if (SITES == 2) QIL_TRY(qil_site_operand(ctx, dt, A, j + 1, Aw1, &A1));
-        double* st = static_cast<double*>(stat);
-        const bool cx = dt == QIL_C64;
-        const hipStream_t s = qil_stream(ctx);
-        for_elem_type(cx, [&](auto t) {
-            using TE = decltype(t);
-            hipLaunchKernelGGL((evolve_begin<TE>), dim3(1), dim3(kThreads), 0, s, (const TE*)y, (TE*)V, (int)nv, dre, dim, st);
-            return 0;
-        });
-        QIL_HIP(hipGetLastError());
+        Work w;
+        QIL_TRY(work_alloc(SITES, j, nv * std::max({d.dl, d.dm, d.dr}), krylov, &w));
+        const void *A0 = w.A0, *A1 = w.A1;
+        void *V = w.V, *H = w.H;
+        QIL_TRY(launch_wg([](auto t) { return &evolve_begin<decltype(t)>; }, y, V, (int)nv, dre, dim, stat));
         // every launch of a pass is issued; behind the stop they return at once.  One read-back per pass.
         for (int pass = 0; pass < substeps; ++pass) {
             for (int i = 0; i < krylov; ++i) {
                 const void* vi = static_cast<char*>(V) + (size_t)(i * nv) * e;
-                if (SITES == 2) QIL_TRY(gemm_matvec(j, A0, A1, vi, T1, T2, H));
-                else QIL_TRY(gemm_matvec1(j, A0, vi, T1, T2, H));
-                for_elem_type(cx, [&](auto t) {
-                    using TE = decltype(t);
-                    hipLaunchKernelGGL((evolve_step<TE>), dim3(1), dim3(kThreads), 0, s, (TE*)V, (TE*)H, (int)nv, tol, krylov,
-                                       pass + 1 == substeps ? 1 : 0, st);
-                    return 0;
-                });
-                QIL_HIP(hipGetLastError());
+                if (SITES == 2) QIL_TRY(gemm_matvec(j, A0, A1, vi, w.T1, w.T2, H));
+                else QIL_TRY(gemm_matvec1(j, A0, vi, w.T1, w.T2, H));
+                QIL_TRY(launch_wg([](auto t) { return &evolve_step<decltype(t)>; }, V, H, (int)nv, tol, krylov,
+                                  pass + 1 == substeps ? 1 : 0, stat));
             }
-            uint64_t ticket = 0;
-            QIL_TRY(qil_read_back_post(ctx, stat, ST_READ * sizeof(double), &ticket));
-            QIL_TRY(qil_read_back_wait(ctx, ticket, hst, ST_READ * sizeof(double)));
+            QIL_TRY(qil_read_back(ctx, hst, stat, ST_READ * sizeof(double)));
             if (hst[ST_STATUS] != 0.0 || hst[ST_FIN] != 0.0) break;
         }
         QIL_TRY(qil_dev_copy(ctx, y, V, (size_t)nv * e));
-        for (void* q : {Aw1, Aw0, V, H, T2, T1})
-            if (q) tmp.free(q);
+        work_free(w);
         return QIL_OK;
     }
 
@@ -490,9 +397,8 @@ struct Evolver : Sweep {
 
 }  // namespace
 
-// The decision qil_mps_evolve switches on for every local exponential: 1 when the LDS evolve_local needs for these dimensions
-// (local_lds_bytes above) is within the 160 KiB budget, QIL_EVOLVE_ROUTE does not say gemm and -- unless it says local -- a matvec
-// stays within kLocalMaxMacs multiply-adds.
+// The decision qil_mps_evolve switches on for every local exponential: local_route_fits with the LDS evolve_local needs for these
+// dimensions (local_lds_bytes above) and the multiply-adds of the two-site or the one-site matvec.
 extern "C" int qil_mps_evolve_local_fits(int complex_, int sites, int64_t xl, int64_t xr, int64_t dl, int64_t dm, int64_t dr,
                                          int krylov, int* fits) {
     QIL_REQUIRE(fits, QIL_EINVAL_ARG, "evolve_local_fits: null argument");
@@ -501,13 +407,10 @@ extern "C" int qil_mps_evolve_local_fits(int complex_, int sites, int64_t xl, in
     QIL_REQUIRE(xl >= 1 && xr >= 1 && dl >= 1 && dm >= 1 && dr >= 1, QIL_EINVAL_ARG,
                 "evolve_local_fits: dimensions must be positive");
     QIL_REQUIRE(krylov >= 1, QIL_EINVAL_ARG, "evolve_local_fits: krylov must be >= 1 (got %d)", krylov);
-    *fits = 0;
-    const int route = route_from(getenv("QIL_EVOLVE_ROUTE"));
-    if (route == ROUTE_GEMM) return QIL_OK;
-    if (std::max({xl, xr, dl, dm, dr}) > kEvolveDimCap || krylov > kMaxKrylov) return QIL_OK;
-    if (local_lds_bytes(complex_ != 0, sites, xl, xr, dl, dm, dr, krylov) > kLdsBudget) return QIL_OK;
-    const long long macs = sites == 2 ? local_matvec_macs(xl, xr, dl, dm, dr) : local_matvec1_macs(xl, xr, dl, dr);
-    *fits = route == ROUTE_LOCAL || macs <= kLocalMaxMacs ? 1 : 0;
+    const bool over = std::max({xl, xr, dl, dm, dr}) > kKrylovDimCap || krylov > kMaxKrylov;
+    const long long bytes = over ? 0 : local_lds_bytes(complex_ != 0, sites, xl, xr, dl, dm, dr, krylov);
+    const long long macs = over ? 0 : (sites == 2 ? local_matvec_macs(xl, xr, dl, dm, dr) : local_matvec1_macs(xl, xr, dl, dr));
+    *fits = local_route_fits(getenv("QIL_EVOLVE_ROUTE"), over, bytes, macs);
     return QIL_OK;
 }
 
@@ -544,11 +447,8 @@ extern "C" int qil_mps_evolve(const qil_mpo* A, const qil_mps* x0, double tau_re
     for (int s = 0; s < steps; ++s) QIL_TRY(ev.step());
     xh->amplitude = x0->amplitude * xh->amplitude * std::exp(ev.log_sum);
     if (info) {
-        int64_t bond = 1;
-        for (int64_t d : xh->dims) bond = std::max(bond, d);
-        info[0] = steps, info[1] = ev.converged, info[2] = ev.worst, info[3] = (double)ev.matvecs, info[4] = (double)bond;
-        info[5] = (double)ev.n_local, info[6] = (double)ev.n_gemm, info[7] = (double)ev.extra_passes, info[8] = ev.growth;
-        info[9] = ev.log_sum;
+        ev.info_head(info, steps, ev.converged, ev.worst);
+        info[7] = (double)ev.extra_passes, info[8] = ev.growth, info[9] = ev.log_sum;
     }
     *out = x_own.release();
     return QIL_OK;

@@ -8,12 +8,15 @@
 //     T2[p, t1, m, s2, l]   = sum_{a,s1} T1[p, a, s1, s2, l] A_k[a, s1, t1, m]
 //     T3[p, t1, t2, b, l]   = sum_{m,s2} T2[p, t1, m, s2, l] A_{k+1}[m, s2, t2, b]
 //     (Hv)[p, t1, t2, q]    = sum_{b,l}  T3[p, t1, t2, b, l] R_A[q, b, l]
-// All three files include this header; the host steps declared here are defined once, in qil_solve.hip.
+// All three files include this header; the host steps declared here are defined once, in qil_twosite.hip.
 // Here: that matvec inside one workgroup on LDS operands (local_matvec) and as four f64-MFMA GEMMs (Sweep::gemm_matvec), its
 // multiply-add count, the environments of <x|A|x> and of the overlaps <x|phi_i> with further states (the right-hand side of the
 // solver, the deflation states of the eigen-solver) and how they grow by one tensor (Sweep::extend), the projection of such a
-// state onto the local space, g_i = Lphi phi_k phi_{k+1} Rphi, by three small GEMMs (Sweep::overlap_local), and the SVD split of
-// the two-site tensor under the project's truncation rule (Sweep::split).
+// state onto the local space, g_i = Lphi phi_k phi_{k+1} Rphi, by three small GEMMs (Sweep::overlap_local), the SVD split of
+// the two-site tensor under the project's truncation rule (Sweep::split), and the frame every verb builds its local problem in:
+// the route decision (local_route_fits, frame_elems, local_bytes), the argument fields, the staging and the launch of the
+// one-workgroup kernels (FrameArgs, stage_frame, Sweep::launch_local), the work blocks and the helper launches of the gemm
+// routes (Sweep::Work, Sweep::launch_wg) and the verbs' tails (sweep_until, Sweep::info_head).
 #pragma once
 
 #include "qil_internal.h"
@@ -23,6 +26,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 namespace qil_twosite {
@@ -32,7 +36,23 @@ using namespace qil_dev;
 constexpr int kThreads = 256;
 constexpr long long kLdsBudget = 160 * 1024;        // one workgroup may claim all of it
 constexpr long long kRedBytes = 128;                // block_sum's scratch, at the base
-constexpr long long kDimCap = 1 << 20;              // the solver's cap: beyond this nothing fits
+// The solver's cap: beyond this nothing fits.  It stays wider than kKrylovDimCap: cl does not enter the solver's LDS formula, so
+// the narrower cap would change its answer for cl in (2^14, 2^20].
+constexpr long long kDimCap = 1 << 20;
+// The cap of the eigen-solver and of the evolution: one dimension beyond this alone needs more than 160 KiB (8 * 2^14 * 4 bytes in
+// every term it enters), and below it every term of the byte and multiply-add formulas stays under 2^50: no overflow for any
+// arguments of the public host entries
+constexpr long long kKrylovDimCap = 1 << 14;
+constexpr int kMaxKrylov = 16;
+constexpr double kBreakdown = 1e-14;                // beta <= kBreakdown * scale: the Krylov space is invariant
+
+// The auto rule of every verb's fit.  One full sweep of the solver, local vs gemm, same operands (tools/_solve_time.py, median of 10,
+// one MI355X, ms, 40 tensors, f64 / c64): chi 4, D 2 .. 8: 10.9 - 13.1 vs 22.8 - 26.5 / 12.8 - 15.5 vs 28.2 - 34.7; chi 8, D 8 (98 k
+// multiply-adds per matvec): 30.0 vs 39.1 / 38.4 vs 52.0; chi 16, D 3 (135 k): 47.5 vs 52.2; chi 16, D 5 (266 k, f64 only: c64 does
+// not fit): 81.4 vs 71.9, and 17.1 vs 16.1 at 12 tensors -- the one workgroup loses once a matvec is a quarter of a million
+// multiply-adds, whatever the element type (the products are latency-bound).  So auto takes the local route up to 200 k (the
+// two-site count, or the one-site count for the evolution's one-site step); QIL_*_ROUTE=local takes it wherever it fits.
+constexpr long long kLocalMaxMacs = 200000;
 
 // multiply-adds of one matvec (the four products): what the single workgroup of a local route runs through per iteration
 inline long long local_matvec_macs(long long xl, long long xr, long long dl, long long dm, long long dr) {
@@ -40,10 +60,26 @@ inline long long local_matvec_macs(long long xl, long long xr, long long dl, lon
 }
 
 enum { ROUTE_AUTO = 0, ROUTE_LOCAL = 1, ROUTE_GEMM = 2 };
-inline int route_from(const char* r) {            // the value of QIL_SOLVE_ROUTE / QIL_EIGS_ROUTE
+inline int route_from(const char* r) {            // the value of QIL_SOLVE_ROUTE / QIL_EIGS_ROUTE / QIL_EVOLVE_ROUTE
     if (r && !strcmp(r, "local")) return ROUTE_LOCAL;
     if (r && !strcmp(r, "gemm")) return ROUTE_GEMM;
     return ROUTE_AUTO;
+}
+// The route rule of the three *_local_fits entries: 1 when the variable does not say gemm, no argument is over the verb's cap, the
+// kernel's LDS is within the budget and -- unless the variable says local -- a matvec stays within kLocalMaxMacs multiply-adds.
+// Over the cap the byte and multiply-add counts are not looked at (their formulas may have overflowed).
+inline int local_route_fits(const char* env, bool over_cap, long long lds_bytes, long long macs) {
+    const int route = route_from(env);
+    if (route == ROUTE_GEMM || over_cap || lds_bytes > kLdsBudget) return 0;
+    return route == ROUTE_LOCAL || macs <= kLocalMaxMacs ? 1 : 0;
+}
+// elements of the operands every local kernel stages: both environments and the operator tensor(s)
+inline long long frame_elems(int sites, long long xl, long long xr, long long dl, long long dm, long long dr) {
+    return xl * xl * dl + xr * xr * dr + (sites == 2 ? 4 * dl * dm + 4 * dm * dr : 4 * dl * dr);
+}
+// LDS bytes of a local kernel: block_sum's scratch, the verb's small area, the frame, n_vec vectors of nv and two ping-pong blocks
+inline long long local_bytes(bool cx, long long small, long long frame, long long n_vec, long long nv, long long blk) {
+    return kRedBytes + small + (cx ? 16 : 8) * (frame + n_vec * nv + 2 * blk);
 }
 
 // sum over the workgroup of one double per thread, the same value in every thread (it went through LDS)
@@ -51,6 +87,45 @@ __device__ __forceinline__ double wg_sum(double v, double* red) {
     double a[1] = {v};
     block_sum<1>(a, red);
     return a[0];
+}
+
+// The argument fields every local kernel has; its own struct derives from this one, so local_matvec finds g.xl .. g.shift.
+struct FrameArgs {
+    const void *LA, *RA, *A0, *A1;     // environments (TE), operator tensor(s) (TA); A1 unused for one site
+    double shift;                      // the matvec's identity term
+    void* y;                           // the local tensor (TE): the start on entry, the result on return
+    double* stat;                      // what the kernel reports
+    int xl, xr, dl, dm, dr;
+    int blk;                           // elements of one ping-pong block
+};
+// What stage_frame hands back: the staged operands and v, the start vector (nv elements), which is the first free element
+template <class TE>
+struct Frame {
+    TE *Ls, *Rs, *W0, *W1, *v;
+};
+// Carves Ls, Rs, W0, W1 and the start vector from `lds` on and stages them: the environments, the operator tensor(s), widened on
+// the way, and g.y.  No barrier.
+template <class TA, class TE, int SITES>
+__device__ __forceinline__ Frame<TE> stage_frame(const FrameArgs& g, unsigned char* lds) {
+    const int xl = g.xl, xr = g.xr, dl = g.dl, dm = g.dm, dr = g.dr, nv = (SITES == 2 ? 4 : 2) * xl * xr;
+    const int n0 = SITES == 2 ? 4 * dl * dm : 4 * dl * dr, n1 = SITES == 2 ? 4 * dm * dr : 0;
+    Frame<TE> f;
+    f.Ls = reinterpret_cast<TE*>(lds);
+    f.Rs = f.Ls + xl * dl * xl;
+    f.W0 = f.Rs + xr * dr * xr;
+    f.W1 = f.W0 + n0;
+    f.v = f.W1 + n1;
+    const TE* LA = static_cast<const TE*>(g.LA);
+    const TE* RA = static_cast<const TE*>(g.RA);
+    const TA* A0 = static_cast<const TA*>(g.A0);
+    const TA* A1 = static_cast<const TA*>(g.A1);
+    const TE* y0 = static_cast<const TE*>(g.y);
+    for (int t = threadIdx.x; t < xl * dl * xl; t += kThreads) f.Ls[t] = LA[t];
+    for (int t = threadIdx.x; t < xr * dr * xr; t += kThreads) f.Rs[t] = RA[t];
+    for (int t = threadIdx.x; t < n0; t += kThreads) f.W0[t] = cast_elem<TE>(A0[t]);
+    for (int t = threadIdx.x; t < n1; t += kThreads) f.W1[t] = cast_elem<TE>(A1[t]);
+    for (int t = threadIdx.x; t < nv; t += kThreads) f.v[t] = y0[t];
+    return f;
 }
 
 // out (block Y) = H v + shift v, v in LDS; X, Y the ping-pong blocks; g carries xl, xr, dl, dm, dr and shift.  Ends behind a barrier.
@@ -157,6 +232,22 @@ template <class TE>
 __device__ __forceinline__ void axpy_own(TE* w, const TE* v, int nv, double cr, double ci) {
     const TE c = make_elem(-cr, -ci, (TE*)nullptr);
     for (int t = threadIdx.x; t < nv; t += kThreads) w[t] = cmul_add(w[t], c, v[t]);
+}
+
+// The unit start of a local problem: V = y / |y| (y may be V), returns |y|; bad: |y| is zero or not finite, and V = 0 y then.
+template <class TE>
+__device__ __forceinline__ double unit_start(const TE* y, TE* V, int nv, double* red, bool& bad) {
+    const double ynorm = wg_norm<TE>(y, nv, red);
+    bad = !(ynorm > 0.0) || !isfinite(ynorm);
+    const double f = bad ? 0.0 : 1.0 / ynorm;
+    for (int t = threadIdx.x; t < nv; t += kThreads) V[t] = scale_t(y[t], f);
+    return ynorm;
+}
+// the next Lanczos vector vn = w / beta, on the thread's own elements
+template <class TE>
+__device__ __forceinline__ void next_vector(TE* vn, const TE* w, int nv, double beta) {
+    const double f = 1.0 / beta;
+    for (int t = threadIdx.x; t < nv; t += kThreads) vn[t] = scale_t(w[t], f);
 }
 
 // One Lanczos step: w holds the matvec of v_j on entry.  Adds the penalty of the n_ortho states G (none: n_ortho = 0), takes alpha_j, orthogonalises w twice against
@@ -295,7 +386,91 @@ struct Sweep {
         }
         return QIL_OK;
     }
+
+    // the dimensions of a local problem: the two-site tensor of bond j (sites 2) or the tensor j (sites 1)
+    struct Dims {
+        int64_t xl, xr, dl, dm, dr;
+    };
+    Dims dims_of(int sites, int64_t j) const {
+        if (sites == 2) return {xd(j), xd(j + 2), ad(j), ad(j + 1), ad(j + 2)};
+        return {xd(j), xd(j + 1), ad(j), ad(j + 1), ad(j + 1)};
+    }
+
+    // ---- local routes
+    // the shared argument fields of the local problem (sites, j): shift 0 and blk = nv max(dl, dm, dr), for the verb to overwrite
+    // (dimensions and blk as int: the caller has the verb's fits decision behind it, or checks its lds against kLdsBudget before the launch)
+    FrameArgs frame(int sites, int64_t j, void* y, void* stat) const;
+
+    // One launch of the one-workgroup kernel `Kernel` with lds bytes of LDS, then its `words` doubles at g.stat read back to hst.
+    // Keyed on the kernel's VALUE: all instantiations of one kernel template share a pointer type, and the grant of
+    // MaxDynamicSharedMemorySize is per kernel.
+    template <auto Kernel, class Args>
+    int launch_local(const Args& g, size_t lds, int words, double* hst) {
+        static qil_lds_grant grant;
+        QIL_HIP(grant.ensure(ctx->device, reinterpret_cast<const void*>(Kernel), lds));
+        hipLaunchKernelGGL(Kernel, dim3(1), dim3(kThreads), lds, qil_stream(ctx), g);
+        QIL_HIP(hipGetLastError());
+        uint64_t ticket = 0;
+        QIL_TRY(qil_read_back_post(ctx, g.stat, (size_t)words * sizeof(double), &ticket));
+        return qil_read_back_wait(ctx, ticket, hst, (size_t)words * sizeof(double));
+    }
+
+    // ---- gemm routes
+    // The blocks of a gemm route for the local problem (sites, j): T1, T2 (blk elements each) and H (nv) of the matvec, the Krylov
+    // basis V (krylov x nv, zeroed; none with krylov = 0) and the operator tensor(s) as operands in dt, A0 / A1 (Aw0 / Aw1: their
+    // widened copies where the operator is real and dt complex).  A failed call leaves what it has to the qil_scratch.
+    struct Work {
+        void *T1 = nullptr, *T2 = nullptr, *H = nullptr, *V = nullptr, *Aw0 = nullptr, *Aw1 = nullptr;
+        const void *A0 = nullptr, *A1 = nullptr;
+    };
+    int work_alloc(int sites, int64_t j, long long blk, int krylov, Work* w);
+    void work_free(const Work& w);
+
+    // One workgroup of the helper kernel kernel_of(element of dt) on the context's stream; pointer arguments are given untyped and
+    // take the kernel's parameter types.
+    template <class K, class... Args>
+    int launch_wg(K kernel_of, Args... args) {
+        for_elem_type(dt == QIL_C64, [&](auto t) {
+            launch_as(kernel_of(t), args...);
+            return 0;
+        });
+        QIL_HIP(hipGetLastError());
+        return QIL_OK;
+    }
+    template <class... P, class... Args>
+    void launch_as(void (*kernel)(P...), Args... args) {
+        hipLaunchKernelGGL(kernel, dim3(1), dim3(kThreads), 0, qil_stream(ctx), wg_arg<P>(args)...);
+    }
+    // an untyped pointer becomes the parameter's pointer type; anything else is passed as it is, so a number in a pointer's place
+    // (or the reverse, or a pointer of another type) does not compile
+    template <class P, class A>
+    static auto wg_arg(A a) {
+        if constexpr (std::is_pointer_v<P> && std::is_pointer_v<A>) return static_cast<P>(a);
+        else return a;
+    }
+
+    // info[0 .. 6] of every verb: sweeps or steps, converged, residual or worst estimate, matvecs, widest bond, local and gemm solves
+    void info_head(double* info, double count, double converged, double res) const;
 };
+
+// go(operand element, work element) for the pairs a sweep has: dt is complex wherever the operand is, so a real sweep has a real
+// operand and only a complex one switches on the operand's type.
+template <class F>
+int for_sweep_types(bool complex_op, bool complex_dt, F go) {
+    if (!complex_dt) return go(double{}, double{});
+    return for_elem_type(complex_op, [&](auto a) { return go(a, c64{}); });
+}
+
+// Sweeps until the worst local residual of a sweep (res, which sweep() sets) is within tol, max_sweeps times at most.
+template <class F>
+int sweep_until(F sweep, const double& res, double tol, int max_sweeps, int* sweeps, int* converged) {
+    for (*sweeps = 0, *converged = 0; *sweeps < max_sweeps && !*converged;) {
+        QIL_TRY(sweep());
+        ++*sweeps;
+        *converged = res <= tol;
+    }
+    return QIL_OK;
+}
 
 // The start of a sweep: src copied into a fresh chain of dt (amplitude as given; start_chain), then cut to maxdim where it is
 // wider and left in the gauge whose centre is tensor 0 (start_gauge).

@@ -37,7 +37,9 @@ def test_both_entries_are_declared_exported_and_prototyped():
     so = ctypes.CDLL(qil.LIB_PATH)
     assert hasattr(so, "qil_mps_eigs") and hasattr(so, "qil_mps_eigs_local_fits")
     assert len(L.PROTOTYPES["qil_mps_eigs"]) == 15 and len(L.PROTOTYPES["qil_mps_eigs_local_fits"]) == 9
-    assert "qil_eigs.hip" in _read("qilaplace.jl_amd", "csrc", "Makefile") and "qil_twosite.h" in _read("qilaplace.jl_amd", "csrc", "Makefile")
+    make = _read("qilaplace.jl_amd", "csrc", "Makefile")
+    assert "qil_eigs.hip" in make and "qil_twosite.hip" in make
+    assert re.search(r"qil_twosite\.o[^\n]*qil_eigs\.o[^\n]*: qil_twosite\.h", make)
     for name in FRONT_ENDS:
         assert name in qil.__all__ and callable(getattr(qil, name)), name
     flat = re.sub(r"\s*\n \* +", " ", header[header.index("extremal eigenpairs (no reference counterpart)"):])
@@ -167,12 +169,17 @@ def test_the_local_route_is_one_launch_of_one_workgroup_and_the_sweep_has_one_ho
     code = re.sub(r"//[^\n]*", "", _read("qilaplace.jl_amd", "csrc", "qil_eigs.hip"))
     solve = re.sub(r"//[^\n]*", "", _read("qilaplace.jl_amd", "csrc", "qil_solve.hip"))
     shared = re.sub(r"//[^\n]*", "", _read("qilaplace.jl_amd", "csrc", "qil_twosite.h"))
+    steps = re.sub(r"//[^\n]*", "", _read("qilaplace.jl_amd", "csrc", "qil_twosite.hip"))
+    evolve = re.sub(r"//[^\n]*", "", _read("qilaplace.jl_amd", "csrc", "qil_evolve.hip"))
     assert len(re.findall(r"__global__ __launch_bounds__\(kThreads\) void eigs_local\(", code)) == 1
-    assert code.count("hipLaunchKernelGGL((eigs_local<") == 1 and "dim3(1), dim3(kThreads), lds" in code
+    launcher = shared[shared.index("int launch_local("):shared.index("struct Work {")]
+    for once in ("qil_lds_grant", "hipLaunchKernelGGL(Kernel, dim3(1), dim3(kThreads), lds", "qil_read_back_post(", "qil_read_back_wait("):
+        assert launcher.count(once) == 1 and shared.count(once) == 1, once          # the one launcher of the local kernels
+    assert code.count("launch_local<eigs_local<") == 1 and code.count("launch_local<") == 1 and code.count("eigs_local<") == 1
+    assert "hipLaunchKernelGGL" not in code and "dim3(" not in code             # no launch of its own
     kernel = code[code.index("void eigs_local("):code.index("void eigs_begin(")]
     assert "rs < g.restarts" in kernel and "j < g.krylov" in kernel and "atomic" not in code and "asm" not in code
     assert "while" not in kernel                                            # bounded loops only
-    assert "qil_lds_grant" in code and "qil_read_back_post(" in code and "qil_read_back_wait(" in code
     assert code.count("qil_mps_eigs_local_fits(dt == QIL_C64") == 1          # the verb switches on the exported decision
     assert 'getenv("QIL_EIGS_ROUTE")' in code
     # one home: both files include the header, the matvec and the environment steps are defined once
@@ -180,7 +187,7 @@ def test_the_local_route_is_one_launch_of_one_workgroup_and_the_sweep_has_one_ho
         assert '#include "qil_twosite.h"' in src and "local_matvec<TE>(g, Ls, Rs, W0, W1," in src
     assert shared.count("void local_matvec(") == 1 and "void local_matvec(" not in code + solve
     for step in ("Sweep::extend(", "Sweep::gemm_matvec(", "Sweep::overlap_local(", "Sweep::split(", "Sweep::init_envs("):
-        assert solve.count("int " + step) == 1 and step not in code, step
+        assert steps.count("int " + step) == 1 and step not in code + solve + evolve, step
     for call in ("qil_dev_gemm_batched(", "qil_apply_overlap_env_step(", "qil_overlap_env_step(", "qil_dev_svd(", "qil_truncation_rank("):
         assert call not in code, call
     for use in ("gemm_matvec(k, A0, A1,", "overlap_local(", "split(k, to_right, y, true)", "init_envs()"):

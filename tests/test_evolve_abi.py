@@ -40,6 +40,7 @@ def test_both_entries_are_declared_exported_and_prototyped():
     assert len(L.PROTOTYPES["qil_mps_evolve"]) == 12 and len(L.PROTOTYPES["qil_mps_evolve_local_fits"]) == 9
     make = _read("qilaplace.jl_amd", "csrc", "Makefile")
     assert "qil_evolve.hip" in make and re.search(r"qil_evolve\.o[^\n]*: qil_twosite\.h", make)
+    assert "qil_twosite.hip" in make and re.search(r"qil_twosite\.o[^\n]*: qil_twosite\.h", make)
     assert "global: qil_*;" in _read("qilaplace.jl_amd", "csrc", "libqilhip.map")
     for name in FRONT_ENDS:
         assert name in qil.__all__ and callable(getattr(qil, name)), name
@@ -180,24 +181,28 @@ def test_the_local_route_is_one_launch_of_one_workgroup_and_the_shared_steps_hav
     solve = re.sub(r"//[^\n]*", "", _read("qilaplace.jl_amd", "csrc", "qil_solve.hip"))
     eigs = re.sub(r"//[^\n]*", "", _read("qilaplace.jl_amd", "csrc", "qil_eigs.hip"))
     shared = re.sub(r"//[^\n]*", "", _read("qilaplace.jl_amd", "csrc", "qil_twosite.h"))
+    steps = re.sub(r"//[^\n]*", "", _read("qilaplace.jl_amd", "csrc", "qil_twosite.hip"))
     assert len(re.findall(r"__global__ __launch_bounds__\(kThreads\) void evolve_local\(", code)) == 1
-    assert code.count("hipLaunchKernelGGL((evolve_local<") == 1 and "dim3(1), dim3(kThreads), lds" in code
+    launcher = shared[shared.index("int launch_local("):shared.index("struct Work {")]
+    for once in ("qil_lds_grant", "hipLaunchKernelGGL(Kernel, dim3(1), dim3(kThreads), lds", "qil_read_back_post(", "qil_read_back_wait("):
+        assert launcher.count(once) == 1 and shared.count(once) == 1, once          # the one launcher of the local kernels
+    assert code.count("launch_local<evolve_local<") == 1 and code.count("launch_local<") == 1 and code.count("evolve_local<") == 1
+    assert "hipLaunchKernelGGL" not in code and "dim3(" not in code             # no launch of its own
     kernel = code[code.index("void evolve_local("):code.index("void evolve_begin(")]
     assert "pass < g.substeps" in kernel and "j < g.krylov" in kernel and "atomic" not in code and "asm" not in code
     assert "while" not in kernel and "while" not in code[code.index("krylov_exp("):code.index("void evolve_local(")]
     assert "h < kMaxHalvings" in code                                       # the halving is a bounded loop
-    assert "qil_lds_grant" in code and "qil_read_back_post(" in code and "qil_read_back_wait(" in code
     assert code.count("qil_mps_evolve_local_fits(dt == QIL_C64") == 1        # the verb switches on the exported decision
     assert 'getenv("QIL_EVOLVE_ROUTE")' in code
-    # one home: the one-site matvecs, the Lanczos step and the small eigen-solver live in the shared header / in qil_solve.hip
+    # one home: the one-site matvecs, the Lanczos step and the small eigen-solver live in the shared header / in qil_twosite.hip
     assert '#include "qil_twosite.h"' in code
     assert shared.count("void local_matvec1(") == 1 and shared.count("void local_matvec(") == 1
     assert shared.count("void lanczos_step(") == 1 and shared.count("void tridiagonal_eig(") == 1
     for name in ("void local_matvec1(", "void local_matvec(", "void lanczos_step(", "void tridiagonal_eig("):
         assert name not in code + solve + eigs, name
-    assert solve.count("int Sweep::gemm_matvec1(") == 1 and "Sweep::gemm_matvec1(" not in code + eigs
+    assert steps.count("int Sweep::gemm_matvec1(") == 1 and "Sweep::gemm_matvec1(" not in code + eigs + solve
     for step in ("Sweep::extend(", "Sweep::gemm_matvec(", "Sweep::split(", "Sweep::init_envs(", "Sweep::two_site("):
-        assert solve.count("int " + step) == 1 and step not in code, step
+        assert steps.count("int " + step) == 1 and step not in code + eigs + solve, step
     for call in ("qil_dev_gemm_batched(", "qil_apply_overlap_env_step(", "qil_dev_svd(", "qil_truncation_rank("):
         assert call not in code, call
     for use in ("local_matvec<TE>(g, Ls, Rs, W0, W1,", "local_matvec1<TE>(g, Ls, Rs, W0,", "gemm_matvec(j, A0, A1,", "gemm_matvec1(j, A0,",

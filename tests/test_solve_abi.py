@@ -35,7 +35,9 @@ def test_both_entries_are_declared_exported_and_prototyped():
     so = ctypes.CDLL(qil.LIB_PATH)
     assert hasattr(so, "qil_mps_solve") and hasattr(so, "qil_mps_solve_local_fits")
     assert len(L.PROTOTYPES["qil_mps_solve"]) == 11 and len(L.PROTOTYPES["qil_mps_solve_local_fits"]) == 10
-    assert "qil_solve.hip" in _read("qilaplace.jl_amd", "csrc", "Makefile")
+    make = _read("qilaplace.jl_amd", "csrc", "Makefile")
+    assert "qil_solve.hip" in make and "qil_twosite.hip" in make
+    assert re.search(r"qil_twosite\.o[^\n]*qil_solve\.o[^\n]*: qil_twosite\.h", make)
     for name in FRONT_ENDS:
         assert name in qil.__all__ and callable(getattr(qil, name)), name
     header = _read("include", "qilaplace_hip.h")
@@ -134,13 +136,19 @@ def test_argument_errors_precede_the_context_activation():
 def test_the_local_route_is_one_launch_of_one_workgroup_without_spins_or_atomics():
     code = re.sub(r"//[^\n]*", "", _read("qilaplace.jl_amd", "csrc", "qil_solve.hip"))
     assert len(re.findall(r"__global__ __launch_bounds__\(kThreads\) void solve_local\(", code)) == 1
-    assert code.count("hipLaunchKernelGGL((solve_local<") == 1 and "dim3(1), dim3(kThreads), lds" in code
+    shared = re.sub(r"//[^\n]*", "", _read("qilaplace.jl_amd", "csrc", "qil_twosite.h"))
+    steps = re.sub(r"//[^\n]*", "", _read("qilaplace.jl_amd", "csrc", "qil_twosite.hip"))
+    launcher = shared[shared.index("int launch_local("):shared.index("struct Work {")]
+    for once in ("qil_lds_grant", "hipLaunchKernelGGL(Kernel, dim3(1), dim3(kThreads), lds", "qil_read_back_post(", "qil_read_back_wait("):
+        assert launcher.count(once) == 1 and shared.count(once) == 1, once          # the one launcher of the local kernels
+    assert code.count("launch_local<solve_local<") == 1 and code.count("launch_local<") == 1 and code.count("solve_local<") == 1
+    assert "hipLaunchKernelGGL" not in code and "dim3(" not in code             # no launch of its own
     kernel = code[code.index("void solve_local("):code.index("void cg_start(")]
     assert "it < g.cg_iters" in kernel and "atomic" not in code and "asm" not in code
-    assert "qil_lds_grant" in code and "qil_read_back_post(" in code and "qil_read_back_wait(" in code
-    for shared in ("qil_gauge_exact(", "qil_dev_svd(", "qil_truncation_rank(", "qil_apply_overlap_env_step(", "qil_overlap_env_step(",
-                   "QIL_SITE_REVERSED", "qil_dev_gemm_batched(", 'getenv("QIL_SOLVE_ROUTE")'):
-        assert shared in code, shared
+    for step in ("qil_gauge_exact(", "qil_dev_svd(", "qil_truncation_rank(", "qil_apply_overlap_env_step(", "qil_overlap_env_step(",
+                 "QIL_SITE_REVERSED", "qil_dev_gemm_batched("):
+        assert step in steps and step not in code, step                            # the host steps live in qil_twosite.hip
+    assert 'getenv("QIL_SOLVE_ROUTE")' in code
     assert code.count("qil_mps_solve_local_fits(dt == QIL_C64") == 1          # the verb switches on the exported decision
 
 

@@ -48,7 +48,9 @@ def gpu_name():
         out = subprocess.run(["rocminfo"], capture_output=True, text=True, timeout=60).stdout
         names = [l.split(":", 1)[1].strip() for l in out.splitlines() if "Marketing Name" in l]
         names = [v for v in names if v]
-        return next((v for v in names if "Instinct" in v or "MI3" in v), names[-1] if names else "unknown")
+        # a GPU agent without a marketing name still has its target as Name; never fall back to the CPU agent's name
+        targets = [l.split(":", 1)[1].strip() for l in out.splitlines() if l.strip().startswith("Name:") and "gfx" in l]
+        return next((v for v in names if "Instinct" in v or "MI3" in v), targets[0] if targets else "unknown")
     except (OSError, subprocess.SubprocessError):
         return "unknown"
 
